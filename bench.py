@@ -405,6 +405,43 @@ def whole_job_value(world, batch_per_rank, steps, elapsed):
     return world * batch_per_rank * steps / elapsed
 
 
+def headline(value, world, steps, warmup, elapsed, scaling, config):
+    """The fields every result line carries: what a plain run prints, and what a --full run adds its measurements to."""
+    return {"metric": "SQP iterations/sec (whole node)", "value": value, "unit": "SQP iterations/s",
+            "n_gpus": world, "steps": steps, "warmup": warmup, "ms_per_step": 1e3 * elapsed / steps,
+            "higher_is_better": True, "scaling": scaling, "vs_baseline": None, "dtype": "f64", "data": "synthetic", "config": config}
+
+
+DUMP_MAX_BYTES = 64 << 20
+DUMP_MAX_INSTANCES = 128
+UN_SOL_FIELDS = ("lmd", "gmm", "q", "v", "a", "u", "beta")
+
+
+def ocp_chain_reader(lib, h, M):
+    """read(field, instance) -> [M][dim]: the solution of one instance along its chain of M stages (idocp_ocp_get_solution_chain)"""
+    from idocp_amd import capi
+    from idocp_amd.workloads import OCP_CHAIN_EXTRA, OCP_SOL_FIELDS, P
+
+    def read(name, instance):
+        out = np.zeros((M, OCP_SOL_FIELDS.get(name) or OCP_CHAIN_EXTRA[name]))
+        capi.check(lib.idocp_ocp_get_solution_chain(h, name.encode(), instance, P(out)), "get_solution_chain " + name)
+        return out
+    return read, list(OCP_SOL_FIELDS) + ["xi"]
+
+
+def dump_outputs(directory, read, fields, batch):
+    """--dump-outputs DIR: what the timed path computed in its last step, i.e. the solution a caller of updateSolution reads back,
+    as DIR/<field>.npy [instances][stages][dim] in float64.  The instances are a fixed, seeded sample of the batch (all of it when it
+    is small), sized so that the files stay under DUMP_MAX_BYTES; DIR/instances.npy holds their indices."""
+    per_instance = sum(read(f, 0).nbytes for f in fields)
+    n = min(batch, DUMP_MAX_INSTANCES, (DUMP_MAX_BYTES - 8 * batch) // per_instance)
+    idx = np.arange(batch) if n == batch else np.sort(np.random.default_rng(0).choice(batch, n, replace=False))
+    os.makedirs(directory, exist_ok=True)
+    np.save(os.path.join(directory, "instances.npy"), idx.astype(np.float64))
+    for f in fields:
+        np.save(os.path.join(directory, f + ".npy"), np.stack([read(f, int(i)) for i in idx]).astype(np.float64))
+
+
 def latency_mode(lib, hip, build, q0, v0, iters=40):
     """The "ms / Riccati sweep" half of the metric: ONE OCP instance (batch 1, what one reference solver object is), the same
     problem as the throughput run.  ms per SQP iteration with plain launches and with the hipGraph replay
@@ -759,18 +796,19 @@ def run_parnmpc_cxx(args, rank, local_rank, world, dist):
     capi.check(lib.idocp_comm_info(comm, C.byref(nr), C.byref(ur), C.byref(ver), C.byref(tr)), "comm_info")
     if nr.value != world or ur.value != rank:
         raise SystemExit("bench.py: RCCL reports rank %d of %d, the launcher started rank %d of %d" % (ur.value, nr.value, rank, world))
-    dev = C.c_double(-1.0)
-    rc_self = lib.idocp_parnmpc_dist_transport_selftest(shard.h, C.byref(dev))
-    worst = np.array([dev.value if rc_self == 0 else np.inf])
-    if dist is not None:
-        import torch
-        tw = torch.from_numpy(worst)
-        dist.all_reduce(tw, op=dist.ReduceOp.MAX)
-    if not (worst[0] <= 1e-9):
-        raise SystemExit("bench.py: transport self-test FAILED on rank %d of %d before the timed region: rc %d, largest deviation over the ranks %r (%s)"
-                         % (rank, world, rc_self, float(worst[0]), lib.idocp_last_error().decode() if rc_self else "halo / collective contents differ from the pattern"))
-    rccl_info = {"rccl_nranks": nr.value, "rccl_version": ver.value, "transport": "rccl" if tr.value else "in-process",
-                 "selftest_max_abs_diff": float(worst[0])}
+    if args.full:
+        dev = C.c_double(-1.0)
+        rc_self = lib.idocp_parnmpc_dist_transport_selftest(shard.h, C.byref(dev))
+        worst = np.array([dev.value if rc_self == 0 else np.inf])
+        if dist is not None:
+            import torch
+            tw = torch.from_numpy(worst)
+            dist.all_reduce(tw, op=dist.ReduceOp.MAX)
+        if not (worst[0] <= 1e-9):
+            raise SystemExit("bench.py: transport self-test FAILED on rank %d of %d before the timed region: rc %d, largest deviation over the ranks %r (%s)"
+                             % (rank, world, rc_self, float(worst[0]), lib.idocp_last_error().decode() if rc_self else "halo / collective contents differ from the pattern"))
+        rccl_info = {"rccl_nranks": nr.value, "rccl_version": ver.value, "transport": "rccl" if tr.value else "in-process",
+                     "selftest_max_abs_diff": float(worst[0])}
     if rank == 0:
         capi.check(lib.idocp_parnmpc_dist_set_initial_state(shard.h, P(q0), P(v0), nq, nv))
     capi.check(lib.idocp_parnmpc_dist_init_backward_correction(shard.h, 0.0), "dist_init_backward_correction")
@@ -804,6 +842,25 @@ def run_parnmpc_cxx(args, rank, local_rank, world, dist):
         hip.rt.hipDeviceSynchronize()
 
     el = run_timed(step, sync, args.steps, args.warmup, dist, "cpu")
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, *ocp_chain_reader(lib, shard.h, len(shard.chain(0.0))), B)
+    desc = ("ANYmal ParNMPCSolver N=%d T=%.2f FP64, %s (BASELINE.json configs[3]); batch=%d OCP instances, the %d stages "
+            "of every instance sharded over %d GPU(s), C++ driver with RCCL halo exchange (idocp_parnmpc_dist_*)"
+            % (N, T, ("TROTTING contact sequence (1 lift + %d impulse events: %d stages in the chain), moving iterate started from "
+                      "the converged ParNMPC solution of this problem (continuation in the step length)" % (n_events - 1, N + 2 * (n_events - 1) + 1))
+               if trot else "4 point contacts on every stage, warm-started from the converged Riccati solution of the same OCP", B, N, world))
+    config = {"workload": desc, "horizon": N, "batch_per_gpu": B, "parallelism": "horizon shards x%d" % world, "stages_per_rank": Nl, "setup": setup}
+
+    def finish():
+        capi.check(lib.idocp_parnmpc_dist_detach(shard.h))
+        lib.idocp_comm_destroy(comm)
+        if dist is not None:
+            dist.destroy_process_group()
+
+    if not args.full:
+        if rank == 0:
+            print(json.dumps(headline(B * args.steps / el, world, args.steps, args.warmup, el, "strong", config)), flush=True)
+        return finish()
     kkt = np.zeros(B)
     capi.check(lib.idocp_parnmpc_dist_kkt_error(shard.h, 0.0, P(kkt)), "dist_kkt_error")
     assert np.isfinite(kkt).all(), "non-finite KKT error after the timed region"
@@ -827,20 +884,9 @@ def run_parnmpc_cxx(args, rank, local_rank, world, dist):
                 ker[PH[k]] = ker.get(PH[k], 0.0) + hip.elapsed_ms(ev[k], ev[k + 1]) / reps
     if rank == 0:
         ms_step = 1e3 * el / args.steps
-        out = {
-            "metric": "SQP iterations/sec (whole node)", "value": B * args.steps / el, "unit": "SQP iterations/s",
-            "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": ms_step,
-            "higher_is_better": True, "scaling": "strong", "vs_baseline": None, "dtype": "f64", "data": "synthetic",
-            "config": {"workload": ("ANYmal ParNMPCSolver N=%d T=%.2f FP64, %s (BASELINE.json configs[3]); batch=%d OCP instances, the %d stages "
-                                    "of every instance sharded over %d GPU(s), C++ driver with RCCL halo exchange (idocp_parnmpc_dist_*)"
-                                    % (N, T, ("TROTTING contact sequence (1 lift + %d impulse events: %d stages in the chain), moving iterate started from "
-                                              "the converged ParNMPC solution of this problem (continuation in the step length)" % (n_events - 1, N + 2 * (n_events - 1) + 1))
-                                       if trot else "4 point contacts on every stage, warm-started from the converged Riccati solution of the same OCP", B, N, world)),
-                       "horizon": N, "batch_per_gpu": B, "parallelism": "horizon shards x%d" % world,
-                       "stages_per_rank": Nl, "setup": setup, "rccl": rccl_info,
-                       "model_ms": parnmpc_model_ms(args.workload, world, ker if world == 1 else None),
-                       "kernel_ms": ker, "max_kkt_error_after": float(kkt.max())},
-        }
+        config.update({"rccl": rccl_info, "model_ms": parnmpc_model_ms(args.workload, world, ker if world == 1 else None),
+                       "kernel_ms": ker, "max_kkt_error_after": float(kkt.max())})
+        out = headline(B * args.steps / el, world, args.steps, args.warmup, el, "strong", config)
         if ker:
             dom = max(ker, key=ker.get)
             alg_bytes = A_STAGE["anymal_parnmpc"] * B * (Nl + (2 * (n_events - 1) + 1 if trot else 0))
@@ -885,10 +931,7 @@ def run_parnmpc_cxx(args, rank, local_rank, world, dist):
                                    "sample": "%d updateSolution calls of one ParNMPC N=%d instance, single thread (oracle/, -O3)" % (n, N),
                                    "ms_per_update": 1e3 * elc / n}
         print(json.dumps(out), flush=True)
-    capi.check(lib.idocp_parnmpc_dist_detach(shard.h))
-    lib.idocp_comm_destroy(comm)
-    if dist is not None:
-        dist.destroy_process_group()
+    finish()
 
 
 def main():
@@ -906,8 +949,12 @@ def main():
                     help="ANYmal workloads: LinearizedFrictionCone (the trotting / running examples) or FrictionCone (examples/anymal/ocp_benchmark.cpp:76)")
     ap.add_argument("--timeout", type=float, default=None, help="--gpus N > 1 started without a launcher: seconds after which the ranks are ended "
                                                               "and the command exits with 124 (default: IDOCP_BENCH_TIMEOUT or 1200)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-latency", action="store_true", help="skip the batch-1 latency measurement (config.latency)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check what the headline figure does not need: per-kernel times, roofline, the KKT error after the "
+                         "timed steps, the batch-1 latency, the CPU baseline and the ParNMPC transport self-test")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline (cpu_baseline)")
+    ap.add_argument("--no-latency", action="store_true", help="--full without the batch-1 latency measurement (config.latency)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the solution the timed path computed in its last step as DIR/<field>.npy")
     args = ap.parse_args()
 
     if args.gpus > 1 and "RANK" not in os.environ:
@@ -1100,8 +1147,21 @@ def main():
             import torch
             torch.cuda.synchronize()
 
-    ev = [[hip.event() for _ in range(len(KERNELS) + 1)] for _ in range(args.steps)]
+    ev = [[hip.event() for _ in range(len(KERNELS) + 1)] for _ in range(args.steps)] if args.full else None
     el = run_timed(step, sync, args.steps, args.warmup, dist, "cuda", ev)
+    if args.dump_outputs and rank == 0:
+        if isinstance(solver, HipOCP):
+            dump_outputs(args.dump_outputs, *ocp_chain_reader(lib, solver.h, N + 1 if args.workload == "anymal" else Mc), B)
+        else:
+            dump_outputs(args.dump_outputs, solver.solution, UN_SOL_FIELDS, B)
+    config = {"workload": desc + "batch=%d independent OCP instances per GPU, replicas across GPUs" % B,
+              "horizon": N, "batch_per_gpu": B, "parallelism": "replicas x%d" % world}
+    if not args.full:
+        if rank == 0:
+            print(json.dumps(headline(whole_job_value(world, B, args.steps, el), world, args.steps, args.warmup, el, "weak", config)), flush=True)
+        if dist is not None:
+            dist.destroy_process_group()
+        return
 
     # per-kernel average durations from the events of the timed region, and the per-step HIP-event time of every timed step (median and
     # spread: a slow box moves all steps alike, a regression moves the median against the committed profile; boxes of this pool differ by ~5 %)
@@ -1139,12 +1199,7 @@ def main():
     if rank == 0:
         ms_step = 1e3 * el / args.steps
         fused = KERNELS[riccati_ids[1]] == "ocp_forward_expand"
-        out = {
-            "metric": "SQP iterations/sec (whole node)", "value": whole_job_value(world, B, args.steps, el), "unit": "SQP iterations/s",
-            "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": ms_step,
-            "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f64", "data": "synthetic",
-            "config": {"workload": desc + "batch=%d independent OCP instances per GPU, replicas across GPUs" % B,
-                       "horizon": N, "batch_per_gpu": B, "parallelism": "replicas x%d" % world,
+        config.update({
                        # the sweeps under their own keys: with the fused forward sweep (batches of instances) the second kernel is S4 + K6 + the
                        # step-size reduction in one walk, so the PAIR is not the "ms / Riccati sweep" of the metric -- that figure (S3 + S4 of one
                        # instance, comparable with cpu_baseline.ms_per_riccati_sweep) is config.latency.ms_per_riccati_sweep
@@ -1154,15 +1209,15 @@ def main():
                        "kernel_ms": {KERNELS[i]: float(kms[i]) for i in range(len(KERNELS))},
                        "step_ms_hip_events": {"median": float(np.median(step_ev)), "min": float(step_ev.min()), "max": float(step_ev.max()),
                                               "mean": float(step_ev.mean()), "note": "first to last event of each of the %d timed steps" % args.steps},
-                       "max_kkt_error_after": float(np.max(kkt)), "latency": latency},
-            "roofline": {"bound": "hbm", "kernel": KERNELS[dom], "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                         "frac": achieved / HBM_PEAK_GBS, "traffic": traffic, "traffic_source": traffic_source,
-                         "algorithmic_bytes_per_launch": alg_bytes, "avg_launch_ms": float(kms[dom]),
-                         # the whole iteration's compulsory bytes over the whole step: one unit per stage of the CHAIN (event stages
-                         # included -- 120 for the default workload, not N + 1 = 101), i.e. the largest per-launch unit count
-                         "whole_step_frac": a_stage * max(units.values()) / (ms_step * 1e-3) / 1e9 / HBM_PEAK_GBS,
-                         "by_stage_class": by_class},
-        }
+                       "max_kkt_error_after": float(np.max(kkt)), "latency": latency})
+        out = headline(whole_job_value(world, B, args.steps, el), world, args.steps, args.warmup, el, "weak", config)
+        out["roofline"] = {"bound": "hbm", "kernel": KERNELS[dom], "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                           "frac": achieved / HBM_PEAK_GBS, "traffic": traffic, "traffic_source": traffic_source,
+                           "algorithmic_bytes_per_launch": alg_bytes, "avg_launch_ms": float(kms[dom]),
+                           # the whole iteration's compulsory bytes over the whole step: one unit per stage of the CHAIN (event stages
+                           # included -- 120 for the default workload, not N + 1 = 101), i.e. the largest per-launch unit count
+                           "whole_step_frac": a_stage * max(units.values()) / (ms_step * 1e-3) / 1e9 / HBM_PEAK_GBS,
+                           "by_stage_class": by_class}
         # the FP64 roofline of the same kernel: exact FLOPs of the reference's formulation (oracle counting build) over the launch time
         frec = oracle_flops_record(args.workload, max(units.values()) // B)
         if frec is not None:

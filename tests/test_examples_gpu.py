@@ -75,13 +75,12 @@ def test_iiwa14_unocp_benchmark_example_matches_oracle():
     assert len(its) >= 10 and its[-1] < init
 
 
-def test_iiwa14_unparnmpc_benchmark_example_matches_oracle():
+def test_iiwa14_unparnmpc_benchmark_example_matches_oracle(tmp_path):
     """examples/iiwa14_unparnmpc_benchmark.cpp = the reference's examples/iiwa14/unparnmpc_benchmark.cpp through the facade
     (idocp::UnParNMPCSolver): the printed KKT errors follow the oracle's iteration and reach its floor."""
     from helpers import OracleUnParNMPC, iiwa14_model, unocp_problem
     build_examples()
-    out = os.path.join(ROOT, "gpurun_out", "unparnmpc_solution")
-    os.makedirs(os.path.dirname(out), exist_ok=True)
+    out = str(tmp_path / "unparnmpc_solution")
     r = subprocess.run([os.path.join(ROOT, "examples", "iiwa14_unparnmpc_benchmark"), IIWA_URDF, out], capture_output=True, text=True,
                        timeout=600)
     assert r.returncode == 0, (r.stdout + r.stderr)[-3000:]

@@ -1,6 +1,6 @@
 """The drop-in claim of INTEGRATION.md section 1, taken literally: the REFERENCE's own example drivers -- `examples/iiwa14/*.cpp`, `examples/anymal/*.cpp`,
 twelve programs -- are compiled UNMODIFIED, from where they lie under the reference tree, against this repository's `include/` and `libidocp_hip.so`
-(`examples/Makefile`, target `ref`; outputs in `examples/_ref/`, git-ignored; nothing of the reference is copied), and run on the GPU.
+(`oracle/Makefile`, target `ref`; outputs in `oracle/_ref/`, git-ignored; nothing of the reference is copied), and run on the GPU.
 
 * without a GPU (here, where the reference tree is present): all twelve compile and link;
 * on the GPU box (the binaries travel with the tree like every built file; the reference does not exist there): all twelve run to completion, print
@@ -17,7 +17,7 @@ import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 REF = os.environ.get("IDOCP_REFERENCE_DIR", "/root/reference")
-REF_BIN = os.path.join(ROOT, "examples", "_ref")
+REF_BIN = os.path.join(ROOT, "oracle", "_ref")
 # reference driver -> this repository's driver of the same workload (None: no twin with the same call sequence)
 TWINS = {
     "iiwa14_unocp_benchmark": "iiwa14_unocp_benchmark",
@@ -45,13 +45,13 @@ def kkt_values(stdout):
 
 @pytest.mark.skipif(not os.path.isdir(os.path.join(REF, "examples", "iiwa14")), reason="the reference tree is not on this machine")
 def test_the_reference_example_drivers_compile_and_link_unmodified():
-    r = subprocess.run(["make", "-C", os.path.join(ROOT, "examples"), "ref", "REF=" + REF], capture_output=True, text=True)
+    r = subprocess.run(["make", "-C", os.path.join(ROOT, "oracle"), "ref", "REF=" + REF], capture_output=True, text=True)
     assert r.returncode == 0, r.stderr[-3000:]
     built = sorted(os.listdir(REF_BIN))
     assert built == sorted(TWINS), built
     # nothing of the reference sits in the tree: the outputs are binaries, and git does not see them
     assert all(open(os.path.join(REF_BIN, b), "rb").read(4) == b"\x7fELF" for b in built)
-    assert subprocess.run(["git", "-C", ROOT, "status", "--porcelain", "examples/_ref"], capture_output=True, text=True).stdout == ""
+    assert subprocess.run(["git", "-C", ROOT, "status", "--porcelain", "oracle/_ref"], capture_output=True, text=True).stdout == ""
 
 
 @pytest.mark.skipif(not os.path.isdir(os.path.join(REF, "examples", "iiwa14")) or shutil.which("cmake") is None, reason="needs the reference tree and cmake")
@@ -77,7 +77,7 @@ def test_the_reference_cmake_projects_configure_and_build_against_the_package_co
 @pytest.mark.gpu
 def test_the_reference_example_drivers_run_on_the_gpu_and_print_what_our_drivers_print(tmp_path):
     if not os.path.isdir(REF_BIN) or sorted(os.listdir(REF_BIN)) != sorted(TWINS):
-        pytest.skip("examples/_ref is not built (it is built where the reference tree is: __graft_entry__.build())")
+        pytest.skip("oracle/_ref is not built (it is built where the reference tree is: __graft_entry__.build())")
     r = subprocess.run(["make", "-C", os.path.join(ROOT, "examples"), "all"], capture_output=True, text=True)
     assert r.returncode == 0, r.stderr[-3000:]
     # the directory the reference's drivers expect: they open ../<robot description>/urdf/<robot>.urdf from their build directory
