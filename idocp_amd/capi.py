@@ -176,6 +176,7 @@ def _proto(lib):
         ("idocp_unparnmpc_launch_phase", [vp, ci, vp, vp]),
         ("idocp_unparnmpc_get_new_solution", [vp, cs, ci, c_double_p]),
         ("idocp_unparnmpc_halo_size", [ci]),
+        ("idocp_unparnmpc_halo_size_of", [vp, ci]),
         ("idocp_unparnmpc_export_halo", [vp, ci, vp]),
         ("idocp_unparnmpc_import_halo", [vp, ci, vp]),
         ("idocp_unparnmpc_prev_state", [vp, P(vp), P(vp)]),

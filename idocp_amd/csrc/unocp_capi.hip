@@ -61,12 +61,59 @@ void toDevModel(const idocp_model_t& m, DevModel& d) {
   std::memcpy(d.gravity, m.gravity, sizeof(double) * 3);
 }
 
-// The UnOCP kernels are compiled for a serial chain of NV revolute joints.
-bool isRevoluteChain(const idocp_model_t& m, int nv) {
-  if (m.njoints != nv || m.nv != nv || m.nq != nv || m.has_floating_base || m.ncontacts != 0) return false;
+// The UnOCP kernels are compiled for serial chains of UN_MIN_NV .. UN_MAX_NV revolute joints (unocp_kernels.hip instantiates UnLaunch<NV>
+// for each).
+constexpr int UN_MIN_NV = 2, UN_MAX_NV = 8;
+bool isRevoluteChain(const idocp_model_t& m) {
+  const int nv = m.nv;
+  if (nv < UN_MIN_NV || nv > UN_MAX_NV) return false;
+  if (m.njoints != nv || m.nq != nv || m.has_floating_base || m.ncontacts != 0) return false;
   for (int i = 0; i < nv; ++i)
     if (m.parent[i] != i - 1 || m.jtype[i] != IDOCP_JOINT_REVOLUTE || m.idx_v[i] != i) return false;
   return true;
+}
+const char* const CHAIN_RANGE = "a fixed-base serial chain of 2 .. 8 revolute joints";
+
+// The record layout UnLayout<NV> of a handle's chain, read at run time by the host side (strides of the device arrays, field offsets)
+struct UnDims {
+  int NV, SOL, CON, KKT, DYN, RIC, GAIN, KINV, AUX, XRES, NX, TASK;
+  int S_LMD, S_GMM, S_Q, S_V, S_A, S_U, S_BETA;
+  int D_DQ, D_DV, D_DA, R_PQQ, R_PQV, R_PVV, R_SQ, R_SV, G_K, G_k;
+  int sym(int r, int c) const { return r <= c ? c * (c + 1) / 2 + r : r * (r + 1) / 2 + c; }      // (UnLayout::sym)
+};
+// The kernels of one chain length, chosen once at creation (idocp_unocp::impl)
+struct UnImpl {
+  UnDims L;
+  decltype(&UnLaunch<7>::linearize) linearize, residual, expand, integrate, initConstraints, parnmpcInitAux;
+  decltype(&UnLaunch<7>::riccati) riccati, parnmpcResidual;
+  decltype(&UnLaunch<7>::single) single, parnmpcPhase;
+  decltype(&UnLaunch<7>::lineSearchEval) lineSearchEval;
+  decltype(&UnLaunch<7>::rneaDerivatives) rneaDerivatives;
+};
+template <int NV>
+const UnImpl* unImpl() {
+  using L = UnLayout<NV>;
+  static_assert(L::S_LMD == 0 && L::S_BETA == 6 * NV, "record order = output order of idocp_unocp_get_split_solution");
+  static const UnImpl impl = {
+      {NV, L::SOL, L::CON, L::KKT, L::DYN, L::RIC, L::GAIN, L::KINV, L::AUX, L::XRES, L::NX, L::TASK,
+       L::S_LMD, L::S_GMM, L::S_Q, L::S_V, L::S_A, L::S_U, L::S_BETA,
+       L::D_DQ, L::D_DV, L::D_DA, L::R_PQQ, L::R_PQV, L::R_PVV, L::R_SQ, L::R_SV, L::G_K, L::G_k},
+      &UnLaunch<NV>::linearize, &UnLaunch<NV>::residual, &UnLaunch<NV>::expand, &UnLaunch<NV>::integrate, &UnLaunch<NV>::initConstraints,
+      &UnLaunch<NV>::parnmpcInitAux, &UnLaunch<NV>::riccati, &UnLaunch<NV>::parnmpcResidual, &UnLaunch<NV>::single, &UnLaunch<NV>::parnmpcPhase,
+      &UnLaunch<NV>::lineSearchEval, &UnLaunch<NV>::rneaDerivatives};
+  return &impl;
+}
+const UnImpl* unImplFor(int nv) {
+  switch (nv) {
+    case 2: return unImpl<2>();
+    case 3: return unImpl<3>();
+    case 4: return unImpl<4>();
+    case 5: return unImpl<5>();
+    case 6: return unImpl<6>();
+    case 7: return unImpl<7>();
+    case 8: return unImpl<8>();
+    default: return nullptr;
+  }
 }
 
 }  // namespace
@@ -76,6 +123,8 @@ struct idocp_unocp {
   idocp_cost_t cost;
   idocp_constraints_t cons;
   int N, batch, device, nv;
+  const UnImpl* impl = nullptr;   // the kernels of the chain's length (model.nv)
+  UnDims L{};                     // ... and its record layout
   double T;
   hipStream_t stream = nullptr;
   UnBuffers B{};
@@ -93,8 +142,6 @@ struct idocp_unocp {
 
 namespace {
 
-using L7 = UnLayout<7>;
-
 int allocBuf(idocp_unocp* h, double** p, size_t n) {
   HIP_TRY(hipMalloc((void**)p, n * sizeof(double)));
   h->allocs.push_back(*p);
@@ -105,14 +152,15 @@ int allocBuf(idocp_unocp* h, double** p, size_t n) {
 
 struct FieldRef { int offset, dim, nstages_extra; };   // nstages = N + nstages_extra
 
-bool solField(const std::string& n, int nv, FieldRef& f) {
-  if (n == "lmd") f = {L7::S_LMD, nv, 1};
-  else if (n == "gmm") f = {L7::S_GMM, nv, 1};
-  else if (n == "q") f = {L7::S_Q, nv, 1};
-  else if (n == "v") f = {L7::S_V, nv, 1};
-  else if (n == "a") f = {L7::S_A, nv, 0};
-  else if (n == "u") f = {L7::S_U, nv, 0};
-  else if (n == "beta") f = {L7::S_BETA, nv, 0};
+bool solField(const std::string& n, const UnDims& L, FieldRef& f) {
+  const int nv = L.NV;
+  if (n == "lmd") f = {L.S_LMD, nv, 1};
+  else if (n == "gmm") f = {L.S_GMM, nv, 1};
+  else if (n == "q") f = {L.S_Q, nv, 1};
+  else if (n == "v") f = {L.S_V, nv, 1};
+  else if (n == "a") f = {L.S_A, nv, 0};
+  else if (n == "u") f = {L.S_U, nv, 0};
+  else if (n == "beta") f = {L.S_BETA, nv, 0};
   else return false;
   return true;
 }
@@ -218,8 +266,9 @@ static int createImpl(const idocp_model_t* model, const idocp_cost_t* cost, cons
   }
   if (model->has_floating_base) { set_last_error("robot has floating base: robot should have no constraints!"); return IDOCP_E_ARG; }
   if (model->ncontacts > 0) { set_last_error("robot can have contacts: robot should have no constraints!"); return IDOCP_E_ARG; }
-  if (!isRevoluteChain(*model, 7)) {
-    set_last_error("idocp_unocp_create: this build carries UnOCP kernels for a 7-dof revolute chain (iiwa14) only");
+  if (!isRevoluteChain(*model)) {
+    set_last_error(std::string(bwd ? "idocp_unparnmpc_create" : "idocp_unocp_create") + ": the fixed-base kernels take " + CHAIN_RANGE + " (this model: " +
+                   std::to_string(model->njoints) + " joints, nv = " + std::to_string(model->nv) + ")");
     return IDOCP_E_UNSUPPORTED;
   }
   if (cost->task_dim != 0) {
@@ -243,6 +292,7 @@ static int createImpl(const idocp_model_t* model, const idocp_cost_t* cost, cons
   idocp_unocp* h = new idocp_unocp();
   h->model = *model; h->cost = *cost; h->cons = *constraints;
   h->N = N; h->batch = batch; h->device = device; h->T = T; h->nv = model->nv; h->bwd = bwd;
+  h->impl = unImplFor(model->nv); h->L = h->impl->L;
   h->level_offset = bwd ? 1 + stage_offset : 0; h->shard = (stage_offset != 0 || !has_terminal || has_prev) ? 1 : 0;
   h->shard_dt = dt; h->shard_offset = stage_offset; h->shard_terminal = has_terminal; h->shard_prev = has_prev;
   int rc = IDOCP_OK;
@@ -254,19 +304,19 @@ static int createImpl(const idocp_model_t* model, const idocp_cost_t* cost, cons
   const size_t nrec1 = (size_t)batch * (N + 1), nrec0 = (size_t)batch * N;
   UnBuffers& B = h->B;
   double* tmp;
-  if ((rc = allocBuf(h, &B.sol, nrec1 * L7::SOL))) return fail(rc);
-  if ((rc = allocBuf(h, &B.dir, nrec1 * L7::SOL))) return fail(rc);
-  if ((rc = allocBuf(h, &B.slack, nrec0 * L7::CON))) return fail(rc);
-  if ((rc = allocBuf(h, &B.dual, nrec0 * L7::CON))) return fail(rc);
+  if ((rc = allocBuf(h, &B.sol, nrec1 * h->L.SOL))) return fail(rc);
+  if ((rc = allocBuf(h, &B.dir, nrec1 * h->L.SOL))) return fail(rc);
+  if ((rc = allocBuf(h, &B.slack, nrec0 * h->L.CON))) return fail(rc);
+  if ((rc = allocBuf(h, &B.dual, nrec0 * h->L.CON))) return fail(rc);
   B.slack_a = nullptr; B.dual_a = nullptr;
   if (constraints->joint_acceleration_lower_limit || constraints->joint_acceleration_upper_limit) {      // rows of components 6, 7
     if ((rc = allocBuf(h, &B.slack_a, nrec0 * 2 * model->nv))) return fail(rc);
     if ((rc = allocBuf(h, &B.dual_a, nrec0 * 2 * model->nv))) return fail(rc);
   }
-  if ((rc = allocBuf(h, &B.kkt, nrec0 * L7::KKT))) return fail(rc);
-  if ((rc = allocBuf(h, &B.dyn, nrec0 * L7::DYN))) return fail(rc);
-  if ((rc = allocBuf(h, &B.ric, nrec1 * L7::RIC))) return fail(rc);
-  if ((rc = allocBuf(h, &B.gain, nrec0 * L7::GAIN))) return fail(rc);
+  if ((rc = allocBuf(h, &B.kkt, nrec0 * h->L.KKT))) return fail(rc);
+  if ((rc = allocBuf(h, &B.dyn, nrec0 * h->L.DYN))) return fail(rc);
+  if ((rc = allocBuf(h, &B.ric, nrec1 * h->L.RIC))) return fail(rc);
+  if ((rc = allocBuf(h, &B.gain, nrec0 * h->L.GAIN))) return fail(rc);
   if ((rc = allocBuf(h, &B.step_stage, nrec0 * 2))) return fail(rc);
   if ((rc = allocBuf(h, &B.step, (size_t)batch * 2))) return fail(rc);
   if ((rc = allocBuf(h, &B.err_stage, nrec1))) return fail(rc);
@@ -281,17 +331,17 @@ static int createImpl(const idocp_model_t* model, const idocp_cost_t* cost, cons
   if ((rc = allocBuf(h, &B.ls_out, (size_t)batch * 2))) return fail(rc);
   h->filters.assign(batch, {});
   if (bwd) {
-    if ((rc = allocBuf(h, &B.kinv, nrec0 * L7::KINV))) return fail(rc);
-    if ((rc = allocBuf(h, &B.snew, nrec1 * L7::SOL))) return fail(rc);
-    if ((rc = allocBuf(h, &B.aux, nrec1 * L7::AUX))) return fail(rc);
-    if ((rc = allocBuf(h, &B.xres, nrec1 * L7::XRES))) return fail(rc);
-    if ((rc = allocBuf(h, &B.xprev, (size_t)batch * L7::NX))) return fail(rc);
+    if ((rc = allocBuf(h, &B.kinv, nrec0 * h->L.KINV))) return fail(rc);
+    if ((rc = allocBuf(h, &B.snew, nrec1 * h->L.SOL))) return fail(rc);
+    if ((rc = allocBuf(h, &B.aux, nrec1 * h->L.AUX))) return fail(rc);
+    if ((rc = allocBuf(h, &B.xres, nrec1 * h->L.XRES))) return fail(rc);
+    if ((rc = allocBuf(h, &B.xprev, (size_t)batch * h->L.NX))) return fail(rc);
   }
   if (cost->task_dim != 0) {
     if ((rc = allocBuf(h, &B.task_ref, (size_t)(N + 1) * 12))) return fail(rc);
-    if ((rc = allocBuf(h, &B.task_term, (size_t)batch * L7::TASK))) return fail(rc);
-    B.task = 1; B.task_stride = L7::TASK;
-    if (cost->task_extra_count > 0 && (rc = allocBuf(h, &B.task_xs, (size_t)batch * N * L7::TASK))) return fail(rc);      // stage terms of the further components
+    if ((rc = allocBuf(h, &B.task_term, (size_t)batch * h->L.TASK))) return fail(rc);
+    B.task = 1; B.task_stride = h->L.TASK;
+    if (cost->task_extra_count > 0 && (rc = allocBuf(h, &B.task_xs, (size_t)batch * N * h->L.TASK))) return fail(rc);      // stage terms of the further components
     std::vector<double> refs((size_t)(N + 1) * 12);
     for (int i = 0; i <= N; ++i) std::memcpy(&refs[12 * i], cost->task_ref, sizeof(double) * 12);
     if (hipMemcpyAsync(B.task_ref, refs.data(), refs.size() * sizeof(double), hipMemcpyHostToDevice, h->stream) != hipSuccess ||
@@ -317,8 +367,8 @@ static int createImpl(const idocp_model_t* model, const idocp_cost_t* cost, cons
   B.model = static_cast<const DevModel*>(d_model);
   B.prob = static_cast<const UnProblem*>(d_prob);
   // the reference constructor ends with initConstraints() (unocp_solver.cpp:47)
-  UnLaunch<7>::initConstraints(B, batch, N, h->stream);
-  if (bwd) UnLaunch<7>::parnmpcInitAux(B, batch, N, h->stream);
+  h->impl->initConstraints(B, batch, N, h->stream);
+  if (bwd) h->impl->parnmpcInitAux(B, batch, N, h->stream);
   if (hipStreamSynchronize(h->stream) != hipSuccess) { set_last_error("initConstraints launch failed"); return fail(IDOCP_E_DEVICE); }
   *out = h;
   return IDOCP_OK;
@@ -402,25 +452,27 @@ int idocp_unparnmpc_create_shard(const idocp_model_t* model, const idocp_cost_t*
 }
 // halo kinds as in idocp_parnmpc_halo_size: 0 state_last (q, v), 1 costate_first (lmd, gmm), 2 aux_first, 3 bwd_first (corrected
 // lmd, gmm), 4 fwd_last (corrected q, v)
-int idocp_unparnmpc_halo_size(int kind) {
+static int haloSize(int nx, int kind) {
   switch (kind) {
-    case 0: case 1: case 3: case 4: return L7::NX;
-    case 2: return L7::NX * L7::NX;
+    case 0: case 1: case 3: case 4: return nx;
+    case 2: return nx * nx;
     default: return 0;
   }
 }
+int idocp_unparnmpc_halo_size(int kind) { return haloSize(UnLayout<7>::NX, kind); }
+int idocp_unparnmpc_halo_size_of(const idocp_unocp_t* h, int kind) { return h ? haloSize(h->L.NX, kind) : 0; }
 int idocp_unparnmpc_export_halo(idocp_unocp_t* h, int kind, double* d_buf) {
   if (!h || !d_buf || kind < 0 || kind > 4) return IDOCP_E_ARG;
   if (wrongKind(h, 1)) return IDOCP_E_ARG;
   int rc = setDevice(h); if (rc) return rc;
-  const long rs = (long)(h->N + 1) * L7::SOL, last = (long)(h->N - 1) * L7::SOL;
-  const int nx = L7::NX;
+  const long rs = (long)(h->N + 1) * h->L.SOL, last = (long)(h->N - 1) * h->L.SOL;
+  const int nx = h->L.NX;
   switch (kind) {
-    case 0: stridedCopy(d_buf, nx, 0, h->B.sol, rs, last + L7::S_Q, nx, h->batch, h->stream); break;
-    case 1: stridedCopy(d_buf, nx, 0, h->B.sol, rs, L7::S_LMD, nx, h->batch, h->stream); break;
-    case 2: stridedCopy(d_buf, nx * nx, 0, h->B.aux, (long)(h->N + 1) * L7::AUX, 0, nx * nx, h->batch, h->stream); break;
-    case 3: stridedCopy(d_buf, nx, 0, h->B.snew, rs, L7::S_LMD, nx, h->batch, h->stream); break;
-    default: stridedCopy(d_buf, nx, 0, h->B.snew, rs, last + L7::S_Q, nx, h->batch, h->stream); break;
+    case 0: stridedCopy(d_buf, nx, 0, h->B.sol, rs, last + h->L.S_Q, nx, h->batch, h->stream); break;
+    case 1: stridedCopy(d_buf, nx, 0, h->B.sol, rs, h->L.S_LMD, nx, h->batch, h->stream); break;
+    case 2: stridedCopy(d_buf, nx * nx, 0, h->B.aux, (long)(h->N + 1) * h->L.AUX, 0, nx * nx, h->batch, h->stream); break;
+    case 3: stridedCopy(d_buf, nx, 0, h->B.snew, rs, h->L.S_LMD, nx, h->batch, h->stream); break;
+    default: stridedCopy(d_buf, nx, 0, h->B.snew, rs, last + h->L.S_Q, nx, h->batch, h->stream); break;
   }
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipStreamSynchronize(h->stream));
@@ -430,16 +482,16 @@ int idocp_unparnmpc_import_halo(idocp_unocp_t* h, int kind, const double* d_buf)
   if (!h || !d_buf || kind < 0 || kind > 4) return IDOCP_E_ARG;
   if (wrongKind(h, 1)) return IDOCP_E_ARG;
   int rc = setDevice(h); if (rc) return rc;
-  const long rs = (long)(h->N + 1) * L7::SOL, next = (long)h->N * L7::SOL;
-  const int nx = L7::NX, nv = h->nv;
+  const long rs = (long)(h->N + 1) * h->L.SOL, next = (long)h->N * h->L.SOL;
+  const int nx = h->L.NX, nv = h->nv;
   switch (kind) {
     case 0:   // the left neighbour's last state becomes this shard's "measured" state
       stridedCopy(h->d_q0, nv, 0, d_buf, nx, 0, nv, h->batch, h->stream);
       stridedCopy(h->d_v0, nv, 0, d_buf, nx, nv, nv, h->batch, h->stream);
       break;
-    case 1: stridedCopy(h->B.sol, rs, next + L7::S_LMD, d_buf, nx, 0, nx, h->batch, h->stream); break;
-    case 2: stridedCopy(h->B.aux, (long)(h->N + 1) * L7::AUX, (long)h->N * L7::AUX, d_buf, nx * nx, 0, nx * nx, h->batch, h->stream); break;
-    case 3: stridedCopy(h->B.snew, rs, next + L7::S_LMD, d_buf, nx, 0, nx, h->batch, h->stream); break;
+    case 1: stridedCopy(h->B.sol, rs, next + h->L.S_LMD, d_buf, nx, 0, nx, h->batch, h->stream); break;
+    case 2: stridedCopy(h->B.aux, (long)(h->N + 1) * h->L.AUX, (long)h->N * h->L.AUX, d_buf, nx * nx, 0, nx * nx, h->batch, h->stream); break;
+    case 3: stridedCopy(h->B.snew, rs, next + h->L.S_LMD, d_buf, nx, 0, nx, h->batch, h->stream); break;
     default: stridedCopy(h->B.xprev, nx, 0, d_buf, nx, 0, nx, h->batch, h->stream); break;
   }
   HIP_TRY(hipGetLastError());
@@ -462,7 +514,7 @@ int idocp_unparnmpc_kkt_error_squared_device(idocp_unocp_t* h, double t, double*
   if (wrongKind(h, 1)) return IDOCP_E_ARG;
   (void)t;
   int rc = setDevice(h); if (rc) return rc;
-  UnLaunch<7>::parnmpcResidual(h->B, h->batch, h->N, h->d_q0, h->d_v0, h->stream);
+  h->impl->parnmpcResidual(h->B, h->batch, h->N, h->d_q0, h->d_v0, h->stream);
   squareInto(d_err2, h->B.err, h->batch, h->stream);
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipStreamSynchronize(h->stream));
@@ -482,15 +534,15 @@ static int setSolutionImpl(idocp_unocp_t* h, const char* name, const double* val
   if (!h || !name || !values) return IDOCP_E_ARG;
   FieldRef f;
   const std::string n(name);
-  if (!(n == "q" || n == "v" || n == "a" || n == "u") || !solField(n, h->nv, f)) {
+  if (!(n == "q" || n == "v" || n == "a" || n == "u") || !solField(n, h->L, f)) {
     set_last_error("invalid arugment: name must be q, v, a, or u!");
     return IDOCP_E_ARG;
   }
   int rc = setDevice(h); if (rc) return rc;
   const size_t cnt = (size_t)(per_instance ? h->batch : 1) * f.dim;
   HIP_TRY(hipMemcpyAsync(h->d_tmp, values, cnt * sizeof(double), hipMemcpyHostToDevice, h->stream));
-  fillField(h->B.sol, L7::SOL, f.offset, f.dim, h->N + 1, h->batch, h->d_tmp, per_instance, h->stream);
-  if (init_constraints) UnLaunch<7>::initConstraints(h->B, h->batch, h->N, h->stream);
+  fillField(h->B.sol, h->L.SOL, f.offset, f.dim, h->N + 1, h->batch, h->d_tmp, per_instance, h->stream);
+  if (init_constraints) h->impl->initConstraints(h->B, h->batch, h->N, h->stream);
   HIP_TRY(hipStreamSynchronize(h->stream));
   return IDOCP_OK;
 }
@@ -516,7 +568,7 @@ int idocp_unocp_set_task_refs(idocp_unocp_t* h, const double* refs) {
 int idocp_unocp_init_constraints(idocp_unocp_t* h) {
   if (!h) return IDOCP_E_ARG;
   int rc = setDevice(h); if (rc) return rc;
-  UnLaunch<7>::initConstraints(h->B, h->batch, h->N, h->stream);
+  h->impl->initConstraints(h->B, h->batch, h->N, h->stream);
   HIP_TRY(hipStreamSynchronize(h->stream));
   return IDOCP_OK;
 }
@@ -527,7 +579,7 @@ int idocp_unocp_init_constraints(idocp_unocp_t* h) {
 // step of every instance.  d_q, d_v: the measured state of the update (device).
 static int lineSearchEval(idocp_unocp_t* h, const std::vector<double>& alpha, const double* d_q, const double* d_v, std::vector<double>& out) {
   HIP_TRY(hipMemcpyAsync(h->B.ls_alpha, alpha.data(), sizeof(double) * h->batch, hipMemcpyHostToDevice, h->stream));
-  UnLaunch<7>::lineSearchEval(h->B, h->batch, h->N, h->bwd != 0, d_q, d_v, h->stream);
+  h->impl->lineSearchEval(h->B, h->batch, h->N, h->bwd != 0, d_q, d_v, h->stream);
   HIP_TRY(hipGetLastError());
   out.resize((size_t)h->batch * 2);
   HIP_TRY(hipMemcpyAsync(out.data(), h->B.ls_out, sizeof(double) * out.size(), hipMemcpyDeviceToHost, h->stream));
@@ -587,10 +639,10 @@ int idocp_unocp_update_solution_device(idocp_unocp_t* h, double t, const double*
   (void)t;   // ConfigurationSpaceCost is time-invariant
   int rc = setDevice(h); if (rc) return rc;
   HIP_TRY(hipMemsetAsync(h->B.status, 0, sizeof(int) * h->batch, h->stream));
-  UnLaunch<7>::linearize(h->B, h->batch, h->N, h->stream);
-  UnLaunch<7>::riccati(h->B, h->batch, h->N, d_q, d_v, h->stream);
-  UnLaunch<7>::expand(h->B, h->batch, h->N, h->stream);
-  UnLaunch<7>::integrate(h->B, h->batch, h->N, h->stream);
+  h->impl->linearize(h->B, h->batch, h->N, h->stream);
+  h->impl->riccati(h->B, h->batch, h->N, d_q, d_v, h->stream);
+  h->impl->expand(h->B, h->batch, h->N, h->stream);
+  h->impl->integrate(h->B, h->batch, h->N, h->stream);
   HIP_TRY(hipGetLastError());
   h->has_direction = true;
   return IDOCP_OK;
@@ -627,13 +679,13 @@ int idocp_unocp_update_solution(idocp_unocp_t* h, double t, const double* q, con
   }
   // unocp_solver.cpp:116-120: the filter line search sits between the direction and the update
   HIP_TRY(hipMemsetAsync(h->B.status, 0, sizeof(int) * h->batch, h->stream));
-  UnLaunch<7>::linearize(h->B, h->batch, h->N, h->stream);
-  UnLaunch<7>::riccati(h->B, h->batch, h->N, h->d_q0, h->d_v0, h->stream);
-  UnLaunch<7>::expand(h->B, h->batch, h->N, h->stream);
+  h->impl->linearize(h->B, h->batch, h->N, h->stream);
+  h->impl->riccati(h->B, h->batch, h->N, h->d_q0, h->d_v0, h->stream);
+  h->impl->expand(h->B, h->batch, h->N, h->stream);
   HIP_TRY(hipGetLastError());
   if ((rc = statusOf(h))) return rc;
   if ((rc = runLineSearch(h, h->d_q0, h->d_v0))) return rc;
-  UnLaunch<7>::integrate(h->B, h->batch, h->N, h->stream);
+  h->impl->integrate(h->B, h->batch, h->N, h->stream);
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipStreamSynchronize(h->stream));
   h->has_direction = true;
@@ -662,7 +714,7 @@ int idocp_unocp_launch_linearize(idocp_unocp_t* h, double t, const double* d_q, 
   (void)t; (void)d_q; (void)d_v;
   if (wrongKind(h, 0)) return IDOCP_E_ARG;
   int rc = setDevice(h); if (rc) return rc;
-  UnLaunch<7>::linearize(h->B, h->batch, h->N, h->stream);
+  h->impl->linearize(h->B, h->batch, h->N, h->stream);
   HIP_TRY(hipGetLastError());
   return IDOCP_OK;
 }
@@ -670,7 +722,7 @@ int idocp_unocp_launch_riccati(idocp_unocp_t* h, const double* d_q, const double
   if (!h || !d_q || !d_v) return IDOCP_E_ARG;
   if (wrongKind(h, 0)) return IDOCP_E_ARG;
   int rc = setDevice(h); if (rc) return rc;
-  UnLaunch<7>::riccati(h->B, h->batch, h->N, d_q, d_v, h->stream);
+  h->impl->riccati(h->B, h->batch, h->N, d_q, d_v, h->stream);
   HIP_TRY(hipGetLastError());
   return IDOCP_OK;
 }
@@ -678,7 +730,7 @@ int idocp_unocp_launch_expand(idocp_unocp_t* h) {
   if (!h) return IDOCP_E_ARG;
   if (wrongKind(h, 0)) return IDOCP_E_ARG;
   int rc = setDevice(h); if (rc) return rc;
-  UnLaunch<7>::expand(h->B, h->batch, h->N, h->stream);
+  h->impl->expand(h->B, h->batch, h->N, h->stream);
   HIP_TRY(hipGetLastError());
   return IDOCP_OK;
 }
@@ -686,7 +738,7 @@ int idocp_unocp_launch_integrate(idocp_unocp_t* h) {
   if (!h) return IDOCP_E_ARG;
   if (wrongKind(h, 0)) return IDOCP_E_ARG;
   int rc = setDevice(h); if (rc) return rc;
-  UnLaunch<7>::integrate(h->B, h->batch, h->N, h->stream);
+  h->impl->integrate(h->B, h->batch, h->N, h->stream);
   HIP_TRY(hipGetLastError());
   return IDOCP_OK;
 }
@@ -695,7 +747,7 @@ int idocp_unocp_launch_kernel(idocp_unocp_t* h, int kernel_id, const double* d_q
   if (!h || kernel_id < 0 || kernel_id > 5 || !d_q || !d_v) return IDOCP_E_ARG;
   if (wrongKind(h, 0)) return IDOCP_E_ARG;
   int rc = setDevice(h); if (rc) return rc;
-  UnLaunch<7>::single(kernel_id, h->B, h->batch, h->N, d_q, d_v, h->stream);
+  h->impl->single(kernel_id, h->B, h->batch, h->N, d_q, d_v, h->stream);
   HIP_TRY(hipGetLastError());
   return IDOCP_OK;
 }
@@ -705,7 +757,7 @@ int idocp_unocp_compute_kkt_residual(idocp_unocp_t* h, double t, const double* q
   if (wrongKind(h, 0)) return IDOCP_E_ARG;
   (void)t;
   int rc = setDevice(h); if (rc) return rc;
-  UnLaunch<7>::residual(h->B, h->batch, h->N, h->stream);
+  h->impl->residual(h->B, h->batch, h->N, h->stream);
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipStreamSynchronize(h->stream));
   return IDOCP_OK;
@@ -724,7 +776,7 @@ int idocp_unparnmpc_init_backward_correction(idocp_unocp_t* h, double t) {      
   if (wrongKind(h, 1)) return IDOCP_E_ARG;
   (void)t;
   int rc = setDevice(h); if (rc) return rc;
-  UnLaunch<7>::parnmpcInitAux(h->B, h->batch, h->N, h->stream);
+  h->impl->parnmpcInitAux(h->B, h->batch, h->N, h->stream);
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipStreamSynchronize(h->stream));
   return IDOCP_OK;
@@ -733,7 +785,7 @@ int idocp_unparnmpc_launch_phase(idocp_unocp_t* h, int phase, const double* d_q,
   if (!h || phase < 0 || phase > 6 || !d_q || !d_v) return IDOCP_E_ARG;
   if (wrongKind(h, 1)) return IDOCP_E_ARG;
   int rc = setDevice(h); if (rc) return rc;
-  UnLaunch<7>::parnmpcPhase(phase, h->B, h->batch, h->N, d_q, d_v, h->stream);
+  h->impl->parnmpcPhase(phase, h->B, h->batch, h->N, d_q, d_v, h->stream);
   HIP_TRY(hipGetLastError());
   return IDOCP_OK;
 }
@@ -743,7 +795,7 @@ int idocp_unparnmpc_update_solution_device(idocp_unocp_t* h, double t, const dou
   (void)t;
   int rc = setDevice(h); if (rc) return rc;
   HIP_TRY(hipMemsetAsync(h->B.status, 0, sizeof(int) * h->batch, h->stream));
-  for (int phase = 0; phase <= 6; ++phase) UnLaunch<7>::parnmpcPhase(phase, h->B, h->batch, h->N, d_q, d_v, h->stream);
+  for (int phase = 0; phase <= 6; ++phase) h->impl->parnmpcPhase(phase, h->B, h->batch, h->N, d_q, d_v, h->stream);
   HIP_TRY(hipGetLastError());
   h->has_direction = true;
   return IDOCP_OK;
@@ -758,10 +810,10 @@ int idocp_unparnmpc_update_solution(idocp_unocp_t* h, double t, const double* q,
     if ((rc = idocp_unparnmpc_update_solution_device(h, t, h->d_q0, h->d_v0))) return rc;
   } else {                                           // unparnmpc_solver.cpp:81-86
     HIP_TRY(hipMemsetAsync(h->B.status, 0, sizeof(int) * h->batch, h->stream));
-    for (int phase = 0; phase <= 5; ++phase) UnLaunch<7>::parnmpcPhase(phase, h->B, h->batch, h->N, h->d_q0, h->d_v0, h->stream);
+    for (int phase = 0; phase <= 5; ++phase) h->impl->parnmpcPhase(phase, h->B, h->batch, h->N, h->d_q0, h->d_v0, h->stream);
     HIP_TRY(hipGetLastError());
     if ((rc = runLineSearch(h, h->d_q0, h->d_v0))) return rc;
-    UnLaunch<7>::parnmpcPhase(6, h->B, h->batch, h->N, h->d_q0, h->d_v0, h->stream);
+    h->impl->parnmpcPhase(6, h->B, h->batch, h->N, h->d_q0, h->d_v0, h->stream);
     HIP_TRY(hipGetLastError());
     h->has_direction = true;
   }
@@ -779,7 +831,7 @@ int idocp_unparnmpc_compute_kkt_residual(idocp_unocp_t* h, double t, const doubl
   int rc = setDevice(h); if (rc) return rc;
   HIP_TRY(hipMemcpyAsync(h->d_q0, q, sizeof(double) * h->batch * h->model.nq, hipMemcpyHostToDevice, h->stream));
   HIP_TRY(hipMemcpyAsync(h->d_v0, v, sizeof(double) * h->batch * h->model.nv, hipMemcpyHostToDevice, h->stream));
-  UnLaunch<7>::parnmpcResidual(h->B, h->batch, h->N, h->d_q0, h->d_v0, h->stream);
+  h->impl->parnmpcResidual(h->B, h->batch, h->N, h->d_q0, h->d_v0, h->stream);
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipStreamSynchronize(h->stream));
   return IDOCP_OK;
@@ -790,10 +842,10 @@ static int getRecords(idocp_unocp_t* h, const double* base, const char* name, in
   std::string n(name);
   if (direction) { if (n.size() < 2 || n[0] != 'd') return IDOCP_E_ARG; n = n.substr(1); }
   FieldRef f;
-  if (!solField(n, h->nv, f)) { set_last_error(std::string("unknown field name: ") + name); return IDOCP_E_ARG; }
+  if (!solField(n, h->L, f)) { set_last_error(std::string("unknown field name: ") + name); return IDOCP_E_ARG; }
   int rc = setDevice(h); if (rc) return rc;
   const size_t nst = h->N + f.nstages_extra;
-  return copyRecords(h, base + (size_t)instance * (h->N + 1) * L7::SOL, L7::SOL, nst, f.offset, f.dim, out);
+  return copyRecords(h, base + (size_t)instance * (h->N + 1) * h->L.SOL, h->L.SOL, nst, f.offset, f.dim, out);
 }
 int idocp_unocp_get_solution(idocp_unocp_t* h, const char* name, int instance, double* out) {
   return getRecords(h, h ? h->B.sol : nullptr, name, instance, out, false);
@@ -803,8 +855,7 @@ int idocp_unocp_get_solution(idocp_unocp_t* h, const char* name, int instance, d
 int idocp_unocp_get_split_solution(idocp_unocp_t* h, int instance, int stage, double* out) {
   if (!h || !out || instance < 0 || instance >= h->batch || stage < 0 || stage > h->N) return IDOCP_E_ARG;
   int rc = setDevice(h); if (rc) return rc;
-  static_assert(L7::S_LMD == 0 && L7::S_BETA == 6 * 7, "record order = output order");
-  HIP_TRY(hipMemcpyAsync(out, h->B.sol + ((size_t)instance * (h->N + 1) + stage) * L7::SOL, sizeof(double) * 7 * h->nv, hipMemcpyDeviceToHost, h->stream));
+  HIP_TRY(hipMemcpyAsync(out, h->B.sol + ((size_t)instance * (h->N + 1) + stage) * h->L.SOL, sizeof(double) * 7 * h->nv, hipMemcpyDeviceToHost, h->stream));
   HIP_TRY(hipStreamSynchronize(h->stream));
   return IDOCP_OK;
 }
@@ -830,26 +881,26 @@ int idocp_unocp_get_riccati(idocp_unocp_t* h, int instance, double* P, double* s
   if (!h || instance < 0 || instance >= h->batch) return IDOCP_E_ARG;
   int rc = setDevice(h); if (rc) return rc;
   const int nv = h->nv, nx = 2 * nv, N = h->N;
-  std::vector<double> ric((size_t)(N + 1) * L7::RIC), gain((size_t)N * L7::GAIN);
-  HIP_TRY(hipMemcpyAsync(ric.data(), h->B.ric + (size_t)instance * (N + 1) * L7::RIC, ric.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-  HIP_TRY(hipMemcpyAsync(gain.data(), h->B.gain + (size_t)instance * N * L7::GAIN, gain.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  std::vector<double> ric((size_t)(N + 1) * h->L.RIC), gain((size_t)N * h->L.GAIN);
+  HIP_TRY(hipMemcpyAsync(ric.data(), h->B.ric + (size_t)instance * (N + 1) * h->L.RIC, ric.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  HIP_TRY(hipMemcpyAsync(gain.data(), h->B.gain + (size_t)instance * N * h->L.GAIN, gain.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream));
   HIP_TRY(hipStreamSynchronize(h->stream));
   for (int i = 0; i <= N; ++i) {
-    const double* r = &ric[(size_t)i * L7::RIC];
+    const double* r = &ric[(size_t)i * h->L.RIC];
     if (P) {
       double* Pm = P + (size_t)i * nx * nx;
       for (int c = 0; c < nv; ++c) for (int rr = 0; rr < nv; ++rr) {
-        Pm[c * nx + rr] = r[L7::R_PQQ + L7::sym(rr, c)];           // Pqq (packed upper triangle)
-        Pm[(nv + c) * nx + rr] = r[L7::R_PQV + c * nv + rr];       // Pqv
-        Pm[c * nx + nv + rr] = r[L7::R_PQV + rr * nv + c];         // Pvq = Pqv^T
-        Pm[(nv + c) * nx + nv + rr] = r[L7::R_PVV + L7::sym(rr, c)];  // Pvv
+        Pm[c * nx + rr] = r[h->L.R_PQQ + h->L.sym(rr, c)];           // Pqq (packed upper triangle)
+        Pm[(nv + c) * nx + rr] = r[h->L.R_PQV + c * nv + rr];       // Pqv
+        Pm[c * nx + nv + rr] = r[h->L.R_PQV + rr * nv + c];         // Pvq = Pqv^T
+        Pm[(nv + c) * nx + nv + rr] = r[h->L.R_PVV + h->L.sym(rr, c)];  // Pvv
       }
     }
-    if (s) { std::memcpy(s + (size_t)i * nx, r + L7::R_SQ, sizeof(double) * nv); std::memcpy(s + (size_t)i * nx + nv, r + L7::R_SV, sizeof(double) * nv); }
+    if (s) { std::memcpy(s + (size_t)i * nx, r + h->L.R_SQ, sizeof(double) * nv); std::memcpy(s + (size_t)i * nx + nv, r + h->L.R_SV, sizeof(double) * nv); }
     if (i < N) {
-      const double* g = &gain[(size_t)i * L7::GAIN];
-      if (K) std::memcpy(K + (size_t)i * nv * nx, g + L7::G_K, sizeof(double) * nv * nx);
-      if (k) std::memcpy(k + (size_t)i * nv, g + L7::G_k, sizeof(double) * nv);
+      const double* g = &gain[(size_t)i * h->L.GAIN];
+      if (K) std::memcpy(K + (size_t)i * nv * nx, g + h->L.G_K, sizeof(double) * nv * nx);
+      if (k) std::memcpy(k + (size_t)i * nv, g + h->L.G_k, sizeof(double) * nv);
     }
   }
   return IDOCP_OK;
@@ -864,12 +915,12 @@ int idocp_unocp_get_torque_feedback_gain(idocp_unocp_t* h, int instance, int sta
   if (h->bwd || !h->B.gain) { set_last_error("idocp_unocp_get_torque_feedback_gain: the LQR policy belongs to UnOCPSolver (UnParNMPCSolver keeps none)"); return IDOCP_E_UNSUPPORTED; }
   int rc = setDevice(h); if (rc) return rc;
   const int nv = h->nv;
-  std::vector<double> dyn(L7::DYN), gain(L7::GAIN);
+  std::vector<double> dyn(h->L.DYN), gain(h->L.GAIN);
   const size_t rec = (size_t)instance * h->N + stage;
-  HIP_TRY(hipMemcpyAsync(dyn.data(), h->B.dyn + rec * L7::DYN, dyn.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-  HIP_TRY(hipMemcpyAsync(gain.data(), h->B.gain + rec * L7::GAIN, gain.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  HIP_TRY(hipMemcpyAsync(dyn.data(), h->B.dyn + rec * h->L.DYN, dyn.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  HIP_TRY(hipMemcpyAsync(gain.data(), h->B.gain + rec * h->L.GAIN, gain.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream));
   HIP_TRY(hipStreamSynchronize(h->stream));
-  const double *dq = &dyn[L7::D_DQ], *dv = &dyn[L7::D_DV], *M = &dyn[L7::D_DA], *Ka = &gain[L7::G_K];
+  const double *dq = &dyn[h->L.D_DQ], *dv = &dyn[h->L.D_DV], *M = &dyn[h->L.D_DA], *Ka = &gain[h->L.G_K];
   for (int c = 0; c < nv; ++c) for (int r = 0; r < nv; ++r) {
     double aq = dq[c * nv + r], av = dv[c * nv + r];
     for (int m = 0; m < nv; ++m) { aq += M[m * nv + r] * Ka[c * nv + m]; av += M[m * nv + r] * Ka[(nv + c) * nv + m]; }
@@ -884,20 +935,20 @@ int idocp_unocp_is_current_solution_feasible(idocp_unocp_t* h, int* feasible, in
   if (!h || !feasible) return IDOCP_E_ARG;
   int rc = setDevice(h); if (rc) return rc;
   const int nv = h->nv, N = h->N;
-  std::vector<double> sol((size_t)h->batch * (N + 1) * L7::SOL);
+  std::vector<double> sol((size_t)h->batch * (N + 1) * h->L.SOL);
   HIP_TRY(hipMemcpyAsync(sol.data(), h->B.sol, sol.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream));
   HIP_TRY(hipStreamSynchronize(h->stream));
   const idocp_model_t& m = h->model;
   for (int b = 0; b < h->batch; ++b) {
     int bad = -1;
     for (int i = 0; i < N && bad < 0; ++i) {
-      const double* s = &sol[((size_t)b * (N + 1) + i) * L7::SOL];
+      const double* s = &sol[((size_t)b * (N + 1) + i) * h->L.SOL];
       for (int r = 0; r < nv && bad < 0; ++r) {
-        if (h->cons.joint_position_limits && i + h->level_offset >= 2 && (s[L7::S_Q + r] < m.q_min[r] || s[L7::S_Q + r] > m.q_max[r])) bad = i;
-        if (h->cons.joint_velocity_limits && i + h->level_offset >= 1 && (s[L7::S_V + r] < -m.v_max[r] || s[L7::S_V + r] > m.v_max[r])) bad = i;
-        if (h->cons.joint_torque_limits && (s[L7::S_U + r] < -m.u_max[r] || s[L7::S_U + r] > m.u_max[r])) bad = i;
-        if (h->cons.joint_acceleration_lower_limit && s[L7::S_A + r] < h->cons.a_min[r]) bad = i;      // joint_acceleration_lower_limit.cpp:38-47
-        if (h->cons.joint_acceleration_upper_limit && s[L7::S_A + r] > h->cons.a_max[r]) bad = i;
+        if (h->cons.joint_position_limits && i + h->level_offset >= 2 && (s[h->L.S_Q + r] < m.q_min[r] || s[h->L.S_Q + r] > m.q_max[r])) bad = i;
+        if (h->cons.joint_velocity_limits && i + h->level_offset >= 1 && (s[h->L.S_V + r] < -m.v_max[r] || s[h->L.S_V + r] > m.v_max[r])) bad = i;
+        if (h->cons.joint_torque_limits && (s[h->L.S_U + r] < -m.u_max[r] || s[h->L.S_U + r] > m.u_max[r])) bad = i;
+        if (h->cons.joint_acceleration_lower_limit && s[h->L.S_A + r] < h->cons.a_min[r]) bad = i;      // joint_acceleration_lower_limit.cpp:38-47
+        if (h->cons.joint_acceleration_upper_limit && s[h->L.S_A + r] > h->cons.a_max[r]) bad = i;
       }
     }
     feasible[b] = bad < 0 ? 1 : 0;
@@ -918,9 +969,9 @@ int idocp_unocp_get_constraint_data(idocp_unocp_t* h, int instance, double* slac
   if (!h || instance < 0 || instance >= h->batch) return IDOCP_E_ARG;
   int rc = setDevice(h); if (rc) return rc;
   const int nv = h->nv, N = h->N, dimc = idocp_unocp_dimc(h);
-  std::vector<double> sl((size_t)N * L7::CON), du((size_t)N * L7::CON);
-  HIP_TRY(hipMemcpyAsync(sl.data(), h->B.slack + (size_t)instance * N * L7::CON, sl.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-  HIP_TRY(hipMemcpyAsync(du.data(), h->B.dual + (size_t)instance * N * L7::CON, du.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  std::vector<double> sl((size_t)N * h->L.CON), du((size_t)N * h->L.CON);
+  HIP_TRY(hipMemcpyAsync(sl.data(), h->B.slack + (size_t)instance * N * h->L.CON, sl.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  HIP_TRY(hipMemcpyAsync(du.data(), h->B.dual + (size_t)instance * N * h->L.CON, du.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream));
   HIP_TRY(hipStreamSynchronize(h->stream));
   std::vector<double> sa, da;
   if (h->B.slack_a) {
@@ -937,8 +988,8 @@ int idocp_unocp_get_constraint_data(idocp_unocp_t* h, int instance, double* slac
       if (!use[c]) continue;
       const bool valid = (c < 2) ? i + h->level_offset >= 2 : ((c < 4) ? i + h->level_offset >= 1 : true);
       for (int r = 0; r < nv; ++r) {
-        const double sv = c < 6 ? sl[(size_t)i * L7::CON + c * nv + r] : sa[(size_t)i * 2 * nv + (c - 6) * nv + r];
-        const double dv = c < 6 ? du[(size_t)i * L7::CON + c * nv + r] : da[(size_t)i * 2 * nv + (c - 6) * nv + r];
+        const double sv = c < 6 ? sl[(size_t)i * h->L.CON + c * nv + r] : sa[(size_t)i * 2 * nv + (c - 6) * nv + r];
+        const double dv = c < 6 ? du[(size_t)i * h->L.CON + c * nv + r] : da[(size_t)i * 2 * nv + (c - 6) * nv + r];
         if (slack) slack[(size_t)i * dimc + off + r] = valid ? sv : 0.0;
         if (dual) dual[(size_t)i * dimc + off + r] = valid ? dv : 0.0;
       }
@@ -951,7 +1002,7 @@ int idocp_unocp_get_constraint_data(idocp_unocp_t* h, int instance, double* slac
 int idocp_rnea_derivatives(const idocp_model_t* model, int n, const double* q, const double* v, const double* a,
                            double* tau, double* dtau_dq, double* dtau_dv, double* dtau_da, int device) {
   if (!model || n <= 0 || !q || !v || !a || !tau || !dtau_dq || !dtau_dv || !dtau_da) return IDOCP_E_ARG;
-  if (!isRevoluteChain(*model, 7)) { set_last_error("idocp_rnea_derivatives: 7-dof revolute chain only in this build"); return IDOCP_E_UNSUPPORTED; }
+  if (!isRevoluteChain(*model)) { set_last_error(std::string("idocp_rnea_derivatives: the model must be ") + CHAIN_RANGE); return IDOCP_E_UNSUPPORTED; }
   int ndev = 0;
   if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) { set_last_error("no HIP device available"); return IDOCP_E_DEVICE; }
   HIP_TRY(hipSetDevice(device));
@@ -970,7 +1021,7 @@ int idocp_rnea_derivatives(const idocp_model_t* model, int n, const double* q, c
   HIP_TRY(hipMemcpy(d_a, a, sizeof(double) * n * nv, hipMemcpyHostToDevice));
   bool zaxes = !std::getenv("IDOCP_GENERAL_AXES");      // (the same choice of the sweep's instantiation as the solvers make)
   for (int i = 0; i < model->njoints; ++i) if (!(model->axis[i][0] == 0.0 && model->axis[i][1] == 0.0 && model->axis[i][2] == 1.0)) zaxes = false;
-  UnLaunch<7>::rneaDerivatives(d_m, n, d_q, d_v, d_a, d_tau, d_dq, d_dv, d_da, zaxes, nullptr);
+  unImplFor(nv)->rneaDerivatives(d_m, n, d_q, d_v, d_a, d_tau, d_dq, d_dv, d_da, zaxes, nullptr);
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipDeviceSynchronize());
   HIP_TRY(hipMemcpy(tau, d_tau, sizeof(double) * n * nv, hipMemcpyDeviceToHost));

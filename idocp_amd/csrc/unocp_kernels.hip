@@ -92,13 +92,18 @@ __device__ unsigned long long g_k1_prof[16];
 #ifndef K1_WAVES
 #define K1_WAVES 2
 #endif
+// rounds of phase B per wavefront: K1_ROUNDS, but two for an eight-joint chain with a task-space cost (with three its rows and motion
+// subspaces of the rounds to come spilled 108 bytes per lane)
+__host__ __device__ constexpr int k1Rounds(int nv, bool task) { return nv == 8 && task ? 2 : K1_ROUNDS; }
+// stages per wavefront of un_linearize_kernel
+__host__ __device__ constexpr int k1Stages(int nv, bool task) { return (64 / (3 * nv)) * k1Rounds(nv, task); }
 template <int NV, int MODE, bool BWD = false, bool TASK = false, bool ZAX = false>
 __global__ __launch_bounds__(64, K1_WAVES) void un_linearize_kernel(UnBuffers B, const double* __restrict__ q0 = nullptr,
                                                           const double* __restrict__ v0 = nullptr) {
   using L = UnLayout<NV>;
   constexpr int LPS = 3 * NV;        // lanes per stage (phase B and the rest of the kernel)
   constexpr int SPW = 64 / LPS;      // stages per round
-  constexpr int ROUNDS = K1_ROUNDS;
+  constexpr int ROUNDS = k1Rounds(NV, TASK);
   constexpr int SPA = SPW * ROUNDS;  // stages per wavefront: phase A of the analytic recursion has a lane per (stage, joint)
   static_assert(SPA * NV <= 64, "whole rounds");
   constexpr int BLK = RneaBlock::LEN;
@@ -1085,15 +1090,17 @@ __global__ void un_fill_field_kernel(double* __restrict__ sol, int stride, int o
 
 // Stand-alone inverse dynamics + derivatives for n samples (parity tests of the rigid-body layer against the reference's golden
 // vectors): the two-phase analytic recursion exactly as K1 runs it -- phase A with a lane per (sample, joint), nine samples per
-// wavefront, then the rows of three samples at a time (dev_rnea_analytic.hpp).
+// wavefront, then the rows of three samples at a time (dev_rnea_analytic.hpp).  Where the samples of phase A do not divide into
+// whole rounds of phase B (six joints: ten samples, three per round) the last round is partial: its groups past the wavefront's
+// samples publish nothing and store nothing.
 template <int NV, bool ZAX>
 __global__ __launch_bounds__(64, 2) void rnea_derivatives_kernel(const DevModel* __restrict__ model, int n,
                                                                 const double* __restrict__ q, const double* __restrict__ v,
                                                                 const double* __restrict__ a, double* __restrict__ tau,
                                                                 double* __restrict__ dq, double* __restrict__ dv,
                                                                 double* __restrict__ da) {
-  constexpr int LPS = 3 * NV, SPW = 64 / LPS, SPA = 64 / NV, ROUNDS = SPA / SPW, BLK = RneaBlock::LEN;
-  static_assert(SPA == SPW * ROUNDS, "whole rounds");
+  constexpr int LPS = 3 * NV, SPW = 64 / LPS, SPA = 64 / NV, ROUNDS = (SPA + SPW - 1) / SPW, BLK = RneaBlock::LEN;
+  constexpr bool WHOLE = SPA % SPW == 0;      // (seven joints: three whole rounds)
   __shared__ ChainConsts<NV> s_model;
   __shared__ double s_cs[SPA][NV][2], s_v[SPA][NV], s_a[SPA][NV];
   __shared__ double s_pub[SPW][NV][BLK];
@@ -1132,7 +1139,7 @@ __global__ __launch_bounds__(64, 2) void rnea_derivatives_kernel(const DevModel*
     double row[NV];
     rneaDerivPhaseB<NV>(&s_pub[g][0][0], BLK, kind, k, row);
     const long smp = smp0 + rho * SPW + g;
-    if (g0 < SPW && smp < n) {
+    if (g0 < SPW && smp < n && (WHOLE || rho * SPW + g < SPA)) {
 #pragma unroll
       for (int c = 0; c < NV; ++c) out[smp * NV * NV + c * NV + k] = row[c];      // element (k, c) of the column-major matrix
     }
@@ -1211,7 +1218,14 @@ __global__ __launch_bounds__(64 * K9U_SPB) void unparnmpc_coarse_update_kernel(U
   if (lane < NK) sres[lane] = kk[L::K_FQ + lane];                     // [Fq Fv la lq lv] are contiguous in the kkt record
   __syncthreads();
   K9_T(0);
-  if (w == 0) spdInverseRowsGrouped<NQ, SPB>(&sQa[0][0], NQ * NQ, lane, s_ok);
+  // (Q^-1 of the SPB stages on wavefront 0 as long as their NQ-lane groups fit in it -- up to seven joints; beyond, the stages it has no room for
+  // go to wavefront 1)
+  constexpr int GQ = 64 / NQ < SPB ? 64 / NQ : SPB;
+  static_assert(GQ == SPB || (SPB > 1 && SPB - GQ <= GQ), "the coarse update's Q^-1 fits in two wavefronts");
+  if (w == 0) spdInverseRowsGrouped<NQ, GQ>(&sQa[0][0], NQ * NQ, lane, s_ok);
+  if constexpr (GQ < SPB) {
+    if (w == 1) spdInverseRowsGrouped<NQ, SPB - GQ>(&sQa[GQ][0], NQ * NQ, lane, s_ok + GQ);
+  }
   __syncthreads();
   K9_T(1);
   for (int e = lane; e < NX * NQ; e += 64) {
@@ -1684,7 +1698,7 @@ __global__ void un_square_kernel(double* __restrict__ out, const double* __restr
 // ------------------------------------------------------------ launchers ----
 template <int NV>
 void UnLaunch<NV>::linearize(const UnBuffers& B, long batch, int N, hipStream_t st) {
-    constexpr int SPA = (64 / (3 * NV)) * K1_ROUNDS;       // stages per wavefront of un_linearize_kernel
+    const int SPA = k1Stages(NV, B.task != 0);       // stages per wavefront of un_linearize_kernel
     const long units = batch * N;
     const dim3 grid((unsigned)((units + SPA - 1) / SPA));
     const double* none = nullptr;
@@ -1699,7 +1713,7 @@ void UnLaunch<NV>::linearize(const UnBuffers& B, long batch, int N, hipStream_t 
   }
 template <int NV>
 void UnLaunch<NV>::residual(const UnBuffers& B, long batch, int N, hipStream_t st) {
-    constexpr int SPA = (64 / (3 * NV)) * K1_ROUNDS;       // stages per wavefront of un_linearize_kernel
+    const int SPA = k1Stages(NV, B.task != 0);       // stages per wavefront of un_linearize_kernel
     const long units = batch * N;
     const dim3 grid((unsigned)((units + SPA - 1) / SPA));
     const double* none = nullptr;
@@ -1771,8 +1785,8 @@ void UnLaunch<NV>::parnmpcPhase(int phase, const UnBuffers& B, long batch, int N
   const unsigned inst_blocks = (unsigned)((batch + 3) / 4);
   switch (phase) {
     case 0:
-      if (B.zaxes) hipLaunchKernelGGL((un_linearize_kernel<NV, 0, true, false, true>), dim3((unsigned)((batch * N + (64 / (3 * NV)) * K1_ROUNDS - 1) / ((64 / (3 * NV)) * K1_ROUNDS))), dim3(64), 0, st, B, q0, v0);
-      else hipLaunchKernelGGL((un_linearize_kernel<NV, 0, true>), dim3((unsigned)((batch * N + (64 / (3 * NV)) * K1_ROUNDS - 1) / ((64 / (3 * NV)) * K1_ROUNDS))), dim3(64), 0, st, B, q0, v0);
+      if (B.zaxes) hipLaunchKernelGGL((un_linearize_kernel<NV, 0, true, false, true>), dim3((unsigned)((batch * N + k1Stages(NV, false) - 1) / k1Stages(NV, false))), dim3(64), 0, st, B, q0, v0);
+      else hipLaunchKernelGGL((un_linearize_kernel<NV, 0, true>), dim3((unsigned)((batch * N + k1Stages(NV, false) - 1) / k1Stages(NV, false))), dim3(64), 0, st, B, q0, v0);
       break;
     case 1: hipLaunchKernelGGL((unparnmpc_coarse_update_kernel<NV>), dim3((unsigned)((batch * N + K9U_SPB - 1) / K9U_SPB)), dim3(64 * K9U_SPB), 0, st, B); break;
     case 2: hipLaunchKernelGGL((unparnmpc_backward_serial_kernel<NV>), dim3(inst_blocks), dim3(64), 0, st, B); break;
@@ -1787,8 +1801,8 @@ void UnLaunch<NV>::parnmpcPhase(int phase, const UnBuffers& B, long batch, int N
 }
 template <int NV>
 void UnLaunch<NV>::parnmpcResidual(const UnBuffers& B, long batch, int N, const double* q0, const double* v0, hipStream_t st) {
-  if (B.zaxes) hipLaunchKernelGGL((un_linearize_kernel<NV, 1, true, false, true>), dim3((unsigned)((batch * N + (64 / (3 * NV)) * K1_ROUNDS - 1) / ((64 / (3 * NV)) * K1_ROUNDS))), dim3(64), 0, st, B, q0, v0);
-  else hipLaunchKernelGGL((un_linearize_kernel<NV, 1, true>), dim3((unsigned)((batch * N + (64 / (3 * NV)) * K1_ROUNDS - 1) / ((64 / (3 * NV)) * K1_ROUNDS))), dim3(64), 0, st, B, q0, v0);
+  if (B.zaxes) hipLaunchKernelGGL((un_linearize_kernel<NV, 1, true, false, true>), dim3((unsigned)((batch * N + k1Stages(NV, false) - 1) / k1Stages(NV, false))), dim3(64), 0, st, B, q0, v0);
+  else hipLaunchKernelGGL((un_linearize_kernel<NV, 1, true>), dim3((unsigned)((batch * N + k1Stages(NV, false) - 1) / k1Stages(NV, false))), dim3(64), 0, st, B, q0, v0);
   hipLaunchKernelGGL((un_kkt_error_kernel<NV>), dim3((unsigned)batch), dim3(64), 0, st, B);
 }
 template <int NV>
@@ -1816,7 +1830,15 @@ void squareInto(double* out, const double* err, long batch, hipStream_t st) {
   hipLaunchKernelGGL(un_square_kernel, dim3((unsigned)((batch + 255) / 256)), dim3(256), 0, st, out, err, batch);
 }
 
+// the fixed-base chains the C ABI accepts: 2 .. 8 revolute joints (NX = 2 NV <= 16: one row of 16 lanes per state in the sweeps and the
+// Riccati kernels)
+template struct UnLaunch<2>;
+template struct UnLaunch<3>;
+template struct UnLaunch<4>;
+template struct UnLaunch<5>;
+template struct UnLaunch<6>;
 template struct UnLaunch<7>;
+template struct UnLaunch<8>;
 
 void fillField(double* sol, int stride, int offset, int dim, long nrec_per_inst, long batch, const double* value,
                int per_instance, hipStream_t st) {

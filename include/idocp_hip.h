@@ -228,7 +228,11 @@ typedef struct idocp_unocp idocp_unocp_t;
 
 /* UnOCPSolver::UnOCPSolver(robot, cost, constraints, T, N, nthreads)
  * (src/unocp/unocp_solver.cpp:11-48).  nthreads has no meaning on the GPU; it
- * is replaced by `batch` independent instances and a device ordinal. */
+ * is replaced by `batch` independent instances and a device ordinal.
+ * The robot is a fixed-base serial chain of 2 .. 8 revolute joints (joint i the
+ * child of joint i - 1, any axes); another model returns IDOCP_E_UNSUPPORTED and
+ * idocp_last_error() names that range.  The same holds for idocp_unparnmpc_create,
+ * idocp_unparnmpc_create_shard and idocp_rnea_derivatives. */
 int idocp_unocp_create(const idocp_model_t* model, const idocp_cost_t* cost,
                        const idocp_constraints_t* constraints, double T, int N,
                        int batch, int device, idocp_unocp_t** out);
@@ -372,7 +376,8 @@ int idocp_unparnmpc_get_new_solution(idocp_unocp_t* h, const char* name, int ins
 int idocp_unparnmpc_create_shard(const idocp_model_t* model, const idocp_cost_t* cost,
                                  const idocp_constraints_t* constraints, double T, int N, int stage_begin,
                                  int stage_end, int batch, int device, idocp_unocp_t** out);
-int idocp_unparnmpc_halo_size(int kind);
+int idocp_unparnmpc_halo_size(int kind);      /* sizes of a 7-joint chain (iiwa14) */
+int idocp_unparnmpc_halo_size_of(const idocp_unocp_t* h, int kind);      /* sizes of the handle's chain: 2 nv, or (2 nv)^2 for kind 2 */
 int idocp_unparnmpc_export_halo(idocp_unocp_t* h, int kind, double* d_buf);
 int idocp_unparnmpc_import_halo(idocp_unocp_t* h, int kind, const double* d_buf);
 /* device buffers of the previous state (rank 0: the measured state) and of the (primal, dual) step sizes [batch][2] */
@@ -396,7 +401,8 @@ int idocp_unocp_launch_kernel(idocp_unocp_t* h, int kernel_id, const double* d_q
                               const double* d_v);
 /* Inverse dynamics + its derivatives for `n` independent samples on the device
  * (Robot::RNEA / RNEADerivatives, include/idocp/robot/robot.hxx:444-500).
- * q[n][nq], v[n][nv], a[n][nv] host; tau[n][nv]; dq/dv/da[n][nv*nv] col-major. */
+ * q[n][nq], v[n][nv], a[n][nv] host; tau[n][nv]; dq/dv/da[n][nv*nv] col-major.
+ * model: a fixed-base serial chain of 2 .. 8 revolute joints. */
 int idocp_rnea_derivatives(const idocp_model_t* model, int n, const double* q,
                            const double* v, const double* a, double* tau,
                            double* dtau_dq, double* dtau_dv, double* dtau_da,

@@ -1,0 +1,67 @@
+"""Fixed-base revolute arms of 2 .. 8 joints for the tests of the fixed-base solvers on chains other than iiwa14: random chains
+written as URDF (random unit axes, joint placements, masses, centres of mass and inertias) and the committed six-joint arm."""
+import os
+
+import numpy as np
+
+from idocp_amd import capi
+from idocp_amd.workloads import GOLDEN
+
+ARM6_URDF = os.path.join(GOLDEN, "urdf", "arm6.urdf")
+
+
+def _f(x):
+    return " ".join(repr(float(e)) for e in x)
+
+
+def random_arm_urdf(nv, seed, zaxes=False):
+    """URDF text of a serial chain of `nv` revolute joints; zaxes: every joint axis is +z (the placements stay random)."""
+    rng = np.random.default_rng(seed)
+    out = ['<?xml version="1.0" ?>', '<robot name="arm%d_%d">' % (nv, seed), '  <link name="world"/>',
+           '  <joint name="base_joint" type="fixed"><origin rpy="0 0 0" xyz="0 0 0"/><parent link="world"/><child link="link_0"/></joint>',
+           '  <link name="link_0"/>']
+    for i in range(1, nv + 1):
+        axis = np.array([0.0, 0.0, 1.0]) if zaxes else rng.normal(size=3)
+        axis /= np.linalg.norm(axis)
+        xyz = rng.uniform(-0.15, 0.15, 3) + np.array([0.0, 0.0, 0.2])
+        rpy = rng.uniform(-np.pi, np.pi, 3)
+        mass = rng.uniform(0.5, 4.0)
+        com = rng.uniform(-0.06, 0.06, 3)
+        p = rng.uniform(0.005, 0.05, 3)             # ixx = y + z etc.: the triangle inequality holds
+        d = np.array([p[1] + p[2], p[0] + p[2], p[0] + p[1]])
+        off = 0.1 * d.min() * rng.uniform(-1, 1, 3)
+        out.append('  <joint name="joint_%d" type="revolute"><origin rpy="%s" xyz="%s"/><parent link="link_%d"/><child link="link_%d"/>'
+                   '<axis xyz="%s"/><limit lower="-3.0" upper="3.0" effort="200" velocity="10"/></joint>' % (i, _f(rpy), _f(xyz), i - 1, i, _f(axis)))
+        out.append('  <link name="link_%d"><inertial><origin rpy="0 0 0" xyz="%s"/><mass value="%r"/>'
+                   '<inertia ixx="%r" ixy="%r" ixz="%r" iyy="%r" iyz="%r" izz="%r"/></inertial></link>'
+                   % (i, _f(com), float(mass), d[0], off[0], off[1], d[1], off[2], d[2]))
+    out.append('</robot>')
+    return "\n".join(out) + "\n"
+
+
+def random_arm(nv, seed, tmp_dir, zaxes=False):
+    path = os.path.join(str(tmp_dir), "arm%d_%d%s.urdf" % (nv, seed, "_z" if zaxes else ""))
+    with open(path, "w") as f:
+        f.write(random_arm_urdf(nv, seed, zaxes))
+    return capi.model_from_urdf(path)
+
+
+def arm6_model():
+    return capi.model_from_urdf(ARM6_URDF)
+
+
+def task_cost(cost, model, dim, weight=100.0, joint=None):
+    """a TaskSpace3DCost / TaskSpace6DCost on a tool frame 0.1 m along z of `joint` (default: the last), constant reference"""
+    cost.task_dim = dim
+    cost.task_joint = model.njoints - 1 if joint is None else joint
+    R = [0.0, 0.0, 1.0, 0.0, 1.0, 0.0, -1.0, 0.0, 0.0]
+    for k in range(9):
+        cost.task_frame_R[k] = float(k % 4 == 0)
+        cost.task_ref[k] = R[k]
+    cost.task_frame_p[0], cost.task_frame_p[1], cost.task_frame_p[2] = 0.0, 0.0, 0.1
+    for k, x in enumerate((0.3, 0.1, 0.5)):
+        cost.task_ref[9 + k] = x
+    for k in range(6):
+        cost.task_weight[k] = weight
+        cost.task_weightf[k] = weight
+    return cost
