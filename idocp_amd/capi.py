@@ -98,6 +98,16 @@ class Constraints(C.Structure):
     ]
 
 
+class RbdIO(C.Structure):
+    """idocp_rbd_io_t: inputs and requested outputs of idocp_rbd_contact_dynamics_batch(_device); a pointer left at None is NULL"""
+    INPUTS = ("q", "v", "a", "f", "contact_points")
+    OUTPUTS = ("tau", "dtau_dq", "dtau_dv", "dtau_da", "C", "dCdq", "dCdv", "dCda", "MJtJinv")
+    _fields_ = [(name, C.c_void_p) for name in INPUTS + OUTPUTS]
+
+
+RBD_STAGE, RBD_IMPULSE = 0, 1
+
+
 class LibraryMissing(RuntimeError):
     pass
 
@@ -155,6 +165,7 @@ def _proto(lib):
         ("idocp_device_alloc", [P(vp), C.c_ulonglong]),
         ("idocp_device_free", [vp]),
         ("idocp_device_upload", [vp, vp, C.c_ulonglong]),
+        ("idocp_device_download", [vp, vp, C.c_ulonglong]),
         ("idocp_device_count", [P(ci)]),
         ("idocp_unocp_compute_kkt_residual", [vp, cd, c_double_p, c_double_p]),
         ("idocp_unocp_kkt_error", [vp, c_double_p]),
@@ -260,6 +271,18 @@ def _proto(lib):
     lib.idocp_ocp_stream.restype = vp
     lib.idocp_comm_destroy.argtypes = [vp]
     lib.idocp_comm_destroy.restype = None
+    lib.idocp_rbd_create.argtypes = [P(Model), ci, P(vp)]
+    lib.idocp_rbd_create.restype = ci
+    lib.idocp_rbd_destroy.argtypes = [vp]
+    lib.idocp_rbd_destroy.restype = None
+    lib.idocp_rbd_synchronize.argtypes = [vp]
+    lib.idocp_rbd_synchronize.restype = ci
+    lib.idocp_rbd_stream.argtypes = [vp]
+    lib.idocp_rbd_stream.restype = vp
+    lib.idocp_rbd_contact_dynamics_batch.argtypes = [vp, ci, ci, c_int_p, cd, P(RbdIO)]
+    lib.idocp_rbd_contact_dynamics_batch.restype = ci
+    lib.idocp_rbd_contact_dynamics_batch_device.argtypes = [vp, ci, ci, c_int_p, cd, P(RbdIO)]
+    lib.idocp_rbd_contact_dynamics_batch_device.restype = ci
     for name, args in [
         ("idocp_ocp_set_contact_status_uniformly", [vp, P(ci), c_double_p]),
         ("idocp_ocp_set_solution", [vp, cs, c_double_p]),

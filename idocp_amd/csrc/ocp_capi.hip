@@ -18,10 +18,12 @@
 #include "dev_lie.hpp"
 #include "host_util.hpp"
 #include "idocp_hip.h"
+#include "model_shapes.hpp"
 #include "ocp_launch.hpp"
 
 using namespace idocp_dev;
 using idocp_host::set_last_error;
+using idocp_host::isQuadruped;
 
 #define HIP_TRY(expr)                                                                         \
   do {                                                                                        \
@@ -37,42 +39,6 @@ namespace {
 
 using DQ = LeggedDims<4, 3>;
 using LQ = OcpLayout<DQ>;
-
-void toDevModelOcp(const idocp_model_t& m, DevModel& d) {
-  std::memset(&d, 0, sizeof(d));
-  d.njoints = m.njoints; d.nq = m.nq; d.nv = m.nv; d.nu = m.nu; d.has_floating_base = m.has_floating_base;
-  for (int i = 0; i < m.njoints; ++i) {
-    d.parent[i] = m.parent[i]; d.jtype[i] = m.jtype[i]; d.idx_q[i] = m.idx_q[i]; d.idx_v[i] = m.idx_v[i];
-    std::memcpy(d.axis[i], m.axis[i], sizeof(double) * 3);
-    std::memcpy(d.R[i], m.plc_R[i], sizeof(double) * 9);
-    std::memcpy(d.p[i], m.plc_p[i], sizeof(double) * 3);
-    d.mass[i] = m.mass[i];
-    const double* c = m.com[i];
-    const double* I = m.inertia[i];
-    const double ms = m.mass[i];
-    for (int k = 0; k < 3; ++k) d.mc[i][k] = ms * c[k];
-    const double cc = c[0] * c[0] + c[1] * c[1] + c[2] * c[2];
-    d.Io[i][0] = I[0] + ms * (cc - c[0] * c[0]); d.Io[i][1] = I[1] - ms * c[0] * c[1]; d.Io[i][2] = I[2] - ms * c[0] * c[2];
-    d.Io[i][3] = I[4] + ms * (cc - c[1] * c[1]); d.Io[i][4] = I[5] - ms * c[1] * c[2]; d.Io[i][5] = I[8] + ms * (cc - c[2] * c[2]);
-  }
-  std::memcpy(d.gravity, m.gravity, sizeof(double) * 3);
-}
-
-// free-flyer (identity placement) + 4 chains of 3 revolute joints, contact c on the tip joint of leg c
-bool isQuadruped(const idocp_model_t& m) {
-  if (!m.has_floating_base || m.njoints != DQ::NJ || m.nv != DQ::NV || m.nq != DQ::NQ || m.ncontacts != DQ::NC) return false;
-  if (m.jtype[0] != IDOCP_JOINT_FREEFLYER || m.parent[0] != -1) return false;
-  const double I3[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1};
-  for (int k = 0; k < 9; ++k) if (std::fabs(m.plc_R[0][k] - I3[k]) > 1e-14) return false;
-  for (int k = 0; k < 3; ++k) if (std::fabs(m.plc_p[0][k]) > 1e-14) return false;
-  for (int leg = 0; leg < DQ::NL; ++leg)
-    for (int j = 0; j < DQ::LJ; ++j) {
-      const int ji = 1 + leg * DQ::LJ + j;
-      if (m.jtype[ji] != IDOCP_JOINT_REVOLUTE || m.parent[ji] != (j == 0 ? 0 : ji - 1) || m.idx_v[ji] != 6 + leg * DQ::LJ + j) return false;
-    }
-  for (int c = 0; c < DQ::NC; ++c) if (m.contact_joint[c] != DQ::LJ * (c + 1)) return false;
-  return true;
-}
 
 }  // namespace
 
@@ -853,7 +819,7 @@ static int createOcpImpl(const idocp_model_t* model, const idocp_cost_t* cost, c
     for (int k = 0; k < 9; ++k) if (model->contact_R[c][k] != I3[k]) B.leg_axes_xyy = 0;
   }
   if (std::getenv("IDOCP_GENERAL_AXES")) B.leg_axes_xyy = 0;      // tests: the general instantiations on a model that qualifies for the special ones
-  DevModel dm; toDevModelOcp(*model, dm);
+  DevModel dm; idocp_host::toDevModel(*model, dm);
   OcpProblem& p = h->prob;
   std::memset(&p, 0, sizeof(p));
   p.N = N; p.batch = batch; p.T = T; p.dt = T / N; p.NS = h->NS; p.E = max_num_impulse; p.backward_euler = parnmpc ? 1 : 0; p.has_terminal = 1; p.has_prev = 0;

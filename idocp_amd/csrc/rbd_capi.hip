@@ -1,0 +1,219 @@
+// C-ABI implementation of the batched rigid-body API (include/idocp_hip.h: idocp_rbd_*).
+//
+// Host side only: a handle owns the model in device memory, a stream and the staging buffers of the host-pointer form; the terms
+// themselves come from rbd_batch_kernel.hip (quadruped) or from the sweep of the fixed-base solvers (UnLaunch<NV>::rneaDerivatives).
+// There is NO CPU fallback: without a GPU idocp_rbd_create returns IDOCP_E_DEVICE.
+#include <hip/hip_runtime.h>
+
+#include <cstring>
+#include <string>
+
+#include "host_util.hpp"
+#include "idocp_hip.h"
+#include "model_shapes.hpp"
+#include "rbd_launch.hpp"
+#include "unocp_launch.hpp"
+
+using namespace idocp_dev;
+using idocp_host::set_last_error;
+
+#define HIP_TRY(expr)                                                                         \
+  do {                                                                                        \
+    hipError_t e_ = (expr);                                                                   \
+    if (e_ != hipSuccess) {                                                                   \
+      set_last_error(std::string(#expr) + ": " + hipGetErrorString(e_));                      \
+      (void)hipGetLastError(); /* HIP keeps a failed call as the thread's "last error": reported here, it must not fail the next handle's launches */ \
+      return IDOCP_E_DEVICE;                                                                  \
+    }                                                                                         \
+  } while (0)
+
+struct idocp_rbd {
+  idocp_model_t model;
+  int device = 0;
+  bool quadruped = false, zaxes = false;
+  hipStream_t stream = nullptr;
+  void* d_model = nullptr;            // DevModel, then RbdFrames
+  const RbdFrames* d_frames = nullptr;
+  double* stage = nullptr;            // host-pointer form: inputs and outputs of one call
+  size_t stage_doubles = 0;
+  double* unwanted = nullptr;         // chain: where the sweep writes the outputs the caller did not ask for
+  size_t unwanted_doubles = 0;
+};
+
+namespace {
+
+constexpr size_t MODEL_BYTES = (sizeof(DevModel) + 15) / 16 * 16;
+
+typedef void (*ChainFn)(const DevModel*, int, const double*, const double*, const double*, double*, double*, double*, double*, bool, hipStream_t);
+ChainFn chainFn(int nv) {
+  switch (nv) {
+    case 2: return &UnLaunch<2>::rneaDerivatives;
+    case 3: return &UnLaunch<3>::rneaDerivatives;
+    case 4: return &UnLaunch<4>::rneaDerivatives;
+    case 5: return &UnLaunch<5>::rneaDerivatives;
+    case 6: return &UnLaunch<6>::rneaDerivatives;
+    case 7: return &UnLaunch<7>::rneaDerivatives;
+    case 8: return &UnLaunch<8>::rneaDerivatives;
+    default: return nullptr;
+  }
+}
+
+int growBuffer(double** buf, size_t* have, size_t want, hipStream_t st) {
+  if (want <= *have) return IDOCP_OK;
+  if (*buf) { HIP_TRY(hipStreamSynchronize(st)); HIP_TRY(hipFree(*buf)); *buf = nullptr; *have = 0; }
+  HIP_TRY(hipMalloc(reinterpret_cast<void**>(buf), sizeof(double) * want));
+  *have = want;
+  return IDOCP_OK;
+}
+
+// doubles per sample of every field of idocp_rbd_io_t, in the order of the struct
+struct FieldSizes { size_t in[5], out[9]; };
+FieldSizes fieldSizes(const idocp_rbd* h) {
+  const size_t nq = h->model.nq, nv = h->model.nv, nf = 3 * (size_t)h->model.ncontacts;
+  return {{nq, nv, nv, nf, nf}, {nv, nv * nv, nv * nv, nv * nv, nf, nf * nv, nf * nv, nf * nv, (nv + nf) * (nv + nf)}};
+}
+
+int checkCall(const idocp_rbd* h, int mode, int n, const int* active, double time_step, const idocp_rbd_io_t* io) {
+  if (!h || !io) { set_last_error("idocp_rbd_contact_dynamics_batch: null handle or io"); return IDOCP_E_ARG; }
+  if (n <= 0) { set_last_error("idocp_rbd_contact_dynamics_batch: n must be positive"); return IDOCP_E_ARG; }
+  if (mode != IDOCP_RBD_STAGE && mode != IDOCP_RBD_IMPULSE) { set_last_error("idocp_rbd_contact_dynamics_batch: unknown mode"); return IDOCP_E_ARG; }
+  if (!io->q || !io->v || !io->a) { set_last_error("idocp_rbd_contact_dynamics_batch: q, v and a are needed"); return IDOCP_E_ARG; }
+  const bool contact_out = io->C || io->dCdq || io->dCdv || io->dCda || io->MJtJinv;
+  if (!h->quadruped) {
+    if (io->f || io->contact_points || contact_out) {
+      set_last_error("idocp_rbd_contact_dynamics_batch: a fixed-base chain has no contacts (f, contact_points and the contact outputs must be NULL)");
+      return IDOCP_E_ARG;
+    }
+    if (mode != IDOCP_RBD_STAGE) { set_last_error("idocp_rbd_contact_dynamics_batch: a fixed-base chain has no impulse mode"); return IDOCP_E_ARG; }
+    return IDOCP_OK;
+  }
+  if (!active) { set_last_error("idocp_rbd_contact_dynamics_batch: the contact status `active` is needed"); return IDOCP_E_ARG; }
+  if (mode == IDOCP_RBD_STAGE) {
+    if (io->C && !io->contact_points) { set_last_error("idocp_rbd_contact_dynamics_batch: C in STAGE mode needs contact_points"); return IDOCP_E_ARG; }
+    if ((io->C || io->dCdq || io->dCdv) && !(time_step > 0.0)) {
+      set_last_error("idocp_rbd_contact_dynamics_batch: the Baumgarte terms need a positive time_step"); return IDOCP_E_ARG;
+    }
+  }
+  return IDOCP_OK;
+}
+
+// io: device pointers
+int launch(idocp_rbd* h, int mode, int n, const int* active, double time_step, const idocp_rbd_io_t& io) {
+  HIP_TRY(hipSetDevice(h->device));
+  const DevModel* d_m = static_cast<const DevModel*>(h->d_model);
+  if (h->quadruped) {
+    int mask = 0;
+    for (int c = 0; c < h->model.ncontacts; ++c) if (active[c]) mask |= 1 << c;
+    // (dC/da and MJtJinv do not depend on the Baumgarte time step: any positive number serves where none was given)
+    rbdBatchQuadruped(d_m, h->d_frames, io, n, mode, mask, (mode == IDOCP_RBD_STAGE && !(time_step > 0.0)) ? 1.0 : time_step, h->stream);
+  } else {
+    const size_t nv = h->model.nv, nvec = (size_t)n * nv, nmat = nvec * nv;
+    double *tau = io.tau, *dq = io.dtau_dq, *dv = io.dtau_dv, *da = io.dtau_da;
+    if (!tau || !dq || !dv || !da) {
+      int rc = growBuffer(&h->unwanted, &h->unwanted_doubles, nvec + 3 * nmat, h->stream); if (rc) return rc;
+      if (!tau) tau = h->unwanted;
+      if (!dq) dq = h->unwanted + nvec;
+      if (!dv) dv = h->unwanted + nvec + nmat;
+      if (!da) da = h->unwanted + nvec + 2 * nmat;
+    }
+    chainFn(h->model.nv)(d_m, n, io.q, io.v, io.a, tau, dq, dv, da, h->zaxes, h->stream);
+  }
+  HIP_TRY(hipGetLastError());
+  return IDOCP_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int idocp_rbd_create(const idocp_model_t* model, int device, idocp_rbd_t** out) {
+  if (!model || !out) { set_last_error("idocp_rbd_create: null argument"); return IDOCP_E_ARG; }
+  *out = nullptr;
+  const bool quad = idocp_host::isQuadruped(*model), chain = idocp_host::isRevoluteChain(*model);
+  if (!quad && !chain) {
+    set_last_error(std::string("idocp_rbd_create: the rigid-body kernels take ") + idocp_host::QUADRUPED_SHAPE + " or " + idocp_host::CHAIN_RANGE);
+    return IDOCP_E_UNSUPPORTED;
+  }
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) {
+    (void)hipGetLastError();
+    set_last_error("no HIP device available: the idocp HIP path has no CPU fallback");
+    return IDOCP_E_DEVICE;
+  }
+  if (device < 0 || device >= ndev) { set_last_error("invalid device ordinal"); return IDOCP_E_ARG; }
+  idocp_rbd* h = new idocp_rbd();
+  h->model = *model; h->device = device; h->quadruped = quad;
+  h->zaxes = true;      // (the instantiation of the chain sweep the solvers and idocp_rnea_derivatives choose for +z axes)
+  for (int i = 0; i < model->njoints; ++i) if (!(model->axis[i][0] == 0.0 && model->axis[i][1] == 0.0 && model->axis[i][2] == 1.0)) h->zaxes = false;
+  auto fail = [&](const char* what) { set_last_error(what); (void)hipGetLastError(); idocp_rbd_destroy(h); return IDOCP_E_DEVICE; };
+  if (hipSetDevice(device) != hipSuccess || hipStreamCreate(&h->stream) != hipSuccess) return fail("hipStreamCreate failed");
+  if (hipMalloc(&h->d_model, MODEL_BYTES + sizeof(RbdFrames)) != hipSuccess) return fail("hipMalloc of the model failed");
+  DevModel dm; idocp_host::toDevModel(*model, dm);
+  RbdFrames fr; std::memset(&fr, 0, sizeof(fr));
+  for (int c = 0; c < model->ncontacts; ++c) {
+    std::memcpy(fr.R[c], model->contact_R[c], sizeof(double) * 9);
+    std::memcpy(fr.p[c], model->contact_p[c], sizeof(double) * 3);
+  }
+  h->d_frames = reinterpret_cast<const RbdFrames*>(static_cast<char*>(h->d_model) + MODEL_BYTES);
+  if (hipMemcpy(h->d_model, &dm, sizeof(dm), hipMemcpyHostToDevice) != hipSuccess ||
+      hipMemcpy(static_cast<char*>(h->d_model) + MODEL_BYTES, &fr, sizeof(fr), hipMemcpyHostToDevice) != hipSuccess) return fail("upload of the model failed");
+  *out = h;
+  return IDOCP_OK;
+}
+
+void idocp_rbd_destroy(idocp_rbd_t* h) {
+  if (!h) return;
+  (void)hipSetDevice(h->device);
+  if (h->stream) (void)hipStreamSynchronize(h->stream);
+  if (h->d_model) (void)hipFree(h->d_model);
+  if (h->stage) (void)hipFree(h->stage);
+  if (h->unwanted) (void)hipFree(h->unwanted);
+  if (h->stream) (void)hipStreamDestroy(h->stream);
+  delete h;
+}
+
+int idocp_rbd_synchronize(idocp_rbd_t* h) {
+  if (!h) return IDOCP_E_ARG;
+  HIP_TRY(hipSetDevice(h->device));
+  HIP_TRY(hipStreamSynchronize(h->stream));
+  return IDOCP_OK;
+}
+
+void* idocp_rbd_stream(idocp_rbd_t* h) { return h ? static_cast<void*>(h->stream) : nullptr; }
+
+int idocp_rbd_contact_dynamics_batch_device(idocp_rbd_t* h, int mode, int n, const int* active, double time_step, const idocp_rbd_io_t* io) {
+  int rc = checkCall(h, mode, n, active, time_step, io); if (rc) return rc;
+  return launch(h, mode, n, active, time_step, *io);
+}
+
+int idocp_rbd_contact_dynamics_batch(idocp_rbd_t* h, int mode, int n, const int* active, double time_step, const idocp_rbd_io_t* io) {
+  int rc = checkCall(h, mode, n, active, time_step, io); if (rc) return rc;
+  HIP_TRY(hipSetDevice(h->device));
+  const FieldSizes fs = fieldSizes(h);
+  const double* const host_in[5] = {io->q, io->v, io->a, io->f, io->contact_points};
+  double* const host_out[9] = {io->tau, io->dtau_dq, io->dtau_dv, io->dtau_da, io->C, io->dCdq, io->dCdv, io->dCda, io->MJtJinv};
+  size_t total = 0;
+  for (int i = 0; i < 5; ++i) if (host_in[i]) total += (fs.in[i] * n + 1) / 2 * 2;
+  for (int i = 0; i < 9; ++i) if (host_out[i]) total += (fs.out[i] * n + 1) / 2 * 2;
+  rc = growBuffer(&h->stage, &h->stage_doubles, total, h->stream); if (rc) return rc;
+  const double* dev_in[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
+  double* dev_out[9] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+  double* cur = h->stage;
+  for (int i = 0; i < 5; ++i) if (host_in[i]) {
+    HIP_TRY(hipMemcpyAsync(cur, host_in[i], sizeof(double) * fs.in[i] * n, hipMemcpyHostToDevice, h->stream));
+    dev_in[i] = cur; cur += (fs.in[i] * n + 1) / 2 * 2;
+  }
+  for (int i = 0; i < 9; ++i) if (host_out[i]) { dev_out[i] = cur; cur += (fs.out[i] * n + 1) / 2 * 2; }
+  idocp_rbd_io_t d;
+  d.q = dev_in[0]; d.v = dev_in[1]; d.a = dev_in[2]; d.f = dev_in[3]; d.contact_points = dev_in[4];
+  d.tau = dev_out[0]; d.dtau_dq = dev_out[1]; d.dtau_dv = dev_out[2]; d.dtau_da = dev_out[3];
+  d.C = dev_out[4]; d.dCdq = dev_out[5]; d.dCdv = dev_out[6]; d.dCda = dev_out[7]; d.MJtJinv = dev_out[8];
+  if (d.MJtJinv) HIP_TRY(hipMemsetAsync(d.MJtJinv, 0, sizeof(double) * fs.out[8] * n, h->stream));      // (the part of a slot behind the packed block)
+  rc = launch(h, mode, n, active, time_step, d); if (rc) return rc;
+  for (int i = 0; i < 9; ++i) if (host_out[i])
+    HIP_TRY(hipMemcpyAsync(host_out[i], dev_out[i], sizeof(double) * fs.out[i] * n, hipMemcpyDeviceToHost, h->stream));
+  HIP_TRY(hipStreamSynchronize(h->stream));
+  return IDOCP_OK;
+}
+
+}  // extern "C"

@@ -19,10 +19,14 @@
 
 #include "host_util.hpp"
 #include "idocp_hip.h"
+#include "model_shapes.hpp"
 #include "unocp_launch.hpp"
 
 using namespace idocp_dev;
 using idocp_host::set_last_error;
+using idocp_host::toDevModel;
+using idocp_host::isRevoluteChain;
+using idocp_host::CHAIN_RANGE;
 
 #define HIP_TRY(expr)                                                                         \
   do {                                                                                        \
@@ -35,44 +39,6 @@ using idocp_host::set_last_error;
   } while (0)
 
 namespace {
-
-void toDevModel(const idocp_model_t& m, DevModel& d) {
-  std::memset(&d, 0, sizeof(d));
-  d.njoints = m.njoints; d.nq = m.nq; d.nv = m.nv; d.nu = m.nu; d.has_floating_base = m.has_floating_base;
-  for (int i = 0; i < m.njoints; ++i) {
-    d.parent[i] = m.parent[i]; d.jtype[i] = m.jtype[i]; d.idx_q[i] = m.idx_q[i]; d.idx_v[i] = m.idx_v[i];
-    std::memcpy(d.axis[i], m.axis[i], sizeof(double) * 3);
-    std::memcpy(d.R[i], m.plc_R[i], sizeof(double) * 9);
-    std::memcpy(d.p[i], m.plc_p[i], sizeof(double) * 3);
-    d.mass[i] = m.mass[i];
-    const double* c = m.com[i];
-    const double* I = m.inertia[i];
-    const double ms = m.mass[i];
-    for (int k = 0; k < 3; ++k) d.mc[i][k] = ms * c[k];
-    // Io = Ic + m (c.c 1 - c c^T)   (inertia about the joint-frame origin)
-    const double cc = c[0] * c[0] + c[1] * c[1] + c[2] * c[2];
-    d.Io[i][0] = I[0] + ms * (cc - c[0] * c[0]);
-    d.Io[i][1] = I[1] - ms * c[0] * c[1];
-    d.Io[i][2] = I[2] - ms * c[0] * c[2];
-    d.Io[i][3] = I[4] + ms * (cc - c[1] * c[1]);
-    d.Io[i][4] = I[5] - ms * c[1] * c[2];
-    d.Io[i][5] = I[8] + ms * (cc - c[2] * c[2]);
-  }
-  std::memcpy(d.gravity, m.gravity, sizeof(double) * 3);
-}
-
-// The UnOCP kernels are compiled for serial chains of UN_MIN_NV .. UN_MAX_NV revolute joints (unocp_kernels.hip instantiates UnLaunch<NV>
-// for each).
-constexpr int UN_MIN_NV = 2, UN_MAX_NV = 8;
-bool isRevoluteChain(const idocp_model_t& m) {
-  const int nv = m.nv;
-  if (nv < UN_MIN_NV || nv > UN_MAX_NV) return false;
-  if (m.njoints != nv || m.nq != nv || m.has_floating_base || m.ncontacts != 0) return false;
-  for (int i = 0; i < nv; ++i)
-    if (m.parent[i] != i - 1 || m.jtype[i] != IDOCP_JOINT_REVOLUTE || m.idx_v[i] != i) return false;
-  return true;
-}
-const char* const CHAIN_RANGE = "a fixed-base serial chain of 2 .. 8 revolute joints";
 
 // The record layout UnLayout<NV> of a handle's chain, read at run time by the host side (strides of the device arrays, field offsets)
 struct UnDims {
@@ -198,6 +164,11 @@ int idocp_device_alloc(void** d_ptr, unsigned long long nbytes) {
 int idocp_device_free(void* d_ptr) { HIP_TRY(hipFree(d_ptr)); return IDOCP_OK; }
 int idocp_device_upload(void* d_dst, const void* h_src, unsigned long long nbytes) {
   HIP_TRY(hipMemcpy(d_dst, h_src, nbytes, hipMemcpyHostToDevice));
+  return IDOCP_OK;
+}
+
+int idocp_device_download(void* h_dst, const void* d_src, unsigned long long nbytes) {
+  HIP_TRY(hipMemcpy(h_dst, d_src, nbytes, hipMemcpyDeviceToHost));
   return IDOCP_OK;
 }
 

@@ -72,11 +72,104 @@ class Robot {
       std::exit(EXIT_FAILURE);
     }
   }
-  // Robot::updateKinematics(q[, v[, a]]) (robot.hxx:166-203): the facade keeps the configuration for the frame queries below; velocities and accelerations of
-  // frames are evaluated inside the stage kernels and have no host-side query.
-  void updateKinematics(const Eigen::VectorXd& q) { updateFrameKinematics(q); }
-  void updateKinematics(const Eigen::VectorXd& q, const Eigen::VectorXd&) { updateFrameKinematics(q); }
-  void updateKinematics(const Eigen::VectorXd& q, const Eigen::VectorXd&, const Eigen::VectorXd&) { updateFrameKinematics(q); }
+  // Robot::updateKinematics(q[, v[, a]]) (robot.hxx:166-203): the facade keeps the state for the frame queries and the contact terms below
+  // (computeBaumgarteResidual ..., evaluated on the GPU at this state); a velocity or acceleration that is not given is zero.
+  void updateKinematics(const Eigen::VectorXd& q) { updateFrameKinematics(q); v_kin_.assign(model_.nv, 0.0); a_kin_.assign(model_.nv, 0.0); }
+  void updateKinematics(const Eigen::VectorXd& q, const Eigen::VectorXd& v) {
+    updateFrameKinematics(q); sized(v, model_.nv, "v");
+    v_kin_.assign(v.data(), v.data() + model_.nv); a_kin_.assign(model_.nv, 0.0);
+  }
+  void updateKinematics(const Eigen::VectorXd& q, const Eigen::VectorXd& v, const Eigen::VectorXd& a) {
+    updateFrameKinematics(q); sized(v, model_.nv, "v"); sized(a, model_.nv, "a");
+    v_kin_.assign(v.data(), v.data() + model_.nv); a_kin_.assign(a.data(), a.data() + model_.nv);
+  }
+
+  // ---- Inverse dynamics and contact terms (robot.hxx:237-320, 408-540), each ONE n = 1 call of the batched rigid-body API
+  // (idocp_rbd_contact_dynamics_batch, idocp_hip.h) on a handle this Robot creates at the first such call; a copy of the Robot creates its own.
+  // The contact outputs are packed like the reference's: three rows per ACTIVE contact, in contact order, from row 0 of the argument.
+  // Robot::setContactForces / setImpulseForces (robot.hxx:408-441): f[i] in the local coordinates of contact frame i, ignored where inactive
+  void setContactForces(const ContactStatus& contact_status, const std::vector<Eigen::Vector3d>& f) { setForces(contact_status.isContactActive(), f, f_act_, f_); }
+  void setImpulseForces(const ImpulseStatus& impulse_status, const std::vector<Eigen::Vector3d>& f) { setForces(impulse_status.isImpulseActive(), f, fi_act_, fi_); }
+  void RNEA(const Eigen::VectorXd& q, const Eigen::VectorXd& v, const Eigen::VectorXd& a, Eigen::VectorXd& tau) {
+    sized(q, model_.nq, "q"); sized(v, model_.nv, "v"); sized(a, model_.nv, "a"); sized(tau, model_.nv, "tau");
+    idocp_rbd_io_t io = dynamicsIO(q.data(), v.data(), a.data(), f_);
+    io.tau = tau.data();
+    rbdCall(IDOCP_RBD_STAGE, f_act_, 0.0, io);
+  }
+  void RNEADerivatives(const Eigen::VectorXd& q, const Eigen::VectorXd& v, const Eigen::VectorXd& a, Eigen::MatrixXd& dRNEA_partial_dq,
+                       Eigen::MatrixXd& dRNEA_partial_dv, Eigen::MatrixXd& dRNEA_partial_da) {
+    sized(q, model_.nq, "q"); sized(v, model_.nv, "v"); sized(a, model_.nv, "a");
+    square(dRNEA_partial_dq, "dRNEA_partial_dq"); square(dRNEA_partial_dv, "dRNEA_partial_dv"); square(dRNEA_partial_da, "dRNEA_partial_da");
+    idocp_rbd_io_t io = dynamicsIO(q.data(), v.data(), a.data(), f_);
+    io.dtau_dq = dRNEA_partial_dq.data(); io.dtau_dv = dRNEA_partial_dv.data(); io.dtau_da = dRNEA_partial_da.data();
+    rbdCall(IDOCP_RBD_STAGE, f_act_, 0.0, io);
+  }
+  void RNEAImpulse(const Eigen::VectorXd& q, const Eigen::VectorXd& dv, Eigen::VectorXd& res) {
+    sized(q, model_.nq, "q"); sized(dv, model_.nv, "dv"); sized(res, model_.nv, "res");
+    const std::vector<double> zero(model_.nv, 0.0);
+    idocp_rbd_io_t io = dynamicsIO(q.data(), zero.data(), dv.data(), fi_);
+    io.tau = res.data();
+    rbdCall(IDOCP_RBD_IMPULSE, fi_act_, 0.0, io);
+  }
+  void RNEAImpulseDerivatives(const Eigen::VectorXd& q, const Eigen::VectorXd& dv, Eigen::MatrixXd& dRNEA_partial_dq, Eigen::MatrixXd& dRNEA_partial_ddv) {
+    sized(q, model_.nq, "q"); sized(dv, model_.nv, "dv");
+    square(dRNEA_partial_dq, "dRNEA_partial_dq"); square(dRNEA_partial_ddv, "dRNEA_partial_ddv");
+    const std::vector<double> zero(model_.nv, 0.0);
+    idocp_rbd_io_t io = dynamicsIO(q.data(), zero.data(), dv.data(), fi_);
+    io.dtau_dq = dRNEA_partial_dq.data(); io.dtau_da = dRNEA_partial_ddv.data();
+    rbdCall(IDOCP_RBD_IMPULSE, fi_act_, 0.0, io);
+  }
+  // at the state of the last updateKinematics(q, v, a)
+  void computeBaumgarteResidual(const ContactStatus& contact_status, const double time_step, const std::vector<Eigen::Vector3d>& contact_points,
+                                Eigen::VectorXd& baumgarte_residual) const {
+    noContacts(); kinematicsKnown();
+    if ((int)contact_points.size() != model_.ncontacts) { std::cerr << "invalid size: contact_points.size() must be " << model_.ncontacts << "!" << '\n'; std::exit(EXIT_FAILURE); }
+    double pts[3 * IDOCP_MAX_CONTACTS], C[3 * IDOCP_MAX_CONTACTS];
+    for (int c = 0; c < model_.ncontacts; ++c) for (int k = 0; k < 3; ++k) pts[3 * c + k] = contact_points[c][k];
+    int act[IDOCP_MAX_CONTACTS];
+    const int dimf = activeOf(contact_status.isContactActive(), act);
+    idocp_rbd_io_t io = dynamicsIO(q_kin_.data(), v_kin_.data(), a_kin_.data(), nullptr);
+    io.contact_points = pts; io.C = C;
+    rbdCall(IDOCP_RBD_STAGE, act, time_step, io);
+    packVector(act, dimf, C, baumgarte_residual, "baumgarte_residual");
+  }
+  void computeBaumgarteDerivatives(const ContactStatus& contact_status, const double time_step, Eigen::MatrixXd& baumgarte_partial_dq,
+                                   Eigen::MatrixXd& baumgarte_partial_dv, Eigen::MatrixXd& baumgarte_partial_da) {
+    noContacts(); kinematicsKnown();
+    int act[IDOCP_MAX_CONTACTS];
+    const int dimf = activeOf(contact_status.isContactActive(), act);
+    std::vector<double> d(3 * (size_t)max_dimf() * model_.nv);
+    idocp_rbd_io_t io = dynamicsIO(q_kin_.data(), v_kin_.data(), a_kin_.data(), nullptr);
+    io.dCdq = d.data(); io.dCdv = d.data() + (size_t)max_dimf() * model_.nv; io.dCda = d.data() + 2 * (size_t)max_dimf() * model_.nv;
+    rbdCall(IDOCP_RBD_STAGE, act, time_step, io);
+    packMatrix(act, dimf, io.dCdq, baumgarte_partial_dq, "baumgarte_partial_dq");
+    packMatrix(act, dimf, io.dCdv, baumgarte_partial_dv, "baumgarte_partial_dv");
+    packMatrix(act, dimf, io.dCda, baumgarte_partial_da, "baumgarte_partial_da");
+  }
+  // the local linear velocity of the active frames at the velocity of the last updateKinematics (the reference's callers pass v + dv there)
+  void computeImpulseVelocityResidual(const ImpulseStatus& impulse_status, Eigen::VectorXd& velocity_residual) const {
+    noContacts(); kinematicsKnown();
+    double C[3 * IDOCP_MAX_CONTACTS];
+    int act[IDOCP_MAX_CONTACTS];
+    const int dimf = activeOf(impulse_status.isImpulseActive(), act);
+    const std::vector<double> zero(model_.nv, 0.0);
+    idocp_rbd_io_t io = dynamicsIO(q_kin_.data(), v_kin_.data(), zero.data(), nullptr);
+    io.C = C;
+    rbdCall(IDOCP_RBD_IMPULSE, act, 0.0, io);
+    packVector(act, dimf, C, velocity_residual, "velocity_residual");
+  }
+  void computeImpulseVelocityDerivatives(const ImpulseStatus& impulse_status, Eigen::MatrixXd& velocity_partial_dq, Eigen::MatrixXd& velocity_partial_dv) {
+    noContacts(); kinematicsKnown();
+    int act[IDOCP_MAX_CONTACTS];
+    const int dimf = activeOf(impulse_status.isImpulseActive(), act);
+    const std::vector<double> zero(model_.nv, 0.0);
+    std::vector<double> d(2 * (size_t)max_dimf() * model_.nv);
+    idocp_rbd_io_t io = dynamicsIO(q_kin_.data(), v_kin_.data(), zero.data(), nullptr);
+    io.dCdq = d.data(); io.dCdv = d.data() + (size_t)max_dimf() * model_.nv;
+    rbdCall(IDOCP_RBD_IMPULSE, act, 0.0, io);
+    packMatrix(act, dimf, io.dCdq, velocity_partial_dq, "velocity_partial_dq");
+    packMatrix(act, dimf, io.dCdv, velocity_partial_dv, "velocity_partial_dv");
+  }
   // Robot::framePosition / frameRotation / framePlacement (robot.hxx:206-233): of any frame of the URDF (pinocchio's frame numbering, as the
   // contact frames and the task-space costs use it), at the configuration of the last updateFrameKinematics / updateKinematics
   Eigen::Vector3d framePosition(const int frame_id) const { return framePlacement(frame_id).translation(); }
@@ -169,6 +262,65 @@ class Robot {
   std::string path_;
   std::vector<double> points_;     // contact-frame positions of the last updateFrameKinematics(q)
   std::vector<double> q_kin_;      // that configuration (frame queries)
+  std::vector<double> v_kin_, a_kin_;      // velocity and acceleration of the last updateKinematics
+  double f_[3 * IDOCP_MAX_CONTACTS] = {}, fi_[3 * IDOCP_MAX_CONTACTS] = {};      // setContactForces / setImpulseForces
+  int f_act_[IDOCP_MAX_CONTACTS] = {}, fi_act_[IDOCP_MAX_CONTACTS] = {};
+  // the handle of the batched rigid-body API: created at the first call that needs it, never shared (a copied Robot creates its own)
+  struct RbdHandle {
+    idocp_rbd_t* h = nullptr;
+    RbdHandle() {}
+    RbdHandle(const RbdHandle&) {}
+    RbdHandle& operator=(const RbdHandle&) { reset(); return *this; }      // (the model may have changed with the assignment)
+    ~RbdHandle() { reset(); }
+    void reset() { if (h) idocp_rbd_destroy(h); h = nullptr; }
+  };
+  mutable RbdHandle rbd_;
+  void rbdCall(int mode, const int* active, double time_step, const idocp_rbd_io_t& io) const {
+    if (!rbd_.h) ok(idocp_rbd_create(&model_, 0, &rbd_.h));
+    ok(idocp_rbd_contact_dynamics_batch(rbd_.h, mode, 1, model_.ncontacts > 0 ? active : nullptr, time_step, &io));
+  }
+  idocp_rbd_io_t dynamicsIO(const double* q, const double* v, const double* a, const double* f) const {
+    idocp_rbd_io_t io = idocp_rbd_io_t();
+    io.q = q; io.v = v; io.a = a; io.f = model_.ncontacts > 0 ? f : nullptr;
+    return io;
+  }
+  void setForces(const std::vector<bool>& active, const std::vector<Eigen::Vector3d>& f, int* act, double* out) {
+    noContacts();
+    if ((int)f.size() != model_.ncontacts || (int)active.size() != model_.ncontacts) {
+      std::cerr << "invalid size: f.size() must be " << model_.ncontacts << "!" << '\n'; std::exit(EXIT_FAILURE);
+    }
+    for (int c = 0; c < model_.ncontacts; ++c) {
+      act[c] = active[c] ? 1 : 0;
+      for (int k = 0; k < 3; ++k) out[3 * c + k] = active[c] ? f[c][k] : 0.0;
+    }
+  }
+  int activeOf(const std::vector<bool>& active, int* act) const {
+    int dimf = 0;
+    for (int c = 0; c < model_.ncontacts; ++c) { act[c] = (c < (int)active.size() && active[c]) ? 1 : 0; dimf += 3 * act[c]; }
+    return dimf;
+  }
+  void kinematicsKnown() const {
+    if (q_kin_.empty() || v_kin_.empty()) { std::cerr << "invalid function call: call updateKinematics(q, v, a) first!" << '\n'; std::exit(EXIT_FAILURE); }
+  }
+  void square(const Eigen::MatrixXd& m, const char* name) const {
+    if (m.rows() != model_.nv || m.cols() != model_.nv) { std::cerr << "invalid size: " << name << " must be " << model_.nv << " x " << model_.nv << "!" << '\n'; std::exit(EXIT_FAILURE); }
+  }
+  // rows of the active contacts, in contact order, to the top of the argument
+  void packVector(const int* act, int dimf, const double* full, Eigen::VectorXd& out, const char* name) const {
+    if (out.size() < dimf) { std::cerr << "invalid size: " << name << ".size() must be at least " << dimf << "!" << '\n'; std::exit(EXIT_FAILURE); }
+    int row = 0;
+    for (int c = 0; c < model_.ncontacts; ++c) if (act[c]) { for (int k = 0; k < 3; ++k) out[row + k] = full[3 * c + k]; row += 3; }
+  }
+  void packMatrix(const int* act, int dimf, const double* full, Eigen::MatrixXd& out, const char* name) const {
+    if (out.rows() < dimf || out.cols() != model_.nv) {
+      std::cerr << "invalid size: " << name << " must have at least " << dimf << " rows and " << model_.nv << " columns!" << '\n'; std::exit(EXIT_FAILURE);
+    }
+    const int nf = max_dimf();
+    for (int j = 0; j < model_.nv; ++j) {
+      int row = 0;
+      for (int c = 0; c < model_.ncontacts; ++c) if (act[c]) { for (int k = 0; k < 3; ++k) out(row + k, j) = full[(size_t)j * nf + 3 * c + k]; row += 3; }
+    }
+  }
   struct FrameLocation { int joint; double R[9], p[3]; };
   mutable std::map<int, FrameLocation> frames_;
   double friction_[IDOCP_MAX_CONTACTS] = {0.8, 0.8, 0.8, 0.8}, restitution_[IDOCP_MAX_CONTACTS] = {0.0, 0.0, 0.0, 0.0};

@@ -285,6 +285,8 @@ void* idocp_unocp_stream(idocp_unocp_t* h);
 int idocp_device_alloc(void** d_ptr, unsigned long long nbytes);
 int idocp_device_free(void* d_ptr);
 int idocp_device_upload(void* d_dst, const void* h_src, unsigned long long nbytes);
+/* Blocking copy back to the host (the results of the *_device entries); synchronize the handle first. */
+int idocp_device_download(void* h_dst, const void* d_src, unsigned long long nbytes);
 int idocp_device_count(int* count);
 
 /* UnOCPSolver::computeKKTResidual(t, q, v) + KKTError() (unocp_solver.cpp:
@@ -759,6 +761,42 @@ int idocp_ocp_set_fused_forward(idocp_ocp_t* h, int mode);
  * latency form; IDOCP_RICCATI_WIDE_MAX_BATCH moves the threshold), 0 throughput form, 1 latency form -- per handle, copied by clone. */
 int idocp_ocp_riccati_sweep(idocp_ocp_t* h);
 int idocp_ocp_set_riccati_sweep(idocp_ocp_t* h, int mode);
+
+/* ---- Batched rigid-body terms on plain arrays: what Robot::RNEA, RNEADerivatives, setContactForces,
+ * computeBaumgarteResidual / Derivatives, RNEAImpulse(+Derivatives), computeImpulseVelocityResidual / Derivatives and computeMJtJinv
+ * (include/idocp/robot/robot.hxx:85-91, 262-283, 444-540, 576-615; contact_dynamics.hxx:105-158) give the reference, for n independent
+ * samples in one launch.  The handle uploads the model once and owns a stream; calls are ordered on it.
+ * Accepted models: a floating-base quadruped (4 legs x 3 revolute joints, 4 point contacts on the tip joints; every output), or a
+ * fixed-base serial chain of 2 .. 8 revolute joints (tau and dtau_* only: f, contact_points and the contact outputs must be NULL).
+ * Anything else returns IDOCP_E_UNSUPPORTED and idocp_last_error() names these shapes.  Without a GPU: IDOCP_E_DEVICE, no CPU fallback. */
+typedef struct idocp_rbd idocp_rbd_t;
+int idocp_rbd_create(const idocp_model_t* model, int device, idocp_rbd_t** out);
+void idocp_rbd_destroy(idocp_rbd_t* h);
+int idocp_rbd_synchronize(idocp_rbd_t* h);
+void* idocp_rbd_stream(idocp_rbd_t* h);      /* hipStream_t */
+
+#define IDOCP_RBD_STAGE 0    /* ID with gravity, Baumgarte constraint */
+#define IDOCP_RBD_IMPULSE 1  /* RNEAImpulse: no gravity, v = 0 in the dynamics, a = dv; impulse velocity constraint at v + dv */
+
+/* n samples; every pointer is host memory (idocp_rbd_contact_dynamics_batch) or device memory (..._batch_device).  Outputs that are NULL
+ * are neither computed nor stored.  Matrices are column-major.  Rows of an inactive contact in C and dC* are zero, its f is ignored. */
+typedef struct idocp_rbd_io {
+  const double *q, *v, *a;      /* [n][nq], [n][nv], [n][nv] */
+  const double *f;              /* [n][ncontacts][3], local contact-frame coordinates; NULL = 0 */
+  const double *contact_points; /* [n][ncontacts][3]; needed for C in STAGE mode */
+  double *tau, *dtau_dq, *dtau_dv, *dtau_da; /* [n][nv], [n][nv * nv] */
+  double *C, *dCdq, *dCdv, *dCda;            /* [n][3 ncontacts], [n][3 ncontacts * nv]; IMPULSE: dCdv and dCda both hold d C / d (v + dv) */
+  double *MJtJinv;              /* [n][(nv + 3 ncontacts)^2] slot; the inverse of [M J^T; J 0] over the active rows (J = dCda), packed
+                                 * (nv + dimf)^2 column-major at the start of the slot like idocp_ocp_get_contact_dynamics packs it;
+                                 * NaN where M or J M^-1 J^T is not positive definite.  The rest of a slot behind the packed block
+                                 * (dimf < 3 ncontacts): zero in the host form, UNSPECIFIED in the device form (left as it was) */
+} idocp_rbd_io_t;
+
+/* active[ncontacts]: contact status shared by the n samples (NULL on a chain); time_step: the Baumgarte time step (STAGE mode with a
+ * contact output).  The host form returns when the outputs are in place; it stages through buffers the handle owns and grows. */
+int idocp_rbd_contact_dynamics_batch(idocp_rbd_t* h, int mode, int n, const int* active, double time_step, const idocp_rbd_io_t* io);
+/* Asynchronous on idocp_rbd_stream(h); allocates nothing on a quadruped, and on a chain only when n grows. */
+int idocp_rbd_contact_dynamics_batch_device(idocp_rbd_t* h, int mode, int n, const int* active, double time_step, const idocp_rbd_io_t* io);
 
 const char* idocp_last_error(void);
 const char* idocp_version(void);

@@ -1,0 +1,99 @@
+"""Throughput of the batched rigid-body API (idocp_rbd_contact_dynamics_batch_device): ANYmal, four active contacts,
+device pointers, n = 122 880 samples per launch by default (the stage count of the headline step: 1 024 instances x 120 stages).  Every launch is
+bracketed by HIP events on the handle's stream after warm-up launches; prints one JSON line with the median / min / max ms per launch and the
+samples per second of each output selection.
+
+    python profiles/rbd_throughput.py [--n 122880] [--launches 20] [--warmup 5]
+"""
+import argparse
+import ctypes as C
+import json
+import os
+import sys
+
+import numpy as np
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from idocp_amd import capi  # noqa: E402
+from idocp_amd.workloads import ANYMAL_Q_STANDING, anymal_model  # noqa: E402
+
+SELECTIONS = (("stage_all", capi.RBD_STAGE, capi.RbdIO.OUTPUTS),
+              ("stage_no_mjtjinv", capi.RBD_STAGE, capi.RbdIO.OUTPUTS[:-1]),
+              ("stage_da_mjtjinv", capi.RBD_STAGE, ("tau", "dtau_da", "C", "dCda", "MJtJinv")),
+              ("stage_tau_C", capi.RBD_STAGE, ("tau", "C")),
+              ("impulse_all", capi.RBD_IMPULSE, capi.RbdIO.OUTPUTS))
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--n", type=int, default=122880)
+    ap.add_argument("--launches", type=int, default=20)
+    ap.add_argument("--warmup", type=int, default=5)
+    args = ap.parse_args()
+    n, lib, rt = args.n, capi.lib(), C.CDLL("libamdhip64.so")
+    rt.hipEventCreate.argtypes = [C.POINTER(C.c_void_p)]
+    rt.hipEventRecord.argtypes = [C.c_void_p, C.c_void_p]
+    rt.hipEventSynchronize.argtypes = [C.c_void_p]
+    rt.hipEventElapsedTime.argtypes = [C.POINTER(C.c_float), C.c_void_p, C.c_void_p]
+    m = anymal_model()
+    nv, nq, nf = m.nv, m.nq, 3 * m.ncontacts
+    h = C.c_void_p()
+    capi.check(lib.idocp_rbd_create(C.byref(m), 0, C.byref(h)), "idocp_rbd_create")
+    lib.idocp_rbd_stream.restype = C.c_void_p
+    stream = C.c_void_p(lib.idocp_rbd_stream(h))
+    rng = np.random.default_rng(0)
+    q = np.tile(ANYMAL_Q_STANDING, (n, 1))
+    q[:, 7:] += rng.uniform(-0.3, 0.3, (n, nv - 6))
+    quat = q[:, 3:7] + rng.normal(scale=0.2, size=(n, 4))
+    q[:, 3:7] = quat / np.linalg.norm(quat, axis=1, keepdims=True)
+    host = {"q": q, "v": rng.uniform(-1, 1, (n, nv)), "a": rng.uniform(-2, 2, (n, nv)), "f": rng.uniform(-30, 30, (n, nf)),
+            "contact_points": rng.uniform(-0.5, 0.5, (n, nf))}
+    sizes = {"tau": nv, "dtau_dq": nv * nv, "dtau_dv": nv * nv, "dtau_da": nv * nv, "C": nf, "dCdq": nf * nv, "dCdv": nf * nv, "dCda": nf * nv,
+             "MJtJinv": (nv + nf) ** 2}
+    dev = {}
+    for k, x in host.items():
+        dev[k] = C.c_void_p()
+        x = np.ascontiguousarray(x)
+        capi.check(lib.idocp_device_alloc(C.byref(dev[k]), x.nbytes), "alloc")
+        capi.check(lib.idocp_device_upload(dev[k], x.ctypes.data, x.nbytes), "upload")
+    for k, sz in sizes.items():
+        dev[k] = C.c_void_p()
+        capi.check(lib.idocp_device_alloc(C.byref(dev[k]), 8 * sz * n), "alloc")
+    active = (C.c_int * 4)(1, 1, 1, 1)
+    events = []
+    for _ in range(args.launches + 1):
+        e = C.c_void_p()
+        assert rt.hipEventCreate(C.byref(e)) == 0
+        events.append(e)
+    res = {"n": n, "launches": args.launches, "warmup": args.warmup}
+    for name, mode, outputs in SELECTIONS:
+        io = capi.RbdIO()
+        for k in capi.RbdIO.INPUTS + tuple(outputs):
+            setattr(io, k, dev[k])
+        launch = lambda: capi.check(lib.idocp_rbd_contact_dynamics_batch_device(h, mode, n, active, 0.05, C.byref(io)), name)  # noqa: E731
+        for _ in range(args.warmup):
+            launch()
+        capi.check(lib.idocp_rbd_synchronize(h), "synchronize")
+        assert rt.hipEventRecord(events[0], stream) == 0
+        for i in range(args.launches):
+            launch()
+            assert rt.hipEventRecord(events[i + 1], stream) == 0
+        assert rt.hipEventSynchronize(events[-1]) == 0
+        ms = []
+        for i in range(args.launches):
+            t = C.c_float()
+            assert rt.hipEventElapsedTime(C.byref(t), events[i], events[i + 1]) == 0
+            ms.append(t.value)
+        med = float(np.median(ms))
+        res[name] = {"ms_median": round(med, 4), "ms_min": round(min(ms), 4), "ms_max": round(max(ms), 4), "samples_per_s": round(n / med * 1e3)}
+    tau = np.zeros((n, nv))
+    capi.check(lib.idocp_device_download(tau.ctypes.data, dev["tau"], tau.nbytes), "download")
+    res["tau_finite"] = bool(np.isfinite(tau).all())
+    for d in dev.values():
+        lib.idocp_device_free(d)
+    lib.idocp_rbd_destroy(h)
+    print(json.dumps(res))
+
+
+if __name__ == "__main__":
+    main()

@@ -1,0 +1,79 @@
+"""Shared by test_rbd_batch_gpu.py / test_rbd_batch_host.py: a thin wrapper of the idocp_rbd_* handle (include/idocp_hip.h)."""
+import ctypes as C
+
+import numpy as np
+
+from idocp_amd import capi
+
+E_ARG, E_DEVICE, E_UNSUPPORTED = -1, -3, -4
+STAGE, IMPULSE = capi.RBD_STAGE, capi.RBD_IMPULSE
+ALL_OUTPUTS = capi.RbdIO.OUTPUTS
+
+
+def out_shapes(m):
+    """per-sample shape of every output, as numpy sees the column-major blocks: [column][row]"""
+    nv, nf = m.nv, 3 * m.ncontacts
+    return {"tau": (nv,), "dtau_dq": (nv, nv), "dtau_dv": (nv, nv), "dtau_da": (nv, nv), "C": (nf,), "dCdq": (nv, nf), "dCdv": (nv, nf),
+            "dCda": (nv, nf), "MJtJinv": ((nv + nf) * (nv + nf),)}
+
+
+class Rbd:
+    def __init__(self, m, device=0):
+        self.m, self.lib, self.h = m, capi.lib(), C.c_void_p()
+        capi.check(self.lib.idocp_rbd_create(C.byref(m), device, C.byref(self.h)), "idocp_rbd_create")
+
+    def close(self):
+        if self.h:
+            self.lib.idocp_rbd_destroy(self.h)
+            self.h = C.c_void_p()
+
+    __del__ = close
+
+    def call_raw(self, mode, n, active, time_step, io, device=False):
+        act = (C.c_int * 4)(*active) if active is not None else None
+        fn = self.lib.idocp_rbd_contact_dynamics_batch_device if device else self.lib.idocp_rbd_contact_dynamics_batch
+        return fn(self.h, mode, n, act, time_step, C.byref(io))
+
+    def call(self, mode, q, v, a, active=None, time_step=0.0, f=None, contact_points=None, outputs=ALL_OUTPUTS, fill=np.nan):
+        """host form; returns {name: array [n][...]} with the matrices turned to [row, column]; MJtJinv as the whole slot"""
+        q = np.ascontiguousarray(q, dtype=np.float64)
+        n = q.shape[0]
+        keep = {"q": q}
+        for name, x in (("v", v), ("a", a), ("f", f), ("contact_points", contact_points)):
+            if x is not None:
+                keep[name] = np.ascontiguousarray(x, dtype=np.float64)
+        shapes = out_shapes(self.m)
+        out = {name: np.full((n,) + shapes[name], fill) for name in outputs}
+        io = capi.RbdIO()
+        for name, x in list(keep.items()) + list(out.items()):
+            setattr(io, name, x.ctypes.data)
+        capi.check(self.call_raw(mode, n, active, time_step, io), "idocp_rbd_contact_dynamics_batch")
+        return {name: (x.transpose(0, 2, 1).copy() if x.ndim == 3 else x) for name, x in out.items()}
+
+
+class DeviceArray:
+    """a float64 array in device memory through the library's own helpers (idocp_device_alloc / upload / download / free)"""
+
+    def __init__(self, x):
+        x = np.ascontiguousarray(x, dtype=np.float64)
+        self.shape, self.nbytes, self.lib, self.ptr = x.shape, x.nbytes, capi.lib(), C.c_void_p()
+        capi.check(self.lib.idocp_device_alloc(C.byref(self.ptr), self.nbytes), "idocp_device_alloc")
+        capi.check(self.lib.idocp_device_upload(self.ptr, x.ctypes.data, self.nbytes), "idocp_device_upload")
+
+    def numpy(self):
+        x = np.empty(self.shape)
+        capi.check(self.lib.idocp_device_download(x.ctypes.data, self.ptr, self.nbytes), "idocp_device_download")
+        return x
+
+    def free(self):
+        if self.ptr:
+            self.lib.idocp_device_free(self.ptr)
+            self.ptr = C.c_void_p()
+
+    __del__ = free
+
+
+def packed_mjtjinv(slot, nv, dimf):
+    """the packed (nv + dimf)^2 column-major block at the start of a slot, as [row, column]"""
+    n = nv + dimf
+    return np.asarray(slot)[:n * n].reshape(n, n).T
