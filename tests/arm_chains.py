@@ -14,9 +14,11 @@ def _f(x):
     return " ".join(repr(float(e)) for e in x)
 
 
-def random_arm_urdf(nv, seed, zaxes=False):
-    """URDF text of a serial chain of `nv` revolute joints; zaxes: every joint axis is +z (the placements stay random)."""
+def random_arm_urdf(nv, seed, zaxes=False, inertial_rpy=False):
+    """URDF text of a serial chain of `nv` revolute joints; zaxes: every joint axis is +z (the placements stay random); inertial_rpy: the inertial
+    origin of every link is rotated by random angles (drawn from a generator of their own: every other number of the text stays what it is without)."""
     rng = np.random.default_rng(seed)
+    rng_inertial = np.random.default_rng([seed, nv, 4711])
     out = ['<?xml version="1.0" ?>', '<robot name="arm%d_%d">' % (nv, seed), '  <link name="world"/>',
            '  <joint name="base_joint" type="fixed"><origin rpy="0 0 0" xyz="0 0 0"/><parent link="world"/><child link="link_0"/></joint>',
            '  <link name="link_0"/>']
@@ -32,17 +34,18 @@ def random_arm_urdf(nv, seed, zaxes=False):
         off = 0.1 * d.min() * rng.uniform(-1, 1, 3)
         out.append('  <joint name="joint_%d" type="revolute"><origin rpy="%s" xyz="%s"/><parent link="link_%d"/><child link="link_%d"/>'
                    '<axis xyz="%s"/><limit lower="-3.0" upper="3.0" effort="200" velocity="10"/></joint>' % (i, _f(rpy), _f(xyz), i - 1, i, _f(axis)))
-        out.append('  <link name="link_%d"><inertial><origin rpy="0 0 0" xyz="%s"/><mass value="%r"/>'
+        irpy = _f(rng_inertial.uniform(-np.pi, np.pi, 3)) if inertial_rpy else "0 0 0"
+        out.append('  <link name="link_%d"><inertial><origin rpy="%s" xyz="%s"/><mass value="%r"/>'
                    '<inertia ixx="%r" ixy="%r" ixz="%r" iyy="%r" iyz="%r" izz="%r"/></inertial></link>'
-                   % (i, _f(com), float(mass), d[0], off[0], off[1], d[1], off[2], d[2]))
+                   % ((i, irpy, _f(com), float(mass)) + tuple(float(x) for x in (d[0], off[0], off[1], d[1], off[2], d[2]))))      # (plain floats: repr of a numpy scalar is not a number the readers parse)
     out.append('</robot>')
     return "\n".join(out) + "\n"
 
 
-def random_arm(nv, seed, tmp_dir, zaxes=False):
-    path = os.path.join(str(tmp_dir), "arm%d_%d%s.urdf" % (nv, seed, "_z" if zaxes else ""))
+def random_arm(nv, seed, tmp_dir, zaxes=False, inertial_rpy=False):
+    path = os.path.join(str(tmp_dir), "arm%d_%d%s%s.urdf" % (nv, seed, "_z" if zaxes else "", "_r" if inertial_rpy else ""))
     with open(path, "w") as f:
-        f.write(random_arm_urdf(nv, seed, zaxes))
+        f.write(random_arm_urdf(nv, seed, zaxes, inertial_rpy))
     return capi.model_from_urdf(path)
 
 

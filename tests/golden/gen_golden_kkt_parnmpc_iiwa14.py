@@ -31,15 +31,16 @@ FIELDS = ("dq", "dv", "da", "du", "dlmd", "dgmm", "dbeta")
 ITERATIONS_BEFORE = 2      # the compared iteration is the third: multipliers, slacks, duals and aux matrices off their start values, the step still large
 
 
-def problem_spec():
-    rng = np.random.default_rng(2718)
-    return {"N": 8, "T": 0.4, "q": rng.uniform(-0.6, 0.6, 7).tolist(), "v": rng.uniform(-0.5, 0.5, 7).tolist(),
-            "q_meas": rng.uniform(-0.6, 0.6, 7).tolist(), "v_meas": rng.uniform(-0.5, 0.5, 7).tolist()}
+def problem_spec(nv=7, seed=2718):
+    """the committed fixture's problem; with another nv / seed: the same for a chain of that many joints (tests/test_golden_kkt.py)"""
+    rng = np.random.default_rng(seed)
+    return {"N": 8, "T": 0.4, "q": rng.uniform(-0.6, 0.6, nv).tolist(), "v": rng.uniform(-0.5, 0.5, nv).tolist(),
+            "q_meas": rng.uniform(-0.6, 0.6, nv).tolist(), "v_meas": rng.uniform(-0.5, 0.5, nv).tolist()}
 
 
-def build(spec, Solver, **kw):
+def build(spec, Solver, model=None, **kw):
     import helpers as H
-    m = H.iiwa14_model()
+    m = H.iiwa14_model() if model is None else model
     cost, cons = H.unocp_problem(m)
     o = Solver(m, cost, cons, spec["T"], spec["N"], **kw)
     o.set_solution("q", np.array(spec["q"]))
@@ -49,18 +50,21 @@ def build(spec, Solver, **kw):
 
 
 class arm_dimensions:
-    """gen_golden_kkt_parnmpc_events.py's assembly with nv = nu = 7 (restored on exit: tests import both generators)"""
+    """gen_golden_kkt_parnmpc_events.py's assembly with nv = nu = 7, or a chain's nv (restored on exit: tests import both generators)"""
+    def __init__(self, nv=7):
+        self.nv = nv
+
     def __enter__(self):
         self.saved = (GE.NV, GE.NU, GE.NX, GE.NQ)
-        GE.NV, GE.NU, GE.NX, GE.NQ = 7, 7, 14, 7
+        GE.NV, GE.NU, GE.NX, GE.NQ = self.nv, self.nv, 2 * self.nv, self.nv
 
     def __exit__(self, *exc):
         GE.NV, GE.NU, GE.NX, GE.NQ = self.saved
 
 
-def dense_direction(o, qm, vm):
+def dense_direction(o, qm, vm, nv=7):
     """capture + coarse update on the oracle's ParNMPCSolver, then the dense solve; the solver is left in front of its correction sweeps"""
-    with arm_dimensions():
+    with arm_dimensions(nv):
         GE.prepare(o, qm, vm)
         whole, info = GE.dense_iteration(o, None, qm)
     return {f: whole[f] for f in FIELDS}, info

@@ -11,6 +11,7 @@ obtained by tests/golden/gen_golden_kkt.py from ONE DENSE SOLVE of the un-conden
 One entry of the fixture is NOT the Newton step, on purpose: on a stage that carries a switching constraint the reference forms [dbeta; dmu]
 without the Phia^T dxi term (contact_dynamics.hxx:171-190); the generator follows the reference there, by a dense solve of the two stationarity
 rows concerned, and records how far that is from the Newton value (`dense_system.newton_minus_reference_dbeta_on_switching_stages`)."""
+import functools
 import json
 import os
 import sys
@@ -158,6 +159,61 @@ def test_hip_fixed_base_direction_is_the_dense_newton_direction():
     g = second_iteration_arm(HipUnOCP, ref["spec"], batch=2)
     for inst in (0, 1):
         compare_arm({f: g.direction(f, inst) for f in GI.FIELDS}, ref, "HIP UnOCP kernels (instance %d)" % inst)
+
+
+# ---- the fixed-base path on chains that are NOT iiwa14: the dense answer computed at test time ----
+# The committed fixture covers seven +z joints.  The same dense un-condensed solve on a two-joint and an eight-joint random chain (arbitrary unit axes and
+# joint rpy; the smallest and the largest UnLaunch<nv>, the two-round linearisation form at eight) and on the committed six-joint arm, from the oracle's
+# un-condensed stage data of a problem built like GI.problem_spec().  The rigid-body terms those stage data consist of are held on these chains by
+# tests/test_independent_rbd_host.py, so the answer shares neither a condensation nor a rigid-body formula with what it checks.
+
+OTHER_CHAINS = {"random2": (2, 1), "arm6": (6, None), "random8": (8, 1)}
+
+
+def other_chain_model(which):
+    """a fresh struct every time: GI.problem / unocp_problem write the torque limits into it"""
+    import tempfile
+    from arm_chains import arm6_model, random_arm
+    nv, seed = OTHER_CHAINS[which]
+    if seed is None:
+        return arm6_model()
+    with tempfile.TemporaryDirectory() as d:
+        return random_arm(nv, seed, d)
+
+
+@functools.lru_cache(maxsize=None)
+def dense_direction_of_chain(which):
+    import ctypes as C
+    nv = OTHER_CHAINS[which][0]
+    spec = GI.problem_spec(nv, seed=7007 + nv)
+    assert spec["N"] == 6
+    o, qm, vm = GI.build(spec, OracleOCP, model=other_chain_model(which))
+    assert o.update(0.0, qm, vm) == 0
+    o.lib.oracle_ocp_keep_uncondensed.argtypes = [C.c_void_p, C.c_int]
+    o.lib.oracle_ocp_keep_uncondensed(o.h, 1)
+    assert o.update(0.0, qm, vm) == 0
+    dense, _, info = GI.dense_direction(o, spec["N"] + 1, o.get("dq")[0], o.get("dv")[0], nv=nv)
+    assert info["max_abs_residual"] < 1e-12 and info["unknowns"] == (spec["N"] + 1) * 4 * nv + spec["N"] * 3 * nv, info
+    assert (G.NV, G.NU, G.NX) == (18, 12, 36)
+    return spec, {"direction": dense}
+
+
+@pytest.mark.parametrize("which", list(OTHER_CHAINS))
+def test_both_oracle_condensations_of_other_chains_are_the_dense_newton_direction(which):
+    spec, ref = dense_direction_of_chain(which)
+    o = second_iteration_arm(OracleOCP, spec, model=other_chain_model(which))
+    compare_arm({f: o.get(f) for f in GI.FIELDS}, ref, "oracle OCPSolver on %s" % which)
+    u = second_iteration_arm(OracleUnOCP, spec, model=other_chain_model(which))
+    compare_arm({f: u.direction(f) for f in GI.FIELDS}, ref, "oracle UnOCPSolver on %s" % which)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("which", list(OTHER_CHAINS))
+def test_hip_fixed_base_direction_on_other_chains_is_the_dense_newton_direction(which):
+    spec, ref = dense_direction_of_chain(which)
+    g = second_iteration_arm(HipUnOCP, spec, model=other_chain_model(which), batch=2)
+    for inst in (0, 1):
+        compare_arm({f: g.direction(f, inst) for f in GI.FIELDS}, ref, "HIP UnOCP kernels on %s (instance %d)" % (which, inst))
 
 
 # ---- the ParNMPC stage: tests/golden/kkt_parnmpc.json (gen_golden_kkt_parnmpc.py) ----
@@ -339,6 +395,36 @@ def test_hip_whole_unparnmpc_iteration_is_the_dense_solve():
     g = direction_of_iteration(HipUnParNMPC, GA.build, ref["spec"], GA.ITERATIONS_BEFORE + 1, batch=2)
     for inst in (0, 1):
         compare_arm_iteration({f: g.get(f, inst) for f in GA.FIELDS}, ref, "HIP UnParNMPC kernels (instance %d)" % inst)
+
+
+# the whole iteration on the two-joint and the eight-joint chain, the dense answer computed at test time (GA.dense_direction with the chain's nv)
+
+@functools.lru_cache(maxsize=None)
+def dense_iteration_of_chain(which):
+    nv = OTHER_CHAINS[which][0]
+    spec = GA.problem_spec(nv, seed=2718 + nv)
+    o, qm, vm = GA.build(spec, OracleParNMPC, model=other_chain_model(which))
+    for _ in range(GA.ITERATIONS_BEFORE - 1):
+        assert o.update(0.0, qm, vm) == 0
+    dense, info = GA.dense_direction(o, qm, vm, nv=nv)
+    assert info["max_abs_residual"] < 1e-12 and info["unknowns"] == spec["N"] * 7 * nv and (GE.NV, GE.NU) == (18, 12), info
+    return spec, {"direction": dense}
+
+
+@pytest.mark.parametrize("which", ["random2", "random8"])
+def test_whole_unparnmpc_iteration_on_other_chains_is_the_dense_solve(which):
+    spec, ref = dense_iteration_of_chain(which)
+    u = direction_of_iteration(OracleUnParNMPC, functools.partial(GA.build, model=other_chain_model(which)), spec, GA.ITERATIONS_BEFORE + 1)
+    compare_arm_iteration({f: u.get(f) for f in GA.FIELDS}, ref, "oracle UnParNMPCSolver on %s" % which)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("which", ["random2", "random8"])
+def test_hip_whole_unparnmpc_iteration_on_other_chains_is_the_dense_solve(which):
+    spec, ref = dense_iteration_of_chain(which)
+    g = direction_of_iteration(HipUnParNMPC, functools.partial(GA.build, model=other_chain_model(which)), spec, GA.ITERATIONS_BEFORE + 1, batch=2)
+    for inst in (0, 1):
+        compare_arm_iteration({f: g.get(f, inst) for f in GA.FIELDS}, ref, "HIP UnParNMPC kernels on %s (instance %d)" % (which, inst))
 
 
 def compare_whole_iteration(o, M, case, what, bar):
