@@ -105,6 +105,13 @@ class RbdIO(C.Structure):
     _fields_ = [(name, C.c_void_p) for name in INPUTS + OUTPUTS]
 
 
+class RbdFdIO(C.Structure):
+    """idocp_rbd_fd_io_t: inputs and requested outputs of idocp_rbd_forward_dynamics_batch(_device); a pointer left at None is NULL"""
+    INPUTS = ("q", "v", "u", "contact_points")
+    OUTPUTS = ("a", "f", "q_next", "v_next")
+    _fields_ = [(name, C.c_void_p) for name in INPUTS + OUTPUTS]
+
+
 RBD_STAGE, RBD_IMPULSE = 0, 1
 
 
@@ -283,6 +290,14 @@ def _proto(lib):
     lib.idocp_rbd_contact_dynamics_batch.restype = ci
     lib.idocp_rbd_contact_dynamics_batch_device.argtypes = [vp, ci, ci, c_int_p, cd, P(RbdIO)]
     lib.idocp_rbd_contact_dynamics_batch_device.restype = ci
+    lib.idocp_rbd_forward_dynamics_batch.argtypes = [vp, ci, ci, c_int_p, cd, cd, P(RbdFdIO)]
+    lib.idocp_rbd_forward_dynamics_batch.restype = ci
+    lib.idocp_rbd_forward_dynamics_batch_device.argtypes = [vp, ci, ci, c_int_p, cd, cd, P(RbdFdIO)]
+    lib.idocp_rbd_forward_dynamics_batch_device.restype = ci
+    lib.idocp_rbd_rollout.argtypes = [vp, ci, ci, c_int_p, cd, cd] + [vp] * 6 + [ci]
+    lib.idocp_rbd_rollout.restype = ci
+    lib.idocp_rbd_rollout_device.argtypes = [vp, ci, ci, c_int_p, cd, cd] + [vp] * 6 + [ci]
+    lib.idocp_rbd_rollout_device.restype = ci
     for name, args in [
         ("idocp_ocp_set_contact_status_uniformly", [vp, P(ci), c_double_p]),
         ("idocp_ocp_set_solution", [vp, cs, c_double_p]),

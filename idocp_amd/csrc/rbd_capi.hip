@@ -5,6 +5,7 @@
 // There is NO CPU fallback: without a GPU idocp_rbd_create returns IDOCP_E_DEVICE.
 #include <hip/hip_runtime.h>
 
+#include <cmath>
 #include <cstring>
 #include <string>
 
@@ -38,6 +39,8 @@ struct idocp_rbd {
   size_t stage_doubles = 0;
   double* unwanted = nullptr;         // chain: where the sweep writes the outputs the caller did not ask for
   size_t unwanted_doubles = 0;
+  double* fd_chain = nullptr;         // chain, forward dynamics: [a = 0 | h | dtau_dq | dtau_dv | M] of the sweep at a = 0
+  size_t fd_chain_doubles = 0;
 };
 
 namespace {
@@ -122,6 +125,121 @@ int launch(idocp_rbd* h, int mode, int n, const int* active, double time_step, c
   return IDOCP_OK;
 }
 
+// ---- forward dynamics ----
+
+int checkForward(const char* who, const idocp_rbd* h, int mode, int n, const int* active, double time_step, double dt, const double* q, const double* v,
+                 const double* contact_points, bool contact_args) {
+  const std::string w(who);
+  if (!h) { set_last_error(w + ": null handle"); return IDOCP_E_ARG; }
+  if (n <= 0) { set_last_error(w + ": n must be positive"); return IDOCP_E_ARG; }
+  if (mode != IDOCP_RBD_STAGE && mode != IDOCP_RBD_IMPULSE) { set_last_error(w + ": unknown mode"); return IDOCP_E_ARG; }
+  if (!q || !v) { set_last_error(w + ": q and v are needed"); return IDOCP_E_ARG; }
+  if (!std::isfinite(dt)) { set_last_error(w + ": dt must be finite"); return IDOCP_E_ARG; }
+  if (!h->quadruped) {
+    if (contact_args) { set_last_error(w + ": a fixed-base chain has no contacts (f and contact_points must be NULL)"); return IDOCP_E_ARG; }
+    if (mode != IDOCP_RBD_STAGE) { set_last_error(w + ": a fixed-base chain has no impulse mode"); return IDOCP_E_ARG; }
+    return IDOCP_OK;
+  }
+  if (!active) { set_last_error(w + ": the contact status `active` is needed"); return IDOCP_E_ARG; }
+  (void)contact_points; (void)time_step;
+  return IDOCP_OK;
+}
+
+// what a STAGE solve with the given status needs beyond checkForward
+int checkStageContacts(const char* who, const idocp_rbd* h, const int* active, double time_step, const double* contact_points) {
+  if (!h->quadruped) return IDOCP_OK;
+  bool any = false;
+  for (int c = 0; c < h->model.ncontacts; ++c) any = any || active[c];
+  if (!any) return IDOCP_OK;
+  if (!contact_points) { set_last_error(std::string(who) + ": STAGE mode with an active contact needs contact_points"); return IDOCP_E_ARG; }
+  if (!(time_step > 0.0) || !std::isfinite(time_step)) {
+    set_last_error(std::string(who) + ": STAGE mode with an active contact needs a positive Baumgarte time_step"); return IDOCP_E_ARG;
+  }
+  return IDOCP_OK;
+}
+
+int maskOf(const idocp_rbd* h, const int* active) {
+  int mask = 0;
+  for (int c = 0; c < h->model.ncontacts; ++c) if (active[c]) mask |= 1 << c;
+  return mask;
+}
+
+// io: device pointers; quadruped: mask = the contact / impulse status
+int launchForward(idocp_rbd* h, int mode, int n, int mask, double time_step, double dt, const idocp_rbd_fd_io_t& io) {
+  const DevModel* d_m = static_cast<const DevModel*>(h->d_model);
+  if (h->quadruped) {
+    rbdForwardQuadruped(d_m, h->d_frames, io, n, mode, mask, time_step, dt, h->stream);
+  } else if (io.a || io.q_next || io.v_next) {
+    const size_t nv = h->model.nv, nvec = (size_t)n * nv, nmat = nvec * nv;
+    if (2 * nvec + 3 * nmat > h->fd_chain_doubles) {
+      int rc = growBuffer(&h->fd_chain, &h->fd_chain_doubles, 2 * nvec + 3 * nmat, h->stream); if (rc) return rc;
+    }
+    double *zero = h->fd_chain, *hh = zero + nvec, *dq = hh + nvec, *dv = dq + nmat, *M = dv + nmat;
+    if (io.a || io.v_next) {
+      HIP_TRY(hipMemsetAsync(zero, 0, sizeof(double) * nvec, h->stream));
+      chainFn(h->model.nv)(d_m, n, io.q, io.v, zero, hh, dq, dv, M, h->zaxes, h->stream);
+      HIP_TRY(hipGetLastError());
+    }
+    rbdForwardChainSolve(h->model.nv, n, hh, M, io.q, io.v, io.u, dt, io.a, io.q_next, io.v_next, h->stream);
+  }
+  HIP_TRY(hipGetLastError());
+  return IDOCP_OK;
+}
+
+// doubles per sample of every field of idocp_rbd_fd_io_t, in the order of the struct
+struct FdSizes { size_t in[4], out[4]; };
+FdSizes fdSizes(const idocp_rbd* h) {
+  const size_t nq = h->model.nq, nv = h->model.nv, nu = h->model.nu, nf = 3 * (size_t)h->model.ncontacts;
+  return {{nq, nv, nu, nf}, {nv, nf, nq, nv}};
+}
+size_t even(size_t x) { return (x + 1) / 2 * 2; }
+
+int checkForwardCall(idocp_rbd* h, int mode, int n, const int* active, double time_step, double dt, const idocp_rbd_fd_io_t* io) {
+  const char* who = "idocp_rbd_forward_dynamics_batch";
+  if (!io) { set_last_error(std::string(who) + ": null io"); return IDOCP_E_ARG; }
+  int rc = checkForward(who, h, mode, n, active, time_step, dt, io->q, io->v, io->contact_points, io->f || io->contact_points); if (rc) return rc;
+  if (mode == IDOCP_RBD_STAGE) { rc = checkStageContacts(who, h, active, time_step, io->contact_points); if (rc) return rc; }
+  return IDOCP_OK;
+}
+
+// the schedule of a rollout: per step the stage mask and the mask of the touchdown impulse in front of it (0: none)
+int checkRollout(idocp_rbd* h, int n, int steps, const int* active, double time_step, double dt, const double* contact_points, const double* q_traj,
+                 const double* v_traj, const double* f_traj) {
+  const char* who = "idocp_rbd_rollout";
+  if (steps < 1) { set_last_error(std::string(who) + ": steps must be at least 1"); return IDOCP_E_ARG; }
+  int rc = checkForward(who, h, IDOCP_RBD_STAGE, n, active, time_step, dt, q_traj, v_traj, contact_points, f_traj || contact_points);
+  if (rc) return rc;
+  if (h->quadruped)
+    for (int k = 0; k < steps; ++k) { rc = checkStageContacts(who, h, active + (size_t)k * h->model.ncontacts, time_step, contact_points); if (rc) return rc; }
+  return IDOCP_OK;
+}
+
+// every pointer: device memory
+int rolloutDevice(idocp_rbd* h, int n, int steps, const int* active, double time_step, double dt, const double* u, const double* contact_points,
+                  double* q_traj, double* v_traj, double* a_traj, double* f_traj, int touchdown_impulse) {
+  const size_t nq = h->model.nq, nv = h->model.nv, nu = h->model.nu, nf = 3 * (size_t)h->model.ncontacts, N = (size_t)n;
+  int prev = 0;
+  for (int k = 0; k < steps; ++k) {
+    const int mask = h->quadruped ? maskOf(h, active + (size_t)k * h->model.ncontacts) : 0;
+    double *qk = q_traj + k * N * nq, *vk = v_traj + k * N * nv;
+    if (touchdown_impulse && k > 0 && (mask & ~prev)) {
+      idocp_rbd_fd_io_t imp = idocp_rbd_fd_io_t();
+      imp.q = qk; imp.v = vk; imp.v_next = vk;            // (in place: slice k becomes the post-impulse velocity)
+      int rc = launchForward(h, IDOCP_RBD_IMPULSE, n, mask & ~prev, time_step, dt, imp); if (rc) return rc;
+    }
+    idocp_rbd_fd_io_t io = idocp_rbd_fd_io_t();
+    io.q = qk; io.v = vk;
+    io.u = u ? u + k * N * nu : nullptr;
+    io.contact_points = contact_points ? contact_points + k * N * nf : nullptr;
+    io.a = a_traj ? a_traj + k * N * nv : nullptr;
+    io.f = f_traj ? f_traj + k * N * nf : nullptr;
+    io.q_next = qk + N * nq; io.v_next = vk + N * nv;
+    int rc = launchForward(h, IDOCP_RBD_STAGE, n, mask, time_step, dt, io); if (rc) return rc;
+    prev = mask;
+  }
+  return IDOCP_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -168,6 +286,7 @@ void idocp_rbd_destroy(idocp_rbd_t* h) {
   if (h->d_model) (void)hipFree(h->d_model);
   if (h->stage) (void)hipFree(h->stage);
   if (h->unwanted) (void)hipFree(h->unwanted);
+  if (h->fd_chain) (void)hipFree(h->fd_chain);
   if (h->stream) (void)hipStreamDestroy(h->stream);
   delete h;
 }
@@ -212,6 +331,74 @@ int idocp_rbd_contact_dynamics_batch(idocp_rbd_t* h, int mode, int n, const int*
   rc = launch(h, mode, n, active, time_step, d); if (rc) return rc;
   for (int i = 0; i < 9; ++i) if (host_out[i])
     HIP_TRY(hipMemcpyAsync(host_out[i], dev_out[i], sizeof(double) * fs.out[i] * n, hipMemcpyDeviceToHost, h->stream));
+  HIP_TRY(hipStreamSynchronize(h->stream));
+  return IDOCP_OK;
+}
+
+int idocp_rbd_forward_dynamics_batch_device(idocp_rbd_t* h, int mode, int n, const int* active, double time_step, double dt, const idocp_rbd_fd_io_t* io) {
+  int rc = checkForwardCall(h, mode, n, active, time_step, dt, io); if (rc) return rc;
+  HIP_TRY(hipSetDevice(h->device));
+  return launchForward(h, mode, n, h->quadruped ? maskOf(h, active) : 0, time_step, dt, *io);
+}
+
+int idocp_rbd_forward_dynamics_batch(idocp_rbd_t* h, int mode, int n, const int* active, double time_step, double dt, const idocp_rbd_fd_io_t* io) {
+  int rc = checkForwardCall(h, mode, n, active, time_step, dt, io); if (rc) return rc;
+  HIP_TRY(hipSetDevice(h->device));
+  const FdSizes fs = fdSizes(h);
+  const double* const host_in[4] = {io->q, io->v, io->u, io->contact_points};
+  double* const host_out[4] = {io->a, io->f, io->q_next, io->v_next};
+  size_t total = 0;
+  for (int i = 0; i < 4; ++i) if (host_in[i]) total += even(fs.in[i] * n);
+  for (int i = 0; i < 4; ++i) if (host_out[i]) total += even(fs.out[i] * n);
+  rc = growBuffer(&h->stage, &h->stage_doubles, total, h->stream); if (rc) return rc;
+  const double* dev_in[4] = {nullptr, nullptr, nullptr, nullptr};
+  double* dev_out[4] = {nullptr, nullptr, nullptr, nullptr};
+  double* cur = h->stage;
+  for (int i = 0; i < 4; ++i) if (host_in[i]) {
+    HIP_TRY(hipMemcpyAsync(cur, host_in[i], sizeof(double) * fs.in[i] * n, hipMemcpyHostToDevice, h->stream));
+    dev_in[i] = cur; cur += even(fs.in[i] * n);
+  }
+  for (int i = 0; i < 4; ++i) if (host_out[i]) { dev_out[i] = cur; cur += even(fs.out[i] * n); }
+  idocp_rbd_fd_io_t d;
+  d.q = dev_in[0]; d.v = dev_in[1]; d.u = dev_in[2]; d.contact_points = dev_in[3];
+  d.a = dev_out[0]; d.f = dev_out[1]; d.q_next = dev_out[2]; d.v_next = dev_out[3];
+  rc = launchForward(h, mode, n, h->quadruped ? maskOf(h, active) : 0, time_step, dt, d); if (rc) return rc;
+  for (int i = 0; i < 4; ++i) if (host_out[i])
+    HIP_TRY(hipMemcpyAsync(host_out[i], dev_out[i], sizeof(double) * fs.out[i] * n, hipMemcpyDeviceToHost, h->stream));
+  HIP_TRY(hipStreamSynchronize(h->stream));
+  return IDOCP_OK;
+}
+
+int idocp_rbd_rollout_device(idocp_rbd_t* h, int n, int steps, const int* active, double time_step, double dt, const double* u, const double* contact_points,
+                             double* q_traj, double* v_traj, double* a_traj, double* f_traj, int touchdown_impulse) {
+  int rc = checkRollout(h, n, steps, active, time_step, dt, contact_points, q_traj, v_traj, f_traj); if (rc) return rc;
+  HIP_TRY(hipSetDevice(h->device));
+  return rolloutDevice(h, n, steps, active, time_step, dt, u, contact_points, q_traj, v_traj, a_traj, f_traj, touchdown_impulse);
+}
+
+int idocp_rbd_rollout(idocp_rbd_t* h, int n, int steps, const int* active, double time_step, double dt, const double* u, const double* contact_points,
+                      double* q_traj, double* v_traj, double* a_traj, double* f_traj, int touchdown_impulse) {
+  int rc = checkRollout(h, n, steps, active, time_step, dt, contact_points, q_traj, v_traj, f_traj); if (rc) return rc;
+  HIP_TRY(hipSetDevice(h->device));
+  const size_t nq = h->model.nq, nv = h->model.nv, nu = h->model.nu, nf = 3 * (size_t)h->model.ncontacts, N = (size_t)n, S = (size_t)steps;
+  // [q_traj | v_traj | u | contact_points | a_traj | f_traj]: staged once, read back once
+  const size_t sz[6] = {(S + 1) * N * nq, (S + 1) * N * nv, u ? S * N * nu : 0, contact_points ? S * N * nf : 0, a_traj ? S * N * nv : 0, f_traj ? S * N * nf : 0};
+  size_t total = 0;
+  for (int i = 0; i < 6; ++i) total += even(sz[i]);
+  rc = growBuffer(&h->stage, &h->stage_doubles, total, h->stream); if (rc) return rc;
+  double* dev[6];
+  double* cur = h->stage;
+  for (int i = 0; i < 6; ++i) { dev[i] = sz[i] ? cur : nullptr; cur += even(sz[i]); }
+  HIP_TRY(hipMemcpyAsync(dev[0], q_traj, sizeof(double) * N * nq, hipMemcpyHostToDevice, h->stream));
+  HIP_TRY(hipMemcpyAsync(dev[1], v_traj, sizeof(double) * N * nv, hipMemcpyHostToDevice, h->stream));
+  if (u) HIP_TRY(hipMemcpyAsync(dev[2], u, sizeof(double) * sz[2], hipMemcpyHostToDevice, h->stream));
+  if (contact_points) HIP_TRY(hipMemcpyAsync(dev[3], contact_points, sizeof(double) * sz[3], hipMemcpyHostToDevice, h->stream));
+  rc = rolloutDevice(h, n, steps, active, time_step, dt, dev[2], dev[3], dev[0], dev[1], dev[4], dev[5], touchdown_impulse); if (rc) return rc;
+  // (slice 0 of v_traj comes back too; it is the input)
+  HIP_TRY(hipMemcpyAsync(q_traj + N * nq, dev[0] + N * nq, sizeof(double) * S * N * nq, hipMemcpyDeviceToHost, h->stream));
+  HIP_TRY(hipMemcpyAsync(v_traj + N * nv, dev[1] + N * nv, sizeof(double) * S * N * nv, hipMemcpyDeviceToHost, h->stream));
+  if (a_traj) HIP_TRY(hipMemcpyAsync(a_traj, dev[4], sizeof(double) * sz[4], hipMemcpyDeviceToHost, h->stream));
+  if (f_traj) HIP_TRY(hipMemcpyAsync(f_traj, dev[5], sizeof(double) * sz[5], hipMemcpyDeviceToHost, h->stream));
   HIP_TRY(hipStreamSynchronize(h->stream));
   return IDOCP_OK;
 }

@@ -19,5 +19,14 @@ constexpr int RBD_WAVES = 2;
 void rbdBatchQuadruped(const DevModel* m, const RbdFrames* frames, const idocp_rbd_io_t& io, int n, int mode, int active_mask,
                        double time_step, hipStream_t st);
 
+// Forward dynamics (rbd_forward_kernel.hip), same shape of launch.  io: DEVICE pointers.  STAGE: (a, f) from (q, v, u); IMPULSE: (dv, lambda)
+// from (q, v); optionally the explicit Euler step over dt.
+void rbdForwardQuadruped(const DevModel* m, const RbdFrames* frames, const idocp_rbd_fd_io_t& io, int n, int mode, int active_mask,
+                         double time_step, double dt, hipStream_t st);
+// Fixed-base chain of nv = 2 .. 8 joints: a = M^-1 (u - h) from h [n][nv] and the column-major M [n][nv * nv] the chain sweep left at a = 0
+// (Cholesky solve, one lane per sample), then the step q + dt v, v + dt a.  Any of a, q_next, v_next may be NULL.
+void rbdForwardChainSolve(int nv, int n, const double* h, const double* M, const double* q, const double* v, const double* u, double dt,
+                          double* a, double* q_next, double* v_next, hipStream_t st);
+
 }  // namespace idocp_dev
 #endif  // IDOCP_RBD_LAUNCH_HPP_

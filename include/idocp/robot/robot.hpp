@@ -170,6 +170,58 @@ class Robot {
     packMatrix(act, dimf, io.dCdq, velocity_partial_dq, "velocity_partial_dq");
     packMatrix(act, dimf, io.dCdv, velocity_partial_dv, "velocity_partial_dv");
   }
+  // ---- Forward dynamics: ADDITIONS the reference's Robot does not have (it only evaluates the inverse direction).  Each is ONE n = 1 call of
+  // idocp_rbd_forward_dynamics_batch (idocp_hip.h) on the same lazily created handle.
+  // (a, f) for which RNEA gives [0_6; u] (u on a fixed-base robot) and the Baumgarte residual vanishes on the active contacts; the contact points are
+  // those of contact_status; f[i] in the local coordinates of contact frame i, zero where inactive.  u: the nu joint torques.
+  void forwardDynamics(const Eigen::VectorXd& q, const Eigen::VectorXd& v, const Eigen::VectorXd& u, const ContactStatus& contact_status,
+                       const double time_step, Eigen::VectorXd& a, std::vector<Eigen::Vector3d>& f) {
+    sized(q, model_.nq, "q"); sized(v, model_.nv, "v"); sized(u, model_.nu, "u");
+    if (a.size() != model_.nv) a.resize(model_.nv);
+    double pts[3 * IDOCP_MAX_CONTACTS] = {}, fo[3 * IDOCP_MAX_CONTACTS] = {};
+    int act[IDOCP_MAX_CONTACTS] = {};
+    idocp_rbd_fd_io_t io = idocp_rbd_fd_io_t();
+    io.q = q.data(); io.v = v.data(); io.u = u.data(); io.a = a.data();
+    if (model_.ncontacts > 0) {
+      activeOf(contact_status.isContactActive(), act);
+      for (int c = 0; c < model_.ncontacts; ++c) for (int k = 0; k < 3; ++k) pts[3 * c + k] = contact_status.contactPoints()[c][k];
+      io.contact_points = pts; io.f = fo;
+    }
+    fdCall(IDOCP_RBD_STAGE, act, time_step, 0.0, io);
+    f.resize(model_.ncontacts);
+    for (int c = 0; c < model_.ncontacts; ++c) for (int k = 0; k < 3; ++k) f[c][k] = fo[3 * c + k];
+  }
+  // (dv, lambda) for which RNEAImpulse vanishes and the velocity of the impulse_status's frames is zero at v + dv
+  void impulseDynamics(const Eigen::VectorXd& q, const Eigen::VectorXd& v, const ImpulseStatus& impulse_status, Eigen::VectorXd& dv,
+                       std::vector<Eigen::Vector3d>& lambda) {
+    noContacts(); sized(q, model_.nq, "q"); sized(v, model_.nv, "v");
+    if (dv.size() != model_.nv) dv.resize(model_.nv);
+    double lo[3 * IDOCP_MAX_CONTACTS] = {};
+    int act[IDOCP_MAX_CONTACTS] = {};
+    activeOf(impulse_status.isImpulseActive(), act);
+    idocp_rbd_fd_io_t io = idocp_rbd_fd_io_t();
+    io.q = q.data(); io.v = v.data(); io.a = dv.data(); io.f = lo;
+    fdCall(IDOCP_RBD_IMPULSE, act, 0.0, 0.0, io);
+    lambda.resize(model_.ncontacts);
+    for (int c = 0; c < model_.ncontacts; ++c) for (int k = 0; k < 3; ++k) lambda[c][k] = lo[3 * c + k];
+  }
+  // the explicit Euler step of the OCP's own discretisation (state_equation.hxx) on the GPU: q_next = q (+) dt v, v_next = v + dt a
+  void stepForwardEuler(const Eigen::VectorXd& q, const Eigen::VectorXd& v, const Eigen::VectorXd& u, const ContactStatus& contact_status,
+                        const double time_step, const double dt, Eigen::VectorXd& q_next, Eigen::VectorXd& v_next) {
+    sized(q, model_.nq, "q"); sized(v, model_.nv, "v"); sized(u, model_.nu, "u");
+    Eigen::VectorXd qn(model_.nq), vn(model_.nv);      // (q_next / v_next may be q / v)
+    double pts[3 * IDOCP_MAX_CONTACTS] = {};
+    int act[IDOCP_MAX_CONTACTS] = {};
+    idocp_rbd_fd_io_t io = idocp_rbd_fd_io_t();
+    io.q = q.data(); io.v = v.data(); io.u = u.data(); io.q_next = qn.data(); io.v_next = vn.data();
+    if (model_.ncontacts > 0) {
+      activeOf(contact_status.isContactActive(), act);
+      for (int c = 0; c < model_.ncontacts; ++c) for (int k = 0; k < 3; ++k) pts[3 * c + k] = contact_status.contactPoints()[c][k];
+      io.contact_points = pts;
+    }
+    fdCall(IDOCP_RBD_STAGE, act, time_step, dt, io);
+    q_next = qn; v_next = vn;
+  }
   // Robot::framePosition / frameRotation / framePlacement (robot.hxx:206-233): of any frame of the URDF (pinocchio's frame numbering, as the
   // contact frames and the task-space costs use it), at the configuration of the last updateFrameKinematics / updateKinematics
   Eigen::Vector3d framePosition(const int frame_id) const { return framePlacement(frame_id).translation(); }
@@ -278,6 +330,10 @@ class Robot {
   void rbdCall(int mode, const int* active, double time_step, const idocp_rbd_io_t& io) const {
     if (!rbd_.h) ok(idocp_rbd_create(&model_, 0, &rbd_.h));
     ok(idocp_rbd_contact_dynamics_batch(rbd_.h, mode, 1, model_.ncontacts > 0 ? active : nullptr, time_step, &io));
+  }
+  void fdCall(int mode, const int* active, double time_step, double dt, const idocp_rbd_fd_io_t& io) const {
+    if (!rbd_.h) ok(idocp_rbd_create(&model_, 0, &rbd_.h));
+    ok(idocp_rbd_forward_dynamics_batch(rbd_.h, mode, 1, model_.ncontacts > 0 ? active : nullptr, time_step, dt, &io));
   }
   idocp_rbd_io_t dynamicsIO(const double* q, const double* v, const double* a, const double* f) const {
     idocp_rbd_io_t io = idocp_rbd_io_t();

@@ -798,6 +798,50 @@ int idocp_rbd_contact_dynamics_batch(idocp_rbd_t* h, int mode, int n, const int*
 /* Asynchronous on idocp_rbd_stream(h); allocates nothing on a quadruped, and on a chain only when n grows. */
 int idocp_rbd_contact_dynamics_batch_device(idocp_rbd_t* h, int mode, int n, const int* active, double time_step, const idocp_rbd_io_t* io);
 
+/* ---- Forward dynamics with contacts, the explicit Euler step and a rollout (an ADDITION: the reference has no counterpart; it only ever
+ * evaluates the inverse direction).  Defined through the call above:
+ *   STAGE    (a, f) is the pair for which idocp_rbd_contact_dynamics_batch(STAGE, q, v, a, f) returns tau = S^T u ([0_6; u] on a quadruped, u
+ *            on a chain) and C = 0 on the active rows:  [M J^T; J 0] [a; -f] = [S^T u - h; -b],  h = ID(q, v, 0, 0), b = C(q, v, 0).
+ *   IMPULSE  (dv, lambda) is the pair for which the IMPULSE call returns tau = 0 and a zero impulse-velocity constraint at v + dv on the
+ *            active rows:  [M J^T; J 0] [dv; -lambda] = [0; -J v].  u is ignored.
+ * A fixed-base chain has STAGE mode only, a = M^-1 (u - h); f and contact_points must be NULL.  The 42 x 42 inverse is never formed: M^-1 by
+ * the block-arrow inverse, one Cholesky solve of J M^-1 J^T over the active rows.  Where M or J M^-1 J^T is not positive definite every
+ * output of that sample is NaN (the convention of MJtJinv).
+ * Outputs left NULL are neither computed nor stored.  q_next may be the very pointer q and v_next the very pointer v (a sample's q and v are
+ * read completely before anything of that sample is written); no other overlap of inputs and outputs is allowed. */
+typedef struct idocp_rbd_fd_io {
+  const double *q, *v;           /* [n][nq], [n][nv] */
+  const double *u;               /* [n][nu] joint torques; NULL = 0; ignored in IMPULSE mode */
+  const double *contact_points;  /* [n][ncontacts][3]; needed in STAGE mode with an active contact */
+  double *a;                     /* [n][nv]: STAGE the acceleration, IMPULSE the velocity jump dv */
+  double *f;                     /* [n][ncontacts][3], local contact-frame coordinates, zero where inactive; IMPULSE: the impulse lambda */
+  double *q_next, *v_next;       /* [n][nq], [n][nv]: the explicit Euler step of the OCP's own discretisation over dt (state_equation.hxx):
+                                  * STAGE q (+) dt v (the SE(3) retraction of idocp_model_integrate_configuration on a floating base, the
+                                  * quaternion normalised like there), v + dt a; IMPULSE q, v + dv */
+} idocp_rbd_fd_io_t;
+/* active[ncontacts]: contact (STAGE) or impulse (IMPULSE) status shared by the n samples, NULL on a chain; time_step: the Baumgarte time step
+ * (positive in STAGE mode with an active contact); dt: the integration step (finite; only q_next / v_next see it). */
+int idocp_rbd_forward_dynamics_batch(idocp_rbd_t* h, int mode, int n, const int* active, double time_step, double dt, const idocp_rbd_fd_io_t* io);
+/* Device pointers, asynchronous on idocp_rbd_stream(h); allocates nothing on a quadruped, and on a chain only when n grows. */
+int idocp_rbd_forward_dynamics_batch_device(idocp_rbd_t* h, int mode, int n, const int* active, double time_step, double dt,
+                                            const idocp_rbd_fd_io_t* io);
+
+/* `steps` forward-dynamics launches with the Euler step, chained on the handle's stream without a synchronisation in between.  Step-major
+ * arrays, so that every step reads and writes one contiguous slice:
+ *   q_traj [steps + 1][n][nq], v_traj [steps + 1][n][nv] (slice 0 is the input), u [steps][n][nu] (NULL = 0), optional a_traj [steps][n][nv],
+ *   f_traj [steps][n][ncontacts][3]; active [steps][ncontacts] (shared by the n samples; NULL on a chain), contact_points
+ *   [steps][n][ncontacts][3] (NULL on a chain).
+ * touchdown_impulse != 0: a step k >= 1 whose status activates contacts that the status of step k - 1 did not have is preceded by one IMPULSE
+ * solve whose impulse status is exactly the newly active contacts (what DiscreteEvent::setDiscreteEvent makes of the two statuses).  The
+ * stored slice k of v_traj is then the POST-impulse velocity, i.e. the velocity the Euler step k is applied from (slice k was the
+ * pre-impulse velocity until then; it is overwritten in place), and v_traj[k + 1] = v_traj[k] + dt a_traj[k] holds for every k.  The impulse
+ * itself is not returned.  Step 0 never takes an impulse.
+ * The host form stages everything once and reads back once; the device form allocates nothing on a quadruped. */
+int idocp_rbd_rollout(idocp_rbd_t* h, int n, int steps, const int* active, double time_step, double dt, const double* u,
+                      const double* contact_points, double* q_traj, double* v_traj, double* a_traj, double* f_traj, int touchdown_impulse);
+int idocp_rbd_rollout_device(idocp_rbd_t* h, int n, int steps, const int* active, double time_step, double dt, const double* u,
+                             const double* contact_points, double* q_traj, double* v_traj, double* a_traj, double* f_traj, int touchdown_impulse);
+
 const char* idocp_last_error(void);
 const char* idocp_version(void);
 

@@ -1,7 +1,8 @@
-"""Throughput of the batched rigid-body API (idocp_rbd_contact_dynamics_batch_device): ANYmal, four active contacts,
+"""Throughput of the batched rigid-body API (idocp_rbd_contact_dynamics_batch_device and idocp_rbd_forward_dynamics_batch_device): ANYmal, four active contacts,
 device pointers, n = 122 880 samples per launch by default (the stage count of the headline step: 1 024 instances x 120 stages).  Every launch is
 bracketed by HIP events on the handle's stream after warm-up launches; prints one JSON line with the median / min / max ms per launch and the
-samples per second of each output selection.
+samples per second of each output selection.  The fd_* rows are the forward dynamics: stage mode (a and f out) and impulse mode (dv and lambda out),
+without and with the Euler step; stage_da_mjtjinv is what a caller needed for the same answer before that call existed.
 
     python profiles/rbd_throughput.py [--n 122880] [--launches 20] [--warmup 5]
 """
@@ -22,6 +23,11 @@ SELECTIONS = (("stage_all", capi.RBD_STAGE, capi.RbdIO.OUTPUTS),
               ("stage_da_mjtjinv", capi.RBD_STAGE, ("tau", "dtau_da", "C", "dCda", "MJtJinv")),
               ("stage_tau_C", capi.RBD_STAGE, ("tau", "C")),
               ("impulse_all", capi.RBD_IMPULSE, capi.RbdIO.OUTPUTS))
+
+FD_SELECTIONS = (("fd_stage_a_f", capi.RBD_STAGE, ("a", "f")),
+                 ("fd_stage_a_f_step", capi.RBD_STAGE, ("a", "f", "q_next", "v_next")),
+                 ("fd_impulse_dv_lambda", capi.RBD_IMPULSE, ("a", "f")),
+                 ("fd_impulse_dv_lambda_step", capi.RBD_IMPULSE, ("a", "f", "q_next", "v_next")))
 
 
 def main():
@@ -50,6 +56,9 @@ def main():
             "contact_points": rng.uniform(-0.5, 0.5, (n, nf))}
     sizes = {"tau": nv, "dtau_dq": nv * nv, "dtau_dv": nv * nv, "dtau_da": nv * nv, "C": nf, "dCdq": nf * nv, "dCdv": nf * nv, "dCda": nf * nv,
              "MJtJinv": (nv + nf) ** 2}
+    host["u"] = rng.uniform(-20, 20, (n, m.nu))
+    fd_sizes = {"fd_a": nv, "fd_f": nf, "fd_q_next": nq, "fd_v_next": nv}
+    sizes.update(fd_sizes)
     dev = {}
     for k, x in host.items():
         dev[k] = C.c_void_p()
@@ -66,11 +75,19 @@ def main():
         assert rt.hipEventCreate(C.byref(e)) == 0
         events.append(e)
     res = {"n": n, "launches": args.launches, "warmup": args.warmup}
-    for name, mode, outputs in SELECTIONS:
-        io = capi.RbdIO()
-        for k in capi.RbdIO.INPUTS + tuple(outputs):
-            setattr(io, k, dev[k])
-        launch = lambda: capi.check(lib.idocp_rbd_contact_dynamics_batch_device(h, mode, n, active, 0.05, C.byref(io)), name)  # noqa: E731
+    for name, mode, outputs in SELECTIONS + FD_SELECTIONS:
+        if name.startswith("fd_"):
+            io = capi.RbdFdIO()
+            for k in capi.RbdFdIO.INPUTS:
+                setattr(io, k, dev[k])
+            for k in outputs:
+                setattr(io, k, dev["fd_" + k])
+            launch = lambda: capi.check(lib.idocp_rbd_forward_dynamics_batch_device(h, mode, n, active, 0.05, 0.01, C.byref(io)), name)  # noqa: E731
+        else:
+            io = capi.RbdIO()
+            for k in capi.RbdIO.INPUTS + tuple(outputs):
+                setattr(io, k, dev[k])
+            launch = lambda: capi.check(lib.idocp_rbd_contact_dynamics_batch_device(h, mode, n, active, 0.05, C.byref(io)), name)  # noqa: E731
         for _ in range(args.warmup):
             launch()
         capi.check(lib.idocp_rbd_synchronize(h), "synchronize")
@@ -89,6 +106,9 @@ def main():
     tau = np.zeros((n, nv))
     capi.check(lib.idocp_device_download(tau.ctypes.data, dev["tau"], tau.nbytes), "download")
     res["tau_finite"] = bool(np.isfinite(tau).all())
+    acc = np.zeros((n, nv))
+    capi.check(lib.idocp_device_download(acc.ctypes.data, dev["fd_a"], acc.nbytes), "download")
+    res["fd_a_finite"] = bool(np.isfinite(acc).all())
     for d in dev.values():
         lib.idocp_device_free(d)
     lib.idocp_rbd_destroy(h)
