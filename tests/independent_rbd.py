@@ -116,7 +116,7 @@ def quadruped(seed):
     """(perturbed struct, its model dict, (q, v, a, f, pts), terms with all four contacts) of other_quadruped(seed), the samples drawn the way the
     `other` fixture of test_rbd_batch_gpu.py draws its own"""
     from test_other_quadrupeds_gpu import other_quadruped
-    from test_rbd_batch_gpu import random_samples
+    from rbd_batch import random_samples
     m, rng = other_quadruped(seed)
     M = model_from_struct(m)
     q, v, a, f, pts = random_samples(rng, QUADRUPED_SAMPLES)

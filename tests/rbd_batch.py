@@ -1,13 +1,16 @@
-"""Shared by test_rbd_batch_gpu.py / test_rbd_batch_host.py: a thin wrapper of the idocp_rbd_* handle (include/idocp_hip.h)."""
+"""Shared by test_rbd_batch_gpu.py / test_rbd_batch_host.py and the other rigid-body tests: a thin wrapper of the idocp_rbd_* handle
+(include/idocp_hip.h), the random quadruped samples and the oracle's answers for one sample.  A plain module: CPU tests import it too."""
 import ctypes as C
 
 import numpy as np
 
+from helpers import P, arr
 from idocp_amd import capi
 
 E_ARG, E_DEVICE, E_UNSUPPORTED = -1, -3, -4
 STAGE, IMPULSE = capi.RBD_STAGE, capi.RBD_IMPULSE
 ALL_OUTPUTS = capi.RbdIO.OUTPUTS
+NV, NQ, NF = 18, 19, 12      # the quadrupeds
 
 
 def out_shapes(m):
@@ -77,3 +80,28 @@ def packed_mjtjinv(slot, nv, dimf):
     """the packed (nv + dimf)^2 column-major block at the start of a slot, as [row, column]"""
     n = nv + dimf
     return np.asarray(slot)[:n * n].reshape(n, n).T
+
+
+def random_samples(rng, n):
+    q = np.zeros((n, NQ))
+    q[:, :3] = rng.uniform(-0.5, 0.5, (n, 3))
+    quat = rng.normal(size=(n, 4))
+    q[:, 3:7] = quat / np.linalg.norm(quat, axis=1, keepdims=True)
+    q[:, 7:] = rng.uniform(-1.0, 1.0, (n, 12))
+    return q, rng.uniform(-1, 1, (n, NV)), rng.uniform(-2, 2, (n, NV)), rng.uniform(-30, 30, (n, 4, 3)), rng.uniform(-0.5, 0.5, (n, 4, 3))
+
+
+def oracle_terms(lib, m, q, v, a, f, pts, dt):
+    """every output of both modes for ONE sample from the oracle's entry points, matrices as [row, column]"""
+    mat = lambda rows: np.zeros((NV, rows))      # noqa: E731  (column-major rows x NV)
+    o = {"tau": np.zeros(NV), "dtau_dq": mat(NV), "dtau_dv": mat(NV), "dtau_da": mat(NV), "C": np.zeros(NF), "dCdq": mat(NF), "dCdv": mat(NF), "dCda": mat(NF),
+         "MJtJinv": np.zeros((NV + NF, NV + NF))}
+    pm, q, v, a, f, pts = C.byref(m), arr(q), arr(v), arr(a), arr(f), arr(pts)
+    lib.oracle_rnea(pm, P(q), P(v), P(a), P(f), 1, P(o["tau"]))
+    lib.oracle_rnea_derivatives(pm, P(q), P(v), P(a), P(f), 1, P(o["dtau_dq"]), P(o["dtau_dv"]), P(o["dtau_da"]))
+    junk = [np.zeros(4 * 6 * NV) for _ in range(8)]
+    lib.oracle_contact_kinematics(pm, P(q), P(v), P(a), P(pts), dt, P(o["C"]), P(o["dCdq"]), P(o["dCdv"]), P(o["dCda"]), *[P(j) for j in junk], P(o["MJtJinv"]))
+    i = {"tau": np.zeros(NV), "dtau_dq": mat(NV), "dtau_da": mat(NV), "C": np.zeros(NF), "dCdq": mat(NF), "dCdv": mat(NF)}
+    lib.oracle_impulse_terms(pm, P(q), P(v), P(a), P(f), P(i["tau"]), P(i["dtau_dq"]), P(i["dtau_da"]), P(i["C"]), P(i["dCdq"]), P(i["dCdv"]))
+    T = lambda d: {k: (x.T.copy() if x.ndim == 2 else x) for k, x in d.items()}      # noqa: E731
+    return T(o), T(i)

@@ -8,7 +8,7 @@ test_independent_rbd_host.py holds the URDF reader and the oracle to.
 
 Elsewhere these paths are checked against the oracle, which reads the same model struct and was extended to general geometry together with the kernels; an
 error the two share (an rpy convention, a general axis in the analytic derivatives, an inertial rotation) shows only here.  The impulse-mode contact rows
-(impulse velocity and its derivatives) have no counterpart in the independent model and stay held by the oracle (test_rbd_batch_gpu.py)."""
+(impulse velocity and its derivatives), every contact set and the hard states: test_rbd_contact_sets_gpu.py."""
 import ctypes as C
 
 import numpy as np

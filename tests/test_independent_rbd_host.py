@@ -5,7 +5,7 @@ tests/test_golden_rbd.py pins reader and oracle on iiwa14 (every axis +z) and AN
 specialised instantiations for.  Here: fixed-base chains of 2 .. 8 joints with arbitrary unit axes and joint rpy (test_other_arms_gpu.CHAINS), the same
 chains with an inertial rpy on every link, the committed six-joint arm, and quadrupeds that exist only as a perturbed struct (other_quadruped(0..2)) --
 the models on which the oracle alone checks the kernels everywhere else.  test_independent_rbd_gpu.py holds the kernels to the same answers at the same
-bars.  The impulse-mode contact rows (impulse velocity and its derivatives) have no counterpart in the independent model and stay held by the oracle."""
+bars.  The impulse-mode contact rows (impulse velocity and its derivatives) are held to the independent model in test_rbd_contact_sets_host.py / _gpu.py."""
 import ctypes as C
 
 import numpy as np
@@ -13,7 +13,7 @@ import pytest
 
 import independent_rbd as IR
 from helpers import P, arr, oracle, rel_err
-from test_rbd_batch_gpu import oracle_terms
+from rbd_batch import oracle_terms
 
 # (id, nv, seed, zaxes, inertial rpy); nv = 0: the committed six-joint arm
 CHAIN_MODELS = ([(name, nv, seed, z, False) for name, nv, seed, z in IR.chain_cases()]

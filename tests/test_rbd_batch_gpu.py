@@ -13,7 +13,8 @@ import pytest
 from arm_chains import arm6_model
 from helpers import GOLDEN, ROOT, P, anymal_model, arr, iiwa14_model, oracle, rel_err
 from idocp_amd import capi
-from rbd_batch import ALL_OUTPUTS, E_ARG, IMPULSE, STAGE, DeviceArray, Rbd, out_shapes, packed_mjtjinv
+from rbd_batch import (ALL_OUTPUTS, E_ARG, IMPULSE, STAGE, DeviceArray, Rbd, oracle_terms, out_shapes, packed_mjtjinv,      # noqa: F401
+                       random_samples)
 from test_other_quadrupeds_gpu import other_quadruped
 
 pytestmark = pytest.mark.gpu
@@ -56,31 +57,6 @@ def test_impulse_terms_against_the_independent_vectors():
     print("rbd_anymal.json, IMPULSE:", errs)
     assert max(errs) < 1e-11, errs
     assert (o["dtau_dv"] == 0).all()
-
-
-def random_samples(rng, n):
-    q = np.zeros((n, NQ))
-    q[:, :3] = rng.uniform(-0.5, 0.5, (n, 3))
-    quat = rng.normal(size=(n, 4))
-    q[:, 3:7] = quat / np.linalg.norm(quat, axis=1, keepdims=True)
-    q[:, 7:] = rng.uniform(-1.0, 1.0, (n, 12))
-    return q, rng.uniform(-1, 1, (n, NV)), rng.uniform(-2, 2, (n, NV)), rng.uniform(-30, 30, (n, 4, 3)), rng.uniform(-0.5, 0.5, (n, 4, 3))
-
-
-def oracle_terms(lib, m, q, v, a, f, pts, dt):
-    """every output of both modes for ONE sample from the oracle's entry points, matrices as [row, column]"""
-    mat = lambda rows: np.zeros((NV, rows))      # noqa: E731  (column-major rows x NV)
-    o = {"tau": np.zeros(NV), "dtau_dq": mat(NV), "dtau_dv": mat(NV), "dtau_da": mat(NV), "C": np.zeros(NF), "dCdq": mat(NF), "dCdv": mat(NF), "dCda": mat(NF),
-         "MJtJinv": np.zeros((NV + NF, NV + NF))}
-    pm, q, v, a, f, pts = C.byref(m), arr(q), arr(v), arr(a), arr(f), arr(pts)
-    lib.oracle_rnea(pm, P(q), P(v), P(a), P(f), 1, P(o["tau"]))
-    lib.oracle_rnea_derivatives(pm, P(q), P(v), P(a), P(f), 1, P(o["dtau_dq"]), P(o["dtau_dv"]), P(o["dtau_da"]))
-    junk = [np.zeros(4 * 6 * NV) for _ in range(8)]
-    lib.oracle_contact_kinematics(pm, P(q), P(v), P(a), P(pts), dt, P(o["C"]), P(o["dCdq"]), P(o["dCdv"]), P(o["dCda"]), *[P(j) for j in junk], P(o["MJtJinv"]))
-    i = {"tau": np.zeros(NV), "dtau_dq": mat(NV), "dtau_da": mat(NV), "C": np.zeros(NF), "dCdq": mat(NF), "dCdv": mat(NF)}
-    lib.oracle_impulse_terms(pm, P(q), P(v), P(a), P(f), P(i["tau"]), P(i["dtau_dq"]), P(i["dtau_da"]), P(i["C"]), P(i["dCdq"]), P(i["dCdv"]))
-    T = lambda d: {k: (x.T.copy() if x.ndim == 2 else x) for k, x in d.items()}      # noqa: E731
-    return T(o), T(i)
 
 
 NMAX = 130

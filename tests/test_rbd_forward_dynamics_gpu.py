@@ -13,16 +13,15 @@ import independent_rbd as IR
 import rbd_forward as F
 from helpers import P, anymal_model, arr, rel_err
 from idocp_amd import capi
-from rbd_batch import E_ARG, IMPULSE, STAGE, DeviceArray, Rbd
+from rbd_batch import E_ARG, IMPULSE, STAGE, DeviceArray, Rbd, random_samples
 from test_other_quadrupeds_gpu import other_quadruped
-from test_rbd_batch_gpu import random_samples
 
 pytestmark = pytest.mark.gpu
 BAR = IR.BAR
 N = 5                       # odd: the last workgroup has one live wavefront
 TS = 0.04                   # Baumgarte time step
 DT = 0.01                   # integration step
-MASKS = ([1, 1, 1, 1], [1, 0, 0, 1], [0, 1, 0, 0], [0, 0, 0, 0])
+MASKS = tuple([(i >> 3) & 1, (i >> 2) & 1, (i >> 1) & 1, i & 1] for i in range(15, -1, -1))      # all 16 contact sets: dimf = 12, 9, 6, 3, 0
 MODELS = ("anymal", 0, 1, 2)
 
 
