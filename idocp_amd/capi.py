@@ -112,6 +112,13 @@ class RbdFdIO(C.Structure):
     _fields_ = [(name, C.c_void_p) for name in INPUTS + OUTPUTS]
 
 
+class RbdPolicy(C.Structure):
+    """idocp_rbd_policy_t: the affine feedback policy of idocp_rbd_feedback_torques_batch(_device) / idocp_rbd_rollout_policy(_device); a pointer left at
+    None is NULL"""
+    ARRAYS = ("u_ff", "K", "q_ref", "v_ref", "u_min", "u_max")
+    _fields_ = [(name, C.c_void_p) for name in ARRAYS] + [("shared_gains", C.c_int), ("shared_ref", C.c_int)]
+
+
 RBD_STAGE, RBD_IMPULSE = 0, 1
 
 
@@ -298,6 +305,14 @@ def _proto(lib):
     lib.idocp_rbd_rollout.restype = ci
     lib.idocp_rbd_rollout_device.argtypes = [vp, ci, ci, c_int_p, cd, cd] + [vp] * 6 + [ci]
     lib.idocp_rbd_rollout_device.restype = ci
+    lib.idocp_rbd_feedback_torques_batch.argtypes = [vp, ci, vp, vp, P(RbdPolicy), vp]
+    lib.idocp_rbd_feedback_torques_batch.restype = ci
+    lib.idocp_rbd_feedback_torques_batch_device.argtypes = [vp, ci, vp, vp, P(RbdPolicy), vp]
+    lib.idocp_rbd_feedback_torques_batch_device.restype = ci
+    lib.idocp_rbd_rollout_policy.argtypes = [vp, ci, ci, c_int_p, cd, cd, P(RbdPolicy)] + [vp] * 6 + [ci]
+    lib.idocp_rbd_rollout_policy.restype = ci
+    lib.idocp_rbd_rollout_policy_device.argtypes = [vp, ci, ci, c_int_p, cd, cd, P(RbdPolicy)] + [vp] * 6 + [ci]
+    lib.idocp_rbd_rollout_policy_device.restype = ci
     for name, args in [
         ("idocp_ocp_set_contact_status_uniformly", [vp, P(ci), c_double_p]),
         ("idocp_ocp_set_solution", [vp, cs, c_double_p]),

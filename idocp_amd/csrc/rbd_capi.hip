@@ -41,6 +41,8 @@ struct idocp_rbd {
   size_t unwanted_doubles = 0;
   double* fd_chain = nullptr;         // chain, forward dynamics: [a = 0 | h | dtau_dq | dtau_dv | M] of the sweep at a = 0
   size_t fd_chain_doubles = 0;
+  double* u_buf = nullptr;            // closed-loop rollout without u_traj: the torques of the current step, [n][nu]
+  size_t u_buf_doubles = 0;
 };
 
 namespace {
@@ -203,9 +205,8 @@ int checkForwardCall(idocp_rbd* h, int mode, int n, const int* active, double ti
 }
 
 // the schedule of a rollout: per step the stage mask and the mask of the touchdown impulse in front of it (0: none)
-int checkRollout(idocp_rbd* h, int n, int steps, const int* active, double time_step, double dt, const double* contact_points, const double* q_traj,
-                 const double* v_traj, const double* f_traj) {
-  const char* who = "idocp_rbd_rollout";
+int checkRollout(const char* who, idocp_rbd* h, int n, int steps, const int* active, double time_step, double dt, const double* contact_points,
+                 const double* q_traj, const double* v_traj, const double* f_traj) {
   if (steps < 1) { set_last_error(std::string(who) + ": steps must be at least 1"); return IDOCP_E_ARG; }
   int rc = checkForward(who, h, IDOCP_RBD_STAGE, n, active, time_step, dt, q_traj, v_traj, contact_points, f_traj || contact_points);
   if (rc) return rc;
@@ -214,9 +215,53 @@ int checkRollout(idocp_rbd* h, int n, int steps, const int* active, double time_
   return IDOCP_OK;
 }
 
-// every pointer: device memory
+// ---- the feedback policy ----
+
+// host_bounds: u_min / u_max are host memory and can be looked at
+int checkPolicy(const char* who, const idocp_rbd* h, const idocp_rbd_policy_t* pol, bool host_bounds) {
+  const std::string w(who);
+  if (!pol) { set_last_error(w + ": null policy"); return IDOCP_E_ARG; }
+  if (pol->K && (!pol->q_ref || !pol->v_ref)) { set_last_error(w + ": gains K need the references q_ref and v_ref"); return IDOCP_E_ARG; }
+  if (host_bounds)
+    for (int j = 0; j < h->model.nu; ++j) {
+      const bool nan = (pol->u_min && std::isnan(pol->u_min[j])) || (pol->u_max && std::isnan(pol->u_max[j]));
+      if (nan || (pol->u_min && pol->u_max && pol->u_min[j] > pol->u_max[j])) {
+        set_last_error(w + ": u_min[" + std::to_string(j) + "] <= u_max[" + std::to_string(j) + "] does not hold (or a bound is NaN)"); return IDOCP_E_ARG;
+      }
+    }
+  return IDOCP_OK;
+}
+
+// slice k of a policy in device memory, evaluated at (q, v) into u
+void launchPolicy(idocp_rbd* h, int n, int k, const idocp_rbd_policy_t& pol, const double* q, const double* v, double* u) {
+  const size_t nq = h->model.nq, nv = h->model.nv, nu = h->model.nu, nk = nu * 2 * nv, N = (size_t)n, K = (size_t)k;
+  RbdPolicyArgs a;
+  a.q = q; a.v = v; a.u = u;
+  a.u_ff = pol.u_ff ? pol.u_ff + K * N * nu : nullptr;
+  a.k_stride = pol.shared_gains ? 0 : (long)nk;
+  a.q_ref_stride = pol.shared_ref ? 0 : (long)nq;
+  a.v_ref_stride = pol.shared_ref ? 0 : (long)nv;
+  a.K = pol.K ? pol.K + K * (pol.shared_gains ? nk : N * nk) : nullptr;
+  a.q_ref = pol.K ? pol.q_ref + K * (pol.shared_ref ? nq : N * nq) : nullptr;
+  a.v_ref = pol.K ? pol.v_ref + K * (pol.shared_ref ? nv : N * nv) : nullptr;
+  a.u_min = pol.u_min; a.u_max = pol.u_max;
+  rbdPolicy(h->model.nv, h->quadruped, a, n, h->stream);
+}
+
+int checkTorques(const char* who, const idocp_rbd* h, int n, const double* q, const double* v, const idocp_rbd_policy_t* pol, const double* u,
+                 bool host_bounds) {
+  const std::string w(who);
+  if (!h) { set_last_error(w + ": null handle"); return IDOCP_E_ARG; }
+  if (n <= 0) { set_last_error(w + ": n must be positive"); return IDOCP_E_ARG; }
+  if (!q || !v || !u) { set_last_error(w + ": q, v and u are needed"); return IDOCP_E_ARG; }
+  return checkPolicy(who, h, pol, host_bounds);
+}
+
+// every pointer: device memory.  Open loop (pol == nullptr): the torques u [steps][n][nu].  Closed loop: the torques of step k come from the policy
+// at the state of step k and go to slice k of u_traj (or, without u_traj, to the handle's buffer).
 int rolloutDevice(idocp_rbd* h, int n, int steps, const int* active, double time_step, double dt, const double* u, const double* contact_points,
-                  double* q_traj, double* v_traj, double* a_traj, double* f_traj, int touchdown_impulse) {
+                  double* q_traj, double* v_traj, double* a_traj, double* f_traj, int touchdown_impulse, const idocp_rbd_policy_t* pol = nullptr,
+                  double* u_traj = nullptr) {
   const size_t nq = h->model.nq, nv = h->model.nv, nu = h->model.nu, nf = 3 * (size_t)h->model.ncontacts, N = (size_t)n;
   int prev = 0;
   for (int k = 0; k < steps; ++k) {
@@ -229,7 +274,14 @@ int rolloutDevice(idocp_rbd* h, int n, int steps, const int* active, double time
     }
     idocp_rbd_fd_io_t io = idocp_rbd_fd_io_t();
     io.q = qk; io.v = vk;
-    io.u = u ? u + k * N * nu : nullptr;
+    if (pol) {
+      double* uk = u_traj ? u_traj + k * N * nu : h->u_buf;
+      launchPolicy(h, n, k, *pol, qk, vk, uk);
+      HIP_TRY(hipGetLastError());
+      io.u = uk;
+    } else {
+      io.u = u ? u + k * N * nu : nullptr;
+    }
     io.contact_points = contact_points ? contact_points + k * N * nf : nullptr;
     io.a = a_traj ? a_traj + k * N * nv : nullptr;
     io.f = f_traj ? f_traj + k * N * nf : nullptr;
@@ -239,6 +291,32 @@ int rolloutDevice(idocp_rbd* h, int n, int steps, const int* active, double time
   }
   return IDOCP_OK;
 }
+
+// The host form of a policy: its arrays behind one another in the staging buffer.  sizes(): doubles of [u_ff | K | q_ref | v_ref | u_min | u_max].
+struct PolicyStage {
+  size_t sz[6];
+  const double* host[6];
+  PolicyStage(const idocp_rbd* h, const idocp_rbd_policy_t& p, size_t N, size_t S) {
+    const size_t nq = h->model.nq, nv = h->model.nv, nu = h->model.nu, nk = nu * 2 * nv;
+    const size_t full[6] = {S * N * nu, S * (p.shared_gains ? 1 : N) * nk, S * (p.shared_ref ? 1 : N) * nq, S * (p.shared_ref ? 1 : N) * nv, nu, nu};
+    const double* ptr[6] = {p.u_ff, p.K, p.K ? p.q_ref : nullptr, p.K ? p.v_ref : nullptr, p.u_min, p.u_max};
+    for (int i = 0; i < 6; ++i) { host[i] = ptr[i]; sz[i] = ptr[i] ? full[i] : 0; }
+  }
+  size_t total() const { size_t t = 0; for (int i = 0; i < 6; ++i) t += even(sz[i]); return t; }
+  // uploads on st from `cur` on; d: the policy with device pointers; returns the first double behind it
+  int upload(double* cur, hipStream_t st, const idocp_rbd_policy_t& p, idocp_rbd_policy_t* d, double** end) const {
+    const double* dev[6];
+    for (int i = 0; i < 6; ++i) {
+      dev[i] = sz[i] ? cur : nullptr;
+      if (sz[i]) HIP_TRY(hipMemcpyAsync(cur, host[i], sizeof(double) * sz[i], hipMemcpyHostToDevice, st));
+      cur += even(sz[i]);
+    }
+    *d = p;
+    d->u_ff = dev[0]; d->K = dev[1]; d->q_ref = dev[2]; d->v_ref = dev[3]; d->u_min = dev[4]; d->u_max = dev[5];
+    *end = cur;
+    return IDOCP_OK;
+  }
+};
 
 }  // namespace
 
@@ -287,6 +365,7 @@ void idocp_rbd_destroy(idocp_rbd_t* h) {
   if (h->stage) (void)hipFree(h->stage);
   if (h->unwanted) (void)hipFree(h->unwanted);
   if (h->fd_chain) (void)hipFree(h->fd_chain);
+  if (h->u_buf) (void)hipFree(h->u_buf);
   if (h->stream) (void)hipStreamDestroy(h->stream);
   delete h;
 }
@@ -371,14 +450,14 @@ int idocp_rbd_forward_dynamics_batch(idocp_rbd_t* h, int mode, int n, const int*
 
 int idocp_rbd_rollout_device(idocp_rbd_t* h, int n, int steps, const int* active, double time_step, double dt, const double* u, const double* contact_points,
                              double* q_traj, double* v_traj, double* a_traj, double* f_traj, int touchdown_impulse) {
-  int rc = checkRollout(h, n, steps, active, time_step, dt, contact_points, q_traj, v_traj, f_traj); if (rc) return rc;
+  int rc = checkRollout("idocp_rbd_rollout", h, n, steps, active, time_step, dt, contact_points, q_traj, v_traj, f_traj); if (rc) return rc;
   HIP_TRY(hipSetDevice(h->device));
   return rolloutDevice(h, n, steps, active, time_step, dt, u, contact_points, q_traj, v_traj, a_traj, f_traj, touchdown_impulse);
 }
 
 int idocp_rbd_rollout(idocp_rbd_t* h, int n, int steps, const int* active, double time_step, double dt, const double* u, const double* contact_points,
                       double* q_traj, double* v_traj, double* a_traj, double* f_traj, int touchdown_impulse) {
-  int rc = checkRollout(h, n, steps, active, time_step, dt, contact_points, q_traj, v_traj, f_traj); if (rc) return rc;
+  int rc = checkRollout("idocp_rbd_rollout", h, n, steps, active, time_step, dt, contact_points, q_traj, v_traj, f_traj); if (rc) return rc;
   HIP_TRY(hipSetDevice(h->device));
   const size_t nq = h->model.nq, nv = h->model.nv, nu = h->model.nu, nf = 3 * (size_t)h->model.ncontacts, N = (size_t)n, S = (size_t)steps;
   // [q_traj | v_traj | u | contact_points | a_traj | f_traj]: staged once, read back once
@@ -397,6 +476,77 @@ int idocp_rbd_rollout(idocp_rbd_t* h, int n, int steps, const int* active, doubl
   // (slice 0 of v_traj comes back too; it is the input)
   HIP_TRY(hipMemcpyAsync(q_traj + N * nq, dev[0] + N * nq, sizeof(double) * S * N * nq, hipMemcpyDeviceToHost, h->stream));
   HIP_TRY(hipMemcpyAsync(v_traj + N * nv, dev[1] + N * nv, sizeof(double) * S * N * nv, hipMemcpyDeviceToHost, h->stream));
+  if (a_traj) HIP_TRY(hipMemcpyAsync(a_traj, dev[4], sizeof(double) * sz[4], hipMemcpyDeviceToHost, h->stream));
+  if (f_traj) HIP_TRY(hipMemcpyAsync(f_traj, dev[5], sizeof(double) * sz[5], hipMemcpyDeviceToHost, h->stream));
+  HIP_TRY(hipStreamSynchronize(h->stream));
+  return IDOCP_OK;
+}
+
+int idocp_rbd_feedback_torques_batch_device(idocp_rbd_t* h, int n, const double* q, const double* v, const idocp_rbd_policy_t* pol, double* u) {
+  int rc = checkTorques("idocp_rbd_feedback_torques_batch_device", h, n, q, v, pol, u, false); if (rc) return rc;
+  HIP_TRY(hipSetDevice(h->device));
+  launchPolicy(h, n, 0, *pol, q, v, u);
+  HIP_TRY(hipGetLastError());
+  return IDOCP_OK;
+}
+
+int idocp_rbd_feedback_torques_batch(idocp_rbd_t* h, int n, const double* q, const double* v, const idocp_rbd_policy_t* pol, double* u) {
+  int rc = checkTorques("idocp_rbd_feedback_torques_batch", h, n, q, v, pol, u, true); if (rc) return rc;
+  HIP_TRY(hipSetDevice(h->device));
+  const size_t nq = h->model.nq, nv = h->model.nv, nu = h->model.nu, N = (size_t)n;
+  const PolicyStage ps(h, *pol, N, 1);
+  rc = growBuffer(&h->stage, &h->stage_doubles, ps.total() + even(N * nq) + even(N * nv) + even(N * nu), h->stream); if (rc) return rc;
+  idocp_rbd_policy_t d;
+  double* cur = nullptr;
+  rc = ps.upload(h->stage, h->stream, *pol, &d, &cur); if (rc) return rc;
+  double *dq = cur, *dv = dq + even(N * nq), *du = dv + even(N * nv);
+  HIP_TRY(hipMemcpyAsync(dq, q, sizeof(double) * N * nq, hipMemcpyHostToDevice, h->stream));
+  HIP_TRY(hipMemcpyAsync(dv, v, sizeof(double) * N * nv, hipMemcpyHostToDevice, h->stream));
+  launchPolicy(h, n, 0, d, dq, dv, du);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipMemcpyAsync(u, du, sizeof(double) * N * nu, hipMemcpyDeviceToHost, h->stream));
+  HIP_TRY(hipStreamSynchronize(h->stream));
+  return IDOCP_OK;
+}
+
+int idocp_rbd_rollout_policy_device(idocp_rbd_t* h, int n, int steps, const int* active, double time_step, double dt, const idocp_rbd_policy_t* pol,
+                                    const double* contact_points, double* q_traj, double* v_traj, double* u_traj, double* a_traj, double* f_traj,
+                                    int touchdown_impulse) {
+  const char* who = "idocp_rbd_rollout_policy_device";
+  int rc = checkRollout(who, h, n, steps, active, time_step, dt, contact_points, q_traj, v_traj, f_traj); if (rc) return rc;
+  rc = checkPolicy(who, h, pol, false); if (rc) return rc;
+  HIP_TRY(hipSetDevice(h->device));
+  if (!u_traj) { rc = growBuffer(&h->u_buf, &h->u_buf_doubles, (size_t)n * h->model.nu, h->stream); if (rc) return rc; }
+  return rolloutDevice(h, n, steps, active, time_step, dt, nullptr, contact_points, q_traj, v_traj, a_traj, f_traj, touchdown_impulse, pol, u_traj);
+}
+
+int idocp_rbd_rollout_policy(idocp_rbd_t* h, int n, int steps, const int* active, double time_step, double dt, const idocp_rbd_policy_t* pol,
+                             const double* contact_points, double* q_traj, double* v_traj, double* u_traj, double* a_traj, double* f_traj,
+                             int touchdown_impulse) {
+  const char* who = "idocp_rbd_rollout_policy";
+  int rc = checkRollout(who, h, n, steps, active, time_step, dt, contact_points, q_traj, v_traj, f_traj); if (rc) return rc;
+  rc = checkPolicy(who, h, pol, true); if (rc) return rc;
+  HIP_TRY(hipSetDevice(h->device));
+  const size_t nq = h->model.nq, nv = h->model.nv, nu = h->model.nu, nf = 3 * (size_t)h->model.ncontacts, N = (size_t)n, S = (size_t)steps;
+  const PolicyStage ps(h, *pol, N, S);
+  // [policy | q_traj | v_traj | contact_points | u_traj | a_traj | f_traj]: staged once, read back once
+  const size_t sz[6] = {(S + 1) * N * nq, (S + 1) * N * nv, contact_points ? S * N * nf : 0, u_traj ? S * N * nu : 0, a_traj ? S * N * nv : 0, f_traj ? S * N * nf : 0};
+  size_t total = ps.total();
+  for (int i = 0; i < 6; ++i) total += even(sz[i]);
+  rc = growBuffer(&h->stage, &h->stage_doubles, total, h->stream); if (rc) return rc;
+  if (!u_traj) { rc = growBuffer(&h->u_buf, &h->u_buf_doubles, N * nu, h->stream); if (rc) return rc; }
+  idocp_rbd_policy_t d;
+  double* cur = nullptr;
+  rc = ps.upload(h->stage, h->stream, *pol, &d, &cur); if (rc) return rc;
+  double* dev[6];
+  for (int i = 0; i < 6; ++i) { dev[i] = sz[i] ? cur : nullptr; cur += even(sz[i]); }
+  HIP_TRY(hipMemcpyAsync(dev[0], q_traj, sizeof(double) * N * nq, hipMemcpyHostToDevice, h->stream));
+  HIP_TRY(hipMemcpyAsync(dev[1], v_traj, sizeof(double) * N * nv, hipMemcpyHostToDevice, h->stream));
+  if (contact_points) HIP_TRY(hipMemcpyAsync(dev[2], contact_points, sizeof(double) * sz[2], hipMemcpyHostToDevice, h->stream));
+  rc = rolloutDevice(h, n, steps, active, time_step, dt, nullptr, dev[2], dev[0], dev[1], dev[4], dev[5], touchdown_impulse, &d, dev[3]); if (rc) return rc;
+  HIP_TRY(hipMemcpyAsync(q_traj + N * nq, dev[0] + N * nq, sizeof(double) * S * N * nq, hipMemcpyDeviceToHost, h->stream));
+  HIP_TRY(hipMemcpyAsync(v_traj + N * nv, dev[1] + N * nv, sizeof(double) * S * N * nv, hipMemcpyDeviceToHost, h->stream));
+  if (u_traj) HIP_TRY(hipMemcpyAsync(u_traj, dev[3], sizeof(double) * sz[3], hipMemcpyDeviceToHost, h->stream));
   if (a_traj) HIP_TRY(hipMemcpyAsync(a_traj, dev[4], sizeof(double) * sz[4], hipMemcpyDeviceToHost, h->stream));
   if (f_traj) HIP_TRY(hipMemcpyAsync(f_traj, dev[5], sizeof(double) * sz[5], hipMemcpyDeviceToHost, h->stream));
   HIP_TRY(hipStreamSynchronize(h->stream));

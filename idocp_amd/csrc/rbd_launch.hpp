@@ -28,5 +28,15 @@ void rbdForwardQuadruped(const DevModel* m, const RbdFrames* frames, const idocp
 void rbdForwardChainSolve(int nv, int n, const double* h, const double* M, const double* q, const double* v, const double* u, double dt,
                           double* a, double* q_next, double* v_next, hipStream_t st);
 
+// The affine feedback policy (rbd_policy_kernel.hip): u [n][nu] = clamp(u_ff + K [q (-) q_ref ; v - v_ref]).  Every pointer: DEVICE memory.
+// k_stride, q_ref_stride, v_ref_stride: doubles between the gains / references of two samples -- nu * 2 nv, nq, nv, or 0 where all samples share
+// one.  u_ff NULL = 0; K NULL = no feedback (q, v, q_ref, v_ref are not read); u_min / u_max [nu], either may be NULL.
+struct RbdPolicyArgs {
+  const double *q, *v, *u_ff, *K, *q_ref, *v_ref, *u_min, *u_max;
+  long k_stride, q_ref_stride, v_ref_stride;
+  double* u;
+};
+void rbdPolicy(int nv, bool quadruped, const RbdPolicyArgs& a, int n, hipStream_t st);
+
 }  // namespace idocp_dev
 #endif  // IDOCP_RBD_LAUNCH_HPP_

@@ -222,6 +222,26 @@ class Robot {
     fdCall(IDOCP_RBD_STAGE, act, time_step, dt, io);
     q_next = qn; v_next = vn;
   }
+  // The solvers' affine feedback policy at one state, an ADDITION like forwardDynamics: u = u_ff + Kq (q (-) q_ref) + Kv (v - v_ref), q (-) q_ref as
+  // subtractConfiguration(q, q_ref) gives it; Kq, Kv: the nu x nv gains of getStateFeedbackGain.  ONE n = 1 call of idocp_rbd_feedback_torques_batch
+  // on the same lazily created handle (the batched call and idocp_rbd_rollout_policy take many states, bounds and a whole policy at once).
+  void stateFeedbackTorques(const Eigen::VectorXd& q, const Eigen::VectorXd& v, const Eigen::VectorXd& q_ref, const Eigen::VectorXd& v_ref,
+                            const Eigen::VectorXd& u_ff, const Eigen::MatrixXd& Kq, const Eigen::MatrixXd& Kv, Eigen::VectorXd& u) {
+    sized(q, model_.nq, "q"); sized(v, model_.nv, "v"); sized(q_ref, model_.nq, "q_ref"); sized(v_ref, model_.nv, "v_ref"); sized(u_ff, model_.nu, "u_ff");
+    const int nu = model_.nu, nv = model_.nv;
+    if (Kq.rows() != nu || Kq.cols() != nv || Kv.rows() != nu || Kv.cols() != nv) {
+      std::cerr << "invalid size: Kq and Kv must be " << nu << " x " << nv << "!" << '\n'; std::exit(EXIT_FAILURE);
+    }
+    std::vector<double> K((size_t)nu * 2 * nv);      // [Kq | Kv], column-major
+    for (int c = 0; c < nv; ++c) for (int r = 0; r < nu; ++r) { K[(size_t)c * nu + r] = Kq(r, c); K[(size_t)(nv + c) * nu + r] = Kv(r, c); }
+    if (u.size() != nu) u.resize(nu);
+    Eigen::VectorXd out(nu);                          // (u may be u_ff)
+    idocp_rbd_policy_t pol = idocp_rbd_policy_t();
+    pol.u_ff = u_ff.data(); pol.K = K.data(); pol.q_ref = q_ref.data(); pol.v_ref = v_ref.data();
+    if (!rbd_.h) ok(idocp_rbd_create(&model_, 0, &rbd_.h));
+    ok(idocp_rbd_feedback_torques_batch(rbd_.h, 1, q.data(), v.data(), &pol, out.data()));
+    u = out;
+  }
   // Robot::framePosition / frameRotation / framePlacement (robot.hxx:206-233): of any frame of the URDF (pinocchio's frame numbering, as the
   // contact frames and the task-space costs use it), at the configuration of the last updateFrameKinematics / updateKinematics
   Eigen::Vector3d framePosition(const int frame_id) const { return framePlacement(frame_id).translation(); }

@@ -842,6 +842,44 @@ int idocp_rbd_rollout(idocp_rbd_t* h, int n, int steps, const int* active, doubl
 int idocp_rbd_rollout_device(idocp_rbd_t* h, int n, int steps, const int* active, double time_step, double dt, const double* u,
                              const double* contact_points, double* q_traj, double* v_traj, double* a_traj, double* f_traj, int touchdown_impulse);
 
+/* ---- Closed loop: the time-varying affine feedback policy of the solvers on the plant above (an ADDITION like the forward dynamics).  Before
+ * every step
+ *   u = clamp(u_ff[k] + K[k] [q (-) q_ref[k] ; v - v_ref[k]])
+ * is evaluated on the GPU (rbd_policy_kernel.hip), without a host round trip.  K[k] is nu x 2 nv column-major with the columns [dq | dv]: the
+ * block idocp_ocp_get_riccati returns, and [Kq | Kv] of getStateFeedbackGain / idocp_unocp_get_torque_feedback_gain.  q (-) q_ref is the tangent
+ * idocp_model_subtract_configuration(q_plus = q, q_minus = q_ref) returns (SE(3) log of the relative base placement in rows 0 .. 5 on a
+ * quadruped, plain differences elsewhere; quaternions are taken as given).  The clamp min(max(u, u_min), u_max) per joint is the last operation.
+ * A non-finite entry in a sample's q, v, q_ref, v_ref, K or u_ff makes all of that sample's torques NaN and touches no other sample.
+ * Gains and references are per sample, or one set shared by all n samples (one policy over many perturbed plants). */
+typedef struct idocp_rbd_policy {
+  const double *u_ff;          /* [steps][n][nu]; NULL = 0 */
+  const double *K;             /* [steps][n][nu * 2 nv], or [steps][nu * 2 nv] if shared_gains; NULL = no feedback (q_ref, v_ref are not read) */
+  const double *q_ref, *v_ref; /* [steps][n][nq | nv], or [steps][nq | nv] if shared_ref; required when K is given */
+  const double *u_min, *u_max; /* [nu], either may be NULL (unbounded on that side) */
+  int shared_gains, shared_ref;
+} idocp_rbd_policy_t;
+
+/* One evaluation (the steps = 1 slices of the policy): u [n][nu] from q [n][nq], v [n][nv].  Host pointers; returns when u is in place.
+ * IDOCP_E_ARG for a null policy, K without q_ref or v_ref, and a bound pair with u_min[j] > u_max[j] or a NaN bound. */
+int idocp_rbd_feedback_torques_batch(idocp_rbd_t* h, int n, const double* q, const double* v, const idocp_rbd_policy_t* policy, double* u);
+/* Device pointers for everything, u_min and u_max included; asynchronous on idocp_rbd_stream(h); allocates nothing.  The bounds are NOT
+ * checked (they are device memory). */
+int idocp_rbd_feedback_torques_batch_device(idocp_rbd_t* h, int n, const double* q, const double* v, const idocp_rbd_policy_t* policy, double* u);
+
+/* idocp_rbd_rollout with the torques of step k computed from the state of step k.  Array shapes, schedule and touchdown rules are those of
+ * idocp_rbd_rollout; per step: the touchdown impulse if any, the policy launch, the forward launch, all on the handle's stream with no
+ * synchronisation in between.  The policy of step k sees the state the Euler step k is applied from -- with a touchdown the POST-impulse
+ * velocity, which is what slice k of v_traj holds afterwards.  u_traj [steps][n][nu] receives the torques applied; NULL: a buffer of n nu
+ * doubles the handle owns (it grows only when n grows).  The host form stages everything once and reads back once and refuses bad bounds like
+ * the call above; the device form takes device pointers for everything, does not check the bounds and allocates nothing beyond that buffer
+ * (a chain also grows the buffers of idocp_rbd_rollout_device). */
+int idocp_rbd_rollout_policy(idocp_rbd_t* h, int n, int steps, const int* active, double time_step, double dt, const idocp_rbd_policy_t* policy,
+                             const double* contact_points, double* q_traj, double* v_traj, double* u_traj, double* a_traj, double* f_traj,
+                             int touchdown_impulse);
+int idocp_rbd_rollout_policy_device(idocp_rbd_t* h, int n, int steps, const int* active, double time_step, double dt,
+                                    const idocp_rbd_policy_t* policy, const double* contact_points, double* q_traj, double* v_traj, double* u_traj,
+                                    double* a_traj, double* f_traj, int touchdown_impulse);
+
 const char* idocp_last_error(void);
 const char* idocp_version(void);
 

@@ -2,9 +2,12 @@
 device pointers, n = 122 880 samples per launch by default (the stage count of the headline step: 1 024 instances x 120 stages).  Every launch is
 bracketed by HIP events on the handle's stream after warm-up launches; prints one JSON line with the median / min / max ms per launch and the
 samples per second of each output selection.  The fd_* rows are the forward dynamics: stage mode (a and f out) and impulse mode (dv and lambda out),
-without and with the Euler step; stage_da_mjtjinv is what a caller needed for the same answer before that call existed.
+without and with the Euler step; stage_da_mjtjinv is what a caller needed for the same answer before that call existed.  The policy_* rows are the
+feedback policy alone (idocp_rbd_feedback_torques_batch_device) with one gain block and reference shared by all samples and with one per sample;
+fd_step_closed_loop is one step of idocp_rbd_rollout_policy_device (policy launch + forward launch with the Euler step, per-sample gains), to be
+read against fd_stage_a_f_step.
 
-    python profiles/rbd_throughput.py [--n 122880] [--launches 20] [--warmup 5]
+    python profiles/rbd_throughput.py [--n 122880] [--launches 20] [--warmup 5] [--rows name,name,...]
 """
 import argparse
 import ctypes as C
@@ -29,13 +32,17 @@ FD_SELECTIONS = (("fd_stage_a_f", capi.RBD_STAGE, ("a", "f")),
                  ("fd_impulse_dv_lambda", capi.RBD_IMPULSE, ("a", "f")),
                  ("fd_impulse_dv_lambda_step", capi.RBD_IMPULSE, ("a", "f", "q_next", "v_next")))
 
+POLICY_ROWS = ("policy_shared", "policy_per_sample", "fd_step_closed_loop")
+
 
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--n", type=int, default=122880)
     ap.add_argument("--launches", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--rows", default="", help="comma-separated row names (default: all)")
     args = ap.parse_args()
+    wanted = [x for x in args.rows.split(",") if x]
     n, lib, rt = args.n, capi.lib(), C.CDLL("libamdhip64.so")
     rt.hipEventCreate.argtypes = [C.POINTER(C.c_void_p)]
     rt.hipEventRecord.argtypes = [C.c_void_p, C.c_void_p]
@@ -57,6 +64,14 @@ def main():
     sizes = {"tau": nv, "dtau_dq": nv * nv, "dtau_dv": nv * nv, "dtau_da": nv * nv, "C": nf, "dCdq": nf * nv, "dCdv": nf * nv, "dCda": nf * nv,
              "MJtJinv": (nv + nf) ** 2}
     host["u"] = rng.uniform(-20, 20, (n, m.nu))
+    if not wanted or set(wanted) & set(POLICY_ROWS):
+        nk = m.nu * 2 * nv
+        host["K"] = rng.uniform(-1, 1, (n, nk))
+        host["q_ref"] = np.tile(ANYMAL_Q_STANDING, (n, 1))
+        host["v_ref"] = np.zeros((n, nv))
+        host["q_traj"] = np.concatenate([q[None], np.zeros((1, n, nq))])
+        host["v_traj"] = np.concatenate([host["v"][None], np.zeros((1, n, nv))])
+        host["u_out"] = np.zeros((n, m.nu))
     fd_sizes = {"fd_a": nv, "fd_f": nf, "fd_q_next": nq, "fd_v_next": nv}
     sizes.update(fd_sizes)
     dev = {}
@@ -75,8 +90,19 @@ def main():
         assert rt.hipEventCreate(C.byref(e)) == 0
         events.append(e)
     res = {"n": n, "launches": args.launches, "warmup": args.warmup}
-    for name, mode, outputs in SELECTIONS + FD_SELECTIONS:
-        if name.startswith("fd_"):
+    for name, mode, outputs in SELECTIONS + FD_SELECTIONS + tuple((x, None, ()) for x in POLICY_ROWS):
+        if wanted and name not in wanted:
+            continue
+        if name in POLICY_ROWS:
+            pol = capi.RbdPolicy()
+            pol.u_ff, pol.K, pol.q_ref, pol.v_ref = dev["u"], dev["K"], dev["q_ref"], dev["v_ref"]
+            pol.shared_gains = pol.shared_ref = int(name == "policy_shared")
+            if name == "fd_step_closed_loop":
+                launch = lambda: capi.check(lib.idocp_rbd_rollout_policy_device(h, n, 1, active, 0.05, 0.01, C.byref(pol), dev["contact_points"], dev["q_traj"],  # noqa: E731
+                                                                                dev["v_traj"], dev["u_out"], dev["fd_a"], dev["fd_f"], 0), name)
+            else:
+                launch = lambda: capi.check(lib.idocp_rbd_feedback_torques_batch_device(h, n, dev["q"], dev["v"], C.byref(pol), dev["u_out"]), name)  # noqa: E731
+        elif name.startswith("fd_"):
             io = capi.RbdFdIO()
             for k in capi.RbdFdIO.INPUTS:
                 setattr(io, k, dev[k])
@@ -103,12 +129,13 @@ def main():
             ms.append(t.value)
         med = float(np.median(ms))
         res[name] = {"ms_median": round(med, 4), "ms_min": round(min(ms), 4), "ms_max": round(max(ms), 4), "samples_per_s": round(n / med * 1e3)}
-    tau = np.zeros((n, nv))
-    capi.check(lib.idocp_device_download(tau.ctypes.data, dev["tau"], tau.nbytes), "download")
-    res["tau_finite"] = bool(np.isfinite(tau).all())
-    acc = np.zeros((n, nv))
-    capi.check(lib.idocp_device_download(acc.ctypes.data, dev["fd_a"], acc.nbytes), "download")
-    res["fd_a_finite"] = bool(np.isfinite(acc).all())
+    ran = [k for k in res if isinstance(res[k], dict)]
+    for key, src, width, rows in (("tau_finite", "tau", nv, ("stage_", "impulse_")), ("fd_a_finite", "fd_a", nv, ("fd_",)),
+                                  ("policy_u_finite", "u_out", m.nu, ("policy_", "fd_step_closed_loop"))):
+        if any(x.startswith(rows) for x in ran):
+            out = np.zeros((n, width))
+            capi.check(lib.idocp_device_download(out.ctypes.data, dev[src], out.nbytes), "download")
+            res[key] = bool(np.isfinite(out).all())
     for d in dev.values():
         lib.idocp_device_free(d)
     lib.idocp_rbd_destroy(h)
