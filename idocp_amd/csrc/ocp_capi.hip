@@ -16,6 +16,7 @@
 #include <vector>
 
 #include "dev_lie.hpp"
+#include "hip_try.hpp"
 #include "host_util.hpp"
 #include "idocp_hip.h"
 #include "model_shapes.hpp"
@@ -24,16 +25,6 @@
 using namespace idocp_dev;
 using idocp_host::set_last_error;
 using idocp_host::isQuadruped;
-
-#define HIP_TRY(expr)                                                                         \
-  do {                                                                                        \
-    hipError_t e_ = (expr);                                                                   \
-    if (e_ != hipSuccess) {                                                                   \
-      set_last_error(std::string(#expr) + ": " + hipGetErrorString(e_));                      \
-      (void)hipGetLastError(); /* HIP keeps a failed call as the thread's "last error": reported here, it must not fail the next handle's launches */ \
-      return IDOCP_E_DEVICE;                                                                  \
-    }                                                                                         \
-  } while (0)
 
 namespace {
 

@@ -9,24 +9,31 @@
 #include <cstring>
 #include <string>
 
+#include "hip_try.hpp"
 #include "host_util.hpp"
 #include "idocp_hip.h"
 #include "model_shapes.hpp"
 #include "rbd_launch.hpp"
+#include "rbd_stage.hpp"
 #include "unocp_launch.hpp"
 
 using namespace idocp_dev;
 using idocp_host::set_last_error;
+using idocp_host::StagePlan;
 
-#define HIP_TRY(expr)                                                                         \
-  do {                                                                                        \
-    hipError_t e_ = (expr);                                                                   \
-    if (e_ != hipSuccess) {                                                                   \
-      set_last_error(std::string(#expr) + ": " + hipGetErrorString(e_));                      \
-      (void)hipGetLastError(); /* HIP keeps a failed call as the thread's "last error": reported here, it must not fail the next handle's launches */ \
-      return IDOCP_E_DEVICE;                                                                  \
-    }                                                                                         \
-  } while (0)
+// scratch in device memory that only grows: a larger request waits for the stream, frees and allocates anew
+struct RbdBuffer {
+  double* ptr = nullptr;
+  size_t doubles = 0;
+  int grow(size_t want, hipStream_t st) {
+    if (want <= doubles) return IDOCP_OK;
+    if (ptr) { HIP_TRY(hipStreamSynchronize(st)); HIP_TRY(hipFree(ptr)); ptr = nullptr; doubles = 0; }
+    HIP_TRY(hipMalloc(reinterpret_cast<void**>(&ptr), sizeof(double) * want));
+    doubles = want;
+    return IDOCP_OK;
+  }
+  void release() { if (ptr) (void)hipFree(ptr); }
+};
 
 struct idocp_rbd {
   idocp_model_t model;
@@ -35,14 +42,10 @@ struct idocp_rbd {
   hipStream_t stream = nullptr;
   void* d_model = nullptr;            // DevModel, then RbdFrames
   const RbdFrames* d_frames = nullptr;
-  double* stage = nullptr;            // host-pointer form: inputs and outputs of one call
-  size_t stage_doubles = 0;
-  double* unwanted = nullptr;         // chain: where the sweep writes the outputs the caller did not ask for
-  size_t unwanted_doubles = 0;
-  double* fd_chain = nullptr;         // chain, forward dynamics: [a = 0 | h | dtau_dq | dtau_dv | M] of the sweep at a = 0
-  size_t fd_chain_doubles = 0;
-  double* u_buf = nullptr;            // closed-loop rollout without u_traj: the torques of the current step, [n][nu]
-  size_t u_buf_doubles = 0;
+  RbdBuffer stage;                    // host-pointer form: inputs and outputs of one call, laid out by a StagePlan
+  RbdBuffer unwanted;                 // chain: where the sweep writes the outputs the caller did not ask for
+  RbdBuffer fd_chain;                 // chain, forward dynamics: [a = 0 | h | dtau_dq | dtau_dv | M] of the sweep at a = 0
+  RbdBuffer u_buf;                    // closed-loop rollout without u_traj: the torques of the current step, [n][nu]
 };
 
 namespace {
@@ -63,43 +66,60 @@ ChainFn chainFn(int nv) {
   }
 }
 
-int growBuffer(double** buf, size_t* have, size_t want, hipStream_t st) {
-  if (want <= *have) return IDOCP_OK;
-  if (*buf) { HIP_TRY(hipStreamSynchronize(st)); HIP_TRY(hipFree(*buf)); *buf = nullptr; *have = 0; }
-  HIP_TRY(hipMalloc(reinterpret_cast<void**>(buf), sizeof(double) * want));
-  *have = want;
+// ---- the host-pointer form: a StagePlan (rbd_stage.hpp) says what lies where in h->stage and what is copied ----
+
+// room for the plan, its slots bound to it, the inputs on their way up, the zero-filled slots cleared
+int stageIn(idocp_rbd* h, const StagePlan& p) {
+  int rc = h->stage.grow(p.total(), h->stream); if (rc) return rc;
+  double* base = h->stage.ptr;
+  p.bind(base);
+  for (int i = 0; i < p.n_up; ++i)
+    HIP_TRY(hipMemcpyAsync(base + p.up[i].offset, p.up[i].host, sizeof(double) * p.up[i].count, hipMemcpyHostToDevice, h->stream));
+  for (int i = 0; i < p.n_zero; ++i) HIP_TRY(hipMemsetAsync(base + p.zero[i].offset, 0, sizeof(double) * p.zero[i].count, h->stream));
   return IDOCP_OK;
 }
 
-// doubles per sample of every field of idocp_rbd_io_t, in the order of the struct
-struct FieldSizes { size_t in[5], out[9]; };
-FieldSizes fieldSizes(const idocp_rbd* h) {
-  const size_t nq = h->model.nq, nv = h->model.nv, nf = 3 * (size_t)h->model.ncontacts;
-  return {{nq, nv, nv, nf, nf}, {nv, nv * nv, nv * nv, nv * nv, nf, nf * nv, nf * nv, nf * nv, (nv + nf) * (nv + nf)}};
+// the outputs on their way down; returns when they are in place
+int stageOut(idocp_rbd* h, const StagePlan& p) {
+  for (int i = 0; i < p.n_down; ++i)
+    HIP_TRY(hipMemcpyAsync(p.down[i].host, h->stage.ptr + p.down[i].offset, sizeof(double) * p.down[i].count, hipMemcpyDeviceToHost, h->stream));
+  HIP_TRY(hipStreamSynchronize(h->stream));
+  return IDOCP_OK;
 }
 
-int checkCall(const idocp_rbd* h, int mode, int n, const int* active, double time_step, const idocp_rbd_io_t* io) {
-  if (!h || !io) { set_last_error("idocp_rbd_contact_dynamics_batch: null handle or io"); return IDOCP_E_ARG; }
-  if (n <= 0) { set_last_error("idocp_rbd_contact_dynamics_batch: n must be positive"); return IDOCP_E_ARG; }
-  if (mode != IDOCP_RBD_STAGE && mode != IDOCP_RBD_IMPULSE) { set_last_error("idocp_rbd_contact_dynamics_batch: unknown mode"); return IDOCP_E_ARG; }
-  if (!io->q || !io->v || !io->a) { set_last_error("idocp_rbd_contact_dynamics_batch: q, v and a are needed"); return IDOCP_E_ARG; }
+// ---- inverse dynamics ----
+
+const char* const INVERSE = "idocp_rbd_contact_dynamics_batch";      // (both forms report under this name)
+
+int checkCall(const char* who, const idocp_rbd* h, int mode, int n, const int* active, double time_step, const idocp_rbd_io_t* io) {
+  const std::string w(who);
+  if (!h || !io) { set_last_error(w + ": null handle or io"); return IDOCP_E_ARG; }
+  if (n <= 0) { set_last_error(w + ": n must be positive"); return IDOCP_E_ARG; }
+  if (mode != IDOCP_RBD_STAGE && mode != IDOCP_RBD_IMPULSE) { set_last_error(w + ": unknown mode"); return IDOCP_E_ARG; }
+  if (!io->q || !io->v || !io->a) { set_last_error(w + ": q, v and a are needed"); return IDOCP_E_ARG; }
   const bool contact_out = io->C || io->dCdq || io->dCdv || io->dCda || io->MJtJinv;
   if (!h->quadruped) {
     if (io->f || io->contact_points || contact_out) {
-      set_last_error("idocp_rbd_contact_dynamics_batch: a fixed-base chain has no contacts (f, contact_points and the contact outputs must be NULL)");
+      set_last_error(w + ": a fixed-base chain has no contacts (f, contact_points and the contact outputs must be NULL)");
       return IDOCP_E_ARG;
     }
-    if (mode != IDOCP_RBD_STAGE) { set_last_error("idocp_rbd_contact_dynamics_batch: a fixed-base chain has no impulse mode"); return IDOCP_E_ARG; }
+    if (mode != IDOCP_RBD_STAGE) { set_last_error(w + ": a fixed-base chain has no impulse mode"); return IDOCP_E_ARG; }
     return IDOCP_OK;
   }
-  if (!active) { set_last_error("idocp_rbd_contact_dynamics_batch: the contact status `active` is needed"); return IDOCP_E_ARG; }
+  if (!active) { set_last_error(w + ": the contact status `active` is needed"); return IDOCP_E_ARG; }
   if (mode == IDOCP_RBD_STAGE) {
-    if (io->C && !io->contact_points) { set_last_error("idocp_rbd_contact_dynamics_batch: C in STAGE mode needs contact_points"); return IDOCP_E_ARG; }
+    if (io->C && !io->contact_points) { set_last_error(w + ": C in STAGE mode needs contact_points"); return IDOCP_E_ARG; }
     if ((io->C || io->dCdq || io->dCdv) && !(time_step > 0.0)) {
-      set_last_error("idocp_rbd_contact_dynamics_batch: the Baumgarte terms need a positive time_step"); return IDOCP_E_ARG;
+      set_last_error(w + ": the Baumgarte terms need a positive time_step"); return IDOCP_E_ARG;
     }
   }
   return IDOCP_OK;
+}
+
+int maskOf(const idocp_rbd* h, const int* active) {
+  int mask = 0;
+  for (int c = 0; c < h->model.ncontacts; ++c) if (active[c]) mask |= 1 << c;
+  return mask;
 }
 
 // io: device pointers
@@ -107,19 +127,17 @@ int launch(idocp_rbd* h, int mode, int n, const int* active, double time_step, c
   HIP_TRY(hipSetDevice(h->device));
   const DevModel* d_m = static_cast<const DevModel*>(h->d_model);
   if (h->quadruped) {
-    int mask = 0;
-    for (int c = 0; c < h->model.ncontacts; ++c) if (active[c]) mask |= 1 << c;
     // (dC/da and MJtJinv do not depend on the Baumgarte time step: any positive number serves where none was given)
-    rbdBatchQuadruped(d_m, h->d_frames, io, n, mode, mask, (mode == IDOCP_RBD_STAGE && !(time_step > 0.0)) ? 1.0 : time_step, h->stream);
+    rbdBatchQuadruped(d_m, h->d_frames, io, n, mode, maskOf(h, active), (mode == IDOCP_RBD_STAGE && !(time_step > 0.0)) ? 1.0 : time_step, h->stream);
   } else {
     const size_t nv = h->model.nv, nvec = (size_t)n * nv, nmat = nvec * nv;
     double *tau = io.tau, *dq = io.dtau_dq, *dv = io.dtau_dv, *da = io.dtau_da;
     if (!tau || !dq || !dv || !da) {
-      int rc = growBuffer(&h->unwanted, &h->unwanted_doubles, nvec + 3 * nmat, h->stream); if (rc) return rc;
-      if (!tau) tau = h->unwanted;
-      if (!dq) dq = h->unwanted + nvec;
-      if (!dv) dv = h->unwanted + nvec + nmat;
-      if (!da) da = h->unwanted + nvec + 2 * nmat;
+      int rc = h->unwanted.grow(nvec + 3 * nmat, h->stream); if (rc) return rc;
+      if (!tau) tau = h->unwanted.ptr;
+      if (!dq) dq = h->unwanted.ptr + nvec;
+      if (!dv) dv = h->unwanted.ptr + nvec + nmat;
+      if (!da) da = h->unwanted.ptr + nvec + 2 * nmat;
     }
     chainFn(h->model.nv)(d_m, n, io.q, io.v, io.a, tau, dq, dv, da, h->zaxes, h->stream);
   }
@@ -129,8 +147,7 @@ int launch(idocp_rbd* h, int mode, int n, const int* active, double time_step, c
 
 // ---- forward dynamics ----
 
-int checkForward(const char* who, const idocp_rbd* h, int mode, int n, const int* active, double time_step, double dt, const double* q, const double* v,
-                 const double* contact_points, bool contact_args) {
+int checkForward(const char* who, const idocp_rbd* h, int mode, int n, const int* active, double dt, const double* q, const double* v, bool contact_args) {
   const std::string w(who);
   if (!h) { set_last_error(w + ": null handle"); return IDOCP_E_ARG; }
   if (n <= 0) { set_last_error(w + ": n must be positive"); return IDOCP_E_ARG; }
@@ -143,7 +160,6 @@ int checkForward(const char* who, const idocp_rbd* h, int mode, int n, const int
     return IDOCP_OK;
   }
   if (!active) { set_last_error(w + ": the contact status `active` is needed"); return IDOCP_E_ARG; }
-  (void)contact_points; (void)time_step;
   return IDOCP_OK;
 }
 
@@ -160,12 +176,6 @@ int checkStageContacts(const char* who, const idocp_rbd* h, const int* active, d
   return IDOCP_OK;
 }
 
-int maskOf(const idocp_rbd* h, const int* active) {
-  int mask = 0;
-  for (int c = 0; c < h->model.ncontacts; ++c) if (active[c]) mask |= 1 << c;
-  return mask;
-}
-
 // io: device pointers; quadruped: mask = the contact / impulse status
 int launchForward(idocp_rbd* h, int mode, int n, int mask, double time_step, double dt, const idocp_rbd_fd_io_t& io) {
   const DevModel* d_m = static_cast<const DevModel*>(h->d_model);
@@ -173,10 +183,8 @@ int launchForward(idocp_rbd* h, int mode, int n, int mask, double time_step, dou
     rbdForwardQuadruped(d_m, h->d_frames, io, n, mode, mask, time_step, dt, h->stream);
   } else if (io.a || io.q_next || io.v_next) {
     const size_t nv = h->model.nv, nvec = (size_t)n * nv, nmat = nvec * nv;
-    if (2 * nvec + 3 * nmat > h->fd_chain_doubles) {
-      int rc = growBuffer(&h->fd_chain, &h->fd_chain_doubles, 2 * nvec + 3 * nmat, h->stream); if (rc) return rc;
-    }
-    double *zero = h->fd_chain, *hh = zero + nvec, *dq = hh + nvec, *dv = dq + nmat, *M = dv + nmat;
+    int rc = h->fd_chain.grow(2 * nvec + 3 * nmat, h->stream); if (rc) return rc;
+    double *zero = h->fd_chain.ptr, *hh = zero + nvec, *dq = hh + nvec, *dv = dq + nmat, *M = dv + nmat;
     if (io.a || io.v_next) {
       HIP_TRY(hipMemsetAsync(zero, 0, sizeof(double) * nvec, h->stream));
       chainFn(h->model.nv)(d_m, n, io.q, io.v, zero, hh, dq, dv, M, h->zaxes, h->stream);
@@ -188,18 +196,10 @@ int launchForward(idocp_rbd* h, int mode, int n, int mask, double time_step, dou
   return IDOCP_OK;
 }
 
-// doubles per sample of every field of idocp_rbd_fd_io_t, in the order of the struct
-struct FdSizes { size_t in[4], out[4]; };
-FdSizes fdSizes(const idocp_rbd* h) {
-  const size_t nq = h->model.nq, nv = h->model.nv, nu = h->model.nu, nf = 3 * (size_t)h->model.ncontacts;
-  return {{nq, nv, nu, nf}, {nv, nf, nq, nv}};
-}
-size_t even(size_t x) { return (x + 1) / 2 * 2; }
-
 int checkForwardCall(idocp_rbd* h, int mode, int n, const int* active, double time_step, double dt, const idocp_rbd_fd_io_t* io) {
   const char* who = "idocp_rbd_forward_dynamics_batch";
   if (!io) { set_last_error(std::string(who) + ": null io"); return IDOCP_E_ARG; }
-  int rc = checkForward(who, h, mode, n, active, time_step, dt, io->q, io->v, io->contact_points, io->f || io->contact_points); if (rc) return rc;
+  int rc = checkForward(who, h, mode, n, active, dt, io->q, io->v, io->f || io->contact_points); if (rc) return rc;
   if (mode == IDOCP_RBD_STAGE) { rc = checkStageContacts(who, h, active, time_step, io->contact_points); if (rc) return rc; }
   return IDOCP_OK;
 }
@@ -208,7 +208,7 @@ int checkForwardCall(idocp_rbd* h, int mode, int n, const int* active, double ti
 int checkRollout(const char* who, idocp_rbd* h, int n, int steps, const int* active, double time_step, double dt, const double* contact_points,
                  const double* q_traj, const double* v_traj, const double* f_traj) {
   if (steps < 1) { set_last_error(std::string(who) + ": steps must be at least 1"); return IDOCP_E_ARG; }
-  int rc = checkForward(who, h, IDOCP_RBD_STAGE, n, active, time_step, dt, q_traj, v_traj, contact_points, f_traj || contact_points);
+  int rc = checkForward(who, h, IDOCP_RBD_STAGE, n, active, dt, q_traj, v_traj, f_traj || contact_points);
   if (rc) return rc;
   if (h->quadruped)
     for (int k = 0; k < steps; ++k) { rc = checkStageContacts(who, h, active + (size_t)k * h->model.ncontacts, time_step, contact_points); if (rc) return rc; }
@@ -260,8 +260,8 @@ int checkTorques(const char* who, const idocp_rbd* h, int n, const double* q, co
 // every pointer: device memory.  Open loop (pol == nullptr): the torques u [steps][n][nu].  Closed loop: the torques of step k come from the policy
 // at the state of step k and go to slice k of u_traj (or, without u_traj, to the handle's buffer).
 int rolloutDevice(idocp_rbd* h, int n, int steps, const int* active, double time_step, double dt, const double* u, const double* contact_points,
-                  double* q_traj, double* v_traj, double* a_traj, double* f_traj, int touchdown_impulse, const idocp_rbd_policy_t* pol = nullptr,
-                  double* u_traj = nullptr) {
+                  double* q_traj, double* v_traj, double* a_traj, double* f_traj, int touchdown_impulse, const idocp_rbd_policy_t* pol,
+                  double* u_traj) {
   const size_t nq = h->model.nq, nv = h->model.nv, nu = h->model.nu, nf = 3 * (size_t)h->model.ncontacts, N = (size_t)n;
   int prev = 0;
   for (int k = 0; k < steps; ++k) {
@@ -275,7 +275,7 @@ int rolloutDevice(idocp_rbd* h, int n, int steps, const int* active, double time
     idocp_rbd_fd_io_t io = idocp_rbd_fd_io_t();
     io.q = qk; io.v = vk;
     if (pol) {
-      double* uk = u_traj ? u_traj + k * N * nu : h->u_buf;
+      double* uk = u_traj ? u_traj + k * N * nu : h->u_buf.ptr;
       launchPolicy(h, n, k, *pol, qk, vk, uk);
       HIP_TRY(hipGetLastError());
       io.u = uk;
@@ -292,31 +292,19 @@ int rolloutDevice(idocp_rbd* h, int n, int steps, const int* active, double time
   return IDOCP_OK;
 }
 
-// The host form of a policy: its arrays behind one another in the staging buffer.  sizes(): doubles of [u_ff | K | q_ref | v_ref | u_min | u_max].
-struct PolicyStage {
-  size_t sz[6];
-  const double* host[6];
-  PolicyStage(const idocp_rbd* h, const idocp_rbd_policy_t& p, size_t N, size_t S) {
-    const size_t nq = h->model.nq, nv = h->model.nv, nu = h->model.nu, nk = nu * 2 * nv;
-    const size_t full[6] = {S * N * nu, S * (p.shared_gains ? 1 : N) * nk, S * (p.shared_ref ? 1 : N) * nq, S * (p.shared_ref ? 1 : N) * nv, nu, nu};
-    const double* ptr[6] = {p.u_ff, p.K, p.K ? p.q_ref : nullptr, p.K ? p.v_ref : nullptr, p.u_min, p.u_max};
-    for (int i = 0; i < 6; ++i) { host[i] = ptr[i]; sz[i] = ptr[i] ? full[i] : 0; }
-  }
-  size_t total() const { size_t t = 0; for (int i = 0; i < 6; ++i) t += even(sz[i]); return t; }
-  // uploads on st from `cur` on; d: the policy with device pointers; returns the first double behind it
-  int upload(double* cur, hipStream_t st, const idocp_rbd_policy_t& p, idocp_rbd_policy_t* d, double** end) const {
-    const double* dev[6];
-    for (int i = 0; i < 6; ++i) {
-      dev[i] = sz[i] ? cur : nullptr;
-      if (sz[i]) HIP_TRY(hipMemcpyAsync(cur, host[i], sizeof(double) * sz[i], hipMemcpyHostToDevice, st));
-      cur += even(sz[i]);
-    }
-    *d = p;
-    d->u_ff = dev[0]; d->K = dev[1]; d->q_ref = dev[2]; d->v_ref = dev[3]; d->u_min = dev[4]; d->u_max = dev[5];
-    *end = cur;
-    return IDOCP_OK;
-  }
-};
+// The host form of a policy: its six arrays as slots of the plan; *d: the policy with device pointers once the plan is bound.
+// N samples, S steps; q_ref and v_ref are not read without K and get no room then.
+void policySlots(StagePlan& p, const idocp_rbd* h, const idocp_rbd_policy_t& pol, size_t N, size_t S, idocp_rbd_policy_t* d) {
+  const size_t nq = h->model.nq, nv = h->model.nv, nu = h->model.nu, nk = nu * 2 * nv;
+  const size_t gains = S * (pol.shared_gains ? 1 : N), refs = S * (pol.shared_ref ? 1 : N);
+  *d = pol;
+  p.in(pol.u_ff, S * N * nu, &d->u_ff);
+  p.in(pol.K, gains * nk, &d->K);
+  p.in(pol.K ? pol.q_ref : nullptr, refs * nq, &d->q_ref);
+  p.in(pol.K ? pol.v_ref : nullptr, refs * nv, &d->v_ref);
+  p.in(pol.u_min, nu, &d->u_min);
+  p.in(pol.u_max, nu, &d->u_max);
+}
 
 }  // namespace
 
@@ -362,10 +350,10 @@ void idocp_rbd_destroy(idocp_rbd_t* h) {
   (void)hipSetDevice(h->device);
   if (h->stream) (void)hipStreamSynchronize(h->stream);
   if (h->d_model) (void)hipFree(h->d_model);
-  if (h->stage) (void)hipFree(h->stage);
-  if (h->unwanted) (void)hipFree(h->unwanted);
-  if (h->fd_chain) (void)hipFree(h->fd_chain);
-  if (h->u_buf) (void)hipFree(h->u_buf);
+  h->stage.release();
+  h->unwanted.release();
+  h->fd_chain.release();
+  h->u_buf.release();
   if (h->stream) (void)hipStreamDestroy(h->stream);
   delete h;
 }
@@ -380,38 +368,33 @@ int idocp_rbd_synchronize(idocp_rbd_t* h) {
 void* idocp_rbd_stream(idocp_rbd_t* h) { return h ? static_cast<void*>(h->stream) : nullptr; }
 
 int idocp_rbd_contact_dynamics_batch_device(idocp_rbd_t* h, int mode, int n, const int* active, double time_step, const idocp_rbd_io_t* io) {
-  int rc = checkCall(h, mode, n, active, time_step, io); if (rc) return rc;
+  int rc = checkCall(INVERSE, h, mode, n, active, time_step, io); if (rc) return rc;
   return launch(h, mode, n, active, time_step, *io);
 }
 
 int idocp_rbd_contact_dynamics_batch(idocp_rbd_t* h, int mode, int n, const int* active, double time_step, const idocp_rbd_io_t* io) {
-  int rc = checkCall(h, mode, n, active, time_step, io); if (rc) return rc;
+  int rc = checkCall(INVERSE, h, mode, n, active, time_step, io); if (rc) return rc;
   HIP_TRY(hipSetDevice(h->device));
-  const FieldSizes fs = fieldSizes(h);
-  const double* const host_in[5] = {io->q, io->v, io->a, io->f, io->contact_points};
-  double* const host_out[9] = {io->tau, io->dtau_dq, io->dtau_dv, io->dtau_da, io->C, io->dCdq, io->dCdv, io->dCda, io->MJtJinv};
-  size_t total = 0;
-  for (int i = 0; i < 5; ++i) if (host_in[i]) total += (fs.in[i] * n + 1) / 2 * 2;
-  for (int i = 0; i < 9; ++i) if (host_out[i]) total += (fs.out[i] * n + 1) / 2 * 2;
-  rc = growBuffer(&h->stage, &h->stage_doubles, total, h->stream); if (rc) return rc;
-  const double* dev_in[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
-  double* dev_out[9] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-  double* cur = h->stage;
-  for (int i = 0; i < 5; ++i) if (host_in[i]) {
-    HIP_TRY(hipMemcpyAsync(cur, host_in[i], sizeof(double) * fs.in[i] * n, hipMemcpyHostToDevice, h->stream));
-    dev_in[i] = cur; cur += (fs.in[i] * n + 1) / 2 * 2;
-  }
-  for (int i = 0; i < 9; ++i) if (host_out[i]) { dev_out[i] = cur; cur += (fs.out[i] * n + 1) / 2 * 2; }
+  const size_t nq = h->model.nq, nv = h->model.nv, nf = 3 * (size_t)h->model.ncontacts, N = (size_t)n;
+  StagePlan p;
   idocp_rbd_io_t d;
-  d.q = dev_in[0]; d.v = dev_in[1]; d.a = dev_in[2]; d.f = dev_in[3]; d.contact_points = dev_in[4];
-  d.tau = dev_out[0]; d.dtau_dq = dev_out[1]; d.dtau_dv = dev_out[2]; d.dtau_da = dev_out[3];
-  d.C = dev_out[4]; d.dCdq = dev_out[5]; d.dCdv = dev_out[6]; d.dCda = dev_out[7]; d.MJtJinv = dev_out[8];
-  if (d.MJtJinv) HIP_TRY(hipMemsetAsync(d.MJtJinv, 0, sizeof(double) * fs.out[8] * n, h->stream));      // (the part of a slot behind the packed block)
+  p.in(io->q, N * nq, &d.q);
+  p.in(io->v, N * nv, &d.v);
+  p.in(io->a, N * nv, &d.a);
+  p.in(io->f, N * nf, &d.f);
+  p.in(io->contact_points, N * nf, &d.contact_points);
+  p.out(io->tau, N * nv, &d.tau);
+  p.out(io->dtau_dq, N * nv * nv, &d.dtau_dq);
+  p.out(io->dtau_dv, N * nv * nv, &d.dtau_dv);
+  p.out(io->dtau_da, N * nv * nv, &d.dtau_da);
+  p.out(io->C, N * nf, &d.C);
+  p.out(io->dCdq, N * nf * nv, &d.dCdq);
+  p.out(io->dCdv, N * nf * nv, &d.dCdv);
+  p.out(io->dCda, N * nf * nv, &d.dCda);
+  p.out(io->MJtJinv, N * (nv + nf) * (nv + nf), &d.MJtJinv, true);      // (zero-filled: the part of a slot behind the packed block)
+  rc = stageIn(h, p); if (rc) return rc;
   rc = launch(h, mode, n, active, time_step, d); if (rc) return rc;
-  for (int i = 0; i < 9; ++i) if (host_out[i])
-    HIP_TRY(hipMemcpyAsync(host_out[i], dev_out[i], sizeof(double) * fs.out[i] * n, hipMemcpyDeviceToHost, h->stream));
-  HIP_TRY(hipStreamSynchronize(h->stream));
-  return IDOCP_OK;
+  return stageOut(h, p);
 }
 
 int idocp_rbd_forward_dynamics_batch_device(idocp_rbd_t* h, int mode, int n, const int* active, double time_step, double dt, const idocp_rbd_fd_io_t* io) {
@@ -423,36 +406,27 @@ int idocp_rbd_forward_dynamics_batch_device(idocp_rbd_t* h, int mode, int n, con
 int idocp_rbd_forward_dynamics_batch(idocp_rbd_t* h, int mode, int n, const int* active, double time_step, double dt, const idocp_rbd_fd_io_t* io) {
   int rc = checkForwardCall(h, mode, n, active, time_step, dt, io); if (rc) return rc;
   HIP_TRY(hipSetDevice(h->device));
-  const FdSizes fs = fdSizes(h);
-  const double* const host_in[4] = {io->q, io->v, io->u, io->contact_points};
-  double* const host_out[4] = {io->a, io->f, io->q_next, io->v_next};
-  size_t total = 0;
-  for (int i = 0; i < 4; ++i) if (host_in[i]) total += even(fs.in[i] * n);
-  for (int i = 0; i < 4; ++i) if (host_out[i]) total += even(fs.out[i] * n);
-  rc = growBuffer(&h->stage, &h->stage_doubles, total, h->stream); if (rc) return rc;
-  const double* dev_in[4] = {nullptr, nullptr, nullptr, nullptr};
-  double* dev_out[4] = {nullptr, nullptr, nullptr, nullptr};
-  double* cur = h->stage;
-  for (int i = 0; i < 4; ++i) if (host_in[i]) {
-    HIP_TRY(hipMemcpyAsync(cur, host_in[i], sizeof(double) * fs.in[i] * n, hipMemcpyHostToDevice, h->stream));
-    dev_in[i] = cur; cur += even(fs.in[i] * n);
-  }
-  for (int i = 0; i < 4; ++i) if (host_out[i]) { dev_out[i] = cur; cur += even(fs.out[i] * n); }
+  const size_t nq = h->model.nq, nv = h->model.nv, nu = h->model.nu, nf = 3 * (size_t)h->model.ncontacts, N = (size_t)n;
+  StagePlan p;
   idocp_rbd_fd_io_t d;
-  d.q = dev_in[0]; d.v = dev_in[1]; d.u = dev_in[2]; d.contact_points = dev_in[3];
-  d.a = dev_out[0]; d.f = dev_out[1]; d.q_next = dev_out[2]; d.v_next = dev_out[3];
+  p.in(io->q, N * nq, &d.q);
+  p.in(io->v, N * nv, &d.v);
+  p.in(io->u, N * nu, &d.u);
+  p.in(io->contact_points, N * nf, &d.contact_points);
+  p.out(io->a, N * nv, &d.a);
+  p.out(io->f, N * nf, &d.f);
+  p.out(io->q_next, N * nq, &d.q_next);
+  p.out(io->v_next, N * nv, &d.v_next);
+  rc = stageIn(h, p); if (rc) return rc;
   rc = launchForward(h, mode, n, h->quadruped ? maskOf(h, active) : 0, time_step, dt, d); if (rc) return rc;
-  for (int i = 0; i < 4; ++i) if (host_out[i])
-    HIP_TRY(hipMemcpyAsync(host_out[i], dev_out[i], sizeof(double) * fs.out[i] * n, hipMemcpyDeviceToHost, h->stream));
-  HIP_TRY(hipStreamSynchronize(h->stream));
-  return IDOCP_OK;
+  return stageOut(h, p);
 }
 
 int idocp_rbd_rollout_device(idocp_rbd_t* h, int n, int steps, const int* active, double time_step, double dt, const double* u, const double* contact_points,
                              double* q_traj, double* v_traj, double* a_traj, double* f_traj, int touchdown_impulse) {
   int rc = checkRollout("idocp_rbd_rollout", h, n, steps, active, time_step, dt, contact_points, q_traj, v_traj, f_traj); if (rc) return rc;
   HIP_TRY(hipSetDevice(h->device));
-  return rolloutDevice(h, n, steps, active, time_step, dt, u, contact_points, q_traj, v_traj, a_traj, f_traj, touchdown_impulse);
+  return rolloutDevice(h, n, steps, active, time_step, dt, u, contact_points, q_traj, v_traj, a_traj, f_traj, touchdown_impulse, nullptr, nullptr);
 }
 
 int idocp_rbd_rollout(idocp_rbd_t* h, int n, int steps, const int* active, double time_step, double dt, const double* u, const double* contact_points,
@@ -460,26 +434,18 @@ int idocp_rbd_rollout(idocp_rbd_t* h, int n, int steps, const int* active, doubl
   int rc = checkRollout("idocp_rbd_rollout", h, n, steps, active, time_step, dt, contact_points, q_traj, v_traj, f_traj); if (rc) return rc;
   HIP_TRY(hipSetDevice(h->device));
   const size_t nq = h->model.nq, nv = h->model.nv, nu = h->model.nu, nf = 3 * (size_t)h->model.ncontacts, N = (size_t)n, S = (size_t)steps;
-  // [q_traj | v_traj | u | contact_points | a_traj | f_traj]: staged once, read back once
-  const size_t sz[6] = {(S + 1) * N * nq, (S + 1) * N * nv, u ? S * N * nu : 0, contact_points ? S * N * nf : 0, a_traj ? S * N * nv : 0, f_traj ? S * N * nf : 0};
-  size_t total = 0;
-  for (int i = 0; i < 6; ++i) total += even(sz[i]);
-  rc = growBuffer(&h->stage, &h->stage_doubles, total, h->stream); if (rc) return rc;
-  double* dev[6];
-  double* cur = h->stage;
-  for (int i = 0; i < 6; ++i) { dev[i] = sz[i] ? cur : nullptr; cur += even(sz[i]); }
-  HIP_TRY(hipMemcpyAsync(dev[0], q_traj, sizeof(double) * N * nq, hipMemcpyHostToDevice, h->stream));
-  HIP_TRY(hipMemcpyAsync(dev[1], v_traj, sizeof(double) * N * nv, hipMemcpyHostToDevice, h->stream));
-  if (u) HIP_TRY(hipMemcpyAsync(dev[2], u, sizeof(double) * sz[2], hipMemcpyHostToDevice, h->stream));
-  if (contact_points) HIP_TRY(hipMemcpyAsync(dev[3], contact_points, sizeof(double) * sz[3], hipMemcpyHostToDevice, h->stream));
-  rc = rolloutDevice(h, n, steps, active, time_step, dt, dev[2], dev[3], dev[0], dev[1], dev[4], dev[5], touchdown_impulse); if (rc) return rc;
-  // (slice 0 of v_traj comes back too; it is the input)
-  HIP_TRY(hipMemcpyAsync(q_traj + N * nq, dev[0] + N * nq, sizeof(double) * S * N * nq, hipMemcpyDeviceToHost, h->stream));
-  HIP_TRY(hipMemcpyAsync(v_traj + N * nv, dev[1] + N * nv, sizeof(double) * S * N * nv, hipMemcpyDeviceToHost, h->stream));
-  if (a_traj) HIP_TRY(hipMemcpyAsync(a_traj, dev[4], sizeof(double) * sz[4], hipMemcpyDeviceToHost, h->stream));
-  if (f_traj) HIP_TRY(hipMemcpyAsync(f_traj, dev[5], sizeof(double) * sz[5], hipMemcpyDeviceToHost, h->stream));
-  HIP_TRY(hipStreamSynchronize(h->stream));
-  return IDOCP_OK;
+  StagePlan p;
+  const double *d_u, *d_points;
+  double *d_q, *d_v, *d_a, *d_f;
+  p.inout(q_traj, (S + 1) * N * nq, N * nq, &d_q);      // (slice 0 goes up, slices 1 .. S come back)
+  p.inout(v_traj, (S + 1) * N * nv, N * nv, &d_v);
+  p.in(u, S * N * nu, &d_u);
+  p.in(contact_points, S * N * nf, &d_points);
+  p.out(a_traj, S * N * nv, &d_a);
+  p.out(f_traj, S * N * nf, &d_f);
+  rc = stageIn(h, p); if (rc) return rc;
+  rc = rolloutDevice(h, n, steps, active, time_step, dt, d_u, d_points, d_q, d_v, d_a, d_f, touchdown_impulse, nullptr, nullptr); if (rc) return rc;
+  return stageOut(h, p);
 }
 
 int idocp_rbd_feedback_torques_batch_device(idocp_rbd_t* h, int n, const double* q, const double* v, const idocp_rbd_policy_t* pol, double* u) {
@@ -493,20 +459,19 @@ int idocp_rbd_feedback_torques_batch_device(idocp_rbd_t* h, int n, const double*
 int idocp_rbd_feedback_torques_batch(idocp_rbd_t* h, int n, const double* q, const double* v, const idocp_rbd_policy_t* pol, double* u) {
   int rc = checkTorques("idocp_rbd_feedback_torques_batch", h, n, q, v, pol, u, true); if (rc) return rc;
   HIP_TRY(hipSetDevice(h->device));
-  const size_t nq = h->model.nq, nv = h->model.nv, nu = h->model.nu, N = (size_t)n;
-  const PolicyStage ps(h, *pol, N, 1);
-  rc = growBuffer(&h->stage, &h->stage_doubles, ps.total() + even(N * nq) + even(N * nv) + even(N * nu), h->stream); if (rc) return rc;
-  idocp_rbd_policy_t d;
-  double* cur = nullptr;
-  rc = ps.upload(h->stage, h->stream, *pol, &d, &cur); if (rc) return rc;
-  double *dq = cur, *dv = dq + even(N * nq), *du = dv + even(N * nv);
-  HIP_TRY(hipMemcpyAsync(dq, q, sizeof(double) * N * nq, hipMemcpyHostToDevice, h->stream));
-  HIP_TRY(hipMemcpyAsync(dv, v, sizeof(double) * N * nv, hipMemcpyHostToDevice, h->stream));
-  launchPolicy(h, n, 0, d, dq, dv, du);
+  const size_t N = (size_t)n;
+  StagePlan p;
+  idocp_rbd_policy_t d_pol;
+  const double *d_q, *d_v;
+  double* d_u;
+  policySlots(p, h, *pol, N, 1, &d_pol);
+  p.in(q, N * h->model.nq, &d_q);
+  p.in(v, N * h->model.nv, &d_v);
+  p.out(u, N * h->model.nu, &d_u);
+  rc = stageIn(h, p); if (rc) return rc;
+  launchPolicy(h, n, 0, d_pol, d_q, d_v, d_u);
   HIP_TRY(hipGetLastError());
-  HIP_TRY(hipMemcpyAsync(u, du, sizeof(double) * N * nu, hipMemcpyDeviceToHost, h->stream));
-  HIP_TRY(hipStreamSynchronize(h->stream));
-  return IDOCP_OK;
+  return stageOut(h, p);
 }
 
 int idocp_rbd_rollout_policy_device(idocp_rbd_t* h, int n, int steps, const int* active, double time_step, double dt, const idocp_rbd_policy_t* pol,
@@ -516,7 +481,7 @@ int idocp_rbd_rollout_policy_device(idocp_rbd_t* h, int n, int steps, const int*
   int rc = checkRollout(who, h, n, steps, active, time_step, dt, contact_points, q_traj, v_traj, f_traj); if (rc) return rc;
   rc = checkPolicy(who, h, pol, false); if (rc) return rc;
   HIP_TRY(hipSetDevice(h->device));
-  if (!u_traj) { rc = growBuffer(&h->u_buf, &h->u_buf_doubles, (size_t)n * h->model.nu, h->stream); if (rc) return rc; }
+  if (!u_traj) { rc = h->u_buf.grow((size_t)n * h->model.nu, h->stream); if (rc) return rc; }
   return rolloutDevice(h, n, steps, active, time_step, dt, nullptr, contact_points, q_traj, v_traj, a_traj, f_traj, touchdown_impulse, pol, u_traj);
 }
 
@@ -528,29 +493,21 @@ int idocp_rbd_rollout_policy(idocp_rbd_t* h, int n, int steps, const int* active
   rc = checkPolicy(who, h, pol, true); if (rc) return rc;
   HIP_TRY(hipSetDevice(h->device));
   const size_t nq = h->model.nq, nv = h->model.nv, nu = h->model.nu, nf = 3 * (size_t)h->model.ncontacts, N = (size_t)n, S = (size_t)steps;
-  const PolicyStage ps(h, *pol, N, S);
-  // [policy | q_traj | v_traj | contact_points | u_traj | a_traj | f_traj]: staged once, read back once
-  const size_t sz[6] = {(S + 1) * N * nq, (S + 1) * N * nv, contact_points ? S * N * nf : 0, u_traj ? S * N * nu : 0, a_traj ? S * N * nv : 0, f_traj ? S * N * nf : 0};
-  size_t total = ps.total();
-  for (int i = 0; i < 6; ++i) total += even(sz[i]);
-  rc = growBuffer(&h->stage, &h->stage_doubles, total, h->stream); if (rc) return rc;
-  if (!u_traj) { rc = growBuffer(&h->u_buf, &h->u_buf_doubles, N * nu, h->stream); if (rc) return rc; }
-  idocp_rbd_policy_t d;
-  double* cur = nullptr;
-  rc = ps.upload(h->stage, h->stream, *pol, &d, &cur); if (rc) return rc;
-  double* dev[6];
-  for (int i = 0; i < 6; ++i) { dev[i] = sz[i] ? cur : nullptr; cur += even(sz[i]); }
-  HIP_TRY(hipMemcpyAsync(dev[0], q_traj, sizeof(double) * N * nq, hipMemcpyHostToDevice, h->stream));
-  HIP_TRY(hipMemcpyAsync(dev[1], v_traj, sizeof(double) * N * nv, hipMemcpyHostToDevice, h->stream));
-  if (contact_points) HIP_TRY(hipMemcpyAsync(dev[2], contact_points, sizeof(double) * sz[2], hipMemcpyHostToDevice, h->stream));
-  rc = rolloutDevice(h, n, steps, active, time_step, dt, nullptr, dev[2], dev[0], dev[1], dev[4], dev[5], touchdown_impulse, &d, dev[3]); if (rc) return rc;
-  HIP_TRY(hipMemcpyAsync(q_traj + N * nq, dev[0] + N * nq, sizeof(double) * S * N * nq, hipMemcpyDeviceToHost, h->stream));
-  HIP_TRY(hipMemcpyAsync(v_traj + N * nv, dev[1] + N * nv, sizeof(double) * S * N * nv, hipMemcpyDeviceToHost, h->stream));
-  if (u_traj) HIP_TRY(hipMemcpyAsync(u_traj, dev[3], sizeof(double) * sz[3], hipMemcpyDeviceToHost, h->stream));
-  if (a_traj) HIP_TRY(hipMemcpyAsync(a_traj, dev[4], sizeof(double) * sz[4], hipMemcpyDeviceToHost, h->stream));
-  if (f_traj) HIP_TRY(hipMemcpyAsync(f_traj, dev[5], sizeof(double) * sz[5], hipMemcpyDeviceToHost, h->stream));
-  HIP_TRY(hipStreamSynchronize(h->stream));
-  return IDOCP_OK;
+  if (!u_traj) { rc = h->u_buf.grow(N * nu, h->stream); if (rc) return rc; }
+  StagePlan p;
+  idocp_rbd_policy_t d_pol;
+  const double* d_points;
+  double *d_q, *d_v, *d_u, *d_a, *d_f;
+  policySlots(p, h, *pol, N, S, &d_pol);
+  p.inout(q_traj, (S + 1) * N * nq, N * nq, &d_q);      // (slice 0 goes up, slices 1 .. S come back)
+  p.inout(v_traj, (S + 1) * N * nv, N * nv, &d_v);
+  p.in(contact_points, S * N * nf, &d_points);
+  p.out(u_traj, S * N * nu, &d_u);
+  p.out(a_traj, S * N * nv, &d_a);
+  p.out(f_traj, S * N * nf, &d_f);
+  rc = stageIn(h, p); if (rc) return rc;
+  rc = rolloutDevice(h, n, steps, active, time_step, dt, nullptr, d_points, d_q, d_v, d_a, d_f, touchdown_impulse, &d_pol, d_u); if (rc) return rc;
+  return stageOut(h, p);
 }
 
 }  // extern "C"

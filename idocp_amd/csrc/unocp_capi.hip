@@ -17,6 +17,7 @@
 #include <utility>
 #include <vector>
 
+#include "hip_try.hpp"
 #include "host_util.hpp"
 #include "idocp_hip.h"
 #include "model_shapes.hpp"
@@ -27,16 +28,6 @@ using idocp_host::set_last_error;
 using idocp_host::toDevModel;
 using idocp_host::isRevoluteChain;
 using idocp_host::CHAIN_RANGE;
-
-#define HIP_TRY(expr)                                                                         \
-  do {                                                                                        \
-    hipError_t e_ = (expr);                                                                   \
-    if (e_ != hipSuccess) {                                                                   \
-      set_last_error(std::string(#expr) + ": " + hipGetErrorString(e_));                      \
-      (void)hipGetLastError(); /* HIP keeps a failed call as the thread's "last error": reported here, it must not fail the next handle's launches */ \
-      return IDOCP_E_DEVICE;                                                                  \
-    }                                                                                         \
-  } while (0)
 
 namespace {
 

@@ -168,9 +168,27 @@ def test_selected_outputs_and_device_pointers():
     assert np.array_equal(copy.numpy().transpose(0, 2, 1), host["dCda"])
     # an output without the input it needs
     io.contact_points = None
-    assert r.call_raw(STAGE, n, ALL, 0.05, io, device=True) == E_ARG
-    assert r.call_raw(2, n, ALL, 0.05, io, device=True) == E_ARG
-    assert r.call_raw(STAGE, 0, ALL, 0.05, io, device=True) == E_ARG
+    CALL = b"idocp_rbd_contact_dynamics_batch"               # (the device form reports under the same name)
+
+    def refused(rc, text):
+        assert rc == E_ARG, text
+        assert capi.lib().idocp_last_error() == CALL + text
+
+    refused(r.call_raw(STAGE, n, ALL, 0.05, io, device=True), b": C in STAGE mode needs contact_points")
+    refused(r.call_raw(2, n, ALL, 0.05, io, device=True), b": unknown mode")
+    refused(r.call_raw(STAGE, 0, ALL, 0.05, io, device=True), b": n must be positive")
+    # two conditions violated at once: the one tested first is the one reported, by both forms
+    for device in (True, False):
+        refused(r.call_raw(2, 0, ALL, 0.05, io, device=device), b": n must be positive")
+        refused(r.call_raw(2, n, None, 0.05, io, device=device), b": unknown mode")
+        refused(r.call_raw(STAGE, n, None, 0.0, io, device=device), b": the contact status `active` is needed")
+        refused(r.call_raw(STAGE, n, ALL, 0.0, io, device=device), b": C in STAGE mode needs contact_points")
+    io.contact_points = d_in["contact_points"].ptr
+    refused(r.call_raw(STAGE, n, ALL, 0.0, io, device=True), b": the Baumgarte terms need a positive time_step")
+    io.q = None
+    refused(r.call_raw(STAGE, n, ALL, 0.05, io, device=True), b": q, v and a are needed")
+    assert r.lib.idocp_rbd_contact_dynamics_batch(r.h, STAGE, n, None, 0.05, None) == E_ARG
+    assert capi.lib().idocp_last_error() == CALL + b": null handle or io"
 
 
 @pytest.mark.parametrize("mode", [STAGE, IMPULSE])
@@ -211,7 +229,11 @@ def test_fixed_base_chains_match_idocp_rnea_derivatives_bit_for_bit(which):
     bufs = [arr(q), arr(v), arr(a), np.zeros((n, 12))]
     io.q, io.v, io.a, io.C = [b.ctypes.data for b in bufs]
     assert r.call_raw(STAGE, n, None, 0.05, io) == E_ARG
-    assert b"no contacts" in capi.lib().idocp_last_error()
+    assert capi.lib().idocp_last_error() == (b"idocp_rbd_contact_dynamics_batch: a fixed-base chain has no contacts "
+                                             b"(f, contact_points and the contact outputs must be NULL)")
+    io.C = None
+    assert r.call_raw(IMPULSE, n, None, 0.05, io) == E_ARG
+    assert capi.lib().idocp_last_error() == b"idocp_rbd_contact_dynamics_batch: a fixed-base chain has no impulse mode"
 
 
 def test_facade_robot_on_the_gpu(tmp_path):

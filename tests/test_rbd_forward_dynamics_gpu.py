@@ -240,10 +240,14 @@ def test_chains(nv, seed, zaxes):
 def test_refusals():
     lib = capi.lib()
 
-    def refused(rc, what):
+    FD, RO = "idocp_rbd_forward_dynamics_batch", "idocp_rbd_rollout"
+    NO_CONTACTS = ": a fixed-base chain has no contacts (f and contact_points must be NULL)"
+
+    def refused(rc, what, text):
+        """the code and the COMPLETE text of idocp_last_error()"""
         assert rc == E_ARG, what
         msg = lib.idocp_last_error().decode()
-        assert msg and ("forward_dynamics" in msg or "rollout" in msg), (what, msg)
+        assert msg == text, (what, msg)
 
     def io_of(**arrays):
         io = capi.RbdFdIO()
@@ -257,12 +261,12 @@ def test_refusals():
     r = Rbd(m)
     q, v, a = np.zeros((n, m.nq)), np.zeros((n, m.nv)), np.zeros((n, m.nv))
     junk = np.zeros((n, 12))
-    refused(F.forward_raw(r, STAGE, n, None, 0.0, DT, io_of(q=q, v=v, a=a, f=junk)), "chain with f")
-    refused(F.forward_raw(r, STAGE, n, None, 0.0, DT, io_of(q=q, v=v, a=a, contact_points=junk)), "chain with contact_points")
-    refused(F.forward_raw(r, IMPULSE, n, None, 0.0, DT, io_of(q=q, v=v, a=a)), "chain in IMPULSE mode")
+    refused(F.forward_raw(r, STAGE, n, None, 0.0, DT, io_of(q=q, v=v, a=a, f=junk)), "chain with f", FD + NO_CONTACTS)
+    refused(F.forward_raw(r, STAGE, n, None, 0.0, DT, io_of(q=q, v=v, a=a, contact_points=junk)), "chain with contact_points", FD + NO_CONTACTS)
+    refused(F.forward_raw(r, IMPULSE, n, None, 0.0, DT, io_of(q=q, v=v, a=a)), "chain in IMPULSE mode", FD + ": a fixed-base chain has no impulse mode")
     qt, vt = np.zeros((2, n, m.nq)), np.zeros((2, n, m.nv))
-    refused(F.rollout_raw(r, n, 1, None, 0.0, DT, None, None, qt, vt, None, junk, 0), "chain rollout with f_traj")
-    refused(F.rollout_raw(r, n, 0, None, 0.0, DT, None, None, qt, vt, None, None, 0), "steps = 0")
+    refused(F.rollout_raw(r, n, 1, None, 0.0, DT, None, None, qt, vt, None, junk, 0), "chain rollout with f_traj", RO + NO_CONTACTS)
+    refused(F.rollout_raw(r, n, 0, None, 0.0, DT, None, None, qt, vt, None, None, 0), "steps = 0", RO + ": steps must be at least 1")
     r.close()
     # a quadruped
     m = anymal_model()
@@ -271,19 +275,31 @@ def test_refusals():
     q[:, 6] = 1.0
     pts = np.zeros((n, 4, 3))
     good = dict(q=q, v=v, a=a, contact_points=pts)
-    refused(F.forward_raw(r, STAGE, n, None, TS, DT, io_of(**good)), "no active")
-    refused(F.forward_raw(r, STAGE, 0, [1, 1, 1, 1], TS, DT, io_of(**good)), "n = 0")
-    refused(F.forward_raw(r, STAGE, n, [1, 1, 1, 1], TS, float("nan"), io_of(**good)), "dt = nan")
-    refused(F.forward_raw(r, STAGE, n, [1, 1, 1, 1], TS, float("inf"), io_of(**good)), "dt = inf")
-    refused(F.forward_raw(r, STAGE, n, [1, 1, 1, 1], TS, DT, io_of(q=q, v=v, a=a)), "active contacts without contact_points")
-    refused(F.forward_raw(r, STAGE, n, [1, 1, 1, 1], 0.0, DT, io_of(**good)), "active contacts without a time step")
-    refused(F.forward_raw(r, 7, n, [1, 1, 1, 1], TS, DT, io_of(**good)), "unknown mode")
-    refused(F.forward_raw(r, STAGE, n, [1, 1, 1, 1], TS, DT, None), "null io")
-    refused(F.forward_raw(r, STAGE, n, [1, 1, 1, 1], TS, DT, io_of(v=v, a=a, contact_points=pts)), "no q")
+    refused(F.forward_raw(r, STAGE, n, None, TS, DT, io_of(**good)), "no active", FD + ": the contact status `active` is needed")
+    refused(F.forward_raw(r, STAGE, 0, [1, 1, 1, 1], TS, DT, io_of(**good)), "n = 0", FD + ": n must be positive")
+    refused(F.forward_raw(r, STAGE, n, [1, 1, 1, 1], TS, float("nan"), io_of(**good)), "dt = nan", FD + ": dt must be finite")
+    refused(F.forward_raw(r, STAGE, n, [1, 1, 1, 1], TS, float("inf"), io_of(**good)), "dt = inf", FD + ": dt must be finite")
+    refused(F.forward_raw(r, STAGE, n, [1, 1, 1, 1], TS, DT, io_of(q=q, v=v, a=a)), "active contacts without contact_points", FD + ": STAGE mode with an active contact needs contact_points")
+    refused(F.forward_raw(r, STAGE, n, [1, 1, 1, 1], 0.0, DT, io_of(**good)), "active contacts without a time step", FD + ": STAGE mode with an active contact needs a positive Baumgarte time_step")
+    refused(F.forward_raw(r, 7, n, [1, 1, 1, 1], TS, DT, io_of(**good)), "unknown mode", FD + ": unknown mode")
+    refused(F.forward_raw(r, STAGE, n, [1, 1, 1, 1], TS, DT, None), "null io", FD + ": null io")
+    refused(F.forward_raw(r, STAGE, n, [1, 1, 1, 1], TS, DT, io_of(v=v, a=a, contact_points=pts)), "no q", FD + ": q and v are needed")
+    # two conditions violated at once: the one tested first is the one reported (n before the mode, the mode before q and v, those before dt)
+    refused(F.forward_raw(r, 7, 0, [1, 1, 1, 1], TS, DT, io_of(**good)), "n = 0 and an unknown mode", FD + ": n must be positive")
+    refused(F.forward_raw(r, 7, n, [1, 1, 1, 1], TS, float("nan"), io_of(v=v, a=a)), "unknown mode, no q, dt = nan", FD + ": unknown mode")
+    refused(F.forward_raw(r, STAGE, n, None, TS, float("nan"), io_of(**good)), "dt = nan and no active", FD + ": dt must be finite")
+    refused(F.forward_raw(r, STAGE, n, [1, 1, 1, 1], 0.0, DT, io_of(q=q, v=v, a=a)), "no contact_points and no time step",
+            FD + ": STAGE mode with an active contact needs contact_points")
     qt, vt = np.zeros((2, n, m.nq)), np.zeros((2, n, m.nv))
-    refused(F.rollout_raw(r, n, 0, [1, 1, 1, 1], TS, DT, None, pts[None], qt, vt, None, None, 0), "steps = 0")
-    refused(F.rollout_raw(r, n, 1, None, TS, DT, None, pts[None], qt, vt, None, None, 0), "rollout without active")
-    refused(F.rollout_raw(r, n, 1, [1, 1, 1, 1], TS, float("nan"), None, pts[None], qt, vt, None, None, 0), "rollout with dt = nan")
+    refused(F.rollout_raw(r, n, 0, [1, 1, 1, 1], TS, DT, None, pts[None], qt, vt, None, None, 0), "steps = 0", RO + ": steps must be at least 1")
+    refused(F.rollout_raw(r, n, 1, None, TS, DT, None, pts[None], qt, vt, None, None, 0), "rollout without active", RO + ": the contact status `active` is needed")
+    refused(F.rollout_raw(r, n, 1, [1, 1, 1, 1], TS, float("nan"), None, pts[None], qt, vt, None, None, 0), "rollout with dt = nan", RO + ": dt must be finite")
+    refused(F.rollout_raw(r, 0, 0, None, TS, DT, None, pts[None], qt, vt, None, None, 0), "steps = 0, n = 0 and no active", RO + ": steps must be at least 1")
+    refused(F.rollout_raw(r, 0, 1, None, TS, DT, None, pts[None], qt, vt, None, None, 0), "n = 0 and no active", RO + ": n must be positive")
+    refused(F.rollout_raw(r, n, 1, [1, 1, 1, 1], TS, DT, None, pts[None], None, vt, None, None, 0), "no q_traj", RO + ": q and v are needed")
+    refused(F.rollout_raw(r, n, 1, [1, 1, 1, 1], TS, DT, None, None, qt, vt, None, None, 0, device=True), "device form: its texts carry the un-suffixed name",
+            RO + ": STAGE mode with an active contact needs contact_points")
+    refused(F.forward_raw(r, STAGE, 0, [1, 1, 1, 1], TS, DT, io_of(**good), device=True), "n = 0, device form", FD + ": n must be positive")
     # the refusals left the handle usable
     o = F.forward(r, STAGE, q, v, None, [0, 0, 0, 0], 0.0, DT)
     assert np.isfinite(o["a"]).all()

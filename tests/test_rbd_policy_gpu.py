@@ -385,10 +385,22 @@ def test_refusals():
     m, M, x = rollout_case()
     n, steps, nu = 2, 1, m.nu
 
-    def refused(rc, call, what):
+    def refused(rc, call, what, text=None):
+        """the code and the COMPLETE text of idocp_last_error(): the call's name, then TEXTS[what] or the text given"""
         assert rc == E_ARG, what
         msg = lib.idocp_last_error().decode()
-        assert call in msg, (what, msg)
+        assert msg == call + (text or TEXTS[what]), (what, msg)
+
+    NO_CONTACTS = ": a fixed-base chain has no contacts (f and contact_points must be NULL)"
+    TEXTS = {"null policy": ": null policy", "null policy, device form": ": null policy",
+             "K without q_ref": ": gains K need the references q_ref and v_ref", "K without v_ref": ": gains K need the references q_ref and v_ref",
+             "u_min > u_max": ": u_min[5] <= u_max[5] does not hold (or a bound is NaN)",
+             "NaN in u_min": ": u_min[11] <= u_max[11] does not hold (or a bound is NaN)", "NaN in u_max": ": u_min[11] <= u_max[11] does not hold (or a bound is NaN)",
+             "n = 0": ": n must be positive", "no q": ": q, v and u are needed", "no u": ": q, v and u are needed",
+             "steps = 0": ": steps must be at least 1", "no active": ": the contact status `active` is needed", "dt = nan": ": dt must be finite",
+             "active contacts without contact_points": ": STAGE mode with an active contact needs contact_points",
+             "active contacts without a time step": ": STAGE mode with an active contact needs a positive Baumgarte time_step",
+             "no q_traj": ": q and v are needed", "chain with contact_points": NO_CONTACTS, "chain with f_traj": NO_CONTACTS}
 
     r = Rbd(m)
     q, v, u = x["q0"][:n].copy(), x["v0"][:n].copy(), np.zeros((n, nu))
@@ -413,6 +425,11 @@ def test_refusals():
     refused(RP.torques_raw(r, n, None, v, pol, u), call, "no q")
     refused(RP.torques_raw(r, n, q, v, pol, None), call, "no u")
     refused(RP.torques_raw(r, n, q, v, None, u, device=True), call + "_device", "null policy, device form")
+    # two conditions violated at once: the one tested first is the one reported
+    refused(RP.torques_raw(r, 0, None, v, None, u), call, "n = 0, no q and a null policy", ": n must be positive")
+    refused(RP.torques_raw(r, n, None, v, None, u), call, "no q and a null policy", ": q, v and u are needed")
+    bad, keep2 = RP.policy_struct(**dict(arrays, q_ref=None, u_min=nan_bound))
+    refused(RP.torques_raw(r, n, q, v, bad, u), call, "K without q_ref and NaN in u_min", ": gains K need the references q_ref and v_ref")
     call = "idocp_rbd_rollout_policy"
     refused(RP.rollout_policy_raw(r, n, steps, act, TS, 1e-2, None, pts, qt, vt, None, None, None, 0), call, "null policy")
     refused(RP.rollout_policy_raw(r, n, steps, act, TS, 1e-2, None, pts, qt, vt, None, None, None, 0, device=True), call + "_device", "null policy, device form")
@@ -426,6 +443,12 @@ def test_refusals():
     refused(RP.rollout_policy_raw(r, n, steps, act, TS, 1e-2, pol, None, qt, vt, None, None, None, 0), call, "active contacts without contact_points")
     refused(RP.rollout_policy_raw(r, n, steps, act, 0.0, 1e-2, pol, pts, qt, vt, None, None, None, 0), call, "active contacts without a time step")
     refused(RP.rollout_policy_raw(r, n, steps, act, TS, 1e-2, pol, pts, None, vt, None, None, None, 0), call, "no q_traj")
+    refused(RP.rollout_policy_raw(r, n, 0, None, TS, 1e-2, None, pts, qt, vt, None, None, None, 0), call, "steps = 0, no active and a null policy",
+            ": steps must be at least 1")
+    refused(RP.rollout_policy_raw(r, n, steps, act, TS, 1e-2, None, None, qt, vt, None, None, None, 0), call, "no contact_points and a null policy",
+            ": STAGE mode with an active contact needs contact_points")
+    refused(RP.rollout_policy_raw(r, 0, steps, act, TS, 1e-2, pol, pts, qt, vt, None, None, None, 0, device=True), call + "_device", "n = 0, device form",
+            ": n must be positive")
     # the refusals left the handle usable
     assert np.isfinite(RP.feedback_torques(r, q, v, **arrays)).all()
     r.close()
