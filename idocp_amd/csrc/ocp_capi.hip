@@ -4,14 +4,13 @@
 // (src/ocp/ocp_solver.cpp:67-92): [host: per-stage reference q_ref(t_i)] ->
 // tangent RNEA (K5a) -> condensation (K5b) -> backward / forward Riccati (S3, S4)
 // -> expand primal + step sizes (K6) -> expand dual + integrate (K7).
-// The hybrid discretisation (OCPDiscretizer) is host-side index logic; this
-// build accepts only event-free horizons, so the schedule is the plain grid.
+// The contact sequence and the hybrid discretisation (OCPDiscretizer) are host-side
+// index logic without a device call: ocp_chain.hpp plans the chain, this file uploads it.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
-#include <limits>
 #include <string>
 #include <vector>
 
@@ -30,15 +29,9 @@ namespace {
 
 using DQ = LeggedDims<4, 3>;
 using LQ = OcpLayout<DQ>;
+static_assert(DQ::NC == IDOCP_MAX_CONTACTS, "the chain planner (ocp_chain.hpp) counts contacts with IDOCP_MAX_CONTACTS");
 
 }  // namespace
-
-// idocp::ContactStatus / ImpulseStatus on the host (include/idocp/robot/contact_status.hxx)
-struct HostStatus {
-  int active[IDOCP_MAX_CONTACTS] = {0, 0, 0, 0};
-  double points[IDOCP_MAX_CONTACTS][3] = {{0, 0, 0}, {0, 0, 0}, {0, 0, 0}, {0, 0, 0}};
-  int dimf() const { int n = 0; for (int c = 0; c < DQ::NC; ++c) n += active[c] ? 3 : 0; return n; }
-};
 
 struct idocp_ocp {
   idocp_model_t model;
@@ -59,36 +52,21 @@ struct idocp_ocp {
   int (*ls_post)(idocp_ocp_t*) = nullptr;      // after the shard's sums are formed: all-reduce them
   std::vector<double> task_refs_host;      // idocp_ocp_set_task_refs: [M][12] for the chain discretised at task_refs_t
   double task_refs_t = 0.0;
-  bool task_refs_lenient = false;          // creation, clone and the chain getters discretise without poses (constant pose in the table)
-  bool task_refs_stale = false;            // ... and leave the table to be redone by the next strict discretisation
+  bool task_refs_stale = false;            // a lenient discretisation (creation, clone, the chain getters) put the constant pose into the table
   void* d_prob = nullptr;
   OcpNode* d_nodes = nullptr;
-  bool contact_status_set = false;
   bool parnmpc = false;               // backward-Euler stages + backward correction instead of the Riccati sweep
   int stage_offset = 0;               // ParNMPC horizon sharding: global index of the first stage of this shard
-  bool has_terminal = true, has_prev = false;
-  // ContactSequence (include/idocp/hybrid/contact_sequence.hxx:56-333)
-  std::vector<HostStatus> phases;
-  std::vector<double> event_time;
-  std::vector<char> is_impulse;
-  std::vector<HostStatus> impulse_status;          // per event
-  // chain of the last discretisation (OCPDiscretizer, ocp_discretizer.hxx:65-374)
-  std::vector<OcpNode> chain;
-  std::vector<int> chain_index;
-  std::vector<double> chain_t;
-  int Ngrid = 0;                      // grid stages after discretisation
+  ContactSequence seq;                // ocp_chain.hpp
+  ChainPlan plan;                     // chain of the last discretisation (planChain), as the device holds it
   double disc_time = NAN;
-  bool seq_dirty = true, has_switch = false;
-  int n_impulse = 0;
+  bool seq_dirty = true;
   int* d_impulse_pos = nullptr;
   int* d_switch_pos = nullptr;
   int* d_general_pos = nullptr;     // ParNMPC: chain positions of the aux (switching rows) / impulse stages
   int* d_cond_pos = nullptr;        // chain positions by stage class of K5b (all feet | half of them | the rest)
-  int cond_n[5] = {0, 0, 0, 0, 0};      // all feet | half of them | the rest | event stages with half of the feet | flight stages
-  int n_general = 0;
   int slice_begin = 0, slice_end = -1;   // ParNMPC with events: this handle keeps the grid stages [slice_begin, slice_end) of the chain (-1: all)
-  int uniform_dimf = -1;              // dimf shared by all stages of an event-free chain, else -1
-  int M() const { return (int)chain.size(); }
+  int M() const { return plan.M(); }
   // hipGraph of one updateSolution (idocp_ocp_update_solution_graph): valid while the discretisation and the input buffers stay
   long disc_epoch = 0, graph_epoch = -1;
   hipGraph_t graph = nullptr;
@@ -163,59 +141,10 @@ double vRefOnAt(const idocp_cost_t& c, double t) {
   return (t > c.tv_t_begin && t < c.tv_t_end) ? 1.0 : 0.0;
 }
 
-int slotOf(const idocp_ocp* h, int kind, int index) {
-  switch (kind) {
-    case 1: return h->N + 1 + index;
-    case 2: return h->N + 1 + h->E + index;
-    case 3: return h->N + 1 + 2 * h->E + index;
-    default: return index;
-  }
-}
-
-void fillStatus(OcpNode& nd, const HostStatus& st) {
-  int row = 0;
-  for (int c = 0; c < DQ::NC; ++c) {
-    nd.active[c] = st.active[c] ? 1 : 0;
-    nd.row_of[c] = st.active[c] ? row : -1;
-    if (st.active[c]) row += 3;
-    for (int k = 0; k < 3; ++k) nd.contact_point[c][k] = st.points[c][k];
-  }
-  nd.dimf = row;
-}
-
-// OCPDiscretizer::discretizeOCP(contact_sequence, t) (ocp_discretizer.hxx:65-374): event times -> time stages, time
-// steps of the stages around an event, contact phase of every stage -- and from those the chain of stages in time
-// order.  Host-side index logic, re-run only when the initial time or the contact sequence changes.
-int discretizeParNMPC(idocp_ocp* h, double t);
-
-// Reference poses of the task-space cost for the M stages of the chain just built: the constant pose of the cost, or -- TimeVarying
-// variants -- the poses the caller evaluated at the stage times (idocp_ocp_get_chain_times -> idocp_ocp_set_task_refs).
-// The host half of a discretisation as it stood before a discretiser started to rewrite it.  The one recoverable error of a
-// discretiser that is only known once the new chain exists -- a TimeVarying task-space cost without reference poses for THIS chain --
-// restores it, so that the handle keeps describing the discretisation its device tables (d_nodes, class lists, d_prob) still hold.
-struct DiscSnapshot {
-  idocp_ocp* h;
-  std::vector<OcpNode> chain;
-  std::vector<int> chain_index;
-  std::vector<double> chain_t;
-  OcpProblem prob;
-  int Ngrid, uniform_dimf, n_impulse, n_general, BM, BNS, Bnimp, Bnsw;
-  bool has_switch, has_terminal, has_prev;
-  explicit DiscSnapshot(idocp_ocp* hh)
-      : h(hh), chain(hh->chain), chain_index(hh->chain_index), chain_t(hh->chain_t), prob(hh->prob), Ngrid(hh->Ngrid), uniform_dimf(hh->uniform_dimf),
-        n_impulse(hh->n_impulse), n_general(hh->n_general), BM(hh->B.M), BNS(hh->B.NS), Bnimp(hh->B.n_impulse_fe), Bnsw(hh->B.n_switch),
-        has_switch(hh->has_switch), has_terminal(hh->has_terminal), has_prev(hh->has_prev) {}
-  void restore() {
-    h->chain.swap(chain); h->chain_index.swap(chain_index); h->chain_t.swap(chain_t);
-    h->prob = prob; h->Ngrid = Ngrid; h->uniform_dimf = uniform_dimf; h->n_impulse = n_impulse; h->n_general = n_general;
-    h->B.M = BM; h->B.NS = BNS; h->B.n_impulse_fe = Bnimp; h->B.n_switch = Bnsw;
-    h->has_switch = has_switch; h->has_terminal = has_terminal; h->has_prev = has_prev;
-  }
-};
-
 // reference poses of a TimeVarying task-space cost must exist for the chain (t, M) unless the caller only asks for the chain's shape
-static int taskRefsAvailable(idocp_ocp* h, double t, int M) {
-  if (h->cost.task_dim == 0 || !h->cost.task_time_varying || h->task_refs_lenient) return IDOCP_OK;
+// (lenient: creation, clone and the chain getters discretise without poses -- the constant pose goes into the table)
+int taskRefsAvailable(idocp_ocp* h, double t, int M, bool lenient) {
+  if (h->cost.task_dim == 0 || !h->cost.task_time_varying || lenient) return IDOCP_OK;
   if (h->task_refs_host.size() != (size_t)M * 12 || h->task_refs_t != t) {
     set_last_error("TimeVarying task-space cost: no reference poses for this chain (idocp_ocp_set_task_refs with the same t, M = the chain's length)");
     return IDOCP_E_ARG;
@@ -223,364 +152,61 @@ static int taskRefsAvailable(idocp_ocp* h, double t, int M) {
   return IDOCP_OK;
 }
 
-static int uploadTaskRefs(idocp_ocp* h, double t, int M) {
-  if (h->cost.task_dim == 0) return IDOCP_OK;
-  std::vector<double> tab((size_t)M * 12);
-  if (h->cost.task_time_varying) {
-    if (h->task_refs_host.size() != (size_t)M * 12 || h->task_refs_t != t) {
-      if (!h->task_refs_lenient) {                       // (not reached: every discretiser asks taskRefsAvailable before it touches the device)
-        set_last_error("TimeVarying task-space cost: no reference poses for this chain (idocp_ocp_set_task_refs with the same t, M = the chain's length)");
-        return IDOCP_E_ARG;
-      }
-      for (int p = 0; p < M; ++p) for (int k = 0; k < 12; ++k) tab[(size_t)p * 12 + k] = h->cost.task_ref[k];
-      h->task_refs_stale = true;
-    } else {
-      tab = h->task_refs_host;
-      h->task_refs_stale = false;
-    }
-  } else {
-    for (int p = 0; p < M; ++p) for (int k = 0; k < 12; ++k) tab[(size_t)p * 12 + k] = h->cost.task_ref[k];
-  }
-  HIP_TRY(hipMemcpyAsync(h->d_taskref, tab.data(), tab.size() * sizeof(double), hipMemcpyHostToDevice, h->stream));
-  HIP_TRY(hipStreamSynchronize(h->stream));
-  return IDOCP_OK;
-}
-
-int discretize(idocp_ocp* h, double t) {
-  if (!h->seq_dirty && h->disc_time == t && !(h->task_refs_stale && !h->task_refs_lenient)) return IDOCP_OK;
-  if (h->parnmpc) return discretizeParNMPC(h, t);
-  const int N_ideal = h->N;
-  const double min_dt = std::sqrt(std::numeric_limits<double>::epsilon());       // ocp_discretizer.hpp:108-109
-  const double dt_ideal = h->T / N_ideal, max_dt = dt_ideal - min_dt;
-  std::vector<int> ev_imp, ev_lift;
-  for (int e = 0; e < (int)h->event_time.size(); ++e) (h->is_impulse[e] ? ev_imp : ev_lift).push_back(e);
-  const int Ni = (int)ev_imp.size(), Nl = (int)ev_lift.size();
-  std::vector<int> tsbi(Ni + 1, -1), tsbl(Nl + 1, -1);
-  std::vector<double> t_imp(Ni + 1, 0.0), t_lift(Nl + 1, 0.0), dt_aux(Ni + 1, 0.0), dt_lift(Nl + 1, 0.0);
-  for (int k = 0; k < Ni; ++k) { t_imp[k] = h->event_time[ev_imp[k]]; tsbi[k] = (int)std::floor((t_imp[k] - t) / dt_ideal); }    // countDiscreteEvents
-  for (int k = 0; k < Nl; ++k) { t_lift[k] = h->event_time[ev_lift[k]]; tsbl[k] = (int)std::floor((t_lift[k] - t) / dt_ideal); }
-  std::vector<double> dts(N_ideal + 1, dt_ideal), ts(N_ideal + 1, 0.0);
-  int ii = 0, li = 0, on_grid = 0;
-  for (int i = 0; i < N_ideal; ++i) {                                                                                           // countTimeSteps
-    const int stage = i - on_grid;
-    if (ii < Ni && i == tsbi[ii]) {
-      dts[stage] = t_imp[ii] - i * dt_ideal - t;
-      if (dts[stage] <= min_dt) { tsbi[ii] = stage - 1; dt_aux[ii] = dt_ideal; ts[stage] = t + (i - 1) * dt_ideal; ++on_grid; ++ii; }
-      else if (dts[stage] >= max_dt) { tsbi[ii] = i + 1; ts[stage] = t + i * dt_ideal; }
-      else { tsbi[ii] = stage; dt_aux[ii] = dt_ideal - dts[stage]; ts[stage] = t + i * dt_ideal; ++ii; }
-    } else if (li < Nl && i == tsbl[li]) {
-      dts[stage] = t_lift[li] - i * dt_ideal - t;
-      if (dts[stage] <= min_dt) { tsbl[li] = stage - 1; dt_lift[li] = dt_ideal; ts[stage] = t + (i - 1) * dt_ideal; ++on_grid; ++li; }
-      else if (dts[stage] >= max_dt) { tsbl[li] = i + 1; ts[stage] = t + i * dt_ideal; }
-      else { tsbl[li] = stage; dt_lift[li] = dt_ideal - dts[stage]; ts[stage] = t + i * dt_ideal; ++li; }
-    } else {
-      dts[stage] = dt_ideal; ts[stage] = t + i * dt_ideal;
-    }
-  }
-  const int Ng = N_ideal - on_grid;
-  ts[Ng] = t + h->T;
-  std::vector<int> imp_after(Ng + 1, -1), lift_after(Ng + 1, -1), phase(Ng + 1, 0);                                             // countTimeStages / countContactPhase
-  ii = 0; li = 0;
-  int num_events = 0;
-  for (int i = 0; i < Ng; ++i) {
-    if (ii < Ni && i == tsbi[ii]) imp_after[i] = ii++;
-    if (li < Nl && i == tsbl[li]) lift_after[i] = li++;
-    phase[i] = num_events;
-    if (imp_after[i] >= 0 && lift_after[i] >= 0) { set_last_error("OCPDiscretizer: an impulse and a lift fall into the same time stage"); return IDOCP_E_ARG; }
-    if (imp_after[i] >= 0 || lift_after[i] >= 0) ++num_events;
-  }
-  phase[Ng] = num_events;
-  if (num_events > (int)h->phases.size() - 1) { set_last_error("OCPDiscretizer: inconsistent contact sequence"); return IDOCP_E_ARG; }
-  DiscSnapshot before(h);
-  h->chain.clear(); h->chain_index.clear(); h->chain_t.clear();
-  auto node = [&](int kind, int index, double tt, double dtt, const HostStatus& st, int level) {
-    OcpNode nd;
-    std::memset(&nd, 0, sizeof(nd));
-    nd.kind = kind; nd.slot = slotOf(h, kind, index); nd.level = level;
-    nd.has_u = (kind == 1) ? 0 : 1;
-    nd.dt = (kind == 1) ? 1.0 : dtt;
-    nd.dtq = (kind == 1) ? 0.0 : dtt;
-    fillStatus(nd, st);
-    h->chain.push_back(nd); h->chain_index.push_back(index); h->chain_t.push_back(tt);
-  };
-  auto addSwitch = [&](OcpNode& nd, int impulse_index, double dt_next) {              // ocp_linearizer.hxx:152-163, 205-217
-    const HostStatus& is = h->impulse_status[ev_imp[impulse_index]];
-    int row = 0;
-    for (int c = 0; c < DQ::NC; ++c) {
-      nd.sw_active[c] = is.active[c] ? 1 : 0;
-      nd.sw_row[c] = is.active[c] ? row : -1;
-      if (is.active[c]) row += 3;
-      for (int k = 0; k < 3; ++k) nd.sw_point[c][k] = is.points[c][k];
-    }
-    nd.sw_dimi = row;
-    nd.sw_dt1 = nd.dtq; nd.sw_dt2 = dt_next;
-  };
-  h->has_switch = false;
-  for (int i = 0; i < Ng; ++i) {
-    node(0, i, ts[i], dts[i], h->phases[phase[i]], i);
-    if (imp_after[i] < 0 && lift_after[i] < 0 && i + 1 < Ng && imp_after[i + 1] >= 0) { addSwitch(h->chain.back(), imp_after[i + 1], dts[i + 1]); h->has_switch = true; }
-    if (imp_after[i] >= 0) {
-      const int k = imp_after[i];
-      node(1, k, t_imp[k], 0.0, h->impulse_status[ev_imp[k]], -1);
-      node(2, k, t_imp[k], dt_aux[k], h->phases[phase[i + 1]], 0);
-    } else if (lift_after[i] >= 0) {
-      const int k = lift_after[i];
-      node(3, k, t_lift[k], dt_lift[k], h->phases[phase[i + 1]], 0);
-      if (i + 1 < Ng && imp_after[i + 1] >= 0) { addSwitch(h->chain.back(), imp_after[i + 1], dts[i + 1]); h->has_switch = true; }
-    }
-  }
-  node(4, Ng, ts[Ng], 0.0, h->phases[phase[Ng]], Ng);
-  const int M = h->M();
-  if (taskRefsAvailable(h, t, M)) { before.restore(); return IDOCP_E_ARG; }
+// The upload half of a discretisation: the plan the handle holds goes to the device together with everything that depends on the cost --
+// vref_on of the nodes, the q_ref table, the reference poses of the task-space cost (the constant pose of the cost, or -- TimeVarying
+// variants -- the poses the caller evaluated at the stage times: idocp_ocp_get_chain_times -> idocp_ocp_set_task_refs) -- and the
+// problem header.  Uploads the lists this solver kind's kernels read, and only those.
+int commitChain(idocp_ocp* h, double t) {
+  ChainPlan& plan = h->plan;
+  const int M = plan.M();
+  std::vector<double> tab((size_t)M * DQ::NQ), poses;
   for (int p = 0; p < M; ++p) {
-    h->chain[p].prev = p > 0 ? h->chain[p - 1].slot : -1;
-    h->chain[p].next = p + 1 < M ? h->chain[p + 1].slot : -1;
+    qRefAt(h->cost, DQ::NQ, plan.chain_t[p], &tab[(size_t)p * DQ::NQ]);
+    plan.nodes[p].vref_on = vRefOnAt(h->cost, plan.chain_t[p]);
+    if (!h->parnmpc) plan.nodes_ls[p].vref_on = plan.nodes[p].vref_on;
+    else if (parnmpcShape<LQ>(plan.nodes[p]).general) plan.general_pos.push_back(p);
   }
-  h->Ngrid = Ng;
-  h->uniform_dimf = -1;
-  if (h->event_time.empty()) h->uniform_dimf = h->chain[0].dimf;
-  // upload: chain, per-stage cost references, problem header
-  std::vector<double> tab((size_t)M * DQ::NQ);
-  for (int p = 0; p < M; ++p) { qRefAt(h->cost, DQ::NQ, h->chain_t[p], &tab[(size_t)p * DQ::NQ]); h->chain[p].vref_on = vRefOnAt(h->cost, h->chain_t[p]); }
   h->prob.M = M; h->prob.NS = h->NS;
+  h->prob.has_terminal = plan.has_terminal ? 1 : 0; h->prob.has_prev = plan.has_prev ? 1 : 0; h->prob.stage_offset = plan.stage_offset;
   h->B.M = M; h->B.NS = h->NS;
-  HIP_TRY(hipMemcpyAsync(h->d_qref, tab.data(), tab.size() * sizeof(double), hipMemcpyHostToDevice, h->stream));
-  { const int rct = uploadTaskRefs(h, t, M); if (rct) return rct; }
-  HIP_TRY(hipMemcpyAsync(h->d_nodes, h->chain.data(), sizeof(OcpNode) * M, hipMemcpyHostToDevice, h->stream));
-  // The chain as the line search pairs it (line_search.cpp:80-113): the state-equation residual of a grid stage in front of an
-  // impulse / lift is evaluated against the NEXT GRID STAGE (the value computed against the event stage is overwritten there).
-  std::vector<OcpNode> chain_ls = h->chain;
-  for (int p = 0; p + 1 < M; ++p)
-    if (chain_ls[p].kind == 0 && (chain_ls[p + 1].kind == 1 || chain_ls[p + 1].kind == 3)) {
-      int pn = p + 2;
-      while (pn < M && chain_ls[pn].kind != 0 && chain_ls[pn].kind != 4) ++pn;
-      if (pn < M) chain_ls[p].next = chain_ls[pn].slot;
-    }
-  HIP_TRY(hipMemcpyAsync(h->d_nodes_ls, chain_ls.data(), sizeof(OcpNode) * M, hipMemcpyHostToDevice, h->stream));
-  std::vector<int> ipos;
-  for (int p = 0; p < M; ++p) if (h->chain[p].kind == 1) ipos.push_back(p);
-  h->n_impulse = (int)ipos.size();
-  h->B.n_impulse_fe = h->parnmpc ? 0 : h->n_impulse;
-  if (!ipos.empty()) HIP_TRY(hipMemcpyAsync(h->d_impulse_pos, ipos.data(), sizeof(int) * ipos.size(), hipMemcpyHostToDevice, h->stream));
-  std::vector<int> spos;
-  for (int p = 0; p + 1 < M; ++p) if (h->chain[p].sw_dimi > 0) spos.push_back(p);
-  h->B.n_switch = (int)spos.size();
-  if (!spos.empty()) HIP_TRY(hipMemcpyAsync(h->d_switch_pos, spos.data(), sizeof(int) * spos.size(), hipMemcpyHostToDevice, h->stream));
-  // stage classes of K5b (OcpLaunch::condenseMixed)
-  std::vector<int> cls[5];
-  for (int p = 0; p < M; ++p) {
-    const OcpNode& nd = h->chain[p];
-    const bool grid = (nd.kind == 0 || nd.kind == 2 || nd.kind == 3), plain = grid && nd.sw_dimi == 0;
-    const bool event_half = !h->parnmpc && !plain && (grid || nd.kind == 1) && nd.dimf == DQ::NF / 2;      // an impulse / a switching constraint on half of the feet
-    const bool flight = !h->parnmpc && plain && nd.dimf == 0;
-    cls[plain && nd.dimf == DQ::NF ? 0 : (plain && nd.dimf == DQ::NF / 2 ? 1 : (event_half ? 3 : (flight ? 4 : 2)))].push_back(p);
+  h->B.n_impulse_fe = h->parnmpc ? 0 : plan.n_impulse();
+  h->B.n_switch = (int)plan.switch_pos.size();
+  auto upload = [&](void* dst, const void* src, size_t bytes) { return bytes ? hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, h->stream) : hipSuccess; };
+  HIP_TRY(upload(h->d_qref, tab.data(), tab.size() * sizeof(double)));
+  if (h->cost.task_dim != 0) {
+    const bool have = h->cost.task_time_varying && h->task_refs_host.size() == (size_t)M * 12 && h->task_refs_t == t;
+    if (have) poses = h->task_refs_host;
+    else { poses.resize((size_t)M * 12); for (int p = 0; p < M; ++p) for (int k = 0; k < 12; ++k) poses[(size_t)p * 12 + k] = h->cost.task_ref[k]; }
+    h->task_refs_stale = h->cost.task_time_varying && !have;      // ... to be redone by the next strict discretisation
+    HIP_TRY(upload(h->d_taskref, poses.data(), poses.size() * sizeof(double)));
   }
-  std::vector<int> cpos;
-  for (int c = 0; c < 5; ++c) { h->cond_n[c] = (int)cls[c].size(); cpos.insert(cpos.end(), cls[c].begin(), cls[c].end()); }
-  HIP_TRY(hipMemcpyAsync(h->d_cond_pos, cpos.data(), sizeof(int) * cpos.size(), hipMemcpyHostToDevice, h->stream));
+  HIP_TRY(upload(h->d_nodes, plan.nodes.data(), sizeof(OcpNode) * M));
+  if (!h->parnmpc) HIP_TRY(upload(h->d_nodes_ls, plan.nodes_ls.data(), sizeof(OcpNode) * M));
+  HIP_TRY(upload(h->d_impulse_pos, plan.impulse_pos.data(), sizeof(int) * plan.impulse_pos.size()));
+  HIP_TRY(upload(h->d_switch_pos, plan.switch_pos.data(), sizeof(int) * plan.switch_pos.size()));
+  HIP_TRY(upload(h->d_general_pos, plan.general_pos.data(), sizeof(int) * plan.general_pos.size()));
+  if (!h->parnmpc) HIP_TRY(upload(h->d_cond_pos, plan.cond_pos.data(), sizeof(int) * plan.cond_pos.size()));
   HIP_TRY(hipMemcpyAsync(h->d_prob, &h->prob, sizeof(OcpProblem), hipMemcpyHostToDevice, h->stream));
-  HIP_TRY(hipStreamSynchronize(h->stream));     // tab is a stack temporary
+  HIP_TRY(hipStreamSynchronize(h->stream));     // tab and poses are stack temporaries
   h->disc_time = t; h->seq_dirty = false; ++h->disc_epoch;
   return IDOCP_OK;
 }
 
-// ParNMPCDiscretizer::discretizeOCP with discrete events (parnmpc_discretizer.hxx:65-72: countDiscreteEvents :246-262,
-// countTimeSteps :265-324, countTimeStages :327-361, countContactPhase :364-373).  The event stages sit IN FRONT of the grid
-// stage that follows the event:  ..., stage i-1, [aux k, impulse k | lift k], stage i, ...; the aux stage carries the
-// switching constraint of its impulse (sw_* fields of the node, with sw_dt1 = sw_dt2 = 0: the constraint acts on the aux
-// stage's own configuration).
-int discretizeParNMPCHybrid(idocp_ocp* h, double t) {
-  if (h->stage_offset != 0) { set_last_error("ParNMPC: a horizon with discrete events is sharded by idocp_parnmpc_create_hybrid_shard"); return IDOCP_E_UNSUPPORTED; }
-  const int Nid = h->N;
-  const double dt_ideal = h->T / Nid, min_dt = std::sqrt(std::numeric_limits<double>::epsilon()), max_dt = dt_ideal - min_dt;
-  std::vector<int> ev_imp, ev_lift;
-  for (int e = 0; e < (int)h->event_time.size(); ++e) (h->is_impulse[e] ? ev_imp : ev_lift).push_back(e);
-  const int Ni = (int)ev_imp.size(), Nl = (int)ev_lift.size();
-  std::vector<int> tsai(Ni + 1, -1), tsal(Nl + 1, -1);        // time stage AFTER the impulse / lift
-  std::vector<double> t_imp(Ni + 1, 0.0), t_lift(Nl + 1, 0.0), dt_aux(Ni + 1, 0.0), dt_lift(Nl + 1, 0.0);
-  for (int k = 0; k < Ni; ++k) { t_imp[k] = h->event_time[ev_imp[k]]; tsai[k] = (int)std::floor((t_imp[k] - t) / dt_ideal); }
-  for (int k = 0; k < Nl; ++k) { t_lift[k] = h->event_time[ev_lift[k]]; tsal[k] = (int)std::floor((t_lift[k] - t) / dt_ideal); }
-  std::vector<double> dts(Nid + 1, dt_ideal), ts(Nid + 1, 0.0);
-  int ii = 0, li = 0, on_grid = 0;
-  for (int i = 0; i < Nid; ++i) {
-    const int stage = i - on_grid;
-    if (ii < Ni && i == tsai[ii]) {
-      dts[stage] = (i + 1) * dt_ideal + t - t_imp[ii];
-      if (dts[stage] <= min_dt) { tsai[ii] = i + 1; ts[stage] = t + (i + 1) * dt_ideal; }
-      else if (dts[stage] >= max_dt) { tsai[ii] = stage - 1; dt_aux[ii] = dt_ideal; ts[stage] = t + i * dt_ideal; ++on_grid; ++ii; }
-      else { tsai[ii] = stage; dt_aux[ii] = dt_ideal - dts[stage]; ts[stage] = t + (i + 1) * dt_ideal; ++ii; }
-    } else if (li < Nl && i == tsal[li]) {
-      dts[stage] = (i + 1) * dt_ideal + t - t_lift[li];
-      if (dts[stage] <= min_dt) { tsal[li] = i + 1; ts[stage] = t + (i + 1) * dt_ideal; }
-      else if (dts[stage] >= max_dt) { tsal[li] = stage - 1; dt_lift[li] = dt_ideal; ts[stage] = t + i * dt_ideal; ++on_grid; ++li; }
-      else { tsal[li] = stage; dt_lift[li] = dt_ideal - dts[stage]; ts[stage] = t + (i + 1) * dt_ideal; ++li; }
-    } else {
-      dts[stage] = dt_ideal; ts[stage] = t + (i + 1) * dt_ideal;
-    }
-  }
-  const int Ng = Nid - on_grid;
-  ts[Ng - 1] = t + h->T;
-  std::vector<int> imp_before(Ng, -1), lift_before(Ng, -1), phase(Ng, 0);
-  ii = 0; li = 0;
-  int num_events = 0;
-  for (int i = 0; i < Ng; ++i) {
-    if (ii < Ni && i == tsai[ii]) imp_before[i] = ii++;
-    if (li < Nl && i == tsal[li]) lift_before[i] = li++;
-    if (imp_before[i] >= 0 && lift_before[i] >= 0) { set_last_error("ParNMPCDiscretizer: an impulse and a lift fall into the same time stage"); return IDOCP_E_ARG; }
-    if (imp_before[i] >= 0 || lift_before[i] >= 0) ++num_events;
-    phase[i] = num_events;
-  }
-  if (ii != Ni || li != Nl) { set_last_error("ParNMPCDiscretizer: a discrete event lies outside the horizon"); return IDOCP_E_ARG; }
-  for (int i = 0; i + 1 < Ng; ++i)
-    if (imp_before[i] >= 0 && imp_before[i + 1] >= 0) { set_last_error("ParNMPCDiscretizer: impulses in consecutive time stages"); return IDOCP_E_ARG; }
-  // a lift or an impulse in front of the first time stage: the event stages are the first elements of the chain and their
-  // predecessor is the measured state (backward_correction_solver.cpp:201-217, 232-246).  The aux stage carries the switching
-  // constraint like every other aux stage: the reference's call at :203-211 omits the impulse status and then sizes the KKT
-  // inverse with it (split_backward_correction.hxx:46-52), which is not defined as written (oracle/ocp.cpp, same place)
-  DiscSnapshot before(h);
-  h->chain.clear(); h->chain_index.clear(); h->chain_t.clear();
-  auto node = [&](int kind, int index, double tt, double dtt, const HostStatus& st, int level) {
-    OcpNode nd;
-    std::memset(&nd, 0, sizeof(nd));
-    nd.kind = kind; nd.slot = slotOf(h, kind, index); nd.level = level;
-    nd.has_u = (kind == 1) ? 0 : 1;
-    nd.dt = (kind == 1) ? 1.0 : dtt;
-    nd.dtq = (kind == 1) ? 0.0 : dtt;
-    fillStatus(nd, st);
-    h->chain.push_back(nd); h->chain_index.push_back(index); h->chain_t.push_back(tt);
-  };
-  h->has_switch = false;
-  for (int i = 0; i < Ng; ++i) {
-    const int phase_before = i > 0 ? phase[i - 1] : 0;
-    if (imp_before[i] >= 0) {
-      const int k = imp_before[i];
-      const HostStatus& is = h->impulse_status[ev_imp[k]];
-      node(2, k, t_imp[k], dt_aux[k], h->phases[phase_before], 0);
-      {
-        OcpNode& nd = h->chain.back();                              // switchingconstraint::linearizeSwitchingConstraint on the aux stage
-        int row = 0;
-        for (int c = 0; c < DQ::NC; ++c) {
-          nd.sw_active[c] = is.active[c] ? 1 : 0;
-          nd.sw_row[c] = is.active[c] ? row : -1;
-          if (is.active[c]) row += 3;
-          for (int k2 = 0; k2 < 3; ++k2) nd.sw_point[c][k2] = is.points[c][k2];
-        }
-        nd.sw_dimi = row; nd.sw_dt1 = 0.0; nd.sw_dt2 = 0.0;
-        h->has_switch = true;
-      }
-      node(1, k, t_imp[k], 0.0, is, -1);
-    } else if (lift_before[i] >= 0) {
-      const int k = lift_before[i];
-      node(3, k, t_lift[k], dt_lift[k], h->phases[phase_before], 0);
-    }
-    node(0, i, ts[i], dts[i], h->phases[phase[i]], (i == Ng - 1) ? Nid : i + 1);      // parnmpc_linearizer.cpp:43-58
-  }
-  bool is_last_shard = true, is_first_shard = true;
-  if (h->slice_end >= 0) {
-    // A shard of the chain (idocp_parnmpc_create_hybrid_shard): the grid stages [slice_begin, slice_end) and the event stages in
-    // front of each of them; slots and constraint levels stay the global ones.  The placeholder behind the slice is the slot of
-    // the right neighbour's first stage, where the imported halos (lmd, gmm, q, aux_mat, corrected lmd, gmm) land.
-    const int lo = h->slice_begin, hi = std::min(h->slice_end, Ng);
-    std::vector<OcpNode> nodes;
-    std::vector<int> idx;
-    std::vector<double> tt;
-    int next_slot = -1;
-    for (size_t p = 0; p < h->chain.size(); ++p) {
-      size_t g = p;
-      while (h->chain[g].kind != 0) ++g;                            // event stages precede their grid stage
-      const int owner = h->chain_index[g];
-      if (owner >= lo && owner < hi) { nodes.push_back(h->chain[p]); idx.push_back(h->chain_index[p]); tt.push_back(h->chain_t[p]); }
-      else if (owner >= hi && next_slot < 0) next_slot = h->chain[p].slot;
-    }
-    if (nodes.empty()) { before.restore(); set_last_error("ParNMPC: empty shard of the chain"); return IDOCP_E_ARG; }
-    h->chain.swap(nodes); h->chain_index.swap(idx); h->chain_t.swap(tt);
-    is_first_shard = lo == 0; is_last_shard = hi >= Ng;
-    if (!is_last_shard) {
-      OcpNode nd;
-      std::memset(&nd, 0, sizeof(nd));
-      nd.kind = 4; nd.slot = next_slot; nd.level = Nid; nd.has_u = 1; nd.dt = dt_ideal; nd.dtq = dt_ideal;
-      fillStatus(nd, h->phases[0]);
-      h->chain.push_back(nd); h->chain_index.push_back(hi); h->chain_t.push_back(t + h->T);
-    }
-    h->has_switch = false;
-    for (const OcpNode& nd : h->chain) if (nd.sw_dimi > 0) h->has_switch = true;
-  }
-  if (is_last_shard) {
-    OcpNode nd;                                                     // placeholder behind the last stage (see below)
-    std::memset(&nd, 0, sizeof(nd));
-    nd.kind = 4; nd.slot = Nid; nd.level = Nid; nd.has_u = 1; nd.dt = dt_ideal; nd.dtq = dt_ideal;
-    fillStatus(nd, h->phases[phase[Ng - 1]]);
-    h->chain.push_back(nd); h->chain_index.push_back(Ng); h->chain_t.push_back(t + h->T);
-  }
-  h->has_terminal = is_last_shard; h->has_prev = !is_first_shard;
-  const int M = h->M();
-  if (taskRefsAvailable(h, t, M)) { before.restore(); return IDOCP_E_ARG; }
-  for (int p = 0; p < M; ++p) {
-    h->chain[p].prev = p > 0 ? h->chain[p - 1].slot : -1;
-    h->chain[p].next = p + 1 < M ? h->chain[p + 1].slot : -1;
-  }
-  h->prob.has_terminal = h->has_terminal ? 1 : 0; h->prob.has_prev = h->has_prev ? 1 : 0; h->prob.stage_offset = 0;
-  h->Ngrid = Ng - 1;
-  h->uniform_dimf = -1;
-  std::vector<double> tab((size_t)M * DQ::NQ);
-  for (int p = 0; p < M; ++p) { qRefAt(h->cost, DQ::NQ, h->chain_t[p], &tab[(size_t)p * DQ::NQ]); h->chain[p].vref_on = vRefOnAt(h->cost, h->chain_t[p]); }
-  h->prob.M = M; h->prob.NS = h->NS;
-  h->B.M = M; h->B.NS = h->NS;
-  HIP_TRY(hipMemcpyAsync(h->d_qref, tab.data(), tab.size() * sizeof(double), hipMemcpyHostToDevice, h->stream));
-  { const int rct = uploadTaskRefs(h, t, M); if (rct) return rct; }
-  HIP_TRY(hipMemcpyAsync(h->d_nodes, h->chain.data(), sizeof(OcpNode) * M, hipMemcpyHostToDevice, h->stream));
-  std::vector<int> ipos;
-  for (int p = 0; p < M; ++p) if (h->chain[p].kind == 1) ipos.push_back(p);
-  h->n_impulse = (int)ipos.size();
-  h->B.n_impulse_fe = h->parnmpc ? 0 : h->n_impulse;
-  if (!ipos.empty()) HIP_TRY(hipMemcpyAsync(h->d_impulse_pos, ipos.data(), sizeof(int) * ipos.size(), hipMemcpyHostToDevice, h->stream));
-  std::vector<int> spos;
-  for (int p = 0; p + 1 < M; ++p) if (h->chain[p].sw_dimi > 0) spos.push_back(p);
-  h->B.n_switch = (int)spos.size();
-  if (!spos.empty()) HIP_TRY(hipMemcpyAsync(h->d_switch_pos, spos.data(), sizeof(int) * spos.size(), hipMemcpyHostToDevice, h->stream));
-  std::vector<int> gpos;
-  for (int p = 0; p < M; ++p) if (parnmpcShape<LQ>(h->chain[p]).general) gpos.push_back(p);
-  h->n_general = (int)gpos.size();
-  if (!gpos.empty()) HIP_TRY(hipMemcpyAsync(h->d_general_pos, gpos.data(), sizeof(int) * gpos.size(), hipMemcpyHostToDevice, h->stream));
-  HIP_TRY(hipMemcpyAsync(h->d_prob, &h->prob, sizeof(OcpProblem), hipMemcpyHostToDevice, h->stream));
-  HIP_TRY(hipStreamSynchronize(h->stream));
-  h->disc_time = t; h->seq_dirty = false;
-  return IDOCP_OK;
+// OCPDiscretizer / ParNMPCDiscretizer::discretizeOCP(contact_sequence, t): planChain (ocp_chain.hpp) builds the chain as a value; the
+// handle takes it -- and the device sees it -- only when nothing refuses it, so a refused discretisation leaves the handle describing
+// the discretisation its device tables still hold.  Re-run only when the initial time or the contact sequence changes.
+int discretize(idocp_ocp* h, double t, bool lenient = false) {
+  if (!h->seq_dirty && h->disc_time == t && !(h->task_refs_stale && !lenient)) return IDOCP_OK;
+  ChainResult r = planChain(h->seq, t, {h->N, h->E, h->T, h->parnmpc, h->stage_offset, h->slice_begin, h->slice_end, h->plan.has_terminal, h->plan.has_prev});
+  if (r.rc) { set_last_error(r.error); return r.rc; }
+  if (taskRefsAvailable(h, t, r.plan.M(), lenient)) return IDOCP_E_ARG;
+  h->plan = std::move(r.plan);
+  return commitChain(h, t);
 }
-
-// ParNMPCDiscretizer for a horizon without events (include/idocp/hybrid/parnmpc_discretizer.hxx): N backward-Euler stages,
-// stage i at time t + (i + 1) dt with constraint level i + 1 (parnmpc_linearizer.cpp:43-58), followed by a placeholder so
-// that the per-stage kernels see the usual "M - 1 stages + one more" chain.
-int discretizeParNMPC(idocp_ocp* h, double t) {
-  if (!h->event_time.empty()) return discretizeParNMPCHybrid(h, t);
-  const int N = h->N;
-  const double dt = h->T / N;
-  if (taskRefsAvailable(h, t, N + 1)) return IDOCP_E_ARG;          // before anything of the handle is rewritten
-  h->chain.clear(); h->chain_index.clear(); h->chain_t.clear();
-  for (int i = 0; i <= N; ++i) {
-    OcpNode nd;
-    std::memset(&nd, 0, sizeof(nd));
-    nd.kind = i < N ? 0 : 4; nd.slot = i; nd.level = h->stage_offset + i + 1; nd.has_u = 1; nd.dt = dt; nd.dtq = dt;
-    nd.prev = i - 1; nd.next = i < N ? i + 1 : -1;
-    fillStatus(nd, h->phases[0]);
-    h->chain.push_back(nd); h->chain_index.push_back(i); h->chain_t.push_back(t + (h->stage_offset + i + 1) * dt);
-  }
-  h->chain_t[N] = t + (h->stage_offset + N) * dt;
-  h->prob.has_terminal = h->has_terminal ? 1 : 0; h->prob.has_prev = h->has_prev ? 1 : 0; h->prob.stage_offset = h->stage_offset;
-  h->Ngrid = N - 1;                  // getters: stages 0 .. N-1
-  h->uniform_dimf = -1; h->has_switch = false; h->n_impulse = 0; h->B.n_impulse_fe = 0; h->n_general = 0; h->B.n_switch = 0;
-  const int M = N + 1;
-  std::vector<double> tab((size_t)M * DQ::NQ);
-  for (int p = 0; p < M; ++p) { qRefAt(h->cost, DQ::NQ, h->chain_t[p], &tab[(size_t)p * DQ::NQ]); h->chain[p].vref_on = vRefOnAt(h->cost, h->chain_t[p]); }
-  h->prob.M = M; h->prob.NS = h->NS;
-  h->B.M = M; h->B.NS = h->NS;
-  HIP_TRY(hipMemcpyAsync(h->d_qref, tab.data(), tab.size() * sizeof(double), hipMemcpyHostToDevice, h->stream));
-  { const int rct = uploadTaskRefs(h, t, M); if (rct) return rct; }
-  HIP_TRY(hipMemcpyAsync(h->d_nodes, h->chain.data(), sizeof(OcpNode) * M, hipMemcpyHostToDevice, h->stream));
-  HIP_TRY(hipMemcpyAsync(h->d_prob, &h->prob, sizeof(OcpProblem), hipMemcpyHostToDevice, h->stream));
-  HIP_TRY(hipStreamSynchronize(h->stream));
-  h->disc_time = t; h->seq_dirty = false;
-  return IDOCP_OK;
+// the chain of the last discretisation, or of t = 0 when there has been none
+int ensureDiscretized(idocp_ocp* h) {
+  if (!h->seq_dirty && h->disc_time == h->disc_time) return IDOCP_OK;
+  return discretize(h, h->disc_time == h->disc_time ? h->disc_time : 0.0);
 }
 
 struct Field { int offset, dim, extra; };
@@ -840,11 +466,7 @@ static int createOcpImpl(const idocp_model_t* model, const idocp_cost_t* cost, c
   if (hipMemcpyAsync(d_model, &dm, sizeof(dm), hipMemcpyHostToDevice, h->stream) != hipSuccess) { set_last_error("hipMemcpy failed"); return fail(IDOCP_E_DEVICE); }
   B.model = static_cast<const DevModel*>(d_model);
   B.prob = static_cast<const OcpProblem*>(h->d_prob);
-  h->phases.assign(1, HostStatus());                      // ContactSequence ctor: default (no contact) status
-  h->task_refs_lenient = true;
-  rc = discretize(h, 0.0);
-  h->task_refs_lenient = false;
-  if (rc) return fail(rc);
+  if ((rc = discretize(h, 0.0, true))) return fail(rc);
   // identity quaternion in every q so that an unset solution is a valid configuration
   {
     std::vector<double> q(DQ::NQ, 0.0); q[6] = 1.0;
@@ -884,114 +506,39 @@ void idocp_ocp_destroy(idocp_ocp_t* h) {
   delete h;
 }
 
-static HostStatus makeStatus(const int* active, const double* contact_points) {
-  HostStatus st;
-  for (int c = 0; c < DQ::NC; ++c) {
-    st.active[c] = active[c] ? 1 : 0;
-    for (int k = 0; k < 3; ++k) st.points[c][k] = contact_points[3 * c + k];
-  }
-  return st;
+// ContactSequence of the handle (ocp_chain.hpp): the outcome of one of its operations goes to idocp_last_error, and the chain is redone
+static int sequenceChanged(idocp_ocp_t* h, int rc, const std::string& err) {
+  if (rc) set_last_error(err); else h->seq_dirty = true;
+  return rc;
 }
-
 int idocp_ocp_set_contact_status_uniformly(idocp_ocp_t* h, const int* active, const double* contact_points) {
   if (!h || !active || !contact_points) return IDOCP_E_ARG;
-  h->phases.assign(1, makeStatus(active, contact_points));            // contact_sequence.hxx:47-51
-  h->event_time.clear(); h->is_impulse.clear(); h->impulse_status.clear();
-  h->contact_status_set = true;
-  h->seq_dirty = true;
-  return IDOCP_OK;
+  h->seq.setUniformly(HostStatus::make(active, contact_points));
+  return sequenceChanged(h, IDOCP_OK, "");
 }
-
 int idocp_ocp_push_back_contact_status(idocp_ocp_t* h, const int* active, const double* contact_points, double switching_time) {
   if (!h || !active || !contact_points) return IDOCP_E_ARG;
-  if (!h->contact_status_set) { set_last_error("Call setContactStatusUniformly() before calling push_back()!"); return IDOCP_E_ARG; }
-  // the sequence holds up to N events (ocp_solver.cpp:16: contact_sequence_(robot, N)); the event stages live in
-  // max_num_impulse impulse / aux / lift slots each (hybrid_container.hpp:39-96), checked below
-  if ((int)h->event_time.size() + 1 > h->N) {
-    set_last_error("Number of discrete events=" + std::to_string(h->event_time.size() + 1) + " exceeds predefined max_num_events=" + std::to_string(h->N) + "!");
-    return IDOCP_E_ARG;
-  }
-  if (!h->event_time.empty() && switching_time <= h->event_time.back()) {
-    set_last_error("event_time=" + std::to_string(switching_time) + " must be larger than the last event time=" + std::to_string(h->event_time.back()) + "!");
-    return IDOCP_E_ARG;
-  }
-  // DiscreteEvent::setDiscreteEvent (discrete_event.hxx:57-84)
-  const HostStatus& pre = h->phases.back();
-  const HostStatus post = makeStatus(active, contact_points);
-  HostStatus imp = post;
-  bool exist_impulse = false, exist_lift = false;
-  for (int c = 0; c < DQ::NC; ++c) {
-    imp.active[c] = 0;
-    if (pre.active[c]) { if (!post.active[c]) exist_lift = true; }
-    else if (post.active[c]) { imp.active[c] = 1; exist_impulse = true; }
-  }
-  if (!exist_impulse && !exist_lift) { set_last_error("discrete_event.existDiscreteEvent() must be true!"); return IDOCP_E_ARG; }
-  {
-    int n_same = 0;
-    for (int e : h->is_impulse) n_same += ((e != 0) == exist_impulse) ? 1 : 0;
-    if (n_same + 1 > h->E) {
-      set_last_error(std::string("Number of ") + (exist_impulse ? "impulse" : "lift") + " events=" + std::to_string(n_same + 1) + " exceeds max_num_impulse=" + std::to_string(h->E) + "!");
-      return IDOCP_E_ARG;
-    }
-  }
-  h->phases.push_back(post);
-  h->event_time.push_back(switching_time);
-  h->is_impulse.push_back(exist_impulse ? 1 : 0);
-  h->impulse_status.push_back(imp);
-  h->seq_dirty = true;
-  return IDOCP_OK;
+  std::string err;
+  return sequenceChanged(h, h->seq.pushBack(HostStatus::make(active, contact_points), switching_time, h->N, h->E, err), err);
 }
-
 int idocp_ocp_set_contact_points(idocp_ocp_t* h, int contact_phase, const double* contact_points) {
   if (!h || !contact_points) return IDOCP_E_ARG;
-  if (contact_phase < 0 || contact_phase >= (int)h->phases.size()) {
-    set_last_error("contact_phase=" + std::to_string(contact_phase) + " must be smaller than numContactPhases()" + std::to_string(h->phases.size()) + "!");
-    return IDOCP_E_ARG;
-  }
-  for (int c = 0; c < DQ::NC; ++c) for (int k = 0; k < 3; ++k) {
-    h->phases[contact_phase].points[c][k] = contact_points[3 * c + k];
-    if (contact_phase > 0 && h->is_impulse[contact_phase - 1]) h->impulse_status[contact_phase - 1].points[c][k] = contact_points[3 * c + k];
-  }
-  h->seq_dirty = true;
-  return IDOCP_OK;
+  std::string err;
+  return sequenceChanged(h, h->seq.setContactPoints(contact_phase, contact_points, err), err);
 }
-
-int idocp_ocp_pop_back_contact_status(idocp_ocp_t* h) {              // contact_sequence.hxx:105-125
-  if (!h) return IDOCP_E_ARG;
-  if (!h->event_time.empty()) {
-    h->event_time.pop_back(); h->is_impulse.pop_back(); h->impulse_status.pop_back(); h->phases.pop_back();
-  } else {
-    h->phases.assign(1, HostStatus());
-  }
-  h->seq_dirty = true;
-  return IDOCP_OK;
-}
-
-int idocp_ocp_pop_front_contact_status(idocp_ocp_t* h) {             // contact_sequence.hxx:126-146
-  if (!h) return IDOCP_E_ARG;
-  if (!h->event_time.empty()) {
-    h->event_time.erase(h->event_time.begin()); h->is_impulse.erase(h->is_impulse.begin());
-    h->impulse_status.erase(h->impulse_status.begin()); h->phases.erase(h->phases.begin());
-  } else {
-    h->phases.assign(1, HostStatus());
-  }
-  h->seq_dirty = true;
-  return IDOCP_OK;
-}
+int idocp_ocp_pop_back_contact_status(idocp_ocp_t* h) { return h ? sequenceChanged(h, h->seq.popBack(), "") : IDOCP_E_ARG; }
+int idocp_ocp_pop_front_contact_status(idocp_ocp_t* h) { return h ? sequenceChanged(h, h->seq.popFront(), "") : IDOCP_E_ARG; }
 
 int idocp_ocp_get_chain(idocp_ocp_t* h, double t, int capacity, int* kind, int* index, int* slot, double* dt, int* dimf, int* sw_dimi) {
   if (!h) return IDOCP_E_ARG;
   int rc = setDev(h); if (rc) return rc;
-  h->task_refs_lenient = true;
-  rc = discretize(h, t);
-  h->task_refs_lenient = false;
-  if (rc) return rc;
+  if ((rc = discretize(h, t, true))) return rc;
   const int M = h->M();
   if (capacity < M) { set_last_error("idocp_ocp_get_chain: capacity too small"); return IDOCP_E_ARG; }
   for (int p = 0; p < M; ++p) {
-    const OcpNode& nd = h->chain[p];
+    const OcpNode& nd = h->plan.nodes[p];
     if (kind) kind[p] = nd.kind;
-    if (index) index[p] = h->chain_index[p];
+    if (index) index[p] = h->plan.chain_index[p];
     if (slot) slot[p] = nd.slot;
     if (dt) dt[p] = nd.dtq;
     if (dimf) dimf[p] = nd.kind == 4 ? 0 : nd.dimf;
@@ -1005,13 +552,10 @@ int idocp_ocp_get_chain_times(idocp_ocp_t* h, double t, int capacity, double* ti
   int rc = setDev(h); if (rc) return rc;
   // (the chain's shape and times do not depend on the reference poses: a TimeVarying task cost without poses yet must not stop the
   //  discretisation that tells the caller where to evaluate them)
-  h->task_refs_lenient = true;
-  rc = discretize(h, t);
-  h->task_refs_lenient = false;
-  if (rc) return rc;
+  if ((rc = discretize(h, t, true))) return rc;
   const int M = h->M();
   if (capacity < M) { set_last_error("idocp_ocp_get_chain_times: capacity too small"); return IDOCP_E_ARG; }
-  for (int p = 0; p < M; ++p) times[p] = h->chain_t[p];
+  for (int p = 0; p < M; ++p) times[p] = h->plan.chain_t[p];
   return M;
 }
 int idocp_ocp_set_task_refs(idocp_ocp_t* h, double t, int M, const double* refs) {
@@ -1092,7 +636,7 @@ int idocp_parnmpc_set_aux_mat(idocp_ocp_t* h, int nstages, const double* values)
 }
 // warm start along the CHAIN of the current discretisation (event stages included): values[M][dim] in the order of idocp_ocp_get_chain
 static int chainLength(idocp_ocp_t* h, int M) {
-  if (h->chain.empty()) { set_last_error("no chain yet: discretise first (initConstraints / initBackwardCorrection / updateSolution)"); return IDOCP_E_ARG; }
+  if (h->plan.nodes.empty()) { set_last_error("no chain yet: discretise first (initConstraints / initBackwardCorrection / updateSolution)"); return IDOCP_E_ARG; }
   if (M <= 0 || M > h->M()) { set_last_error("chain setter: M out of range"); return IDOCP_E_ARG; }
   return IDOCP_OK;
 }
@@ -1125,8 +669,8 @@ int idocp_ocp_init_constraints(idocp_ocp_t* h, double t) {
 
 // K5b: one launch on an event-free chain with all feet in contact, else one launch per stage class
 static void launchCondenseO(idocp_ocp_t* h, int M, const double* d_q, int part = 0, hipStream_t st_imp = nullptr) {
-  if (h->uniform_dimf == DQ::NF || h->cond_n[0] + h->cond_n[1] + h->cond_n[3] + h->cond_n[4] == 0) OcpLaunch<DQ>::condense(h->B, h->batch, M, h->uniform_dimf, d_q, h->stream, part);
-  else OcpLaunch<DQ>::condenseMixed(h->B, h->batch, M, h->cond_n, d_q, h->stream, part, st_imp);
+  if (h->plan.uniform_dimf == DQ::NF || h->plan.cond_n[0] + h->plan.cond_n[1] + h->plan.cond_n[3] + h->plan.cond_n[4] == 0) OcpLaunch<DQ>::condense(h->B, h->batch, M, h->plan.uniform_dimf, d_q, h->stream, part);
+  else OcpLaunch<DQ>::condenseMixed(h->B, h->batch, M, h->plan.cond_n, d_q, h->stream, part, st_imp);
 }
 
 // The forward sweep that expands as it walks (ocp_forward_expand_kernel) pays when the stage-parallel expansion it absorbs is bandwidth: a
@@ -1175,8 +719,8 @@ static void launchForwardO(idocp_ocp_t* h, int M, const double* d_q, const doubl
 // K5s (and ParNMPC's impulse kernel K5a) in front of the condensation: on the side stream where the handle has one and the chain carries
 // switching constraints (fork here, join in joinSideO before the condensation launches), else on the handle's stream
 static int launchSwitchO(idocp_ocp_t* h, int M) {
-  OcpLaunch<DQ>::rnea(h->B, h->batch, M, h->n_impulse, h->stream);
-  if (!h->has_switch) return IDOCP_OK;
+  OcpLaunch<DQ>::rnea(h->B, h->batch, M, h->plan.n_impulse(), h->stream);
+  if (!h->plan.has_switch) return IDOCP_OK;
   if (!h->side) { OcpLaunch<DQ>::switching(h->B, h->batch, M, h->stream); return IDOCP_OK; }
   HIP_TRY(hipEventRecord(h->ev_fork, h->stream));
   HIP_TRY(hipStreamWaitEvent(h->side, h->ev_fork, 0));
@@ -1211,18 +755,18 @@ static int launchIntegrateO(idocp_ocp_t* h, int M) {
 static int launchCondenseClassesO(idocp_ocp_t* h, int M, const double* d_q) {
   int rc;
   if ((rc = joinSideO(h))) return rc;
-  const bool mixed = !(h->uniform_dimf == DQ::NF || h->cond_n[0] + h->cond_n[1] + h->cond_n[3] + h->cond_n[4] == 0);
+  const bool mixed = !(h->plan.uniform_dimf == DQ::NF || h->plan.cond_n[0] + h->plan.cond_n[1] + h->plan.cond_n[3] + h->plan.cond_n[4] == 0);
   // OFF by default: measured (round 6, profiles/experiments/r06_side_stream.md) -- two different instantiations of the 57 kB condensation kernel
   // resident together take 3.2 instead of 2.24 ms (configs[2]); IDOCP_SIDE_STREAM_K5=1 repeats the experiment
   static const bool split = getenv("IDOCP_SIDE_STREAM_K5") && atoi(getenv("IDOCP_SIDE_STREAM_K5")) != 0;
-  if (!mixed || !h->side || !split || h->cond_n[1] == 0) { launchCondenseO(h, M, d_q, 2); return IDOCP_OK; }
+  if (!mixed || !h->side || !split || h->plan.cond_n[1] == 0) { launchCondenseO(h, M, d_q, 2); return IDOCP_OK; }
   HIP_TRY(hipEventRecord(h->ev_fork, h->stream));
   HIP_TRY(hipStreamWaitEvent(h->side, h->ev_fork, 0));
-  OcpLaunch<DQ>::condenseMixed(h->B, h->batch, M, h->cond_n, d_q, h->stream, 3);
-  OcpLaunch<DQ>::condenseMixed(h->B, h->batch, M, h->cond_n, d_q, h->side, 4);
+  OcpLaunch<DQ>::condenseMixed(h->B, h->batch, M, h->plan.cond_n, d_q, h->stream, 3);
+  OcpLaunch<DQ>::condenseMixed(h->B, h->batch, M, h->plan.cond_n, d_q, h->side, 4);
   HIP_TRY(hipEventRecord(h->ev_join, h->side));
   HIP_TRY(hipStreamWaitEvent(h->stream, h->ev_join, 0));
-  OcpLaunch<DQ>::condenseMixed(h->B, h->batch, M, h->cond_n, d_q, h->stream, 5);
+  OcpLaunch<DQ>::condenseMixed(h->B, h->batch, M, h->plan.cond_n, d_q, h->stream, 5);
   return IDOCP_OK;
 }
 static int launchUpdateO(idocp_ocp_t* h, int M, const double* d_q, const double* d_v) {
@@ -1231,7 +775,7 @@ static int launchUpdateO(idocp_ocp_t* h, int M, const double* d_q, const double*
   if ((rc = launchSwitchO(h, M))) return rc;
   if ((rc = launchNominalO(h, M, d_q))) return rc;        // nominal sweeps (+ Lie tasks, external rows): beside K5s
   if ((rc = launchCondenseClassesO(h, M, d_q))) return rc;
-  OcpLaunch<DQ>::riccatiBackward(h->B, h->batch, M, h->has_switch, h->stream, wideSweep(h));
+  OcpLaunch<DQ>::riccatiBackward(h->B, h->batch, M, h->plan.has_switch, h->stream, wideSweep(h));
   launchForwardO(h, M, d_q, d_v);
   if ((rc = launchIntegrateO(h, M))) return rc;
   HIP_TRY(hipGetLastError());
@@ -1241,7 +785,7 @@ static int launchUpdateO(idocp_ocp_t* h, int M, const double* d_q, const double*
 int idocp_ocp_launch_kernel(idocp_ocp_t* h, int kernel_id, const double* d_q, const double* d_v) {
   if (!h || kernel_id < 0 || kernel_id > 8 || !d_q || !d_v) return IDOCP_E_ARG;
   int rc = setDev(h); if (rc) return rc;
-  if (h->seq_dirty || h->disc_time != h->disc_time) { if ((rc = discretize(h, h->disc_time == h->disc_time ? h->disc_time : 0.0))) return rc; }
+  if ((rc = ensureDiscretized(h))) return rc;
   const int M = h->M();
   switch (kernel_id) {
     case 0: if ((rc = launchSwitchO(h, M))) return rc; break;      // (with a side stream: K5s starts there and id 8 / 1 waits for it)
@@ -1249,7 +793,7 @@ int idocp_ocp_launch_kernel(idocp_ocp_t* h, int kernel_id, const double* d_q, co
     case 7: if ((rc = launchNominalO(h, M, d_q))) return rc; break;      // the two halves of 1: the nominal rigid-body sweeps (+ external rows) ...
     case 8: if ((rc = launchCondenseClassesO(h, M, d_q))) return rc; break;      // ... and the condensation launches proper
     case 2: if ((rc = joinSideO(h))) return rc;      // (a caller that skips the condensation ids still gets K5s in front of the sweep)
-            OcpLaunch<DQ>::riccatiBackward(h->B, h->batch, M, h->has_switch, h->stream, wideSweep(h)); break;
+            OcpLaunch<DQ>::riccatiBackward(h->B, h->batch, M, h->plan.has_switch, h->stream, wideSweep(h)); break;
     // 3: the forward sweep.  Since round 5 it expands as it walks (S4 + K6 + the step-size reduction in one kernel, ocp_forward_expand_kernel);
     // ids 4 and 5 are then empty.  IDOCP_FUSED_FORWARD=0 restores the three kernels behind ids 3, 4, 5.
     case 3: if (fusedForward(h)) OcpLaunch<DQ>::forwardExpand(h->B, h->batch, M, d_q, d_v, h->stream); else OcpLaunch<DQ>::riccatiForward(h->B, h->batch, M, d_q, d_v, h->stream); break;
@@ -1263,7 +807,7 @@ int idocp_ocp_launch_kernel(idocp_ocp_t* h, int kernel_id, const double* d_q, co
 
 int idocp_ocp_update_solution_device(idocp_ocp_t* h, double t, const double* d_q, const double* d_v) {
   if (!h || !d_q || !d_v) return IDOCP_E_ARG;
-  if (!h->contact_status_set) { set_last_error("idocp_ocp_update_solution: call setContactStatusUniformly first"); return IDOCP_E_ARG; }
+  if (!h->seq.status_set) { set_last_error("idocp_ocp_update_solution: call setContactStatusUniformly first"); return IDOCP_E_ARG; }
   int rc = setDev(h); if (rc) return rc;
   if ((rc = discretize(h, t))) return rc;                 // ocp_.discretize(contact_sequence_, t) (ocp_solver.cpp:72)
   const int M = h->M();
@@ -1277,7 +821,7 @@ int idocp_ocp_update_solution_device(idocp_ocp_t* h, double t, const double* d_q
 // discretisation (chain length, stage classes, events) or the input buffers change; the host-side discretiser itself stays outside.
 int idocp_ocp_update_solution_graph(idocp_ocp_t* h, double t, const double* d_q, const double* d_v) {
   if (!h || !d_q || !d_v) return IDOCP_E_ARG;
-  if (!h->contact_status_set) { set_last_error("idocp_ocp_update_solution: call setContactStatusUniformly first"); return IDOCP_E_ARG; }
+  if (!h->seq.status_set) { set_last_error("idocp_ocp_update_solution: call setContactStatusUniformly first"); return IDOCP_E_ARG; }
   int rc = setDev(h); if (rc) return rc;
   if (!h->launched_eagerly) return idocp_ocp_update_solution_device(h, t, d_q, d_v);      // first call: plain launches (one-time kernel attributes)
   if ((rc = discretize(h, t))) return rc;
@@ -1311,7 +855,7 @@ void* idocp_ocp_stream(idocp_ocp_t* h) { return h ? (void*)h->stream : nullptr; 
 // The filter line search of ParNMPCSolver runs on one shard (horizons with discrete events included: every stage of the chain is
 // evaluated against the trial iterate of its chain predecessor, src/line_search/line_search.cpp:199-301, line_search.hpp:224-264).
 static int parnmpcLineSearchSupported(const idocp_ocp_t* h) {
-  if ((h->has_prev || !h->has_terminal) && !(h->ls_pre && h->ls_post)) {
+  if ((h->plan.has_prev || !h->plan.has_terminal) && !(h->ls_pre && h->ls_post)) {
     set_last_error("line_search=true on a shard of a ParNMPC horizon needs the sharded driver (idocp_parnmpc_dist_update_solution_ls)");
     return IDOCP_E_UNSUPPORTED;
   }
@@ -1332,16 +876,16 @@ static int lineSearchEvalO(idocp_ocp_t* h, const std::vector<double>& alpha, con
     if (h->ls_pre) {
       const int rcp = h->ls_pre(h);
       if (rcp) return rcp;
-      if (h->has_prev) { pq = h->d_qtry; pv = h->d_vtry; }
+      if (h->plan.has_prev) { pq = h->d_qtry; pv = h->d_vtry; }
     }
-    OcpLaunch<DQ>::rnea(Bt, h->batch, M, h->n_impulse, h->stream);
-    if (h->has_switch) OcpLaunch<DQ>::switching(Bt, h->batch, M, h->stream);
+    OcpLaunch<DQ>::rnea(Bt, h->batch, M, h->plan.n_impulse(), h->stream);
+    if (h->plan.has_switch) OcpLaunch<DQ>::switching(Bt, h->batch, M, h->stream);
     OcpLaunch<DQ>::meritBackwardEuler(Bt, h->batch, M, pq, pv, h->stream);
-    OcpLaunch<DQ>::parnmpcImpulseMerit(Bt, h->batch, h->n_impulse, pq, pv, h->stream);
+    OcpLaunch<DQ>::parnmpcImpulseMerit(Bt, h->batch, h->plan.n_impulse(), pq, pv, h->stream);
   } else {
     Bt.nodes = h->B.nodes_ls;
-    OcpLaunch<DQ>::rnea(Bt, h->batch, M, h->n_impulse, h->stream);
-    if (h->has_switch) OcpLaunch<DQ>::switching(Bt, h->batch, M, h->stream);
+    OcpLaunch<DQ>::rnea(Bt, h->batch, M, h->plan.n_impulse(), h->stream);
+    if (h->plan.has_switch) OcpLaunch<DQ>::switching(Bt, h->batch, M, h->stream);
     OcpLaunch<DQ>::merit(Bt, h->batch, M, d_q, h->stream);
   }
   OcpLaunch<DQ>::meritReduce(h->B, h->batch, h->stream);
@@ -1398,17 +942,17 @@ static int runLineSearchO(idocp_ocp_t* h, const double* d_q) {
 // idocp_ocp_line_search_eval probes trial steps
 int idocp_ocp_compute_direction(idocp_ocp_t* h, double t, const double* q, const double* v) {
   if (!h || !q || !v) return IDOCP_E_ARG;
-  if (!h->contact_status_set) { set_last_error("idocp_ocp_update_solution: call setContactStatusUniformly first"); return IDOCP_E_ARG; }
+  if (!h->seq.status_set) { set_last_error("idocp_ocp_update_solution: call setContactStatusUniformly first"); return IDOCP_E_ARG; }
   int rc = setDev(h); if (rc) return rc;
   HIP_TRY(hipMemcpyAsync(h->d_q0, q, sizeof(double) * h->batch * DQ::NQ, hipMemcpyHostToDevice, h->stream));
   HIP_TRY(hipMemcpyAsync(h->d_v0, v, sizeof(double) * h->batch * DQ::NV, hipMemcpyHostToDevice, h->stream));
   if ((rc = discretize(h, t))) return rc;
   const int M = h->M();
   HIP_TRY(hipMemsetAsync(h->B.status, 0, sizeof(int) * h->batch, h->stream));
-  OcpLaunch<DQ>::rnea(h->B, h->batch, M, h->n_impulse, h->stream);
-  if (h->has_switch) OcpLaunch<DQ>::switching(h->B, h->batch, M, h->stream);
+  OcpLaunch<DQ>::rnea(h->B, h->batch, M, h->plan.n_impulse(), h->stream);
+  if (h->plan.has_switch) OcpLaunch<DQ>::switching(h->B, h->batch, M, h->stream);
   launchCondenseO(h, M, h->d_q0);
-  OcpLaunch<DQ>::riccatiBackward(h->B, h->batch, M, h->has_switch, h->stream, wideSweep(h));
+  OcpLaunch<DQ>::riccatiBackward(h->B, h->batch, M, h->plan.has_switch, h->stream, wideSweep(h));
   launchForwardO(h, M, h->d_q0, h->d_v0);
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipStreamSynchronize(h->stream));
@@ -1437,14 +981,14 @@ int idocp_ocp_update_solution(idocp_ocp_t* h, double t, const double* q, const d
   HIP_TRY(hipMemcpyAsync(h->d_v0, v, sizeof(double) * h->batch * DQ::NV, hipMemcpyHostToDevice, h->stream));
   if (line_search) {
     // OCPSolver::updateSolution(t, q, v, true) (ocp_solver.cpp:67-92): direction, filter line search on the primal step, integration
-    if (!h->contact_status_set) { set_last_error("idocp_ocp_update_solution: call setContactStatusUniformly first"); return IDOCP_E_ARG; }
+    if (!h->seq.status_set) { set_last_error("idocp_ocp_update_solution: call setContactStatusUniformly first"); return IDOCP_E_ARG; }
     if ((rc = discretize(h, t))) return rc;
     const int M = h->M();
     HIP_TRY(hipMemsetAsync(h->B.status, 0, sizeof(int) * h->batch, h->stream));
-    OcpLaunch<DQ>::rnea(h->B, h->batch, M, h->n_impulse, h->stream);
-    if (h->has_switch) OcpLaunch<DQ>::switching(h->B, h->batch, M, h->stream);
+    OcpLaunch<DQ>::rnea(h->B, h->batch, M, h->plan.n_impulse(), h->stream);
+    if (h->plan.has_switch) OcpLaunch<DQ>::switching(h->B, h->batch, M, h->stream);
     launchCondenseO(h, M, h->d_q0);
-    OcpLaunch<DQ>::riccatiBackward(h->B, h->batch, M, h->has_switch, h->stream, wideSweep(h));
+    OcpLaunch<DQ>::riccatiBackward(h->B, h->batch, M, h->plan.has_switch, h->stream, wideSweep(h));
     launchForwardO(h, M, h->d_q0, h->d_v0);
     HIP_TRY(hipGetLastError());
     if ((rc = runLineSearchO(h, h->d_q0))) return rc;
@@ -1466,8 +1010,8 @@ int idocp_ocp_compute_kkt_residual(idocp_ocp_t* h, double t, const double* q, co
   if ((rc = discretize(h, t))) return rc;
   const int M = h->M();
   HIP_TRY(hipMemcpyAsync(h->d_q0, q, sizeof(double) * h->batch * DQ::NQ, hipMemcpyHostToDevice, h->stream));
-  OcpLaunch<DQ>::rnea(h->B, h->batch, M, h->n_impulse, h->stream);
-  if (h->has_switch) OcpLaunch<DQ>::switching(h->B, h->batch, M, h->stream);
+  OcpLaunch<DQ>::rnea(h->B, h->batch, M, h->plan.n_impulse(), h->stream);
+  if (h->plan.has_switch) OcpLaunch<DQ>::switching(h->B, h->batch, M, h->stream);
   OcpLaunch<DQ>::residual(h->B, h->batch, M, h->d_q0, h->stream);
   ocpKktErrorReduce(h->B, h->batch, h->stream);
   HIP_TRY(hipGetLastError());
@@ -1488,13 +1032,13 @@ int idocp_ocp_get_solution(idocp_ocp_t* h, const char* name, int instance, doubl
   Field f;
   if (!solFieldO(name, f)) { set_last_error(std::string("unknown field name: ") + name); return IDOCP_E_ARG; }
   int rc = setDev(h); if (rc) return rc;
-  return copyField(h, h->B.sol + (size_t)instance * h->NS * LQ::SOL, LQ::SOL, h->parnmpc ? h->N : h->Ngrid + f.extra, f, out);
+  return copyField(h, h->B.sol + (size_t)instance * h->NS * LQ::SOL, LQ::SOL, h->parnmpc ? h->N : h->plan.Ngrid + f.extra, f, out);
 }
 // OCPSolver::getSolution(stage) (ocp_solver.hpp:97): the whole split solution of ONE grid stage in one device-to-host copy --
 // what an MPC loop reads every cycle (getSolution(0).u).  out: lmd gmm q v a u beta f mu nu_passive, the order of the sol record
 // (split_solution.hxx:10-31); on the terminal stage only lmd gmm q v are meaningful.
 int idocp_ocp_get_split_solution(idocp_ocp_t* h, int instance, int stage, double* out) {
-  if (!h || !out || instance < 0 || instance >= h->batch || stage < 0 || stage > (h->parnmpc ? h->N - 1 : h->Ngrid)) return IDOCP_E_ARG;
+  if (!h || !out || instance < 0 || instance >= h->batch || stage < 0 || stage > (h->parnmpc ? h->N - 1 : h->plan.Ngrid)) return IDOCP_E_ARG;
   int rc = setDev(h); if (rc) return rc;
   static_assert(LQ::S_LMD == 0 && LQ::S_NUP > LQ::S_MU, "record order = output order");
   const size_t n = LQ::S_NUP + 6;
@@ -1506,8 +1050,8 @@ int idocp_ocp_get_split_solution(idocp_ocp_t* h, int instance, int stage, double
 // split_solution.hxx:41-57: isContactActive(i), dimf): active[ncontacts] flags; returns dimf = 3 * (number of active contacts) or a
 // negative error code.  What sizes SplitSolution::f_stack() / mu_stack() of getSolution(stage) (split_solution.hpp:93-122).
 int idocp_ocp_get_stage_contact_status(idocp_ocp_t* h, int stage, int* active) {
-  if (!h || !active || stage < 0 || stage > (h->parnmpc ? h->N - 1 : h->Ngrid)) return IDOCP_E_ARG;
-  for (const OcpNode& nd : h->chain) {
+  if (!h || !active || stage < 0 || stage > (h->parnmpc ? h->N - 1 : h->plan.Ngrid)) return IDOCP_E_ARG;
+  for (const OcpNode& nd : h->plan.nodes) {
     if ((nd.kind == 0 || nd.kind == 4) && nd.slot == stage) {
       for (int c = 0; c < DQ::NC; ++c) active[c] = nd.kind == 4 ? 0 : nd.active[c];
       return nd.kind == 4 ? 0 : nd.dimf;
@@ -1532,12 +1076,12 @@ int idocp_ocp_get_direction(idocp_ocp_t* h, const char* name, int instance, doub
   Field f;
   if (!dirFieldO(name, f)) { set_last_error(std::string("unknown field name: ") + name); return IDOCP_E_ARG; }
   int rc = setDev(h); if (rc) return rc;
-  const size_t nrec = h->parnmpc ? h->N : h->Ngrid + f.extra;
+  const size_t nrec = h->parnmpc ? h->N : h->plan.Ngrid + f.extra;
   rc = copyField(h, h->B.dir + (size_t)instance * h->NS * LQ::DIR, LQ::DIR, nrec, f, out);
   if (rc) return rc;
   const std::string n(name);
   if (n == "df" || n == "dmu" || n == "dxi")
-    for (const OcpNode& nd : h->chain)
+    for (const OcpNode& nd : h->plan.nodes)
       if ((nd.kind == 0 || nd.kind == 4) && nd.slot >= 0 && (size_t)nd.slot < nrec) maskAbsentDirectionRows(n, nd, out + (size_t)nd.slot * f.dim);
   return IDOCP_OK;
 }
@@ -1550,7 +1094,7 @@ static int getChainField(idocp_ocp_t* h, const double* base, size_t stride, cons
   std::vector<double> all((size_t)h->NS * stride);
   HIP_TRY(hipMemcpyAsync(all.data(), base + (size_t)instance * h->NS * stride, all.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream));
   HIP_TRY(hipStreamSynchronize(h->stream));
-  for (int p = 0; p < M; ++p) std::memcpy(out + (size_t)p * f.dim, &all[(size_t)h->chain[p].slot * stride + f.offset], sizeof(double) * f.dim);
+  for (int p = 0; p < M; ++p) std::memcpy(out + (size_t)p * f.dim, &all[(size_t)h->plan.nodes[p].slot * stride + f.offset], sizeof(double) * f.dim);
   return IDOCP_OK;
 }
 // the correction state along the chain: out[M][nx * nx] (column-major per stage), the counterpart of idocp_parnmpc_set_aux_mat_chain --
@@ -1591,7 +1135,7 @@ int idocp_ocp_get_direction_chain(idocp_ocp_t* h, const char* name, int instance
   if (rc) return rc;
   const std::string n(name);
   if (n == "df" || n == "dmu" || n == "dxi")
-    for (int p = 0; p < h->M(); ++p) maskAbsentDirectionRows(n, h->chain[p], out + (size_t)p * f.dim);
+    for (int p = 0; p < h->M(); ++p) maskAbsentDirectionRows(n, h->plan.nodes[p], out + (size_t)p * f.dim);
   return IDOCP_OK;
 }
 
@@ -1610,13 +1154,13 @@ static int getRiccati(idocp_ocp_t* h, int instance, int chain, double* P, double
   if (!h || instance < 0 || instance >= h->batch) return IDOCP_E_ARG;
   int rc = setDev(h); if (rc) return rc;
   const int nv = DQ::NV, nx = DQ::NX, nu = DQ::NU;
-  const int n = chain ? h->M() : h->Ngrid + 1;
+  const int n = chain ? h->M() : h->plan.Ngrid + 1;
   std::vector<double> ric((size_t)h->NS * LQ::RIC), gain((size_t)h->NS * LQ::GAIN);
   HIP_TRY(hipMemcpyAsync(ric.data(), h->B.ric + (size_t)instance * h->NS * LQ::RIC, ric.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream));
   HIP_TRY(hipMemcpyAsync(gain.data(), h->B.gain + (size_t)instance * h->NS * LQ::GAIN, gain.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream));
   HIP_TRY(hipStreamSynchronize(h->stream));
   for (int i = 0; i < n; ++i) {
-    const int slot = chain ? h->chain[i].slot : i;
+    const int slot = chain ? h->plan.nodes[i].slot : i;
     const double* r = &ric[(size_t)slot * LQ::RIC];
     if (P) {
       double* Pm = P + (size_t)i * nx * nx;
@@ -1640,7 +1184,7 @@ int idocp_ocp_get_riccati(idocp_ocp_t* h, int instance, double* P, double* s, do
 int idocp_ocp_get_riccati_chain(idocp_ocp_t* h, int instance, double* P, double* s, double* K, double* k) { return getRiccati(h, instance, 1, P, s, K, k); }
 
 int idocp_ocp_get_state_feedback_gain(idocp_ocp_t* h, int instance, int stage, double* Kq, double* Kv) {
-  if (!h || instance < 0 || instance >= h->batch || stage < 0 || stage >= h->Ngrid || !Kq || !Kv) return IDOCP_E_ARG;
+  if (!h || instance < 0 || instance >= h->batch || stage < 0 || stage >= h->plan.Ngrid || !Kq || !Kv) return IDOCP_E_ARG;
   int rc = setDev(h); if (rc) return rc;
   std::vector<double> g(LQ::GAIN);
   HIP_TRY(hipMemcpyAsync(g.data(), h->B.gain + ((size_t)instance * h->NS + stage) * LQ::GAIN, g.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream));
@@ -1658,7 +1202,7 @@ int idocp_ocp_get_state_feedback_gain(idocp_ocp_t* h, int instance, int stage, d
 int idocp_ocp_is_current_solution_feasible(idocp_ocp_t* h, int* feasible, int* where) {
   if (!h || !feasible) return IDOCP_E_ARG;
   int rc = setDev(h); if (rc) return rc;
-  if (h->seq_dirty || h->disc_time != h->disc_time) { if ((rc = discretize(h, h->disc_time == h->disc_time ? h->disc_time : 0.0))) return rc; }
+  if ((rc = ensureDiscretized(h))) return rc;
   const int M = h->M(), nu = DQ::NU;
   const OcpProblem& P = h->prob;
   std::vector<double> sol((size_t)h->batch * h->NS * LQ::SOL);
@@ -1698,7 +1242,7 @@ int idocp_ocp_is_current_solution_feasible(idocp_ocp_t* h, int* feasible, int* w
     int bad = -1;
     for (int kind = 0; kind < 4 && bad < 0; ++kind)
       for (int p = 0; p < M && bad < 0; ++p) {
-        const OcpNode& nd = h->chain[p];
+        const OcpNode& nd = h->plan.nodes[p];
         if (nd.kind != kind) continue;
         if (!stageOk(nd, &sol[((size_t)b * h->NS + nd.slot) * LQ::SOL])) bad = p;
       }
@@ -1719,7 +1263,7 @@ int idocp_ocp_dimc(const idocp_ocp_t* h) {
 int idocp_ocp_get_constraint_data(idocp_ocp_t* h, int instance, double* slack, double* dual) {
   if (!h || instance < 0 || instance >= h->batch) return IDOCP_E_ARG;
   int rc = setDev(h); if (rc) return rc;
-  const int N = h->Ngrid, dimc = idocp_ocp_dimc(h);
+  const int N = h->plan.Ngrid, dimc = idocp_ocp_dimc(h);
   std::vector<double> sl((size_t)N * LQ::CON), du((size_t)N * LQ::CON);
   HIP_TRY(hipMemcpyAsync(sl.data(), h->B.slack + (size_t)instance * h->NS * LQ::CON, sl.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream));
   HIP_TRY(hipMemcpyAsync(du.data(), h->B.dual + (size_t)instance * h->NS * LQ::CON, du.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream));
@@ -1760,7 +1304,7 @@ int idocp_ocp_get_profile(idocp_ocp_t* h, long long* out, int n) {
 int idocp_ocp_set_lqr_stage(idocp_ocp_t* h, int stage, int terminal, const double* Qxx, const double* Qxu, const double* Quu, const double* Fqq6,
                             const double* Fqv6, const double* Fvq, const double* Fvv, const double* Fvu, const double* lx, const double* lu,
                             const double* Fx) {
-  if (!h || !Qxx || !lx || stage < 0 || stage > h->Ngrid) return IDOCP_E_ARG;
+  if (!h || !Qxx || !lx || stage < 0 || stage > h->plan.Ngrid) return IDOCP_E_ARG;
   if (!terminal && (!Qxu || !Quu || !Fqq6 || !Fqv6 || !Fvq || !Fvv || !Fvu || !lu || !Fx)) return IDOCP_E_ARG;
   int rc = setDev(h); if (rc) return rc;
   const int nv = DQ::NV, nx = DQ::NX, nu = DQ::NU;
@@ -1791,7 +1335,7 @@ static int getContactDynamics(idocp_ocp_t* h, int instance, int stage, int dimf,
 int idocp_ocp_get_contact_dynamics(idocp_ocp_t* h, int instance, int stage, double* MJtJinv, double* MJtJinv_dIDCdqv, double* MJtJinv_IDC) {
   if (!h || !MJtJinv || !MJtJinv_dIDCdqv || !MJtJinv_IDC || instance < 0 || instance >= h->batch) return IDOCP_E_ARG;
   int dimf = -1;
-  for (const OcpNode& nd : h->chain) if (nd.kind == 0 && nd.slot == stage) dimf = nd.dimf;
+  for (const OcpNode& nd : h->plan.nodes) if (nd.kind == 0 && nd.slot == stage) dimf = nd.dimf;
   if (dimf < 0) { set_last_error("idocp_ocp_get_contact_dynamics: stage " + std::to_string(stage) + " is not a grid stage of the current discretisation"); return IDOCP_E_ARG; }
   return getContactDynamics(h, instance, stage, dimf, MJtJinv, MJtJinv_dIDCdqv, MJtJinv_IDC);
 }
@@ -1799,7 +1343,7 @@ int idocp_ocp_get_contact_dynamics(idocp_ocp_t* h, int instance, int stage, doub
 // impulse_dynamics_forward_euler_data.hxx: MJtJinv of the impulse's contacts, the blocks of [ImD; V] in place of [ID; C])
 int idocp_ocp_get_contact_dynamics_chain(idocp_ocp_t* h, int instance, int position, double* MJtJinv, double* MJtJinv_dIDCdqv, double* MJtJinv_IDC) {
   if (!h || !MJtJinv || !MJtJinv_dIDCdqv || !MJtJinv_IDC || instance < 0 || instance >= h->batch || position < 0 || position >= h->M()) return IDOCP_E_ARG;
-  const OcpNode& nd = h->chain[position];
+  const OcpNode& nd = h->plan.nodes[position];
   if (nd.kind == 4) { set_last_error("idocp_ocp_get_contact_dynamics_chain: the terminal stage has no dynamics"); return IDOCP_E_ARG; }
   return getContactDynamics(h, instance, nd.slot, nd.dimf, MJtJinv, MJtJinv_dIDCdqv, MJtJinv_IDC);
 }
@@ -1817,7 +1361,7 @@ static int getContactDynamics(idocp_ocp_t* h, int instance, int stage, int dimf,
 
 int idocp_ocp_get_lqr_stage(idocp_ocp_t* h, int instance, int stage, double* Qxx, double* Qxu, double* Quu, double* A, double* Bm,
                             double* lx, double* lu, double* Fx) {
-  if (!h || instance < 0 || instance >= h->batch || stage < 0 || stage >= h->Ngrid) return IDOCP_E_ARG;
+  if (!h || instance < 0 || instance >= h->batch || stage < 0 || stage >= h->plan.Ngrid) return IDOCP_E_ARG;
   int rc = setDev(h); if (rc) return rc;
   const int nv = DQ::NV, nx = DQ::NX, nu = DQ::NU;
   std::vector<double> k(LQ::KKT);
@@ -1829,7 +1373,7 @@ int idocp_ocp_get_lqr_stage(idocp_ocp_t* h, int instance, int stage, double* Qxx
   std::memset(A, 0, sizeof(double) * nx * nx);
   std::memset(Bm, 0, sizeof(double) * nx * nu);
   double dt = h->T / h->N;
-  for (const OcpNode& nd : h->chain) if (nd.slot == stage) dt = nd.dtq;
+  for (const OcpNode& nd : h->plan.nodes) if (nd.slot == stage) dt = nd.dtq;
   for (int c = 0; c < nv; ++c) for (int r = 0; r < nv; ++r) {
     double fqq = (r == c) ? 1.0 : 0.0, fqv = (r == c) ? dt : 0.0;
     if (r < 6 && c < 6) { fqq = k[LQ::K_FQQ + r + 6 * c]; fqv = k[LQ::K_FQV + r + 6 * c]; }
@@ -1863,7 +1407,7 @@ int idocp_parnmpc_init_backward_correction(idocp_ocp_t* h, double t) {
   if (!h || !h->parnmpc) return IDOCP_E_ARG;
   int rc = setDev(h); if (rc) return rc;
   if ((rc = discretize(h, t))) return rc;
-  OcpLaunch<DQ>::parnmpcPhase(4, h->B, h->batch, h->M(), h->has_terminal, h->d_q0, h->d_v0, h->stream);
+  OcpLaunch<DQ>::parnmpcPhase(4, h->B, h->batch, h->M(), h->plan.has_terminal, h->d_q0, h->d_v0, h->stream);
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipStreamSynchronize(h->stream));
   return IDOCP_OK;
@@ -1876,20 +1420,20 @@ int idocp_parnmpc_init_backward_correction(idocp_ocp_t* h, double t) {
 int idocp_parnmpc_launch_phase(idocp_ocp_t* h, int phase, const double* d_q, const double* d_v) {
   if (!h || !h->parnmpc || phase < 0 || phase > 9 || !d_q || !d_v) return IDOCP_E_ARG;
   int rc = setDev(h); if (rc) return rc;
-  if (h->seq_dirty || h->disc_time != h->disc_time) { if ((rc = discretize(h, h->disc_time == h->disc_time ? h->disc_time : 0.0))) return rc; }
+  if ((rc = ensureDiscretized(h))) return rc;
   const int M = h->M();
   switch (phase) {
-    case 0: OcpLaunch<DQ>::rnea(h->B, h->batch, M, h->n_impulse, h->stream); break;
+    case 0: OcpLaunch<DQ>::rnea(h->B, h->batch, M, h->plan.n_impulse(), h->stream); break;
     case 1:
-      if (h->has_switch) OcpLaunch<DQ>::switching(h->B, h->batch, M, h->stream);          // P, Pq of the aux stages
+      if (h->plan.has_switch) OcpLaunch<DQ>::switching(h->B, h->batch, M, h->stream);          // P, Pq of the aux stages
       OcpLaunch<DQ>::condenseBackwardEuler(h->B, h->batch, M, d_q, d_v, false, h->stream);
-      OcpLaunch<DQ>::parnmpcImpulseCondense(h->B, h->batch, h->n_impulse, false, d_q, d_v, h->stream);
+      OcpLaunch<DQ>::parnmpcImpulseCondense(h->B, h->batch, h->plan.n_impulse(), false, d_q, d_v, h->stream);
       break;
     case 2:
       OcpLaunch<DQ>::parnmpcInverse(h->B, h->batch, M, h->stream);
-      OcpLaunch<DQ>::parnmpcEventInverse(h->B, h->batch, h->n_general, h->stream);
+      OcpLaunch<DQ>::parnmpcEventInverse(h->B, h->batch, h->plan.n_general(), h->stream);
       break;
-    case 3: case 4: case 5: case 6: OcpLaunch<DQ>::parnmpcPhase(phase - 3, h->B, h->batch, M, h->has_terminal, d_q, d_v, h->stream); break;
+    case 3: case 4: case 5: case 6: OcpLaunch<DQ>::parnmpcPhase(phase - 3, h->B, h->batch, M, h->plan.has_terminal, d_q, d_v, h->stream); break;
     case 7: OcpLaunch<DQ>::single(4, h->B, h->batch, M, h->stream); break;
     case 8: OcpLaunch<DQ>::single(5, h->B, h->batch, M, h->stream); break;
     default: OcpLaunch<DQ>::single(6, h->B, h->batch, M, h->stream); break;
@@ -1900,7 +1444,7 @@ int idocp_parnmpc_launch_phase(idocp_ocp_t* h, int phase, const double* d_q, con
 
 int idocp_parnmpc_update_solution_device(idocp_ocp_t* h, double t, const double* d_q, const double* d_v) {
   if (!h || !h->parnmpc || !d_q || !d_v) return IDOCP_E_ARG;
-  if (!h->contact_status_set) { set_last_error("idocp_parnmpc_update_solution: call setContactStatusUniformly first"); return IDOCP_E_ARG; }
+  if (!h->seq.status_set) { set_last_error("idocp_parnmpc_update_solution: call setContactStatusUniformly first"); return IDOCP_E_ARG; }
   int rc = setDev(h); if (rc) return rc;
   if ((rc = discretize(h, t))) return rc;
   HIP_TRY(hipMemsetAsync(h->B.status, 0, sizeof(int) * h->batch, h->stream));
@@ -1912,7 +1456,7 @@ int idocp_parnmpc_update_solution_device(idocp_ocp_t* h, double t, const double*
 // idocp_ocp_line_search_eval probes trial steps
 int idocp_parnmpc_compute_direction(idocp_ocp_t* h, double t, const double* q, const double* v) {
   if (!h || !h->parnmpc || !q || !v) return IDOCP_E_ARG;
-  if (!h->contact_status_set) { set_last_error("idocp_parnmpc_update_solution: call setContactStatusUniformly first"); return IDOCP_E_ARG; }
+  if (!h->seq.status_set) { set_last_error("idocp_parnmpc_update_solution: call setContactStatusUniformly first"); return IDOCP_E_ARG; }
   int rc = setDev(h); if (rc) return rc;
   HIP_TRY(hipMemcpyAsync(h->d_q0, q, sizeof(double) * h->batch * DQ::NQ, hipMemcpyHostToDevice, h->stream));
   HIP_TRY(hipMemcpyAsync(h->d_v0, v, sizeof(double) * h->batch * DQ::NV, hipMemcpyHostToDevice, h->stream));
@@ -1929,7 +1473,7 @@ int idocp_parnmpc_update_solution(idocp_ocp_t* h, double t, const double* q, con
   if (line_search) {
     // ParNMPCSolver::updateSolution(t, q, v, true) (parnmpc_solver.cpp:73-103): direction, filter line search on the primal step, integration
     // (the support check needs the chain of this t; nothing has touched the direction / Riccati records when it refuses)
-    if (!h->contact_status_set) { set_last_error("idocp_parnmpc_update_solution: call setContactStatusUniformly first"); return IDOCP_E_ARG; }
+    if (!h->seq.status_set) { set_last_error("idocp_parnmpc_update_solution: call setContactStatusUniformly first"); return IDOCP_E_ARG; }
     if ((rc = discretize(h, t))) return rc;
     if ((rc = parnmpcLineSearchSupported(h))) return rc;
     if ((rc = idocp_parnmpc_compute_direction(h, t, q, v))) return rc;
@@ -1955,10 +1499,10 @@ int idocp_parnmpc_compute_kkt_residual(idocp_ocp_t* h, double t, const double* q
   const int M = h->M();
   HIP_TRY(hipMemcpyAsync(h->d_q0, q, sizeof(double) * h->batch * DQ::NQ, hipMemcpyHostToDevice, h->stream));
   HIP_TRY(hipMemcpyAsync(h->d_v0, v, sizeof(double) * h->batch * DQ::NV, hipMemcpyHostToDevice, h->stream));
-  OcpLaunch<DQ>::rnea(h->B, h->batch, M, h->n_impulse, h->stream);
-  if (h->has_switch) OcpLaunch<DQ>::switching(h->B, h->batch, M, h->stream);
+  OcpLaunch<DQ>::rnea(h->B, h->batch, M, h->plan.n_impulse(), h->stream);
+  if (h->plan.has_switch) OcpLaunch<DQ>::switching(h->B, h->batch, M, h->stream);
   OcpLaunch<DQ>::condenseBackwardEuler(h->B, h->batch, M, h->d_q0, h->d_v0, true, h->stream);
-  OcpLaunch<DQ>::parnmpcImpulseCondense(h->B, h->batch, h->n_impulse, true, h->d_q0, h->d_v0, h->stream);
+  OcpLaunch<DQ>::parnmpcImpulseCondense(h->B, h->batch, h->plan.n_impulse(), true, h->d_q0, h->d_v0, h->stream);
   ocpKktErrorReduce(h->B, h->batch, h->stream);
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipStreamSynchronize(h->stream));
@@ -1972,7 +1516,7 @@ int idocp_parnmpc_create_shard(const idocp_model_t* model, const idocp_cost_t* c
   if (stage_offset < 0) { set_last_error("invalid value: stage_offset must be non-negative!"); return IDOCP_E_ARG; }
   int rc = createOcpImpl(model, cost, constraints, T, N, 0, batch, device, true, out);
   if (rc) return rc;
-  (*out)->stage_offset = stage_offset; (*out)->has_terminal = has_terminal != 0; (*out)->has_prev = has_prev != 0;
+  (*out)->stage_offset = stage_offset; (*out)->plan.has_terminal = has_terminal != 0; (*out)->plan.has_prev = has_prev != 0;
   (*out)->seq_dirty = true;
   return IDOCP_OK;
 }
@@ -1985,7 +1529,7 @@ int idocp_parnmpc_create_hybrid_shard(const idocp_model_t* model, const idocp_co
   int rc = createOcpImpl(model, cost, constraints, T, N, max_num_impulse, batch, device, true, out);
   if (rc) return rc;
   (*out)->slice_begin = stage_begin; (*out)->slice_end = stage_end;
-  (*out)->has_terminal = stage_end == N; (*out)->has_prev = stage_begin > 0;
+  (*out)->plan.has_terminal = stage_end == N; (*out)->plan.has_prev = stage_begin > 0;
   (*out)->seq_dirty = true;
   return IDOCP_OK;
 }
@@ -2004,7 +1548,7 @@ int idocp_parnmpc_halo_size(int kind) {
 static int haloImpl(idocp_ocp_t* h, int kind, bool do_import, double* d_buf, bool sync) {
   if (!h || !h->parnmpc || !d_buf || idocp_parnmpc_halo_size(kind) < 0) return IDOCP_E_ARG;
   int rc = setDev(h); if (rc) return rc;
-  if (h->seq_dirty || h->disc_time != h->disc_time) { if ((rc = discretize(h, h->disc_time == h->disc_time ? h->disc_time : 0.0))) return rc; }
+  if ((rc = ensureDiscretized(h))) return rc;
   OcpLaunch<DQ>::parnmpcHalo(h->B, h->batch, kind, do_import, d_buf, h->d_q0, h->d_v0, h->stream);
   HIP_TRY(hipGetLastError());
   if (sync) HIP_TRY(hipStreamSynchronize(h->stream));
@@ -2075,10 +1619,10 @@ int idocp_parnmpc_kkt_error_squared_device(idocp_ocp_t* h, double t, double* d_e
   int rc = setDev(h); if (rc) return rc;
   if ((rc = discretize(h, t))) return rc;
   const int M = h->M();
-  OcpLaunch<DQ>::rnea(h->B, h->batch, M, h->n_impulse, h->stream);
-  if (h->has_switch) OcpLaunch<DQ>::switching(h->B, h->batch, M, h->stream);
+  OcpLaunch<DQ>::rnea(h->B, h->batch, M, h->plan.n_impulse(), h->stream);
+  if (h->plan.has_switch) OcpLaunch<DQ>::switching(h->B, h->batch, M, h->stream);
   OcpLaunch<DQ>::condenseBackwardEuler(h->B, h->batch, M, h->d_q0, h->d_v0, true, h->stream);
-  OcpLaunch<DQ>::parnmpcImpulseCondense(h->B, h->batch, h->n_impulse, true, h->d_q0, h->d_v0, h->stream);
+  OcpLaunch<DQ>::parnmpcImpulseCondense(h->B, h->batch, h->plan.n_impulse(), true, h->d_q0, h->d_v0, h->stream);
   ocpKktErrorReduce(h->B, h->batch, h->stream, d_err2);      // stays on the device and on the stream
   HIP_TRY(hipGetLastError());
   return IDOCP_OK;
@@ -2173,8 +1717,7 @@ int idocp_ocp_clone(idocp_ocp_t* src, idocp_ocp_t** out) {
   }
   if (hipStreamSynchronize(h->stream) != hipSuccess) return fail(IDOCP_E_DEVICE);
   h->task_refs_host = src->task_refs_host; h->task_refs_t = src->task_refs_t;
-  h->contact_status_set = src->contact_status_set; h->stage_offset = src->stage_offset; h->has_terminal = src->has_terminal; h->has_prev = src->has_prev;
-  h->phases = src->phases; h->event_time = src->event_time; h->is_impulse = src->is_impulse; h->impulse_status = src->impulse_status;
+  h->seq = src->seq; h->stage_offset = src->stage_offset; h->plan.has_terminal = src->plan.has_terminal; h->plan.has_prev = src->plan.has_prev;
   h->slice_begin = src->slice_begin; h->slice_end = src->slice_end;
   h->fused_forward_mode = src->fused_forward_mode;
   h->riccati_sweep_mode = src->riccati_sweep_mode;
@@ -2182,10 +1725,7 @@ int idocp_ocp_clone(idocp_ocp_t* src, idocp_ocp_t** out) {
   h->prob = src->prob;
   h->seq_dirty = true;                       // the chain is rebuilt (and uploaded) on first use
   if (src->disc_time == src->disc_time) {
-    h->task_refs_lenient = true;
-    rc = discretize(h, src->disc_time);
-    h->task_refs_lenient = false;
-    if (rc) return fail(rc);
+    if ((rc = discretize(h, src->disc_time, true))) return fail(rc);
   }
   *out = h;
   return IDOCP_OK;

@@ -10,6 +10,7 @@
 #ifndef IDOCP_OCP_DEVICE_HPP_
 #define IDOCP_OCP_DEVICE_HPP_
 
+#include "ocp_chain.hpp"      // OcpNode: the chain of stages, planned on the host
 #include "unocp_device.hpp"
 
 namespace idocp_dev {
@@ -110,24 +111,6 @@ struct OcpLayout {
   static constexpr int KINV = roundUp16(2 * NKG * NX);
   static constexpr int AUX = roundUp16(NX * NX);
   static constexpr int XRES = roundUp16(NX);
-};
-
-// One stage of the CHAIN (time order): stage, [impulse, aux | lift], stage, ..., terminal.  Every stage owns a fixed
-// storage SLOT (grid stage i -> i, impulse k -> N+1+k, aux k -> N+1+E+k, lift k -> N+1+2E+k, like the separate arrays
-// of the reference's hybrid_container.hpp:60-168); the chain is rebuilt by the host-side discretiser
-// (OCPDiscretizer, ocp_discretizer.hxx:65-374) and says who the neighbours are.
-struct OcpNode {
-  int slot, next, prev;     // prev = -1: the predecessor is the initial state
-  int kind;                 // 0 stage, 1 impulse, 2 aux, 3 lift, 4 terminal
-  int level;                // time step for the constraint gating (constraints_data.hpp:18-42): stage index, 0 aux / lift
-  int has_u;                // 0 on impulse stages (no torque variables)
-  int dimf, active[IDOCP_MAX_CONTACTS], row_of[IDOCP_MAX_CONTACTS];   // contact (or impulse) status of this stage
-  double dt;                // scaling of cost / constraint / dynamics multipliers: the time step, 1 on impulse stages
-  double dtq;               // q+ = q (+) dtq v: the time step, 0 on impulse stages
-  double vref_on;           // 1, or 0 where a time-varying cost switches its velocity reference off (stage time outside its window)
-  double contact_point[IDOCP_MAX_CONTACTS][3];
-  int sw_dimi, sw_active[IDOCP_MAX_CONTACTS], sw_row[IDOCP_MAX_CONTACTS];     // switching constraint carried by this stage
-  double sw_dt1, sw_dt2, sw_point[IDOCP_MAX_CONTACTS][3];
 };
 
 // ParNMPC: shape of a stage's KKT matrix (SplitBackwardCorrection / ImpulseSplitBackwardCorrection::dimKKT_)

@@ -208,8 +208,11 @@ def test_time_varying_reference_on_a_trotting_chain(frame, dim):
     gc.init_constraints(0.0)
     assert gc.update(0.0, q, v) == 0
     assert np.abs(gc.get_chain("dq", M) - g.get_chain("dq", M)).max() > 1e-6
-    # a call at another time needs poses for that chain
+    # a call at another time needs poses for that chain; the refusal leaves the handle on the chain its device tables hold
+    dq0, q0 = g.get_chain("dq", M), g.get_chain("q", M)
     assert g.update(0.05, q, v) != 0
+    assert np.array_equal(g.get_chain("dq", M), dq0) and np.array_equal(g.get_chain("q", M), q0)
+    assert g.update(0.0, q, v) == 0
     t2 = g.chain_times(0.05)
     g.set_task_refs(0.05, moving_reference(t2, dim))
     assert g.update(0.05, q, v) == 0
