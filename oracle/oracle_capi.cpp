@@ -606,6 +606,29 @@ int oracle_ocp_set_solution(void* h, const char* name, const double* value) {
   try { s->setSolution(n, toVec(value, dim)); } catch (...) { return -1; }
   return 0;
 }
+// one field of ONE stage of either solver: name in q v a (dv on an impulse stage) u f (all contacts stacked) lmd gmm beta mu (stacked)
+static int setStageField(SplitSolutionC& x, const Robot& robot, const char* name, const double* value) {
+  const std::string n(name);
+  const int nv = robot.dimv(), nc = robot.maxPointContacts();
+  if (n == "q") x.q = toVec(value, robot.dimq());
+  else if (n == "v") x.v = toVec(value, nv);
+  else if (n == "a") x.a = toVec(value, nv);
+  else if (n == "u") x.u = toVec(value, robot.dimu());
+  else if (n == "lmd") x.lmd = toVec(value, nv);
+  else if (n == "gmm") x.gmm = toVec(value, nv);
+  else if (n == "beta") x.beta = toVec(value, nv);
+  else if (n == "f") for (int c = 0; c < nc; ++c) x.f[c] = toVec(value + 3 * c, 3);
+  else if (n == "mu") for (int c = 0; c < nc; ++c) x.mu[c] = toVec(value + 3 * c, 3);
+  else return -1;
+  return 0;
+}
+// ... of ONE storage slot of an OCPSolver (oracle_ocp_chain maps chain positions to slots), like oracle_parnmpc_set_stage: for the tests that
+// hold the stage terms of distinct iterates per stage (tests/ocp_stage_cases.py)
+int oracle_ocp_set_stage(void* h, int slot, const char* name, const double* value) {
+  OCPSolver* s = static_cast<OCPSolver*>(h);
+  if (slot < 0 || slot >= (int)s->s.size()) return -1;
+  return setStageField(s->s[slot], s->robot, name, value);
+}
 int oracle_ocp_init_constraints(void* h, double t) { static_cast<OCPSolver*>(h)->initConstraints(t); return 0; }
 int oracle_ocp_update_solution(void* h, double t, const double* q, const double* v) {
   OCPSolver* s = static_cast<OCPSolver*>(h);
@@ -947,20 +970,7 @@ int oracle_parnmpc_set_solution(void* h, const char* name, const double* value) 
 int oracle_parnmpc_set_stage(void* h, int i, const char* name, const double* value) {
   ParNMPCSolver* s = static_cast<ParNMPCSolver*>(h);
   if (i < 0 || i >= (int)s->s.size()) return -1;
-  const std::string n(name);
-  SplitSolutionC& x = s->s[i];
-  const int nv = s->robot.dimv(), nc = s->robot.maxPointContacts();
-  if (n == "q") x.q = toVec(value, s->robot.dimq());
-  else if (n == "v") x.v = toVec(value, nv);
-  else if (n == "a") x.a = toVec(value, nv);
-  else if (n == "u") x.u = toVec(value, s->robot.dimu());
-  else if (n == "lmd") x.lmd = toVec(value, nv);
-  else if (n == "gmm") x.gmm = toVec(value, nv);
-  else if (n == "beta") x.beta = toVec(value, nv);
-  else if (n == "f") for (int c = 0; c < nc; ++c) x.f[c] = toVec(value + 3 * c, 3);
-  else if (n == "mu") for (int c = 0; c < nc; ++c) x.mu[c] = toVec(value + 3 * c, 3);
-  else return -1;
-  return 0;
+  return setStageField(s->s[i], s->robot, name, value);
 }
 int oracle_parnmpc_set_aux_mat(void* h, int i, const double* mat /* nx x nx col-major */) {
   ParNMPCSolver* s = static_cast<ParNMPCSolver*>(h);

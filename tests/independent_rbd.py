@@ -52,7 +52,7 @@ def joint_forces(M, f, active):
     return fext
 
 
-def terms(M, q, v, a, f=None, contact_points=None, time_step=None, active=None):
+def terms(M, q, v, a, f=None, contact_points=None, time_step=None, active=None, impulse_forms=True):
     """One sample from the generator's own functions, matrices as [row, column].
     tau, dtau_dq, dtau_dv, dtau_da (with the forces f[nc][3] of the active contacts, if given); on a model with contacts the impulse forms
     (no gravity, v = 0) tau_impulse, dimp_dq, dimp_da; with contact_points and time_step the Baumgarte C, dCdq, dCdv, dCda over the ACTIVE rows,
@@ -63,7 +63,7 @@ def terms(M, q, v, a, f=None, contact_points=None, time_step=None, active=None):
     fext = joint_forces(M, f, act) if f is not None else None
     out = {"tau": RBD.rnea(M, q, v, a, fext)}
     out["dtau_dq"], out["dtau_dv"], out["dtau_da"] = RBD.rnea_derivatives(M, q, v, a, fext)
-    if nc:
+    if nc and impulse_forms:      # (impulse_forms = False: a caller that holds a regular stage only)
         z = np.zeros(nv)
         out["tau_impulse"] = RBD.rnea(M, q, z, a, fext, gravity=False)
         out["dimp_dq"], _, out["dimp_da"] = RBD.rnea_derivatives(M, q, z, a, fext, gravity=False)

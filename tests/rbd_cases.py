@@ -203,7 +203,7 @@ def kkt_residual(t, u, mask, a, f):
     return float(np.abs(K.astype(np.longdouble) @ x - rhs.astype(np.longdouble)).max() / max(1.0, np.abs(rhs).max()))
 
 
-def _solve_longdouble(A, B):
+def solve_longdouble(A, B):
     """Gaussian elimination with partial pivoting in np.longdouble (numpy's own solvers are double only)"""
     A, B = np.array(A, dtype=np.longdouble), np.array(B, dtype=np.longdouble).reshape(A.shape[0], -1)
     n = A.shape[0]
@@ -226,12 +226,12 @@ def solve_schur(t, u, mask):
     tau = np.zeros(nv)
     if u is not None:
         tau[nv - len(u):] = u
-    y = _solve_longdouble(t["M"], tau - t["h"]).reshape(-1)
+    y = solve_longdouble(t["M"], tau - t["h"]).reshape(-1)
     f = np.zeros(3 * nc)
     if rows.any():
         J, b, Gm = t["J"][rows].astype(np.longdouble), t["b"][rows].astype(np.longdouble), t["G"][:, rows]
-        T = _solve_longdouble(t["M"], Gm)
-        g = _solve_longdouble(J @ T, J @ y + b).reshape(-1)
+        T = solve_longdouble(t["M"], Gm)
+        g = solve_longdouble(J @ T, J @ y + b).reshape(-1)
         y = y - T @ g
         f[rows] = g.astype(np.float64)
     return y.astype(np.float64), f.reshape(nc, 3)

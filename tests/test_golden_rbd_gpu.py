@@ -12,6 +12,7 @@ import pytest
 
 from helpers import GOLDEN, HipOCP, P, anymal_model, anymal_problem, arr, rel_err
 from idocp_amd import capi
+from ocp_stage_cases import unpack
 
 pytestmark = pytest.mark.gpu
 NV, NF = 18, 12
@@ -22,9 +23,8 @@ def contact_dynamics_of_stage_0(g, instance):
     MJ, MJD, MJIDC = np.zeros(n * n), np.zeros(n * 2 * NV), np.zeros(n)
     dimf = g.lib.idocp_ocp_get_contact_dynamics(g.h, instance, 0, P(MJ), P(MJD), P(MJIDC))
     assert dimf == NF, (dimf, capi.lib().idocp_last_error())
-    MJ, MJD = MJ.reshape(n, n).T, MJD.reshape(2 * NV, n).T      # column-major -> [row, column]
-    K = np.linalg.inv(MJ)                                       # [M J^T; J 0]
-    return MJ, K, K @ MJD, K @ MJIDC
+    t = unpack(MJ.reshape(n, n).T, MJD.reshape(2 * NV, n).T, MJIDC, NV)      # column-major -> [row, column]; the shared helper takes the record apart
+    return t["MJtJinv"], t["K"], np.block([[t["dID/dq"], t["dID/dv"]], [t["dC/dq"], t["dC/dv"]]]), np.concatenate([t["ID - S^T u"], t["C"]])
 
 
 def linearise(sample, f=None, time_step=0.05, contact_points=None):
