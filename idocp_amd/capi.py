@@ -119,7 +119,15 @@ class RbdPolicy(C.Structure):
     _fields_ = [(name, C.c_void_p) for name in ARRAYS] + [("shared_gains", C.c_int), ("shared_ref", C.c_int)]
 
 
+class RbdScoreIO(C.Structure):
+    """idocp_rbd_score_io_t: the slices and requested results of idocp_rbd_score_rollout(_device); a pointer left at None is NULL"""
+    INPUTS = ("q_traj", "v_traj", "u_traj", "a_traj", "f_traj")
+    OUTPUTS = ("cost", "violation", "stage_cost")
+    _fields_ = [(name, C.c_void_p) for name in INPUTS + OUTPUTS]
+
+
 RBD_STAGE, RBD_IMPULSE = 0, 1
+RBD_SCORE_MAX_WINDOW = 1024
 
 
 class LibraryMissing(RuntimeError):
@@ -313,6 +321,18 @@ def _proto(lib):
     lib.idocp_rbd_rollout_policy.restype = ci
     lib.idocp_rbd_rollout_policy_device.argtypes = [vp, ci, ci, c_int_p, cd, cd, P(RbdPolicy)] + [vp] * 6 + [ci]
     lib.idocp_rbd_rollout_policy_device.restype = ci
+    lib.idocp_rbd_objective_create.argtypes = [vp, P(Cost), P(Constraints), cd, cd, ci, P(vp)]
+    lib.idocp_rbd_objective_create.restype = ci
+    lib.idocp_rbd_objective_destroy.argtypes = [vp]
+    lib.idocp_rbd_objective_destroy.restype = None
+    lib.idocp_rbd_objective_get_reference.argtypes = [vp, ci, vp, vp]
+    lib.idocp_rbd_objective_get_reference.restype = ci
+    lib.idocp_rbd_objective_reference_device.argtypes = [vp, P(vp), P(vp)]
+    lib.idocp_rbd_objective_reference_device.restype = ci
+    lib.idocp_rbd_score_rollout.argtypes = [vp, vp, ci, ci, ci, c_int_p, ci, ci, P(RbdScoreIO)]
+    lib.idocp_rbd_score_rollout.restype = ci
+    lib.idocp_rbd_score_rollout_device.argtypes = [vp, vp, ci, ci, ci, c_int_p, ci, ci, P(RbdScoreIO)]
+    lib.idocp_rbd_score_rollout_device.restype = ci
     for name, args in [
         ("idocp_ocp_set_contact_status_uniformly", [vp, P(ci), c_double_p]),
         ("idocp_ocp_set_solution", [vp, cs, c_double_p]),

@@ -6,7 +6,18 @@
 #ifndef IDOCP_DEV_LIE_HPP_
 #define IDOCP_DEV_LIE_HPP_
 
+#ifdef IDOCP_NO_HIP_RUNTIME      // a plain C++17 translation unit (a CPU program under tests/cpp): the same closed forms without the HIP runtime header
+#include <cmath>
+#ifndef __host__
+#define __host__
+#define __device__
+#endif
+#ifndef __forceinline__
+#define __forceinline__ inline
+#endif
+#else
 #include <hip/hip_runtime.h>
+#endif
 
 namespace idocp_dev {
 

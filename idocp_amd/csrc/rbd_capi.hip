@@ -48,6 +48,14 @@ struct idocp_rbd {
   RbdBuffer u_buf;                    // closed-loop rollout without u_traj: the torques of the current step, [n][nu]
 };
 
+// the objective of the rollout scoring: the plan of rbd_objective.hpp and its three pieces in ONE block of device memory
+struct idocp_rbd_objective {
+  idocp_rbd* owner = nullptr;
+  idocp_host::RbdObjectivePlan plan;
+  double *d_q_ref = nullptr, *d_v_ref = nullptr;      // [steps + 1][nq], [steps + 1][nv]
+  idocp_host::RbdScoreBlock* d_block = nullptr;
+};
+
 namespace {
 
 constexpr size_t MODEL_BYTES = (sizeof(DevModel) + 15) / 16 * 16;
@@ -306,6 +314,24 @@ void policySlots(StagePlan& p, const idocp_rbd* h, const idocp_rbd_policy_t& pol
   p.in(pol.u_max, nu, &d->u_max);
 }
 
+// ---- the score of a rollout ----
+
+// everything that is refused, and the kernel's arguments but for the eight array pointers of io
+int checkScore(const char* who, const idocp_rbd* h, const idocp_rbd_objective* o, int n, int first_step, int steps, const int* active, int terminal,
+               int accumulate, const idocp_rbd_score_io_t* io, RbdScoreArgs* a) {
+  const std::string w(who);
+  if (!h || !o || !io) { set_last_error(w + ": null handle, objective or io"); return IDOCP_E_ARG; }
+  if (o->owner != h) { set_last_error(w + ": the objective was created on another handle"); return IDOCP_E_ARG; }
+  const idocp_host::RbdScoreCall c = idocp_host::planScoreCall(who, o->plan, n, first_step, steps, active, io->q_traj, io->v_traj, io->u_traj, io->a_traj, io->f_traj);
+  if (c.rc) { set_last_error(c.error); return c.rc; }
+  std::memcpy(a->masks, c.masks, sizeof(c.masks));
+  a->q_ref = o->d_q_ref + (size_t)first_step * o->plan.nq;
+  a->v_ref = o->d_v_ref + (size_t)first_step * o->plan.nv;
+  a->block = o->d_block;
+  a->steps = steps; a->terminal = terminal != 0; a->accumulate = accumulate != 0;
+  return IDOCP_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -507,6 +533,88 @@ int idocp_rbd_rollout_policy(idocp_rbd_t* h, int n, int steps, const int* active
   p.out(f_traj, S * N * nf, &d_f);
   rc = stageIn(h, p); if (rc) return rc;
   rc = rolloutDevice(h, n, steps, active, time_step, dt, nullptr, d_points, d_q, d_v, d_a, d_f, touchdown_impulse, &d_pol, d_u); if (rc) return rc;
+  return stageOut(h, p);
+}
+
+int idocp_rbd_objective_create(idocp_rbd_t* h, const idocp_cost_t* cost, const idocp_constraints_t* constraints, double t0, double dt, int steps,
+                               idocp_rbd_objective_t** out) {
+  if (!h || !out) { set_last_error("idocp_rbd_objective_create: null handle or out"); return IDOCP_E_ARG; }
+  *out = nullptr;
+  idocp_rbd_objective* o = new idocp_rbd_objective();
+  o->plan = idocp_host::planObjective(h->model, h->quadruped, cost, constraints, t0, dt, steps);
+  if (o->plan.rc) { const int rc = o->plan.rc; set_last_error(o->plan.error); delete o; return rc; }
+  o->owner = h;
+  const size_t nq_tab = (o->plan.q_ref.size() + 1) / 2 * 2, nv_tab = (o->plan.v_ref.size() + 1) / 2 * 2;      // (16-byte pieces)
+  auto fail = [&](const char* what) { set_last_error(what); (void)hipGetLastError(); idocp_rbd_objective_destroy(o); return IDOCP_E_DEVICE; };
+  if (hipSetDevice(h->device) != hipSuccess) return fail("idocp_rbd_objective_create: hipSetDevice failed");
+  if (hipMalloc(reinterpret_cast<void**>(&o->d_q_ref), sizeof(double) * (nq_tab + nv_tab) + sizeof(idocp_host::RbdScoreBlock)) != hipSuccess)
+    return fail("idocp_rbd_objective_create: hipMalloc of the objective failed");
+  o->d_v_ref = o->d_q_ref + nq_tab;
+  o->d_block = reinterpret_cast<idocp_host::RbdScoreBlock*>(o->d_v_ref + nv_tab);
+  if (hipMemcpyAsync(o->d_q_ref, o->plan.q_ref.data(), sizeof(double) * o->plan.q_ref.size(), hipMemcpyHostToDevice, h->stream) != hipSuccess ||
+      hipMemcpyAsync(o->d_v_ref, o->plan.v_ref.data(), sizeof(double) * o->plan.v_ref.size(), hipMemcpyHostToDevice, h->stream) != hipSuccess ||
+      hipMemcpyAsync(o->d_block, &o->plan.block, sizeof(idocp_host::RbdScoreBlock), hipMemcpyHostToDevice, h->stream) != hipSuccess ||
+      hipStreamSynchronize(h->stream) != hipSuccess) return fail("idocp_rbd_objective_create: upload of the objective failed");
+  *out = o;
+  return IDOCP_OK;
+}
+
+void idocp_rbd_objective_destroy(idocp_rbd_objective_t* o) {
+  if (!o) return;
+  if (o->d_q_ref) {
+    (void)hipSetDevice(o->owner->device);
+    (void)hipStreamSynchronize(o->owner->stream);
+    (void)hipFree(o->d_q_ref);
+  }
+  delete o;
+}
+
+int idocp_rbd_objective_get_reference(const idocp_rbd_objective_t* o, int k, double* q_ref, double* v_ref) {
+  if (!o) { set_last_error("idocp_rbd_objective_get_reference: null objective"); return IDOCP_E_ARG; }
+  if (k < 0 || k > o->plan.steps) { set_last_error("idocp_rbd_objective_get_reference: k must be 0 .. steps"); return IDOCP_E_ARG; }
+  if (q_ref) std::memcpy(q_ref, &o->plan.q_ref[(size_t)k * o->plan.nq], sizeof(double) * o->plan.nq);
+  if (v_ref) std::memcpy(v_ref, &o->plan.v_ref[(size_t)k * o->plan.nv], sizeof(double) * o->plan.nv);
+  return IDOCP_OK;
+}
+
+int idocp_rbd_objective_reference_device(const idocp_rbd_objective_t* o, const double** d_q_ref, const double** d_v_ref) {
+  if (!o) { set_last_error("idocp_rbd_objective_reference_device: null objective"); return IDOCP_E_ARG; }
+  if (d_q_ref) *d_q_ref = o->d_q_ref;
+  if (d_v_ref) *d_v_ref = o->d_v_ref;
+  return IDOCP_OK;
+}
+
+int idocp_rbd_score_rollout_device(idocp_rbd_t* h, const idocp_rbd_objective_t* o, int n, int first_step, int steps, const int* active, int terminal,
+                                   int accumulate, const idocp_rbd_score_io_t* io) {
+  RbdScoreArgs a;
+  int rc = checkScore("idocp_rbd_score_rollout_device", h, o, n, first_step, steps, active, terminal, accumulate, io, &a); if (rc) return rc;
+  HIP_TRY(hipSetDevice(h->device));
+  a.q = io->q_traj; a.v = io->v_traj; a.u = io->u_traj; a.a = io->a_traj; a.f = io->f_traj;
+  a.cost = io->cost; a.violation = io->violation; a.stage_cost = io->stage_cost;
+  rbdScore(h->model.nv, h->quadruped, a, n, h->stream);
+  HIP_TRY(hipGetLastError());
+  return IDOCP_OK;
+}
+
+int idocp_rbd_score_rollout(idocp_rbd_t* h, const idocp_rbd_objective_t* o, int n, int first_step, int steps, const int* active, int terminal,
+                            int accumulate, const idocp_rbd_score_io_t* io) {
+  RbdScoreArgs a;
+  int rc = checkScore("idocp_rbd_score_rollout", h, o, n, first_step, steps, active, terminal, accumulate, io, &a); if (rc) return rc;
+  HIP_TRY(hipSetDevice(h->device));
+  const size_t nq = h->model.nq, nv = h->model.nv, nu = h->model.nu, nf = 3 * (size_t)o->plan.ncontacts, N = (size_t)n, S = (size_t)steps;
+  const size_t slices = S + (terminal ? 1 : 0);
+  StagePlan p;
+  p.in(io->q_traj, slices * N * nq, &a.q);
+  p.in(io->v_traj, slices * N * nv, &a.v);
+  p.in(io->u_traj, S * N * nu, &a.u);
+  p.in(io->a_traj, S * N * nv, &a.a);
+  p.in(io->f_traj, S * N * nf, &a.f);
+  if (accumulate) { p.update(io->cost, N, &a.cost); p.update(io->violation, N, &a.violation); }
+  else { p.out(io->cost, N, &a.cost); p.out(io->violation, N, &a.violation); }
+  p.out(io->stage_cost, slices * N, &a.stage_cost);
+  rc = stageIn(h, p); if (rc) return rc;
+  rbdScore(h->model.nv, h->quadruped, a, n, h->stream);
+  HIP_TRY(hipGetLastError());
   return stageOut(h, p);
 }
 

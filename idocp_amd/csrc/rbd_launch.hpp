@@ -6,6 +6,7 @@
 
 #include "dev_rbd.hpp"
 #include "idocp_hip.h"
+#include "rbd_objective.hpp"
 
 namespace idocp_dev {
 
@@ -37,6 +38,19 @@ struct RbdPolicyArgs {
   double* u;
 };
 void rbdPolicy(int nv, bool quadruped, const RbdPolicyArgs& a, int n, hipStream_t st);
+
+// The score of a rollout (rbd_score_kernel.hip).  Every pointer: DEVICE memory, step-major slices of the window: q, v [steps (+ 1 if terminal)][n][..],
+// u, a, f [steps][n][..] (any of the three may be NULL: its terms are left out), q_ref / v_ref the objective's tables AT the window's first step,
+// block the objective's weights and bounds.  masks: 4 bits per step of the window, bit c = contact c is active.  cost, violation [n] and
+// stage_cost [steps (+ 1)][n] may be NULL.
+struct RbdScoreArgs {
+  const double *q, *v, *u, *a, *f, *q_ref, *v_ref;
+  const idocp_host::RbdScoreBlock* block;
+  double *cost, *violation, *stage_cost;
+  int steps, terminal, accumulate;
+  unsigned masks[idocp_host::RBD_SCORE_MASK_WORDS];
+};
+void rbdScore(int nv, bool quadruped, const RbdScoreArgs& a, int n, hipStream_t st);
 
 }  // namespace idocp_dev
 #endif  // IDOCP_RBD_LAUNCH_HPP_

@@ -242,6 +242,50 @@ class Robot {
     ok(idocp_rbd_feedback_torques_batch(rbd_.h, 1, q.data(), v.data(), &pol, out.data()));
     u = out;
   }
+  // The solvers' cost and a constraint violation of ONE trajectory, an ADDITION the reference does not have (it evaluates these sums for the
+  // solver's own iterate only): q, v of the steps + 1 states, a, u, f of the steps stages (f[k][i] in the local coordinates of contact frame i;
+  // only the active ones of contact_status[k] are read; f and contact_status stay empty on a fixed-base robot), against a CostFunction /
+  // Constraints pair -- through their native() blocks, the conversion the solver facades use -- on the grid t0 + k dt.  The last state is scored
+  // with the terminal weights.  ONE n = 1 call of idocp_rbd_score_rollout on the same lazily created handle (idocp_hip.h defines both sums; the
+  // batched call scores many trajectories, windows of them and device arrays).
+  template <class CostFunctionT, class ConstraintsT>
+  void scoreTrajectory(const CostFunctionT& cost, const ConstraintsT& constraints, const double t0, const double dt,
+                       const std::vector<Eigen::VectorXd>& q, const std::vector<Eigen::VectorXd>& v, const std::vector<Eigen::VectorXd>& a,
+                       const std::vector<Eigen::VectorXd>& u, const std::vector<std::vector<Eigen::Vector3d>>& f,
+                       const std::vector<ContactStatus>& contact_status, double& total_cost, double& violation) {
+    const int steps = (int)u.size(), nc = model_.ncontacts;
+    if (steps < 1 || (int)q.size() != steps + 1 || (int)v.size() != steps + 1 || (int)a.size() != steps ||
+        (nc > 0 && ((int)f.size() != steps || (int)contact_status.size() != steps))) {
+      std::cerr << "invalid size: a trajectory of N stages has N + 1 states q, v and N of a, u, f and contact_status!" << '\n'; std::exit(EXIT_FAILURE);
+    }
+    const size_t nq = model_.nq, nv = model_.nv, nu = model_.nu;
+    std::vector<double> qs((steps + 1) * nq), vs((steps + 1) * nv), as(steps * nv), us(steps * nu), fs((size_t)steps * 3 * nc, 0.0);
+    std::vector<int> act((size_t)steps * nc, 0);
+    for (int k = 0; k <= steps; ++k) {
+      sized(q[k], model_.nq, "q"); sized(v[k], model_.nv, "v");
+      for (size_t j = 0; j < nq; ++j) qs[k * nq + j] = q[k][j];
+      for (size_t j = 0; j < nv; ++j) vs[k * nv + j] = v[k][j];
+      if (k == steps) break;
+      sized(a[k], model_.nv, "a"); sized(u[k], model_.nu, "u");
+      for (size_t j = 0; j < nv; ++j) as[k * nv + j] = a[k][j];
+      for (size_t j = 0; j < nu; ++j) us[k * nu + j] = u[k][j];
+      for (int c = 0; c < nc; ++c) {
+        act[(size_t)k * nc + c] = contact_status[k].isContactActive(c) ? 1 : 0;
+        if (act[(size_t)k * nc + c]) for (int x = 0; x < 3; ++x) fs[((size_t)k * nc + c) * 3 + x] = f[k][c][x];
+      }
+    }
+    const idocp_cost_t c = cost.native();
+    const idocp_constraints_t g = constraints.native();
+    if (!rbd_.h) ok(idocp_rbd_create(&model_, 0, &rbd_.h));
+    idocp_rbd_objective_t* objective = nullptr;
+    ok(idocp_rbd_objective_create(rbd_.h, &c, &g, t0, dt, steps, &objective));
+    idocp_rbd_score_io_t io = idocp_rbd_score_io_t();
+    io.q_traj = qs.data(); io.v_traj = vs.data(); io.a_traj = as.data(); io.u_traj = us.data(); io.f_traj = nc > 0 ? fs.data() : nullptr;
+    io.cost = &total_cost; io.violation = &violation;
+    const int rc = idocp_rbd_score_rollout(rbd_.h, objective, 1, 0, steps, nc > 0 ? act.data() : nullptr, 1, 0, &io);
+    idocp_rbd_objective_destroy(objective);
+    ok(rc);
+  }
   // Robot::framePosition / frameRotation / framePlacement (robot.hxx:206-233): of any frame of the URDF (pinocchio's frame numbering, as the
   // contact frames and the task-space costs use it), at the configuration of the last updateFrameKinematics / updateKinematics
   Eigen::Vector3d framePosition(const int frame_id) const { return framePlacement(frame_id).translation(); }

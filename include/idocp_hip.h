@@ -880,6 +880,65 @@ int idocp_rbd_rollout_policy_device(idocp_rbd_t* h, int n, int steps, const int*
                                     const idocp_rbd_policy_t* policy, const double* contact_points, double* q_traj, double* v_traj, double* u_traj,
                                     double* a_traj, double* f_traj, int touchdown_impulse);
 
+/* ---- Scoring a rollout: the solvers' cost and a constraint violation per sample, on the GPU (rbd_score_kernel.hip).
+ * The objective holds what scoring needs: the weights of an idocp_cost_t, the switches and bounds of an idocp_constraints_t (the joint limits
+ * themselves are the model's q_min, q_max, v_max, u_max) and the configuration-space reference of every step t_k = t0 + k dt, k = 0 .. steps,
+ * by the rules the solvers use (constant, use_trotting_ref, use_time_varying_ref; a chain takes the constant one).  The stored velocity
+ * reference of a step is the one the cost compares with: v_ref (v_ref[0] = step_length / t_period under use_trotting_ref), zero outside the
+ * window of use_time_varying_ref.
+ * The cost mirrors what idocp_ocp_line_search_eval sums for a grid stage and the terminal stage of an iterate (SplitOCP::stageCost,
+ * TerminalOCP::terminalCost), the barrier term left out; with e = q (-) q_ref(t_k), the tangent of idocp_model_subtract_configuration(q_plus = q,
+ * q_minus = q_ref):
+ *   stage_cost[k][i] = dt 1/2 (sum_r q_weight[r] e[r]^2 + v_weight[r] (v[r] - v_ref_k[r])^2 + a_weight[r] a[r]^2 + sum_j u_weight[j] (u[j] - u_ref[j])^2
+ *                             + sum_{c active at step k} sum_x f_weight[c][x] (f[c][x] - f_ref[c][x])^2)
+ *   terminal[i]      = 1/2 sum_r qf_weight[r] e[r]^2 + vf_weight[r] (v[r] - v_ref[r])^2      on the slice behind the last step
+ *   cost[i]          = sum_k stage_cost[k][i] (+ terminal[i])
+ * The violation is an ADDITION (the reference's |g + slack|_1 belongs to an interior-point iterate; a rollout has no slacks):
+ *   violation[i] = sum_k dt sum_rows max(0, g_row)
+ * over the rows switched on: per actuated joint q_min - q, q - q_max, -v_max - v, v - v_max, -u_max - u, u - u_max, a_min - a, a - a_max; per
+ * contact active at step k the five rows of LinearizedFrictionCone (Jc f, Jc = {{0,0,-1},{1,0,-m},{-1,0,-m},{0,1,-m},{0,-1,-m}}, m = mu / sqrt 2)
+ * or the two of FrictionCone (-fz, fx^2 + fy^2 - mu^2 fz^2).  The terminal slice has no constraints.
+ * Not carried, refused by create with IDOCP_E_UNSUPPORTED: task-space cost components (task_dim != 0), contact_distance, both cones together,
+ * and the trotting / time-varying reference on a chain.  The impulse-stage weights (qi_, vi_, dvi_, fi_weight) and the impulse cones are
+ * ignored: a rollout does not return its touchdown impulses, so there is nothing to score them on.  barrier and fraction_to_boundary_rate are
+ * not read. */
+#define IDOCP_RBD_SCORE_MAX_WINDOW 1024      /* most steps of one scoring call */
+typedef struct idocp_rbd_objective idocp_rbd_objective_t;
+/* ADDITION.  constraints NULL: no rows.  dt positive, steps >= 1.  Uploads once, on the handle's stream, and returns when the upload is done;
+ * nothing is allocated afterwards.  The objective belongs to the handle h and is destroyed before it. */
+int idocp_rbd_objective_create(idocp_rbd_t* h, const idocp_cost_t* cost, const idocp_constraints_t* constraints, double t0, double dt, int steps,
+                               idocp_rbd_objective_t** out);
+void idocp_rbd_objective_destroy(idocp_rbd_objective_t* o);
+/* The reference of step k = 0 .. steps, host copy: q_ref [nq], v_ref [nv] (either may be NULL).  Mirrors the q_ref(t) the cost components
+ * of the solvers form per stage (TrottingConfigurationSpaceCost::update_q_ref, TimeVaryingConfigurationSpaceCost::set_q_ref). */
+int idocp_rbd_objective_get_reference(const idocp_rbd_objective_t* o, int k, double* q_ref, double* v_ref);
+/* ADDITION.  The device tables [steps + 1][nq] and [steps + 1][nv], bit for bit what get_reference returns: directly usable as q_ref / v_ref of
+ * an idocp_rbd_policy_t with shared_ref = 1 in the device form of the policy rollout.  They live as long as the objective. */
+int idocp_rbd_objective_reference_device(const idocp_rbd_objective_t* o, const double** d_q_ref, const double** d_v_ref);
+
+/* The step-major layout of idocp_rbd_rollout, so that its outputs can be passed straight in. */
+typedef struct idocp_rbd_score_io {
+  const double *q_traj, *v_traj;          /* [steps + 1][n][nq | nv] when terminal, else [steps][n][..]: the window's own slices */
+  const double *u_traj, *a_traj, *f_traj; /* [steps][n][nu | nv | ncontacts * 3]; NULL is allowed only where no enabled weight or row reads the array
+                                           * (else IDOCP_E_ARG naming it).  The f of a contact that is not active at a step is not read */
+  double *cost, *violation;               /* [n]; either may be NULL */
+  double *stage_cost;                     /* [steps (+ 1 when terminal)][n], the last slice the terminal cost; NULL = not stored */
+} idocp_rbd_score_io_t;
+/* ADDITION.  Scores the window of `steps` steps whose slice 0 is step first_step of the objective (first_step + steps <= the objective's steps; at
+ * most IDOCP_RBD_SCORE_MAX_WINDOW steps per call).  active [steps][ncontacts]: the contact status per step, shared by the n samples (NULL on a
+ * chain).  terminal != 0: the slice behind the last step of the window is scored with the terminal weights against the reference of step
+ * first_step + steps.  accumulate != 0: adds to what cost / violation hold, so that a caller who keeps only a ring of slices scores window by
+ * window.  One launch.  The sums are folded in a fixed order -- the rows of a step by a fixed tree, the steps in index order, the terminal
+ * term last -- so a sample's results are bit for bit the same whatever n is, and whether it was scored at once or window by window.
+ * A non-finite entry anywhere in the slices read of a sample (q, v, and u, a, f where given; an inactive contact's f is not read) makes both
+ * of that sample's results NaN and touches no other sample; its stage_cost is unspecified.
+ * Host pointers; returns when the results are in place. */
+int idocp_rbd_score_rollout(idocp_rbd_t* h, const idocp_rbd_objective_t* o, int n, int first_step, int steps, const int* active, int terminal,
+                            int accumulate, const idocp_rbd_score_io_t* io);
+/* Device pointers, asynchronous on idocp_rbd_stream(h); allocates nothing. */
+int idocp_rbd_score_rollout_device(idocp_rbd_t* h, const idocp_rbd_objective_t* o, int n, int first_step, int steps, const int* active, int terminal,
+                                   int accumulate, const idocp_rbd_score_io_t* io);
+
 const char* idocp_last_error(void);
 const char* idocp_version(void);
 

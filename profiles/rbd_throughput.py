@@ -5,7 +5,10 @@ samples per second of each output selection.  The fd_* rows are the forward dyna
 without and with the Euler step; stage_da_mjtjinv is what a caller needed for the same answer before that call existed.  The policy_* rows are the
 feedback policy alone (idocp_rbd_feedback_torques_batch_device) with one gain block and reference shared by all samples and with one per sample;
 fd_step_closed_loop is one step of idocp_rbd_rollout_policy_device (policy launch + forward launch with the Euler step, per-sample gains), to be
-read against fd_stage_a_f_step.
+read against fd_stage_a_f_step.  The score_* rows are idocp_rbd_score_rollout_device on a window of 1 and of 16 steps (terminal slice included): every
+weight, the joint limits and the linearized cone (score_sK_all_linearized) or the FrictionCone (score_sK_all_cone), and the cost alone
+(score_sK_cost_only); score_sK_copy is a device-to-device copy of exactly the bytes the call reads, timed in the same run, and each score row carries
+its ratio to that copy.
 
     python profiles/rbd_throughput.py [--n 122880] [--launches 20] [--warmup 5] [--rows name,name,...]
 """
@@ -33,6 +36,75 @@ FD_SELECTIONS = (("fd_stage_a_f", capi.RBD_STAGE, ("a", "f")),
                  ("fd_impulse_dv_lambda_step", capi.RBD_IMPULSE, ("a", "f", "q_next", "v_next")))
 
 POLICY_ROWS = ("policy_shared", "policy_per_sample", "fd_step_closed_loop")
+SCORE_STEPS = (1, 16)
+SCORE_KINDS = ("copy", "all_linearized", "all_cone", "cost_only")
+SCORE_ROWS = tuple("score_s%d_%s" % (s, k) for s in SCORE_STEPS for k in SCORE_KINDS)
+
+
+def score_rows(args, wanted, lib, rt, h, stream, m, n, host, measure, res):
+    """the score_* rows: the slices of one step repeated over the window (what is read is what matters, not what it holds)"""
+    from idocp_amd.workloads import anymal_problem
+    rt.hipMemcpyAsync.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p]
+    nv, nq, nu, nf = m.nv, m.nq, m.nu, 3 * m.ncontacts
+    cost, cons = anymal_problem(m, trotting_ref=False)
+    cost.set("u_weight", np.full(nu, 0.01))
+    objectives = {}
+    for kind in SCORE_KINDS[1:]:
+        k = capi.Constraints.from_buffer_copy(cons)
+        k.linearized_friction_cone, k.friction_cone = int(kind == "all_linearized"), int(kind == "all_cone")
+        if kind != "cost_only":
+            k.joint_position_limits = k.joint_velocity_limits = k.joint_torque_limits = 1
+        objectives[kind] = C.c_void_p()
+        capi.check(lib.idocp_rbd_objective_create(h, C.byref(cost), C.byref(k) if kind != "cost_only" else None, 0.0, 0.01, max(SCORE_STEPS), C.byref(objectives[kind])),
+                   "idocp_rbd_objective_create")
+    for steps in SCORE_STEPS:
+        names = ["score_s%d_%s" % (steps, kind) for kind in SCORE_KINDS]
+        if wanted and not set(names) & set(wanted):
+            continue
+        arrays = {"q_traj": (host["q"], steps + 1), "v_traj": (host["v"], steps + 1), "u_traj": (host["u"], steps), "a_traj": (host["a"], steps), "f_traj": (host["f"], steps)}
+        dev, nbytes = {}, 0
+        for key, (x, slices) in arrays.items():
+            x = np.ascontiguousarray(x)
+            dev[key] = C.c_void_p()
+            capi.check(lib.idocp_device_alloc(C.byref(dev[key]), x.nbytes * slices), "alloc")
+            for s in range(slices):
+                capi.check(lib.idocp_device_upload(C.c_void_p(dev[key].value + s * x.nbytes), x.ctypes.data, x.nbytes), "upload")
+            nbytes += x.nbytes * slices
+        for key, size in (("cost", 8 * n), ("violation", 8 * n), ("copy", nbytes)):
+            dev[key] = C.c_void_p()
+            capi.check(lib.idocp_device_alloc(C.byref(dev[key]), size), "alloc")
+        active = (C.c_int * (4 * steps))(*([1] * (4 * steps)))
+        io = capi.RbdScoreIO()
+        for key in capi.RbdScoreIO.INPUTS + ("cost", "violation"):
+            setattr(io, key, dev[key])
+
+        def copy():
+            at = 0
+            for key, (x, slices) in arrays.items():      # the very bytes the call reads, array by array
+                size = np.ascontiguousarray(x).nbytes * slices
+                assert rt.hipMemcpyAsync(C.c_void_p(dev["copy"].value + at), dev[key], size, 3, stream) == 0
+                at += size
+
+        for name, kind in zip(names, SCORE_KINDS):
+            if wanted and name not in wanted:
+                continue
+            if kind == "copy":
+                measure(name, copy)
+            else:
+                measure(name, lambda: capi.check(lib.idocp_rbd_score_rollout_device(h, objectives[kind], n, 0, steps, active, 1, 0, C.byref(io)), name))
+            res[name]["input_bytes"] = nbytes
+            res[name]["GB_per_s"] = round(nbytes / res[name]["ms_median"] / 1e6, 1)
+        for name in names[1:]:
+            if name in res and names[0] in res:
+                res[name]["ratio_to_copy"] = round(res[name]["ms_median"] / res[names[0]]["ms_median"], 3)
+        out = np.zeros((2, n))
+        capi.check(lib.idocp_device_download(out[0].ctypes.data, dev["cost"], 8 * n), "download")
+        capi.check(lib.idocp_device_download(out[1].ctypes.data, dev["violation"], 8 * n), "download")
+        res["score_s%d_finite" % steps] = bool(np.isfinite(out).all())
+        for d in dev.values():
+            lib.idocp_device_free(d)
+    for o in objectives.values():
+        lib.idocp_rbd_objective_destroy(o)
 
 
 def main():
@@ -90,6 +162,24 @@ def main():
         assert rt.hipEventCreate(C.byref(e)) == 0
         events.append(e)
     res = {"n": n, "launches": args.launches, "warmup": args.warmup}
+
+    def measure(name, launch):
+        for _ in range(args.warmup):
+            launch()
+        capi.check(lib.idocp_rbd_synchronize(h), "synchronize")
+        assert rt.hipEventRecord(events[0], stream) == 0
+        for i in range(args.launches):
+            launch()
+            assert rt.hipEventRecord(events[i + 1], stream) == 0
+        assert rt.hipEventSynchronize(events[-1]) == 0
+        ms = []
+        for i in range(args.launches):
+            t = C.c_float()
+            assert rt.hipEventElapsedTime(C.byref(t), events[i], events[i + 1]) == 0
+            ms.append(t.value)
+        med = float(np.median(ms))
+        res[name] = {"ms_median": round(med, 4), "ms_min": round(min(ms), 4), "ms_max": round(max(ms), 4), "samples_per_s": round(n / med * 1e3)}
+
     for name, mode, outputs in SELECTIONS + FD_SELECTIONS + tuple((x, None, ()) for x in POLICY_ROWS):
         if wanted and name not in wanted:
             continue
@@ -114,21 +204,9 @@ def main():
             for k in capi.RbdIO.INPUTS + tuple(outputs):
                 setattr(io, k, dev[k])
             launch = lambda: capi.check(lib.idocp_rbd_contact_dynamics_batch_device(h, mode, n, active, 0.05, C.byref(io)), name)  # noqa: E731
-        for _ in range(args.warmup):
-            launch()
-        capi.check(lib.idocp_rbd_synchronize(h), "synchronize")
-        assert rt.hipEventRecord(events[0], stream) == 0
-        for i in range(args.launches):
-            launch()
-            assert rt.hipEventRecord(events[i + 1], stream) == 0
-        assert rt.hipEventSynchronize(events[-1]) == 0
-        ms = []
-        for i in range(args.launches):
-            t = C.c_float()
-            assert rt.hipEventElapsedTime(C.byref(t), events[i], events[i + 1]) == 0
-            ms.append(t.value)
-        med = float(np.median(ms))
-        res[name] = {"ms_median": round(med, 4), "ms_min": round(min(ms), 4), "ms_max": round(max(ms), 4), "samples_per_s": round(n / med * 1e3)}
+        measure(name, launch)
+    if not wanted or set(wanted) & set(SCORE_ROWS):
+        score_rows(args, wanted, lib, rt, h, stream, m, n, host, measure, res)
     ran = [k for k in res if isinstance(res[k], dict)]
     for key, src, width, rows in (("tau_finite", "tau", nv, ("stage_", "impulse_")), ("fd_a_finite", "fd_a", nv, ("fd_",)),
                                   ("policy_u_finite", "u_out", m.nu, ("policy_", "fd_step_closed_loop"))):
