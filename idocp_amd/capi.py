@@ -128,6 +128,9 @@ class RbdScoreIO(C.Structure):
 
 RBD_STAGE, RBD_IMPULSE = 0, 1
 RBD_SCORE_MAX_WINDOW = 1024
+RBD_REDUCE_CHUNK = 1024      # IDOCP_RBD_REDUCE_CHUNK: samples per chunk of the fixed-order sums
+RBD_WEIGHT_STATS = 5         # {|F|, s_min, argmin, W, effective sample size}
+RBD_MEAN_MAX_COLUMNS = 64
 
 
 class LibraryMissing(RuntimeError):
@@ -333,6 +336,13 @@ def _proto(lib):
     lib.idocp_rbd_score_rollout.restype = ci
     lib.idocp_rbd_score_rollout_device.argtypes = [vp, vp, ci, ci, ci, c_int_p, ci, ci, P(RbdScoreIO)]
     lib.idocp_rbd_score_rollout_device.restype = ci
+    for form in ("", "_device"):
+        for name, args in (("idocp_rbd_perturb_torques", [vp, ci, ci, ci, vp, vp, vp, vp, C.c_ulonglong, C.c_uint, vp]),
+                           ("idocp_rbd_importance_weights", [vp, ci, vp, vp, cd, cd, vp, vp]),
+                           ("idocp_rbd_weighted_mean", [vp, ci, ci, ci, vp, vp, vp])):
+            f = getattr(lib, name + form)
+            f.argtypes = args
+            f.restype = ci
     for name, args in [
         ("idocp_ocp_set_contact_status_uniformly", [vp, P(ci), c_double_p]),
         ("idocp_ocp_set_solution", [vp, cs, c_double_p]),

@@ -5,6 +5,7 @@
 // There is NO CPU fallback: without a GPU idocp_rbd_create returns IDOCP_E_DEVICE.
 #include <hip/hip_runtime.h>
 
+#include <climits>
 #include <cmath>
 #include <cstring>
 #include <string>
@@ -46,6 +47,7 @@ struct idocp_rbd {
   RbdBuffer unwanted;                 // chain: where the sweep writes the outputs the caller did not ask for
   RbdBuffer fd_chain;                 // chain, forward dynamics: [a = 0 | h | dtau_dq | dtau_dv | M] of the sweep at a = 0
   RbdBuffer u_buf;                    // closed-loop rollout without u_traj: the torques of the current step, [n][nu]
+  RbdBuffer reduce;                   // sampling: the chunk partials of the sums over the sample axis, RBD_PARTIAL_STRIDE per (row, chunk)
 };
 
 // the objective of the rollout scoring: the plan of rbd_objective.hpp and its three pieces in ONE block of device memory
@@ -332,6 +334,91 @@ int checkScore(const char* who, const idocp_rbd* h, const idocp_rbd_objective* o
   return IDOCP_OK;
 }
 
+// ---- sampling around a torque sequence ----
+
+int checkPerturb(const char* who, const idocp_rbd* h, int n, int first_step, int steps, const double* u_nominal, const double* sigma, const double* u_min,
+                 const double* u_max, const double* u_samples, bool host) {
+  const std::string w(who);
+  if (!h) { set_last_error(w + ": null handle"); return IDOCP_E_ARG; }
+  if (n <= 0) { set_last_error(w + ": n must be positive"); return IDOCP_E_ARG; }
+  if (steps < 1) { set_last_error(w + ": steps must be at least 1"); return IDOCP_E_ARG; }
+  if (first_step < 0 || first_step > INT_MAX - steps) { set_last_error(w + ": first_step must be non-negative, and first_step + steps must fit an int"); return IDOCP_E_ARG; }
+  if (!u_nominal || !sigma || !u_samples) { set_last_error(w + ": u_nominal, sigma and u_samples are needed"); return IDOCP_E_ARG; }
+  if (!host) return IDOCP_OK;
+  for (int j = 0; j < h->model.nu; ++j)
+    if (!std::isfinite(sigma[j]) || sigma[j] < 0.0) {
+      set_last_error(w + ": sigma[" + std::to_string(j) + "] must be finite and non-negative"); return IDOCP_E_ARG;
+    }
+  idocp_rbd_policy_t bounds = idocp_rbd_policy_t();
+  bounds.u_min = u_min; bounds.u_max = u_max;
+  return checkPolicy(who, h, &bounds, true);
+}
+
+int launchPerturb(idocp_rbd* h, int n, int first_step, int steps, const double* u_nominal, const double* sigma, const double* u_min, const double* u_max,
+                  unsigned long long seed, unsigned draw, double* u_samples) {
+  RbdPerturbArgs a;
+  a.u_nominal = u_nominal; a.sigma = sigma; a.u_min = u_min; a.u_max = u_max; a.u_samples = u_samples;
+  a.seed = seed; a.draw = draw; a.n = n; a.nu = h->model.nu; a.first_step = first_step; a.steps = steps;
+  rbdPerturb(a, h->stream);
+  HIP_TRY(hipGetLastError());
+  return IDOCP_OK;
+}
+
+int chunksOf(int n) { return (int)(((long long)n + IDOCP_RBD_REDUCE_CHUNK - 1) / IDOCP_RBD_REDUCE_CHUNK); }
+
+// room for the chunk partials of `rows` rows: grows only when rows * ceil(n / chunk) does
+int growReduce(idocp_rbd* h, int rows, int n) { return h->reduce.grow((size_t)rows * chunksOf(n) * RBD_PARTIAL_STRIDE, h->stream); }
+
+int checkWeights(const char* who, const idocp_rbd* h, int n, const double* cost, double penalty, double temperature, const double* weights,
+                 const double* stats) {
+  const std::string w(who);
+  if (!h) { set_last_error(w + ": null handle"); return IDOCP_E_ARG; }
+  if (n <= 0) { set_last_error(w + ": n must be positive"); return IDOCP_E_ARG; }
+  if (!cost || !weights || !stats) { set_last_error(w + ": cost, weights and stats are needed"); return IDOCP_E_ARG; }
+  if (!std::isfinite(temperature) || !(temperature > 0.0)) { set_last_error(w + ": temperature must be finite and positive"); return IDOCP_E_ARG; }
+  if (!std::isfinite(penalty) || penalty < 0.0) { set_last_error(w + ": penalty must be finite and non-negative"); return IDOCP_E_ARG; }
+  return IDOCP_OK;
+}
+
+int launchWeights(idocp_rbd* h, int n, const double* cost, const double* violation, double penalty, double temperature, double* weights, double* stats) {
+  int rc = growReduce(h, 1, n); if (rc) return rc;
+  RbdWeightArgs a;
+  a.cost = cost; a.violation = violation; a.penalty = penalty; a.temperature = temperature;
+  a.weights = weights; a.stats = stats; a.scratch = h->reduce.ptr; a.n = n; a.nchunks = chunksOf(n);
+  rbdWeights(a, h->stream);
+  HIP_TRY(hipGetLastError());
+  return IDOCP_OK;
+}
+
+int checkMean(const char* who, const idocp_rbd* h, int n, int rows, int m, const double* weights, const double* x, const double* mean, bool host) {
+  const std::string w(who);
+  if (!h) { set_last_error(w + ": null handle"); return IDOCP_E_ARG; }
+  if (n <= 0) { set_last_error(w + ": n must be positive"); return IDOCP_E_ARG; }
+  if (rows < 1) { set_last_error(w + ": rows must be at least 1"); return IDOCP_E_ARG; }
+  if (m < 1 || m > IDOCP_RBD_MEAN_MAX_COLUMNS) {
+    set_last_error(w + ": m must be 1 .. " + std::to_string(IDOCP_RBD_MEAN_MAX_COLUMNS) + " (IDOCP_RBD_MEAN_MAX_COLUMNS)"); return IDOCP_E_ARG;
+  }
+  if (!weights || !x || !mean) { set_last_error(w + ": weights, x and mean are needed"); return IDOCP_E_ARG; }
+  if ((long long)rows * chunksOf(n) > INT_MAX || (long long)rows * m > INT_MAX) {
+    set_last_error(w + ": rows * ceil(n / IDOCP_RBD_REDUCE_CHUNK) and rows * m must fit an int (one workgroup per row and chunk)"); return IDOCP_E_UNSUPPORTED;
+  }
+  if (host)
+    for (int i = 0; i < n; ++i)
+      if (!std::isfinite(weights[i]) || weights[i] < 0.0) {
+        set_last_error(w + ": weights[" + std::to_string(i) + "] must be finite and non-negative"); return IDOCP_E_ARG;
+      }
+  return IDOCP_OK;
+}
+
+int launchMean(idocp_rbd* h, int n, int rows, int m, const double* weights, const double* x, double* mean) {
+  int rc = growReduce(h, rows, n); if (rc) return rc;
+  RbdMeanArgs a;
+  a.weights = weights; a.x = x; a.mean = mean; a.scratch = h->reduce.ptr; a.n = n; a.rows = rows; a.m = m; a.nchunks = chunksOf(n);
+  rbdMean(a, h->stream);
+  HIP_TRY(hipGetLastError());
+  return IDOCP_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -380,6 +467,7 @@ void idocp_rbd_destroy(idocp_rbd_t* h) {
   h->unwanted.release();
   h->fd_chain.release();
   h->u_buf.release();
+  h->reduce.release();
   if (h->stream) (void)hipStreamDestroy(h->stream);
   delete h;
 }
@@ -615,6 +703,74 @@ int idocp_rbd_score_rollout(idocp_rbd_t* h, const idocp_rbd_objective_t* o, int 
   rc = stageIn(h, p); if (rc) return rc;
   rbdScore(h->model.nv, h->quadruped, a, n, h->stream);
   HIP_TRY(hipGetLastError());
+  return stageOut(h, p);
+}
+
+int idocp_rbd_perturb_torques_device(idocp_rbd_t* h, int n, int first_step, int steps, const double* u_nominal, const double* sigma, const double* u_min,
+                                     const double* u_max, unsigned long long seed, unsigned draw, double* u_samples) {
+  int rc = checkPerturb("idocp_rbd_perturb_torques_device", h, n, first_step, steps, u_nominal, sigma, u_min, u_max, u_samples, false); if (rc) return rc;
+  HIP_TRY(hipSetDevice(h->device));
+  return launchPerturb(h, n, first_step, steps, u_nominal, sigma, u_min, u_max, seed, draw, u_samples);
+}
+
+int idocp_rbd_perturb_torques(idocp_rbd_t* h, int n, int first_step, int steps, const double* u_nominal, const double* sigma, const double* u_min,
+                              const double* u_max, unsigned long long seed, unsigned draw, double* u_samples) {
+  int rc = checkPerturb("idocp_rbd_perturb_torques", h, n, first_step, steps, u_nominal, sigma, u_min, u_max, u_samples, true); if (rc) return rc;
+  HIP_TRY(hipSetDevice(h->device));
+  const size_t nu = h->model.nu, N = (size_t)n, S = (size_t)steps;
+  StagePlan p;
+  const double *d_nominal, *d_sigma, *d_min, *d_max;
+  double* d_samples;
+  p.in(u_nominal, S * nu, &d_nominal);
+  p.in(sigma, nu, &d_sigma);
+  p.in(u_min, nu, &d_min);
+  p.in(u_max, nu, &d_max);
+  p.out(u_samples, S * N * nu, &d_samples);
+  rc = stageIn(h, p); if (rc) return rc;
+  rc = launchPerturb(h, n, first_step, steps, d_nominal, d_sigma, d_min, d_max, seed, draw, d_samples); if (rc) return rc;
+  return stageOut(h, p);
+}
+
+int idocp_rbd_importance_weights_device(idocp_rbd_t* h, int n, const double* cost, const double* violation, double penalty, double temperature,
+                                        double* weights, double* stats) {
+  int rc = checkWeights("idocp_rbd_importance_weights_device", h, n, cost, penalty, temperature, weights, stats); if (rc) return rc;
+  HIP_TRY(hipSetDevice(h->device));
+  return launchWeights(h, n, cost, violation, penalty, temperature, weights, stats);
+}
+
+int idocp_rbd_importance_weights(idocp_rbd_t* h, int n, const double* cost, const double* violation, double penalty, double temperature,
+                                 double* weights, double* stats) {
+  int rc = checkWeights("idocp_rbd_importance_weights", h, n, cost, penalty, temperature, weights, stats); if (rc) return rc;
+  HIP_TRY(hipSetDevice(h->device));
+  StagePlan p;
+  const double *d_cost, *d_violation;
+  double *d_weights, *d_stats;
+  p.in(cost, (size_t)n, &d_cost);
+  p.in(violation, (size_t)n, &d_violation);
+  p.out(weights, (size_t)n, &d_weights);
+  p.out(stats, IDOCP_RBD_WEIGHT_STATS, &d_stats);
+  rc = stageIn(h, p); if (rc) return rc;
+  rc = launchWeights(h, n, d_cost, d_violation, penalty, temperature, d_weights, d_stats); if (rc) return rc;
+  return stageOut(h, p);
+}
+
+int idocp_rbd_weighted_mean_device(idocp_rbd_t* h, int n, int rows, int m, const double* weights, const double* x, double* mean) {
+  int rc = checkMean("idocp_rbd_weighted_mean_device", h, n, rows, m, weights, x, mean, false); if (rc) return rc;
+  HIP_TRY(hipSetDevice(h->device));
+  return launchMean(h, n, rows, m, weights, x, mean);
+}
+
+int idocp_rbd_weighted_mean(idocp_rbd_t* h, int n, int rows, int m, const double* weights, const double* x, double* mean) {
+  int rc = checkMean("idocp_rbd_weighted_mean", h, n, rows, m, weights, x, mean, true); if (rc) return rc;
+  HIP_TRY(hipSetDevice(h->device));
+  StagePlan p;
+  const double *d_weights, *d_x;
+  double* d_mean;
+  p.in(weights, (size_t)n, &d_weights);
+  p.in(x, (size_t)rows * n * m, &d_x);
+  p.out(mean, (size_t)rows * m, &d_mean);
+  rc = stageIn(h, p); if (rc) return rc;
+  rc = launchMean(h, n, rows, m, d_weights, d_x, d_mean); if (rc) return rc;
   return stageOut(h, p);
 }
 

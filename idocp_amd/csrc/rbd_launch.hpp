@@ -52,5 +52,35 @@ struct RbdScoreArgs {
 };
 void rbdScore(int nv, bool quadruped, const RbdScoreArgs& a, int n, hipStream_t st);
 
+// Sampling around a torque sequence (rbd_sample_kernel.hip).  Every pointer: DEVICE memory.  Workgroups of RBD_SAMPLE_THREADS lanes; a chunk is
+// IDOCP_RBD_REDUCE_CHUNK consecutive samples, nchunks = ceil(n / chunk).  scratch: RBD_PARTIAL_STRIDE doubles per (row, chunk) -- the column
+// partials of the mean with the chunk's weight sum in the last place; the weights call (rows = 1) keeps its five arrays of nchunks doubles there.
+constexpr int RBD_SAMPLE_THREADS = 256;
+constexpr int RBD_PARTIAL_STRIDE = IDOCP_RBD_MEAN_MAX_COLUMNS + 1;
+// u_samples [steps][n][nu] = clamp(u_nominal [steps][nu] + sigma [nu] z); u_min / u_max [nu], either may be NULL.  One launch.
+struct RbdPerturbArgs {
+  const double *u_nominal, *sigma, *u_min, *u_max;
+  double* u_samples;
+  unsigned long long seed;
+  unsigned draw;
+  int n, nu, first_step, steps;
+};
+void rbdPerturb(const RbdPerturbArgs& a, hipStream_t st);
+// weights [n] and stats [IDOCP_RBD_WEIGHT_STATS] from cost [n] and violation [n] (NULL: left out).  Four launches.
+struct RbdWeightArgs {
+  const double *cost, *violation;
+  double penalty, temperature;
+  double *weights, *stats, *scratch;
+  int n, nchunks;
+};
+void rbdWeights(const RbdWeightArgs& a, hipStream_t st);
+// mean [rows][m] of x [rows][n][m] under weights [n], 1 <= m <= IDOCP_RBD_MEAN_MAX_COLUMNS; rows * nchunks workgroups.  Two launches.
+struct RbdMeanArgs {
+  const double *weights, *x;
+  double *mean, *scratch;
+  int n, rows, m, nchunks;
+};
+void rbdMean(const RbdMeanArgs& a, hipStream_t st);
+
 }  // namespace idocp_dev
 #endif  // IDOCP_RBD_LAUNCH_HPP_

@@ -939,6 +939,64 @@ int idocp_rbd_score_rollout(idocp_rbd_t* h, const idocp_rbd_objective_t* o, int 
 int idocp_rbd_score_rollout_device(idocp_rbd_t* h, const idocp_rbd_objective_t* o, int n, int first_step, int steps, const int* active, int terminal,
                                    int accumulate, const idocp_rbd_score_io_t* io);
 
+/* ---- Sampling around a torque sequence: perturb, weigh, average (rbd_sample_kernel.hip).  Every call of this block is an ADDITION (the reference
+ * has no counterpart).  With idocp_rbd_rollout_policy_device and idocp_rbd_score_rollout_device between the first and the second, one iteration of
+ * a sampling-based refinement (the MPPI update: the softmin-weighted mean of the sampled torque sequences) runs on the handle's stream without a
+ * synchronisation.  Both model kinds work; only nu matters.
+ * Every sum over the sample axis is folded in a FIXED order: partial sums over chunks of IDOCP_RBD_REDUCE_CHUNK consecutive samples (within a
+ * chunk: each of 256 lanes adds its samples in index order, then a fixed tree over the lanes), then the chunks in index order.  No floating-point
+ * atomics.  Results are therefore bit for bit equal from run to run and between the host and the device form, and a row of
+ * idocp_rbd_weighted_mean depends neither on `rows` nor on the call that carried it.
+ * The chunk partials live in one more buffer the handle owns; it grows only when rows * ceil(n / IDOCP_RBD_REDUCE_CHUNK) grows (rows = 1 for
+ * idocp_rbd_importance_weights). */
+#define IDOCP_RBD_REDUCE_CHUNK 1024
+#define IDOCP_RBD_WEIGHT_STATS 5
+#define IDOCP_RBD_MEAN_MAX_COLUMNS 64
+
+/* ADDITION.  u_samples[k][i][j] = clamp(u_nominal[k][j] + sigma[j] z(seed, draw, first_step + k, i, j)) for k < steps, i < n, j < nu, with
+ * u_nominal [steps][nu], sigma [nu], u_min / u_max [nu] (either may be NULL) and the clamp min(max(u, u_min), u_max) of the policy.
+ * z = 0 exactly for sample 0: the nominal itself is always among the candidates.  Otherwise z is a standard normal from Philox4x32-10 (multipliers
+ * 0xD2511F53, 0xCD9E8D57; key increments 0x9E3779B9, 0xBB67AE85) with the key (seed low word, seed high word) and the counter
+ * (i, first_step + k, j / 2, draw); of its output words r0 .. r3
+ *   u1 = (((r0 | r1 << 32) >> 12) + 0.5) 2^-52 in (0, 1),  u2 = ((r2 | r3 << 32) >> 11) 2^-53 in [0, 1),  rho = sqrt(-2 ln u1),
+ * an even j takes rho cos(2 pi u2) and an odd j rho sin(2 pi u2); |z| <= sqrt(106 ln 2) = 8.57.  draw is the caller's iteration counter: a new
+ * value gives fresh noise.  A sample's values depend on (seed, draw, step, i, j) alone: they are bit for bit the same whatever n is and whether
+ * the steps came in one call or window by window (first_step).  n >= 1, first_step >= 0, steps >= 1.
+ * Host pointers; returns when u_samples is in place.  Refuses (IDOCP_E_ARG) a sigma that is negative or not finite, and bounds like
+ * idocp_rbd_feedback_torques_batch. */
+int idocp_rbd_perturb_torques(idocp_rbd_t* h, int n, int first_step, int steps, const double* u_nominal, const double* sigma, const double* u_min,
+                              const double* u_max, unsigned long long seed, unsigned draw, double* u_samples);
+/* Device pointers for everything; asynchronous on idocp_rbd_stream(h); one launch; allocates nothing.  sigma and the bounds are NOT checked. */
+int idocp_rbd_perturb_torques_device(idocp_rbd_t* h, int n, int first_step, int steps, const double* u_nominal, const double* sigma,
+                                     const double* u_min, const double* u_max, unsigned long long seed, unsigned draw, double* u_samples);
+
+/* ADDITION.  The softmin importance weights of n scores s_i = cost[i] + penalty violation[i] (violation NULL: s_i = cost[i]).  F = the samples whose
+ * s_i is finite (a diverged plant scores NaN), s_min = min over F:
+ *   weights[i] = exp(-(s_i - s_min) / temperature) on F, exactly 0 elsewhere
+ * so the best sample weighs exactly 1 and W = sum_i weights[i] >= 1 unless F is empty.  stats [IDOCP_RBD_WEIGHT_STATS] = {|F|, s_min, the argmin
+ * (the lowest index at a tie), W, the effective sample size W^2 / sum_i weights[i]^2}; with F empty all weights are 0 and stats = {0, NaN, -1, 0, 0}.
+ * temperature finite and positive, penalty finite and non-negative, else IDOCP_E_ARG (in both forms).
+ * Host pointers; returns when weights and stats are in place. */
+int idocp_rbd_importance_weights(idocp_rbd_t* h, int n, const double* cost, const double* violation, double penalty, double temperature,
+                                 double* weights, double* stats);
+/* Device pointers, stats included; asynchronous on idocp_rbd_stream(h); four launches; allocates only when ceil(n / IDOCP_RBD_REDUCE_CHUNK) grows
+ * beyond what any earlier call of this block needed. */
+int idocp_rbd_importance_weights_device(idocp_rbd_t* h, int n, const double* cost, const double* violation, double penalty, double temperature,
+                                        double* weights, double* stats);
+
+/* ADDITION.  The weighted mean over the sample axis of a step-major array x [rows][n][m], 1 <= m <= IDOCP_RBD_MEAN_MAX_COLUMNS (nu, nv, nq and
+ * 3 ncontacts fit: u_traj, q_traj, f_traj ... of a rollout can be passed straight in), rows >= 1:
+ *   mean[r][c] = sum_i weights[i] x[r][i][c] / sum_i weights[i]
+ * A sample with weights[i] == 0 is SKIPPED, not multiplied: its x may hold NaN or Inf (what a diverged rollout leaves) without touching the
+ * result.  A non-finite x under a positive weight makes exactly the entries mean[r][c] it enters non-finite.  sum_i weights[i] == 0 gives NaN
+ * everywhere (read stats[0] of the call above first).
+ * Host pointers; returns when mean is in place.  Refuses (IDOCP_E_ARG) a weight that is negative or not finite. */
+int idocp_rbd_weighted_mean(idocp_rbd_t* h, int n, int rows, int m, const double* weights, const double* x, double* mean);
+/* Device pointers; asynchronous on idocp_rbd_stream(h); two launches (the chunk partials, then the fold and the division); the weights are NOT
+ * checked; allocates only when rows * ceil(n / IDOCP_RBD_REDUCE_CHUNK) grows beyond what any earlier call of this block needed.  mean may lie
+ * anywhere outside x and weights -- e.g. be the u_nominal of the next idocp_rbd_perturb_torques_device. */
+int idocp_rbd_weighted_mean_device(idocp_rbd_t* h, int n, int rows, int m, const double* weights, const double* x, double* mean);
+
 const char* idocp_last_error(void);
 const char* idocp_version(void);
 

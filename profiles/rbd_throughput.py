@@ -8,7 +8,10 @@ fd_step_closed_loop is one step of idocp_rbd_rollout_policy_device (policy launc
 read against fd_stage_a_f_step.  The score_* rows are idocp_rbd_score_rollout_device on a window of 1 and of 16 steps (terminal slice included): every
 weight, the joint limits and the linearized cone (score_sK_all_linearized) or the FrictionCone (score_sK_all_cone), and the cost alone
 (score_sK_cost_only); score_sK_copy is a device-to-device copy of exactly the bytes the call reads, timed in the same run, and each score row carries
-its ratio to that copy.
+its ratio to that copy.  The sample_* rows are the sampling calls on 16 steps of the 12 torques: sample_perturb (idocp_rbd_perturb_torques_device writes
+u_samples [16][n][12]), sample_mean (idocp_rbd_weighted_mean_device reads an array of that shape) -- both read against sample_copy, a device-to-device
+copy of that array -- and sample_weights (idocp_rbd_importance_weights_device: cost and violation in, weights out) against sample_weights_copy, a copy of
+those three arrays.
 
     python profiles/rbd_throughput.py [--n 122880] [--launches 20] [--warmup 5] [--rows name,name,...]
 """
@@ -39,6 +42,58 @@ POLICY_ROWS = ("policy_shared", "policy_per_sample", "fd_step_closed_loop")
 SCORE_STEPS = (1, 16)
 SCORE_KINDS = ("copy", "all_linearized", "all_cone", "cost_only")
 SCORE_ROWS = tuple("score_s%d_%s" % (s, k) for s in SCORE_STEPS for k in SCORE_KINDS)
+SAMPLE_STEPS = 16
+SAMPLE_ROWS = ("sample_copy", "sample_perturb", "sample_mean", "sample_weights_copy", "sample_weights")
+
+
+def sample_rows(wanted, lib, rt, h, stream, m, n, measure, res):
+    """the sample_* rows; the weights come from random scores, so that the mean multiplies rather than skips"""
+    rt.hipMemcpyAsync.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p]
+    nu, steps = m.nu, SAMPLE_STEPS
+    rng = np.random.default_rng(1)
+    host = {"nominal": rng.uniform(-20, 20, (steps, nu)), "sigma": np.full(nu, 2.0), "cost": rng.uniform(1, 5, n), "violation": rng.uniform(0, 1, n)}
+    dev = {}
+    for key, x in host.items():
+        dev[key] = C.c_void_p()
+        capi.check(lib.idocp_device_alloc(C.byref(dev[key]), x.nbytes), "alloc")
+        capi.check(lib.idocp_device_upload(dev[key], x.ctypes.data, x.nbytes), "upload")
+    big = 8 * steps * n * nu
+    for key, size in (("samples", big), ("copy", big), ("weights", 8 * n), ("small_copy", 3 * 8 * n), ("stats", 8 * capi.RBD_WEIGHT_STATS), ("mean", 8 * steps * nu)):
+        dev[key] = C.c_void_p()
+        capi.check(lib.idocp_device_alloc(C.byref(dev[key]), size), "alloc")
+
+    def small_copy():
+        for at, key in enumerate(("cost", "violation", "weights")):
+            assert rt.hipMemcpyAsync(C.c_void_p(dev["small_copy"].value + at * 8 * n), dev[key], 8 * n, 3, stream) == 0
+
+    launches = {
+        "sample_copy": lambda: rt.hipMemcpyAsync(dev["copy"], dev["samples"], big, 3, stream),
+        "sample_perturb": lambda: capi.check(lib.idocp_rbd_perturb_torques_device(h, n, 0, steps, dev["nominal"], dev["sigma"], None, None, 7, 1, dev["samples"]), "perturb"),
+        "sample_weights_copy": small_copy,
+        "sample_weights": lambda: capi.check(lib.idocp_rbd_importance_weights_device(h, n, dev["cost"], dev["violation"], 10.0, 1.0, dev["weights"], dev["stats"]), "weights"),
+        "sample_mean": lambda: capi.check(lib.idocp_rbd_weighted_mean_device(h, n, steps, nu, dev["weights"], dev["samples"], dev["mean"]), "mean"),
+    }
+    launches["sample_perturb"]()                           # whatever rows are asked for, the mean has samples and weights to read
+    launches["sample_weights"]()
+    for name in ("sample_copy", "sample_perturb", "sample_weights_copy", "sample_weights", "sample_mean"):
+        if wanted and name not in wanted:
+            continue
+        measure(name, launches[name])
+        nbytes = 3 * 8 * n if "weights" in name else big
+        res[name]["bytes"] = nbytes
+        res[name]["GB_per_s"] = round(nbytes / res[name]["ms_median"] / 1e6, 1)
+    for name, base in (("sample_perturb", "sample_copy"), ("sample_mean", "sample_copy"), ("sample_weights", "sample_weights_copy")):
+        if name in res and base in res:
+            res[name]["ratio_to_copy"] = round(res[name]["ms_median"] / res[base]["ms_median"], 3)
+    out, stats = np.zeros((steps, nu)), np.zeros(capi.RBD_WEIGHT_STATS)
+    capi.check(lib.idocp_device_download(out.ctypes.data, dev["mean"], out.nbytes), "download")
+    capi.check(lib.idocp_device_download(stats.ctypes.data, dev["stats"], stats.nbytes), "download")
+    if "sample_mean" in res:
+        res["sample_mean_finite"] = bool(np.isfinite(out).all())
+        res["sample_mean_max_shift"] = float(np.abs(out - host["nominal"]).max())      # (the mean of n perturbations stays near the nominal)
+    res["sample_stats"] = [float(x) for x in stats]
+    for d in dev.values():
+        lib.idocp_device_free(d)
 
 
 def score_rows(args, wanted, lib, rt, h, stream, m, n, host, measure, res):
@@ -207,6 +262,8 @@ def main():
         measure(name, launch)
     if not wanted or set(wanted) & set(SCORE_ROWS):
         score_rows(args, wanted, lib, rt, h, stream, m, n, host, measure, res)
+    if not wanted or set(wanted) & set(SAMPLE_ROWS):
+        sample_rows(wanted, lib, rt, h, stream, m, n, measure, res)
     ran = [k for k in res if isinstance(res[k], dict)]
     for key, src, width, rows in (("tau_finite", "tau", nv, ("stage_", "impulse_")), ("fd_a_finite", "fd_a", nv, ("fd_",)),
                                   ("policy_u_finite", "u_out", m.nu, ("policy_", "fd_step_closed_loop"))):
