@@ -126,6 +126,19 @@ class RbdScoreIO(C.Structure):
     _fields_ = [(name, C.c_void_p) for name in INPUTS + OUTPUTS]
 
 
+class RbdKinIO(C.Structure):
+    """idocp_rbd_kin_io_t: inputs and requested outputs of idocp_rbd_contact_kinematics_batch(_device); a pointer left at None is NULL"""
+    INPUTS = ("q", "v")
+    OUTPUTS = ("points", "rotation", "velocity", "jacobian")
+    _fields_ = [(name, C.c_void_p) for name in INPUTS + OUTPUTS]
+
+
+class RbdFootholdRollout(C.Structure):
+    """idocp_rbd_foothold_rollout_t: the arrays of idocp_rbd_rollout_footholds(_device); a pointer left at None is NULL"""
+    ARRAYS = ("contact_points", "q_traj", "v_traj", "u_traj", "a_traj", "f_traj")
+    _fields_ = [("u", C.c_void_p), ("policy", C.POINTER(RbdPolicy))] + [(name, C.c_void_p) for name in ARRAYS]
+
+
 RBD_STAGE, RBD_IMPULSE = 0, 1
 RBD_SCORE_MAX_WINDOW = 1024
 RBD_REDUCE_CHUNK = 1024      # IDOCP_RBD_REDUCE_CHUNK: samples per chunk of the fixed-order sums
@@ -336,6 +349,12 @@ def _proto(lib):
     lib.idocp_rbd_score_rollout.restype = ci
     lib.idocp_rbd_score_rollout_device.argtypes = [vp, vp, ci, ci, ci, c_int_p, ci, ci, P(RbdScoreIO)]
     lib.idocp_rbd_score_rollout_device.restype = ci
+    for form in ("", "_device"):
+        for name, args in (("idocp_rbd_contact_kinematics_batch", [vp, ci, P(RbdKinIO)]),
+                           ("idocp_rbd_rollout_footholds", [vp, ci, ci, c_int_p, cd, cd, P(RbdFootholdRollout), ci, ci])):
+            f = getattr(lib, name + form)
+            f.argtypes = args
+            f.restype = ci
     for form in ("", "_device"):
         for name, args in (("idocp_rbd_perturb_torques", [vp, ci, ci, ci, vp, vp, vp, vp, C.c_ulonglong, C.c_uint, vp]),
                            ("idocp_rbd_importance_weights", [vp, ci, vp, vp, cd, cd, vp, vp]),

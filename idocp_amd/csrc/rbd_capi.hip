@@ -14,6 +14,7 @@
 #include "host_util.hpp"
 #include "idocp_hip.h"
 #include "model_shapes.hpp"
+#include "rbd_foothold_plan.hpp"
 #include "rbd_launch.hpp"
 #include "rbd_stage.hpp"
 #include "unocp_launch.hpp"
@@ -271,16 +272,25 @@ int checkTorques(const char* who, const idocp_rbd* h, int n, const double* q, co
 // at the state of step k and go to slice k of u_traj (or, without u_traj, to the handle's buffer).
 int rolloutDevice(idocp_rbd* h, int n, int steps, const int* active, double time_step, double dt, const double* u, const double* contact_points,
                   double* q_traj, double* v_traj, double* a_traj, double* f_traj, int touchdown_impulse, const idocp_rbd_policy_t* pol,
-                  double* u_traj) {
+                  double* u_traj, double* latched = nullptr, int latch_first = 0) {
   const size_t nq = h->model.nq, nv = h->model.nv, nu = h->model.nu, nf = 3 * (size_t)h->model.ncontacts, N = (size_t)n;
   int prev = 0;
   for (int k = 0; k < steps; ++k) {
-    const int mask = h->quadruped ? maskOf(h, active + (size_t)k * h->model.ncontacts) : 0;
+    int mask = h->quadruped ? maskOf(h, active + (size_t)k * h->model.ncontacts) : 0;
+    int touchdown = (touchdown_impulse && k > 0) ? (mask & ~prev) : 0;
     double *qk = q_traj + k * N * nq, *vk = v_traj + k * N * nv;
-    if (touchdown_impulse && k > 0 && (mask & ~prev)) {
+    if (latched) {
+      // the foothold rollout (quadruped): slice k of the contact points before anything of step k reads it (rbd_foothold_plan.hpp)
+      const idocp_host::FootholdStep s = idocp_host::footholdStep(active, h->model.ncontacts, k, touchdown_impulse != 0, latch_first != 0);
+      mask = s.stage; touchdown = s.impulse;
+      rbdLatchQuadruped(static_cast<const DevModel*>(h->d_model), h->d_frames, qk, k > 0 ? latched + (k - 1) * N * nf : nullptr, latched + k * N * nf,
+                        s.carry, n, h->stream);
+      HIP_TRY(hipGetLastError());
+    }
+    if (touchdown) {
       idocp_rbd_fd_io_t imp = idocp_rbd_fd_io_t();
       imp.q = qk; imp.v = vk; imp.v_next = vk;            // (in place: slice k becomes the post-impulse velocity)
-      int rc = launchForward(h, IDOCP_RBD_IMPULSE, n, mask & ~prev, time_step, dt, imp); if (rc) return rc;
+      int rc = launchForward(h, IDOCP_RBD_IMPULSE, n, touchdown, time_step, dt, imp); if (rc) return rc;
     }
     idocp_rbd_fd_io_t io = idocp_rbd_fd_io_t();
     io.q = qk; io.v = vk;
@@ -298,6 +308,39 @@ int rolloutDevice(idocp_rbd* h, int n, int steps, const int* active, double time
     io.q_next = qk + N * nq; io.v_next = vk + N * nv;
     int rc = launchForward(h, IDOCP_RBD_STAGE, n, mask, time_step, dt, io); if (rc) return rc;
     prev = mask;
+  }
+  return IDOCP_OK;
+}
+
+// ---- contact-frame kinematics and the rollout that latches its footholds ----
+
+int checkKinematics(const char* who, const idocp_rbd* h, int n, const idocp_rbd_kin_io_t* io) {
+  const std::string w(who);
+  if (!h || !io) { set_last_error(w + ": null handle or io"); return IDOCP_E_ARG; }
+  if (!h->quadruped) { set_last_error(w + ": a fixed-base chain has no contact frames"); return IDOCP_E_UNSUPPORTED; }
+  if (n <= 0) { set_last_error(w + ": n must be positive"); return IDOCP_E_ARG; }
+  if (!io->q) { set_last_error(w + ": q is needed"); return IDOCP_E_ARG; }
+  if (io->velocity && !io->v) { set_last_error(w + ": velocity needs v"); return IDOCP_E_ARG; }
+  if (!io->points && !io->rotation && !io->velocity && !io->jacobian) { set_last_error(w + ": no output was asked for"); return IDOCP_E_ARG; }
+  return IDOCP_OK;
+}
+
+// host_bounds: the policy's arrays are host memory
+int checkFootholds(const char* who, const idocp_rbd* h, int n, int steps, const int* active, double time_step, double dt,
+                   const idocp_rbd_foothold_rollout_t* io, bool host_bounds) {
+  const std::string w(who);
+  if (!h || !io) { set_last_error(w + ": null handle or io"); return IDOCP_E_ARG; }
+  if (!h->quadruped) { set_last_error(w + ": a fixed-base chain has no contact frames"); return IDOCP_E_UNSUPPORTED; }
+  if (n <= 0) { set_last_error(w + ": n must be positive"); return IDOCP_E_ARG; }
+  if (steps < 1) { set_last_error(w + ": steps must be at least 1"); return IDOCP_E_ARG; }
+  if (!io->contact_points || !io->q_traj || !io->v_traj || !active) {
+    set_last_error(w + ": contact_points, q_traj, v_traj and active are needed"); return IDOCP_E_ARG;
+  }
+  if (io->u && io->policy) { set_last_error(w + ": u and policy exclude one another"); return IDOCP_E_ARG; }
+  if (!std::isfinite(dt)) { set_last_error(w + ": dt must be finite"); return IDOCP_E_ARG; }
+  if (io->policy) { int rc = checkPolicy(who, h, io->policy, host_bounds); if (rc) return rc; }
+  if (idocp_host::footholdAnyActive(active, h->model.ncontacts, steps) && (!(time_step > 0.0) || !std::isfinite(time_step))) {
+    set_last_error(w + ": an active contact needs a positive Baumgarte time_step"); return IDOCP_E_ARG;
   }
   return IDOCP_OK;
 }
@@ -621,6 +664,66 @@ int idocp_rbd_rollout_policy(idocp_rbd_t* h, int n, int steps, const int* active
   p.out(f_traj, S * N * nf, &d_f);
   rc = stageIn(h, p); if (rc) return rc;
   rc = rolloutDevice(h, n, steps, active, time_step, dt, nullptr, d_points, d_q, d_v, d_a, d_f, touchdown_impulse, &d_pol, d_u); if (rc) return rc;
+  return stageOut(h, p);
+}
+
+int idocp_rbd_contact_kinematics_batch_device(idocp_rbd_t* h, int n, const idocp_rbd_kin_io_t* io) {
+  int rc = checkKinematics("idocp_rbd_contact_kinematics_batch_device", h, n, io); if (rc) return rc;
+  HIP_TRY(hipSetDevice(h->device));
+  rbdKinematicsQuadruped(static_cast<const DevModel*>(h->d_model), h->d_frames, *io, n, h->stream);
+  HIP_TRY(hipGetLastError());
+  return IDOCP_OK;
+}
+
+int idocp_rbd_contact_kinematics_batch(idocp_rbd_t* h, int n, const idocp_rbd_kin_io_t* io) {
+  int rc = checkKinematics("idocp_rbd_contact_kinematics_batch", h, n, io); if (rc) return rc;
+  HIP_TRY(hipSetDevice(h->device));
+  const size_t nq = h->model.nq, nv = h->model.nv, nf = 3 * (size_t)h->model.ncontacts, N = (size_t)n;
+  StagePlan p;
+  idocp_rbd_kin_io_t d;
+  p.in(io->q, N * nq, &d.q);
+  p.in(io->velocity ? io->v : nullptr, N * nv, &d.v);      // (v is read for the velocity alone)
+  p.out(io->points, N * nf, &d.points);
+  p.out(io->rotation, N * nf * 3, &d.rotation);
+  p.out(io->velocity, N * nf, &d.velocity);
+  p.out(io->jacobian, N * nf * nv, &d.jacobian);
+  rc = stageIn(h, p); if (rc) return rc;
+  rbdKinematicsQuadruped(static_cast<const DevModel*>(h->d_model), h->d_frames, d, n, h->stream);
+  HIP_TRY(hipGetLastError());
+  return stageOut(h, p);
+}
+
+int idocp_rbd_rollout_footholds_device(idocp_rbd_t* h, int n, int steps, const int* active, double time_step, double dt,
+                                       const idocp_rbd_foothold_rollout_t* io, int touchdown_impulse, int latch_first) {
+  int rc = checkFootholds("idocp_rbd_rollout_footholds_device", h, n, steps, active, time_step, dt, io, false); if (rc) return rc;
+  HIP_TRY(hipSetDevice(h->device));
+  if (io->policy && !io->u_traj) { rc = h->u_buf.grow((size_t)n * h->model.nu, h->stream); if (rc) return rc; }
+  return rolloutDevice(h, n, steps, active, time_step, dt, io->u, io->contact_points, io->q_traj, io->v_traj, io->a_traj, io->f_traj, touchdown_impulse,
+                       io->policy, io->policy ? io->u_traj : nullptr, io->contact_points, latch_first);
+}
+
+int idocp_rbd_rollout_footholds(idocp_rbd_t* h, int n, int steps, const int* active, double time_step, double dt,
+                                const idocp_rbd_foothold_rollout_t* io, int touchdown_impulse, int latch_first) {
+  int rc = checkFootholds("idocp_rbd_rollout_footholds", h, n, steps, active, time_step, dt, io, true); if (rc) return rc;
+  HIP_TRY(hipSetDevice(h->device));
+  const size_t nq = h->model.nq, nv = h->model.nv, nu = h->model.nu, nf = 3 * (size_t)h->model.ncontacts, N = (size_t)n, S = (size_t)steps;
+  if (io->policy && !io->u_traj) { rc = h->u_buf.grow(N * nu, h->stream); if (rc) return rc; }
+  StagePlan p;
+  idocp_rbd_policy_t d_pol;
+  const double* d_u;
+  double *d_points, *d_q, *d_v, *d_ut, *d_a, *d_f;
+  if (io->policy) policySlots(p, h, *io->policy, N, S, &d_pol);
+  p.inout(io->q_traj, (S + 1) * N * nq, N * nq, &d_q);      // (slice 0 goes up, slices 1 .. S come back)
+  p.inout(io->v_traj, (S + 1) * N * nv, N * nv, &d_v);
+  p.in(io->u, S * N * nu, &d_u);
+  p.inoutAll(io->contact_points, S * N * nf, N * nf, &d_points);      // (slice 0 goes up, every slice comes back)
+  p.out(io->policy ? io->u_traj : nullptr, S * N * nu, &d_ut);
+  p.out(io->a_traj, S * N * nv, &d_a);
+  p.out(io->f_traj, S * N * nf, &d_f);
+  rc = stageIn(h, p); if (rc) return rc;
+  rc = rolloutDevice(h, n, steps, active, time_step, dt, d_u, d_points, d_q, d_v, d_a, d_f, touchdown_impulse, io->policy ? &d_pol : nullptr, d_ut,
+                     d_points, latch_first);
+  if (rc) return rc;
   return stageOut(h, p);
 }
 

@@ -82,5 +82,14 @@ struct RbdMeanArgs {
 };
 void rbdMean(const RbdMeanArgs& a, hipStream_t st);
 
+// Contact-frame kinematics (rbd_kinematics_kernel.hip).  One lane per (sample, leg), RBD_KIN_THREADS / 4 samples per workgroup, any n.
+// io: DEVICE pointers; a NULL output is neither computed nor stored.  One launch.
+constexpr int RBD_KIN_THREADS = 256;
+void rbdKinematicsQuadruped(const DevModel* m, const RbdFrames* frames, const idocp_rbd_kin_io_t& io, int n, hipStream_t st);
+// The latch step of the foothold rollout, the same kernel: points [n][nc][3] = carry bit c ? prev[i][c] : p_c(q[i]).  prev NULL: a carried
+// entry of `points` is left as it is.  One launch.
+void rbdLatchQuadruped(const DevModel* m, const RbdFrames* frames, const double* q, const double* prev, double* points, int carry_mask, int n,
+                       hipStream_t st);
+
 }  // namespace idocp_dev
 #endif  // IDOCP_RBD_LAUNCH_HPP_

@@ -24,6 +24,8 @@ struct StagePlan {
   void out(double* host, size_t size, double** dev, bool zero_fill = false) { add(host, host ? size : 0, 0, 0, zero_fill, constPtr(dev)); }
   // the first `prefix` doubles go up, the rest comes back (a trajectory whose slice 0 is the input)
   void inout(double* host, size_t size, size_t prefix, double** dev) { add(host, host ? size : 0, prefix, prefix, false, constPtr(dev)); }
+  // the first `prefix` doubles go up, everything comes back (a trajectory whose slice 0 is an input the call rewrites as well)
+  void inoutAll(double* host, size_t size, size_t prefix, double** dev) { add(host, host ? size : 0, prefix, 0, false, constPtr(dev)); }
   // uploaded in full and downloaded in full (sums a call adds to)
   void update(double* host, size_t size, double** dev) { add(host, host ? size : 0, size, 0, false, constPtr(dev)); }
   // room without a copy

@@ -880,6 +880,59 @@ int idocp_rbd_rollout_policy_device(idocp_rbd_t* h, int n, int steps, const int*
                                     const idocp_rbd_policy_t* policy, const double* contact_points, double* q_traj, double* v_traj, double* u_traj,
                                     double* a_traj, double* f_traj, int touchdown_impulse);
 
+/* ---- Contact-frame kinematics for n states (rbd_kinematics_kernel.hip): the batched counterpart of Robot::updateFrameKinematics with
+ * getContactPoints, frameRotation and getFrameJacobian, which idocp_model_contact_positions / idocp_model_frame_world_placement give one state
+ * on the host.  Quadrupeds only (a fixed-base chain has no contact frames: IDOCP_E_UNSUPPORTED).  Per sample i and contact c:
+ *   points   [n][nc][3]      world position of the contact frame origin, the quantity idocp_model_contact_positions returns
+ *   rotation [n][nc][9]      world rotation of the contact frame, row-major: it takes the local force coordinates of f_traj to the world frame
+ *   velocity [n][nc][3]      world-frame linear velocity of the frame origin: d/d eps points(q (+) eps v) at eps = 0, (+) the retraction of
+ *                            idocp_model_integrate_configuration; equal to rotation times the LOCAL linear frame velocity.  Needs v.
+ *   jacobian [n][3 nc * nv]  the 3 nc x nv matrix J, column-major: column r is d/d eps points(q (+) eps e_r), so velocity = J v.  Every entry
+ *                            is written, the structural zeros of the other legs' columns included.  This is the WORLD-frame Jacobian; dCda
+ *                            of idocp_rbd_contact_dynamics_batch is the LOCAL one: its rows of contact c are rotation[c]^T times these.
+ * A NULL output is neither computed nor stored.  The quaternion is taken as given.  A sample's results are bit for bit the same alone or in a
+ * batch and for any selection of outputs.  A non-finite entry in a sample's q makes all of that sample's outputs NaN, one in its v the
+ * sample's velocity, and touches no other sample. */
+typedef struct idocp_rbd_kin_io {
+  const double *q, *v;                       /* [n][nq], [n][nv]; v only for velocity */
+  double *points, *rotation, *velocity, *jacobian;
+} idocp_rbd_kin_io_t;
+/* ADDITION.  Host pointers; returns when the outputs are in place.  IDOCP_E_ARG for n <= 0, a null handle, io or q, velocity without v and no
+ * output at all. */
+int idocp_rbd_contact_kinematics_batch(idocp_rbd_t* h, int n, const idocp_rbd_kin_io_t* io);
+/* ADDITION.  Device pointers; asynchronous on idocp_rbd_stream(h); one launch; allocates nothing. */
+int idocp_rbd_contact_kinematics_batch_device(idocp_rbd_t* h, int n, const idocp_rbd_kin_io_t* io);
+
+/* ---- A rollout that latches its footholds: idocp_rbd_rollout / idocp_rbd_rollout_policy with contact_points an IN / OUT trajectory, so that a
+ * schedule with lift-offs and touchdowns anchors every plant where ITS foot is.  With
+ *   stays(k, c) = active[k][c] && (k > 0 ? active[k - 1][c] : !latch_first)
+ * slice k of contact_points [steps][n][nc][3] is, per sample i and contact c,
+ *   stays(k, c)   contact_points[k - 1][i][c], carried bit for bit (at k = 0: the caller's value, left as it is)
+ *   otherwise     points_c(q_traj[k][i]) of the call above: the foot at the state the Euler step k is applied from (a touchdown impulse
+ *                 changes v, not q).
+ * A contact that becomes active is anchored at that plant's foot, and the entry of an open contact tracks the swing foot: every slice is fully
+ * defined and doubles as the foot trajectory.  Only slice 0 is read, and of it only the contacts active at step 0 with latch_first == 0.
+ * Everything else -- array shapes, the touchdown impulse on the newly active contacts, the policy before the forward launch, the NaN
+ * conventions -- is idocp_rbd_rollout (u given), idocp_rbd_rollout_policy (policy given) or idocp_rbd_rollout with u = NULL (neither); u
+ * together with policy is IDOCP_E_ARG.  Feeding the contact_points this call produced into those calls reproduces its trajectories bit for
+ * bit.  Per step: the latch launch, the touchdown impulse if any, the policy launch if any, the forward launch, all on the handle's stream
+ * with no synchronisation in between.  Quadrupeds only (IDOCP_E_UNSUPPORTED on a chain). */
+typedef struct idocp_rbd_foothold_rollout {
+  const double* u;                   /* open loop [steps][n][nu], or NULL */
+  const idocp_rbd_policy_t* policy;  /* closed loop, or NULL; u and policy both given: IDOCP_E_ARG; both NULL: zero torques */
+  double* contact_points;            /* [steps][n][nc][3], IN (slice 0) / OUT (every slice) */
+  double *q_traj, *v_traj, *u_traj, *a_traj, *f_traj;   /* as idocp_rbd_rollout_policy (u_traj is written only with a policy) */
+} idocp_rbd_foothold_rollout_t;
+/* ADDITION.  Host pointers (those of the policy included); stages everything once -- slice 0 of contact_points goes up, every slice comes back
+ * -- and refuses bad policy bounds like idocp_rbd_rollout_policy.  contact_points, q_traj, v_traj and active are needed; time_step must be
+ * positive if any step has an active contact. */
+int idocp_rbd_rollout_footholds(idocp_rbd_t* h, int n, int steps, const int* active, double time_step, double dt,
+                                const idocp_rbd_foothold_rollout_t* io, int touchdown_impulse, int latch_first);
+/* ADDITION.  Device pointers for everything the struct and the policy point to (io and *policy themselves are host memory); asynchronous on
+ * idocp_rbd_stream(h); allocates nothing beyond what idocp_rbd_rollout_policy_device may (the torque buffer when u_traj is NULL). */
+int idocp_rbd_rollout_footholds_device(idocp_rbd_t* h, int n, int steps, const int* active, double time_step, double dt,
+                                       const idocp_rbd_foothold_rollout_t* io, int touchdown_impulse, int latch_first);
+
 /* ---- Scoring a rollout: the solvers' cost and a constraint violation per sample, on the GPU (rbd_score_kernel.hip).
  * The objective holds what scoring needs: the weights of an idocp_cost_t, the switches and bounds of an idocp_constraints_t (the joint limits
  * themselves are the model's q_min, q_max, v_max, u_max) and the configuration-space reference of every step t_k = t0 + k dt, k = 0 .. steps,

@@ -11,7 +11,10 @@ weight, the joint limits and the linearized cone (score_sK_all_linearized) or th
 its ratio to that copy.  The sample_* rows are the sampling calls on 16 steps of the 12 torques: sample_perturb (idocp_rbd_perturb_torques_device writes
 u_samples [16][n][12]), sample_mean (idocp_rbd_weighted_mean_device reads an array of that shape) -- both read against sample_copy, a device-to-device
 copy of that array -- and sample_weights (idocp_rbd_importance_weights_device: cost and violation in, weights out) against sample_weights_copy, a copy of
-those three arrays.
+those three arrays.  The kin_* rows are idocp_rbd_contact_kinematics_batch_device: kin_points (q in, points out) and kin_all (q and v in, all four
+outputs), each against kin_*_copy, a device-to-device copy of the bytes the call reads and writes.  rollout is idocp_rbd_rollout_device over
+ROLLOUT_STEPS open-loop steps with every contact active and no touchdown impulse, rollout_footholds the same schedule through
+idocp_rbd_rollout_footholds_device (one latch launch more per step); both carry ms_per_step.
 
     python profiles/rbd_throughput.py [--n 122880] [--launches 20] [--warmup 5] [--rows name,name,...]
 """
@@ -44,6 +47,78 @@ SCORE_KINDS = ("copy", "all_linearized", "all_cone", "cost_only")
 SCORE_ROWS = tuple("score_s%d_%s" % (s, k) for s in SCORE_STEPS for k in SCORE_KINDS)
 SAMPLE_STEPS = 16
 SAMPLE_ROWS = ("sample_copy", "sample_perturb", "sample_mean", "sample_weights_copy", "sample_weights")
+KIN_ROWS = ("kin_points_copy", "kin_points", "kin_all_copy", "kin_all", "rollout", "rollout_footholds")
+ROLLOUT_STEPS = 4
+
+
+def kin_rows(wanted, lib, rt, h, stream, m, n, host, measure, res):
+    """the kin_* rows and the two rollouts"""
+    rt.hipMemcpyAsync.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p]
+    nv, nq, nu, nf, steps = m.nv, m.nq, m.nu, 3 * m.ncontacts, ROLLOUT_STEPS
+    sizes = {"q": nq, "v": nv, "points": nf, "rotation": 3 * nf, "velocity": nf, "jacobian": nf * nv}
+    dev = {}
+    for key, size in list(sizes.items()) + [("copy", sum(sizes.values())), ("q_traj", (steps + 1) * nq), ("v_traj", (steps + 1) * nv), ("u", steps * nu),
+                                             ("pts", steps * nf), ("a_traj", steps * nv), ("f_traj", steps * nf)]:
+        dev[key] = C.c_void_p()
+        capi.check(lib.idocp_device_alloc(C.byref(dev[key]), 8 * n * size), "alloc")
+    for key, x in (("q", host["q"]), ("v", host["v"]), ("q_traj", host["q"]), ("v_traj", 0.1 * host["v"])):
+        x = np.ascontiguousarray(x)
+        capi.check(lib.idocp_device_upload(dev[key], x.ctypes.data, x.nbytes), "upload")
+    u = np.zeros((steps, n, nu))
+    capi.check(lib.idocp_device_upload(dev["u"], u.ctypes.data, u.nbytes), "upload")
+    feet = np.zeros((n, nf))
+    kin = capi.RbdKinIO()
+    kin.q, kin.points = dev["q"], dev["points"]
+    capi.check(lib.idocp_rbd_contact_kinematics_batch_device(h, n, C.byref(kin)), "kinematics")      # every plant stands on its own feet
+    capi.check(lib.idocp_rbd_synchronize(h), "synchronize")
+    capi.check(lib.idocp_device_download(feet.ctypes.data, dev["points"], feet.nbytes), "download")
+    pts = np.ascontiguousarray(np.repeat(feet[None], steps, axis=0))
+    capi.check(lib.idocp_device_upload(dev["pts"], pts.ctypes.data, pts.nbytes), "upload")
+    selections = {"kin_points": ("q", "points"), "kin_all": ("q", "v", "points", "rotation", "velocity", "jacobian")}
+
+    def copy(keys):
+        at = 0
+        for key in keys:      # the very bytes the call reads and writes, array by array
+            assert rt.hipMemcpyAsync(C.c_void_p(dev["copy"].value + at), dev[key], 8 * n * sizes[key], 3, stream) == 0
+            at += 8 * n * sizes[key]
+
+    for name, keys in selections.items():
+        io = capi.RbdKinIO()
+        for key in keys:
+            setattr(io, key, dev[key])
+        nbytes = 8 * n * sum(sizes[key] for key in keys)
+        for row, launch in ((name + "_copy", lambda: copy(keys)),
+                            (name, lambda: capi.check(lib.idocp_rbd_contact_kinematics_batch_device(h, n, C.byref(io)), name))):
+            if wanted and row not in wanted:
+                continue
+            measure(row, launch)
+            res[row]["bytes"] = nbytes
+            res[row]["GB_per_s"] = round(nbytes / res[row]["ms_median"] / 1e6, 1)
+        if name in res and name + "_copy" in res:
+            res[name]["ratio_to_copy"] = round(res[name]["ms_median"] / res[name + "_copy"]["ms_median"], 3)
+    active = (C.c_int * (4 * steps))(*([1] * (4 * steps)))
+    fio = capi.RbdFootholdRollout()
+    fio.u, fio.contact_points, fio.q_traj, fio.v_traj, fio.a_traj, fio.f_traj = dev["u"], dev["pts"], dev["q_traj"], dev["v_traj"], dev["a_traj"], dev["f_traj"]
+    launches = {
+        "rollout": lambda: capi.check(lib.idocp_rbd_rollout_device(h, n, steps, active, 0.05, 0.01, dev["u"], dev["pts"], dev["q_traj"], dev["v_traj"],
+                                                                   dev["a_traj"], dev["f_traj"], 0), "rollout"),
+        "rollout_footholds": lambda: capi.check(lib.idocp_rbd_rollout_footholds_device(h, n, steps, active, 0.05, 0.01, C.byref(fio), 0, 0), "rollout_footholds"),
+    }
+    for row, launch in launches.items():
+        if wanted and row not in wanted:
+            continue
+        measure(row, launch)
+        res[row]["steps"] = steps
+        res[row]["ms_per_step"] = round(res[row]["ms_median"] / steps, 4)
+    if "rollout" in res and "rollout_footholds" in res:
+        res["rollout_footholds"]["ratio_to_rollout"] = round(res["rollout_footholds"]["ms_median"] / res["rollout"]["ms_median"], 3)
+        res["rollout_footholds"]["latch_ms_per_step"] = round((res["rollout_footholds"]["ms_median"] - res["rollout"]["ms_median"]) / steps, 4)
+    out = np.zeros((n, nf * nv))
+    capi.check(lib.idocp_device_download(out.ctypes.data, dev["jacobian"], out.nbytes), "download")
+    if "kin_all" in res:
+        res["kin_finite"] = bool(np.isfinite(out).all())
+    for d in dev.values():
+        lib.idocp_device_free(d)
 
 
 def sample_rows(wanted, lib, rt, h, stream, m, n, measure, res):
@@ -264,6 +339,8 @@ def main():
         score_rows(args, wanted, lib, rt, h, stream, m, n, host, measure, res)
     if not wanted or set(wanted) & set(SAMPLE_ROWS):
         sample_rows(wanted, lib, rt, h, stream, m, n, measure, res)
+    if not wanted or set(wanted) & set(KIN_ROWS):
+        kin_rows(wanted, lib, rt, h, stream, m, n, host, measure, res)
     ran = [k for k in res if isinstance(res[k], dict)]
     for key, src, width, rows in (("tau_finite", "tau", nv, ("stage_", "impulse_")), ("fd_a_finite", "fd_a", nv, ("fd_",)),
                                   ("policy_u_finite", "u_out", m.nu, ("policy_", "fd_step_closed_loop"))):
