@@ -112,6 +112,13 @@ class RbdFdIO(C.Structure):
     _fields_ = [(name, C.c_void_p) for name in INPUTS + OUTPUTS]
 
 
+class RbdFddIO(C.Structure):
+    """idocp_rbd_fdd_io_t: inputs and requested outputs of idocp_rbd_forward_dynamics_derivatives_batch(_device); a pointer left at None is NULL"""
+    INPUTS = ("q", "v", "u", "contact_points")
+    OUTPUTS = ("a", "f", "da_dq", "da_dv", "da_du", "df_dq", "df_dv", "df_du", "A", "B")
+    _fields_ = [(name, C.c_void_p) for name in INPUTS + OUTPUTS]
+
+
 class RbdPolicy(C.Structure):
     """idocp_rbd_policy_t: the affine feedback policy of idocp_rbd_feedback_torques_batch(_device) / idocp_rbd_rollout_policy(_device); a pointer left at
     None is NULL"""
@@ -325,6 +332,16 @@ def _proto(lib):
     lib.idocp_rbd_forward_dynamics_batch.restype = ci
     lib.idocp_rbd_forward_dynamics_batch_device.argtypes = [vp, ci, ci, c_int_p, cd, cd, P(RbdFdIO)]
     lib.idocp_rbd_forward_dynamics_batch_device.restype = ci
+    lib.idocp_rbd_forward_dynamics_derivatives_batch.argtypes = [vp, ci, ci, c_int_p, cd, cd, P(RbdFddIO)]
+    lib.idocp_rbd_forward_dynamics_derivatives_batch.restype = ci
+    lib.idocp_rbd_forward_dynamics_derivatives_batch_device.argtypes = [vp, ci, ci, c_int_p, cd, cd, P(RbdFddIO)]
+    lib.idocp_rbd_forward_dynamics_derivatives_batch_device.restype = ci
+    for form in ("", "_device"):
+        f = getattr(lib, "idocp_rbd_linearize_rollout" + form)
+        f.argtypes = [vp, ci, ci, c_int_p, cd, cd] + [vp] * 6 + [ci]
+        f.restype = ci
+    lib.idocp_rbd_set_derivatives_chunk.argtypes = [vp, ci]      # (a test hook of the library, not in idocp_hip.h)
+    lib.idocp_rbd_set_derivatives_chunk.restype = ci
     lib.idocp_rbd_rollout.argtypes = [vp, ci, ci, c_int_p, cd, cd] + [vp] * 6 + [ci]
     lib.idocp_rbd_rollout.restype = ci
     lib.idocp_rbd_rollout_device.argtypes = [vp, ci, ci, c_int_p, cd, cd] + [vp] * 6 + [ci]

@@ -227,5 +227,35 @@ __host__ __device__ __forceinline__ void lieDIntegrateArg0(const double* R, cons
   }
 }
 
+// pinocchio::dIntegrate(q, v, ARG1) for the free-flyer: the right Jacobian of exp6 at v = (lin, ang), column r = d/d eps of
+// log6(exp6(v)^-1 exp6(v + eps e_r)) (6x6 column-major).  Jr(v) = Jl(-v) with the left Jacobian in closed form, Jl = [[Jl3, Q], [0, Jl3]]
+// (Barfoot, State Estimation for Robotics, eq. 7.85-7.86); below 0.05 rad the four coefficients come from their series (the closed forms
+// cancel there; the first term left out is below 1e-18 of the leading one).
+__host__ __device__ __forceinline__ void lieDIntegrateArg1(const double* vin, double* J) {
+  const double rho[3] = {-vin[0], -vin[1], -vin[2]}, phi[3] = {-vin[3], -vin[4], -vin[5]};
+  const double t2 = phi[0] * phi[0] + phi[1] * phi[1] + phi[2] * phi[2], t = sqrt(t2);
+  double b, c, c3, c4;      // (1 - cos t) / t^2, (t - sin t) / t^3, (1 - t^2 / 2 - cos t) / t^4, (t - sin t - t^3 / 6) / t^5
+  if (t < 0.05) {
+    b = 0.5 - t2 * (1.0 / 24 - t2 * (1.0 / 720 - t2 * (1.0 / 40320 - t2 / 3628800)));
+    c = 1.0 / 6 - t2 * (1.0 / 120 - t2 * (1.0 / 5040 - t2 * (1.0 / 362880 - t2 / 39916800)));
+    c3 = -1.0 / 24 + t2 * (1.0 / 720 - t2 * (1.0 / 40320 - t2 * (1.0 / 3628800 - t2 / 479001600)));
+    c4 = -1.0 / 120 + t2 * (1.0 / 5040 - t2 * (1.0 / 362880 - t2 * (1.0 / 39916800 - t2 / 6227020800.0)));
+  } else {
+    const double st = sin(t), ct = cos(t), t4 = t2 * t2;
+    b = (1 - ct) / t2; c = (t - st) / (t2 * t); c3 = (1 - 0.5 * t2 - ct) / t4; c4 = (t - st - t2 * t / 6) / (t4 * t);
+  }
+  double P[9], Rh[9], P2[9], PR[9], RP[9], PRP[9], PPR[9], RPP[9], PRPP[9], PPRP[9];
+  lieSkew(phi, P); lieSkew(rho, Rh);
+  lieMatmul3(P, P, P2); lieMatmul3(P, Rh, PR); lieMatmul3(Rh, P, RP); lieMatmul3(PR, P, PRP);
+  lieMatmul3(P2, Rh, PPR); lieMatmul3(Rh, P2, RPP); lieMatmul3(PRP, P, PRPP); lieMatmul3(P, PRP, PPRP);
+  const double c5 = 0.5 * (c3 - 3 * c4);
+  for (int r = 0; r < 3; ++r) for (int s = 0; s < 3; ++s) {
+    const int i = 3 * r + s;
+    const double j3 = (r == s ? 1.0 : 0.0) + b * P[i] + c * P2[i];
+    const double qb = 0.5 * Rh[i] + c * (PR[i] + RP[i] + PRP[i]) - c3 * (PPR[i] + RPP[i] - 3 * PRP[i]) - c5 * (PRPP[i] + PPRP[i]);
+    J[r + 6 * s] = j3; J[(3 + r) + 6 * (3 + s)] = j3; J[r + 6 * (3 + s)] = qb; J[(3 + r) + 6 * s] = 0.0;
+  }
+}
+
 }  // namespace idocp_dev
 #endif  // IDOCP_DEV_LIE_HPP_

@@ -14,6 +14,7 @@
 #include "host_util.hpp"
 #include "idocp_hip.h"
 #include "model_shapes.hpp"
+#include "rbd_fdd_plan.hpp"
 #include "rbd_foothold_plan.hpp"
 #include "rbd_launch.hpp"
 #include "rbd_stage.hpp"
@@ -49,6 +50,9 @@ struct idocp_rbd {
   RbdBuffer fd_chain;                 // chain, forward dynamics: [a = 0 | h | dtau_dq | dtau_dv | M] of the sweep at a = 0
   RbdBuffer u_buf;                    // closed-loop rollout without u_traj: the torques of the current step, [n][nu]
   RbdBuffer reduce;                   // sampling: the chunk partials of the sums over the sample axis, RBD_PARTIAL_STRIDE per (row, chunk)
+  RbdBuffer fdd;                      // forward-dynamics derivatives: what one pass keeps between its launches (rbd_fdd_plan.hpp), at most 256 MiB
+  int fdd_limit = 0;                  // idocp_rbd_set_derivatives_chunk (a test hook, not in idocp_hip.h): bound on the samples of a pass (0: none)
+  RbdBuffer lin;                      // rollout linearisation at a touchdown: [v_pre [n][nv] | E [n][2 nv * 2 nv]]
 };
 
 // the objective of the rollout scoring: the plan of rbd_objective.hpp and its three pieces in ONE block of device memory
@@ -462,6 +466,106 @@ int launchMean(idocp_rbd* h, int n, int rows, int m, const double* weights, cons
   return IDOCP_OK;
 }
 
+// ---- derivatives of the forward dynamics ----
+
+int checkDerivatives(const char* who, const idocp_rbd* h, int mode, int n, const int* active, double time_step, double dt, const idocp_rbd_fdd_io_t* io) {
+  const std::string w(who);
+  if (!h || !io) { set_last_error(w + ": null handle or io"); return IDOCP_E_ARG; }
+  if (!h->quadruped && (io->f || io->contact_points || io->df_dq || io->df_dv || io->df_du)) {
+    set_last_error(w + ": a fixed-base chain has no contacts (f, contact_points and the contact outputs df_dq, df_dv, df_du must be NULL)");
+    return IDOCP_E_ARG;
+  }
+  int rc = checkForward(who, h, mode, n, active, dt, io->q, io->v, false); if (rc) return rc;
+  if (mode == IDOCP_RBD_IMPULSE && (io->u || io->da_du || io->df_du || io->B)) {
+    set_last_error(w + ": IMPULSE mode takes no torques (u, da_du, df_du and B must be NULL)"); return IDOCP_E_ARG;
+  }
+  if (mode == IDOCP_RBD_STAGE) { rc = checkStageContacts(who, h, active, time_step, io->contact_points); if (rc) return rc; }
+  return IDOCP_OK;
+}
+
+// io: device pointers.  Per pass of the plan: the forward launch, the inverse launch at its solution, the products.
+int launchDerivatives(idocp_rbd* h, int mode, int n, int mask, double time_step, double dt, const idocp_rbd_fdd_io_t& io) {
+  const size_t nq = h->model.nq, nv = h->model.nv, nu = h->model.nu, nf = h->quadruped ? 3 * (size_t)h->model.ncontacts : 0, nx = 2 * nv;
+  const idocp_host::FddPlan p = idocp_host::fddPlan((int)nv, (int)nf, n, h->fdd_limit);
+  int rc = h->fdd.grow(p.total, h->stream); if (rc) return rc;
+  double* const S = h->fdd.ptr;
+  const DevModel* d_m = static_cast<const DevModel*>(h->d_model);
+  auto at = [](double* x, size_t off) { return x ? x + off : nullptr; };
+  for (int i = 0; i < p.nchunks; ++i) {
+    const size_t F = (size_t)p.first(i);
+    const int cnt = p.count(i, n);
+    idocp_rbd_fd_io_t fd = idocp_rbd_fd_io_t();
+    fd.q = io.q + F * nq; fd.v = io.v + F * nv;
+    fd.u = io.u ? io.u + F * nu : nullptr;
+    fd.contact_points = io.contact_points ? io.contact_points + F * nf : nullptr;
+    fd.a = S + p.a; fd.f = h->quadruped ? S + p.f : nullptr;
+    rc = launchForward(h, mode, cnt, mask, time_step, dt, fd); if (rc) return rc;
+    RbdFddArgs g;
+    g.q = fd.q; g.v = fd.v; g.a = S + p.a; g.f = fd.f; g.dtau_dq = S + p.dtau_dq; g.dtau_dv = S + p.dtau_dv;
+    g.dCdq = S + p.dCdq; g.dCdv = S + p.dCdv; g.MJtJinv = S + p.MJtJinv;
+    g.a_out = at(io.a, F * nv); g.f_out = at(io.f, F * nf);
+    g.da_dq = at(io.da_dq, F * nv * nv); g.da_dv = at(io.da_dv, F * nv * nv); g.da_du = at(io.da_du, F * nv * nu);
+    g.df_dq = at(io.df_dq, F * nf * nv); g.df_dv = at(io.df_dv, F * nf * nv); g.df_du = at(io.df_du, F * nf * nu);
+    g.A = at(io.A, F * nx * nx); g.B = at(io.B, F * nx * nu);
+    g.dt = dt;
+    if (h->quadruped) {
+      idocp_rbd_io_t b = idocp_rbd_io_t();
+      b.q = fd.q; b.v = fd.v; b.a = S + p.a; b.f = S + p.f; b.contact_points = fd.contact_points;
+      b.dtau_dq = S + p.dtau_dq; b.dtau_dv = S + p.dtau_dv; b.dCdq = S + p.dCdq; b.dCdv = S + p.dCdv; b.MJtJinv = S + p.MJtJinv;
+      rbdBatchQuadruped(d_m, h->d_frames, b, cnt, mode, mask, (mode == IDOCP_RBD_STAGE && !(time_step > 0.0)) ? 1.0 : time_step, h->stream);
+      HIP_TRY(hipGetLastError());
+      rbdFddQuadruped(d_m, h->d_frames, g, cnt, mode, mask, h->stream);
+    } else {
+      chainFn(h->model.nv)(d_m, cnt, fd.q, fd.v, S + p.a, S + p.tau, S + p.dtau_dq, S + p.dtau_dv, S + p.MJtJinv, h->zaxes, h->stream);
+      HIP_TRY(hipGetLastError());
+      rbdFddChain(h->model.nv, g, cnt, h->stream);
+    }
+    HIP_TRY(hipGetLastError());
+  }
+  return IDOCP_OK;
+}
+
+int checkLinearize(const char* who, idocp_rbd* h, int n, int steps, const int* active, double time_step, double dt, const double* contact_points,
+                   const double* q_traj, const double* v_traj) {
+  if (steps < 1) { set_last_error(std::string(who) + ": steps must be at least 1"); return IDOCP_E_ARG; }
+  int rc = checkForward(who, h, IDOCP_RBD_STAGE, n, active, dt, q_traj, v_traj, contact_points != nullptr); if (rc) return rc;
+  if (h->quadruped)
+    for (int k = 0; k < steps; ++k) { rc = checkStageContacts(who, h, active + (size_t)k * h->model.ncontacts, time_step, contact_points); if (rc) return rc; }
+  return IDOCP_OK;
+}
+
+// every pointer: device memory
+int linearizeDevice(idocp_rbd* h, int n, int steps, const int* active, double time_step, double dt, const double* u, const double* contact_points,
+                    const double* q_traj, const double* v_traj, double* A_traj, double* B_traj, int touchdown_impulse) {
+  const size_t nq = h->model.nq, nv = h->model.nv, nu = h->model.nu, nf = 3 * (size_t)h->model.ncontacts, N = (size_t)n, nx = 2 * nv;
+  if (!A_traj && !B_traj) return IDOCP_OK;
+  for (int k = 0; k < steps; ++k) {
+    const int mask = h->quadruped ? maskOf(h, active + (size_t)k * h->model.ncontacts) : 0;
+    const int next = (h->quadruped && k + 1 < steps) ? maskOf(h, active + (size_t)(k + 1) * h->model.ncontacts) : 0;
+    const int touchdown = touchdown_impulse ? (next & ~mask) : 0;      // the impulse in front of step k + 1
+    const double *qk = q_traj + k * N * nq, *vk = v_traj + k * N * nv;
+    const double* uk = u ? u + k * N * nu : nullptr;
+    const double* pk = contact_points ? contact_points + k * N * nf : nullptr;
+    idocp_rbd_fdd_io_t io = idocp_rbd_fdd_io_t();
+    io.q = qk; io.v = vk; io.u = uk; io.contact_points = pk;
+    io.A = A_traj ? A_traj + k * N * nx * nx : nullptr;
+    io.B = B_traj ? B_traj + k * N * nx * nu : nullptr;
+    int rc = launchDerivatives(h, IDOCP_RBD_STAGE, n, mask, time_step, dt, io); if (rc) return rc;
+    if (!touchdown) continue;
+    rc = h->lin.grow(N * nv + N * nx * nx, h->stream); if (rc) return rc;
+    double *v_pre = h->lin.ptr, *E = v_pre + N * nv;
+    idocp_rbd_fd_io_t fd = idocp_rbd_fd_io_t();
+    fd.q = qk; fd.v = vk; fd.u = uk; fd.contact_points = pk; fd.v_next = v_pre;      // the pre-impulse velocity v_k + dt a, recomputed
+    rc = launchForward(h, IDOCP_RBD_STAGE, n, mask, time_step, dt, fd); if (rc) return rc;
+    idocp_rbd_fdd_io_t imp = idocp_rbd_fdd_io_t();
+    imp.q = qk + N * nq; imp.v = v_pre; imp.A = E;
+    rc = launchDerivatives(h, IDOCP_RBD_IMPULSE, n, touchdown, time_step, dt, imp); if (rc) return rc;
+    rbdFddImpulseProduct((int)nx, (int)nu, E, io.A, io.B, n, h->stream);
+    HIP_TRY(hipGetLastError());
+  }
+  return IDOCP_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -511,6 +615,8 @@ void idocp_rbd_destroy(idocp_rbd_t* h) {
   h->fd_chain.release();
   h->u_buf.release();
   h->reduce.release();
+  h->fdd.release();
+  h->lin.release();
   if (h->stream) (void)hipStreamDestroy(h->stream);
   delete h;
 }
@@ -577,6 +683,77 @@ int idocp_rbd_forward_dynamics_batch(idocp_rbd_t* h, int mode, int n, const int*
   rc = stageIn(h, p); if (rc) return rc;
   rc = launchForward(h, mode, n, h->quadruped ? maskOf(h, active) : 0, time_step, dt, d); if (rc) return rc;
   return stageOut(h, p);
+}
+
+int idocp_rbd_forward_dynamics_derivatives_batch_device(idocp_rbd_t* h, int mode, int n, const int* active, double time_step, double dt,
+                                                        const idocp_rbd_fdd_io_t* io) {
+  int rc = checkDerivatives("idocp_rbd_forward_dynamics_derivatives_batch_device", h, mode, n, active, time_step, dt, io); if (rc) return rc;
+  HIP_TRY(hipSetDevice(h->device));
+  return launchDerivatives(h, mode, n, h->quadruped ? maskOf(h, active) : 0, time_step, dt, *io);
+}
+
+int idocp_rbd_forward_dynamics_derivatives_batch(idocp_rbd_t* h, int mode, int n, const int* active, double time_step, double dt,
+                                                 const idocp_rbd_fdd_io_t* io) {
+  int rc = checkDerivatives("idocp_rbd_forward_dynamics_derivatives_batch", h, mode, n, active, time_step, dt, io); if (rc) return rc;
+  HIP_TRY(hipSetDevice(h->device));
+  const size_t nq = h->model.nq, nv = h->model.nv, nu = h->model.nu, nf = 3 * (size_t)h->model.ncontacts, N = (size_t)n, nx = 2 * nv;
+  StagePlan p;
+  idocp_rbd_fdd_io_t d;
+  p.in(io->q, N * nq, &d.q);
+  p.in(io->v, N * nv, &d.v);
+  p.in(io->u, N * nu, &d.u);
+  p.in(io->contact_points, N * nf, &d.contact_points);
+  p.out(io->a, N * nv, &d.a);
+  p.out(io->f, N * nf, &d.f);
+  p.out(io->da_dq, N * nv * nv, &d.da_dq);
+  p.out(io->da_dv, N * nv * nv, &d.da_dv);
+  p.out(io->da_du, N * nv * nu, &d.da_du);
+  p.out(io->df_dq, N * nf * nv, &d.df_dq);
+  p.out(io->df_dv, N * nf * nv, &d.df_dv);
+  p.out(io->df_du, N * nf * nu, &d.df_du);
+  p.out(io->A, N * nx * nx, &d.A);
+  p.out(io->B, N * nx * nu, &d.B);
+  rc = stageIn(h, p); if (rc) return rc;
+  rc = launchDerivatives(h, mode, n, h->quadruped ? maskOf(h, active) : 0, time_step, dt, d); if (rc) return rc;
+  return stageOut(h, p);
+}
+
+int idocp_rbd_linearize_rollout_device(idocp_rbd_t* h, int n, int steps, const int* active, double time_step, double dt, const double* u_traj,
+                                       const double* contact_points, const double* q_traj, const double* v_traj, double* A_traj, double* B_traj,
+                                       int touchdown_impulse) {
+  int rc = checkLinearize("idocp_rbd_linearize_rollout", h, n, steps, active, time_step, dt, contact_points, q_traj, v_traj); if (rc) return rc;
+  HIP_TRY(hipSetDevice(h->device));
+  return linearizeDevice(h, n, steps, active, time_step, dt, u_traj, contact_points, q_traj, v_traj, A_traj, B_traj, touchdown_impulse);
+}
+
+int idocp_rbd_linearize_rollout(idocp_rbd_t* h, int n, int steps, const int* active, double time_step, double dt, const double* u_traj,
+                                const double* contact_points, const double* q_traj, const double* v_traj, double* A_traj, double* B_traj,
+                                int touchdown_impulse) {
+  int rc = checkLinearize("idocp_rbd_linearize_rollout", h, n, steps, active, time_step, dt, contact_points, q_traj, v_traj); if (rc) return rc;
+  HIP_TRY(hipSetDevice(h->device));
+  const size_t nq = h->model.nq, nv = h->model.nv, nu = h->model.nu, nf = 3 * (size_t)h->model.ncontacts, N = (size_t)n, S = (size_t)steps, nx = 2 * nv;
+  StagePlan p;
+  const double *d_u, *d_points, *d_q, *d_v;
+  double *d_A, *d_B;
+  p.in(u_traj, S * N * nu, &d_u);
+  p.in(contact_points, S * N * nf, &d_points);
+  p.in(q_traj, (S + 1) * N * nq, &d_q);
+  p.in(v_traj, (S + 1) * N * nv, &d_v);
+  p.out(A_traj, S * N * nx * nx, &d_A);
+  p.out(B_traj, S * N * nx * nu, &d_B);
+  rc = stageIn(h, p); if (rc) return rc;
+  rc = linearizeDevice(h, n, steps, active, time_step, dt, d_u, d_points, d_q, d_v, d_A, d_B, touchdown_impulse); if (rc) return rc;
+  return stageOut(h, p);
+}
+
+// A test hook, deliberately NOT in include/idocp_hip.h: an upper bound on the samples one pass of the derivative call takes (0, the default:
+// only the 256 MiB cap bounds a pass), handed to idocp_host::fddPlan as its `limit` argument.  It changes the number of launches, never a bit.
+int idocp_rbd_set_derivatives_chunk(idocp_rbd_t* h, int max_samples);
+int idocp_rbd_set_derivatives_chunk(idocp_rbd_t* h, int max_samples) {
+  if (!h) { set_last_error("idocp_rbd_set_derivatives_chunk: null handle"); return IDOCP_E_ARG; }
+  if (max_samples < 0) { set_last_error("idocp_rbd_set_derivatives_chunk: max_samples must not be negative (0: no bound)"); return IDOCP_E_ARG; }
+  h->fdd_limit = max_samples;
+  return IDOCP_OK;
 }
 
 int idocp_rbd_rollout_device(idocp_rbd_t* h, int n, int steps, const int* active, double time_step, double dt, const double* u, const double* contact_points,

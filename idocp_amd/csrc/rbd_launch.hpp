@@ -91,5 +91,20 @@ void rbdKinematicsQuadruped(const DevModel* m, const RbdFrames* frames, const id
 void rbdLatchQuadruped(const DevModel* m, const RbdFrames* frames, const double* q, const double* prev, double* points, int carry_mask, int n,
                        hipStream_t st);
 
+// Derivatives of the forward dynamics (rbd_fd_derivatives_kernel.hip): the last launch of the composition.  Every pointer: DEVICE memory.  Reads the
+// forward solution a [n][nv], f [n][nf] and the terms of the inverse call at (q, v, a, f) -- dtau_dq, dtau_dv [n][nv * nv], dCdq, dCdv
+// [n][nf * nv], the slots of MJtJinv [n][(nv + nf)^2]; on a chain MJtJinv is M = dtau_da [n][nv * nv] and f, dCdq, dCdv are not read -- and v
+// and q for the retraction and the correction of dC (the kernel's head has it); writes the outputs that are not NULL.  One launch, one wavefront per sample (chain: one lane per sample), any n.
+struct RbdFddArgs {
+  const double *q, *v, *a, *f, *dtau_dq, *dtau_dv, *dCdq, *dCdv, *MJtJinv;
+  double *a_out, *f_out, *da_dq, *da_dv, *da_du, *df_dq, *df_dv, *df_du, *A, *B;
+  double dt;
+};
+void rbdFddQuadruped(const DevModel* m, const RbdFrames* frames, const RbdFddArgs& a, int n, int mode, int active_mask, hipStream_t st);
+void rbdFddChain(int nv, const RbdFddArgs& a, int n, hipStream_t st);
+// The impulse product of the rollout linearisation, the same file: A [n][nx * nx] = E A and B [n][nx * nu] = E B in place, E [n][nx * nx], all
+// column-major, nx <= 36, nu <= 12; A or B may be NULL.  One wavefront per sample, fixed order of summation.  One launch.
+void rbdFddImpulseProduct(int nx, int nu, const double* E, double* A, double* B, int n, hipStream_t st);
+
 }  // namespace idocp_dev
 #endif  // IDOCP_RBD_LAUNCH_HPP_

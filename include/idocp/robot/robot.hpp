@@ -191,6 +191,33 @@ class Robot {
     f.resize(model_.ncontacts);
     for (int c = 0; c < model_.ncontacts; ++c) for (int k = 0; k < 3; ++k) f[c][k] = fo[3 * c + k];
   }
+  // The linearised Euler step, an ADDITION like forwardDynamics: A (2 nv x 2 nv) and B (2 nv x nu), the Jacobians of x_next = (q (+) dt v, v + dt a)
+  // with respect to the tangent [dq; dv] and to u at the forward solution (a, f), which is returned as well.  ONE n = 1 call of
+  // idocp_rbd_forward_dynamics_derivatives_batch (idocp_hip.h has the definitions).
+  void forwardDynamicsDerivatives(const Eigen::VectorXd& q, const Eigen::VectorXd& v, const Eigen::VectorXd& u, const ContactStatus& contact_status,
+                                  const double time_step, const double dt, Eigen::VectorXd& a, std::vector<Eigen::Vector3d>& f, Eigen::MatrixXd& A,
+                                  Eigen::MatrixXd& B) {
+    sized(q, model_.nq, "q"); sized(v, model_.nv, "v"); sized(u, model_.nu, "u");
+    if (a.size() != model_.nv) a.resize(model_.nv);
+    const size_t nx = 2 * (size_t)model_.nv;
+    std::vector<double> Ao(nx * nx), Bo(nx * model_.nu);
+    double pts[3 * IDOCP_MAX_CONTACTS] = {}, fo[3 * IDOCP_MAX_CONTACTS] = {};
+    int act[IDOCP_MAX_CONTACTS] = {};
+    idocp_rbd_fdd_io_t io = idocp_rbd_fdd_io_t();
+    io.q = q.data(); io.v = v.data(); io.u = u.data(); io.a = a.data(); io.A = Ao.data(); io.B = Bo.data();
+    if (model_.ncontacts > 0) {
+      activeOf(contact_status.isContactActive(), act);
+      for (int c = 0; c < model_.ncontacts; ++c) for (int k = 0; k < 3; ++k) pts[3 * c + k] = contact_status.contactPoints()[c][k];
+      io.contact_points = pts; io.f = fo;
+    }
+    if (!rbd_.h) ok(idocp_rbd_create(&model_, 0, &rbd_.h));
+    ok(idocp_rbd_forward_dynamics_derivatives_batch(rbd_.h, IDOCP_RBD_STAGE, 1, model_.ncontacts > 0 ? act : nullptr, time_step, dt, &io));
+    f.resize(model_.ncontacts);
+    for (int c = 0; c < model_.ncontacts; ++c) for (int k = 0; k < 3; ++k) f[c][k] = fo[3 * c + k];
+    A.resize((int)nx, (int)nx); B.resize((int)nx, model_.nu);
+    for (size_t j = 0; j < nx; ++j) for (size_t i = 0; i < nx; ++i) A((int)i, (int)j) = Ao[i + nx * j];
+    for (size_t j = 0; j < (size_t)model_.nu; ++j) for (size_t i = 0; i < nx; ++i) B((int)i, (int)j) = Bo[i + nx * j];
+  }
   // (dv, lambda) for which RNEAImpulse vanishes and the velocity of the impulse_status's frames is zero at v + dv
   void impulseDynamics(const Eigen::VectorXd& q, const Eigen::VectorXd& v, const ImpulseStatus& impulse_status, Eigen::VectorXd& dv,
                        std::vector<Eigen::Vector3d>& lambda) {

@@ -842,6 +842,56 @@ int idocp_rbd_rollout(idocp_rbd_t* h, int n, int steps, const int* active, doubl
 int idocp_rbd_rollout_device(idocp_rbd_t* h, int n, int steps, const int* active, double time_step, double dt, const double* u,
                              const double* contact_points, double* q_traj, double* v_traj, double* a_traj, double* f_traj, int touchdown_impulse);
 
+/* ---- Derivatives of the forward dynamics and the linearised Euler step (an ADDITION like the forward dynamics; rbd_fd_derivatives_kernel.hip).
+ * At the forward solution (a, f) of [M J^T; J 0] [a; -f] = [S^T u - h; -b], with theta = q (in the tangent q (+) eps e_r of
+ * idocp_model_integrate_configuration) or v, differentiating ID(q, v, a, f) = S^T u and C(q, v, a) = 0 gives
+ *   d[a; -f]/dtheta = -MJtJinv [dID/dtheta ; dC/dtheta],      d[a; -f]/du = MJtJinv[:, 0 : nv] S^T,
+ * every block the one idocp_rbd_contact_dynamics_batch returns at (q, v, a, f), over the active rows.  The call is that composition: the forward
+ * launch, the inverse launch at its solution into scratch the handle owns, and one kernel that forms the products.  The scratch only grows
+ * and is CAPPED at 256 MiB whatever n is: a larger call takes the sample axis in several passes on the handle's stream.
+ * Inputs are those of idocp_rbd_fd_io_t.  Every output is optional and column-major; a NULL output is not stored (the products are formed
+ * all the same, so that a sample's bits do not depend on what was asked for):
+ *   a, f                 as idocp_rbd_forward_dynamics_batch returns them, bit for bit
+ *   da_dq, da_dv         [n][nv * nv]            da_du  [n][nv * nu]
+ *   df_dq, df_dv         [n][3 ncontacts * nv]   df_du  [n][3 ncontacts * nu]; the rows of inactive contacts are zero; the sign is that of f
+ *   A [n][2 nv * 2 nv], B [n][2 nv * nu]: the Jacobians of the OCP's explicit Euler step x_next = (q (+) dt v, v + dt a) with respect to
+ *     x = [dq; dv] and u.  Column r of the top rows of A is d/d eps [(q (+) eps e_r (+) dt v) (-) (q (+) dt v)] at eps = 0 -- it lives in the
+ *     tangent at q_next; (+) / (-) are idocp_model_integrate_configuration / idocp_model_subtract_configuration.  The bottom rows of A are
+ *     [dt da_dq, I + dt da_dv]; B = [0; dt da_du].  On a chain the top rows of A are [I, dt I].
+ * IMPULSE mode: a is dv and f is lambda; u and the *_du outputs must be NULL; A is the Jacobian of (q, v + dv), top rows [I 0]; B must be NULL.
+ * A fixed-base chain takes STAGE mode only (da_dq = -M^-1 dtau/dq, da_dv = -M^-1 dtau/dv, da_du = M^-1), and its contact outputs must be NULL.
+ * Where M or J M^-1 J^T of a sample is not positive definite, or an input of that sample is not finite, every output of that sample is NaN and
+ * no other sample is touched.  A sample's bits depend neither on n, nor on the outputs that were asked for, nor on how the sample axis was cut.
+ * No input may overlap an output.  IDOCP_E_ARG with a text in idocp_last_error() for everything refused. */
+typedef struct idocp_rbd_fdd_io {
+  const double *q, *v, *u, *contact_points;   /* as in idocp_rbd_fd_io_t */
+  double *a, *f;
+  double *da_dq, *da_dv, *da_du;
+  double *df_dq, *df_dv, *df_du;
+  double *A, *B;
+} idocp_rbd_fdd_io_t;
+/* ADDITION.  Host pointers; stages through the handle's buffers and returns when the outputs are in place. */
+int idocp_rbd_forward_dynamics_derivatives_batch(idocp_rbd_t* h, int mode, int n, const int* active, double time_step, double dt,
+                                                 const idocp_rbd_fdd_io_t* io);
+/* ADDITION.  Device pointers; asynchronous on idocp_rbd_stream(h); allocates only when the scratch has to grow. */
+int idocp_rbd_forward_dynamics_derivatives_batch_device(idocp_rbd_t* h, int mode, int n, const int* active, double time_step, double dt,
+                                                        const idocp_rbd_fdd_io_t* io);
+/* ADDITION.  Linearises a trajectory that idocp_rbd_rollout / _policy / _footholds has ALREADY produced, about the torques that were applied:
+ *   u_traj [steps][n][nu] (NULL = 0), contact_points [steps][n][ncontacts][3], q_traj [steps + 1][n][nq], v_traj [steps + 1][n][nv]: inputs;
+ *   A_traj [steps][n][2 nv * 2 nv], B_traj [steps][n][2 nv * nu]: outputs, step-major, column-major blocks; either may be NULL.
+ * A_traj[k] is the Jacobian of STORED slice k + 1 with respect to STORED slice k, so that the product of the A_traj[k] is the sensitivity of what
+ * the rollout stored.  Where step k + 1 carries a touchdown impulse (the rule of idocp_rbd_rollout, touchdown_impulse != 0), stored slice k + 1 is
+ * post-impulse: A_traj[k] = E A_k and B_traj[k] = E B_k, with A_k, B_k of the call above on slice k and E the IMPULSE-mode A of that call at
+ * (q_traj[k + 1], v_traj[k] + dt a) -- the pre-impulse velocity is recomputed, not read from slice k + 1 -- with the newly active contacts.
+ * Elsewhere E = I.  The contact points are held FIXED: the latch of idocp_rbd_rollout_footholds is not differentiated, nor is the clamp of a
+ * policy.  Asynchronous on the handle's stream in the device form, without a synchronisation between the steps. */
+int idocp_rbd_linearize_rollout(idocp_rbd_t* h, int n, int steps, const int* active, double time_step, double dt, const double* u_traj,
+                                const double* contact_points, const double* q_traj, const double* v_traj, double* A_traj, double* B_traj,
+                                int touchdown_impulse);
+int idocp_rbd_linearize_rollout_device(idocp_rbd_t* h, int n, int steps, const int* active, double time_step, double dt, const double* u_traj,
+                                       const double* contact_points, const double* q_traj, const double* v_traj, double* A_traj, double* B_traj,
+                                       int touchdown_impulse);
+
 /* ---- Closed loop: the time-varying affine feedback policy of the solvers on the plant above (an ADDITION like the forward dynamics).  Before
  * every step
  *   u = clamp(u_ff[k] + K[k] [q (-) q_ref[k] ; v - v_ref[k]])

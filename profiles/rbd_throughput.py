@@ -11,7 +11,7 @@ weight, the joint limits and the linearized cone (score_sK_all_linearized) or th
 its ratio to that copy.  The sample_* rows are the sampling calls on 16 steps of the 12 torques: sample_perturb (idocp_rbd_perturb_torques_device writes
 u_samples [16][n][12]), sample_mean (idocp_rbd_weighted_mean_device reads an array of that shape) -- both read against sample_copy, a device-to-device
 copy of that array -- and sample_weights (idocp_rbd_importance_weights_device: cost and violation in, weights out) against sample_weights_copy, a copy of
-those three arrays.  The kin_* rows are idocp_rbd_contact_kinematics_batch_device: kin_points (q in, points out) and kin_all (q and v in, all four
+those three arrays.  The fdd_* rows are the forward-dynamics derivatives (fdd_rows has their description).  The kin_* rows are idocp_rbd_contact_kinematics_batch_device: kin_points (q in, points out) and kin_all (q and v in, all four
 outputs), each against kin_*_copy, a device-to-device copy of the bytes the call reads and writes.  rollout is idocp_rbd_rollout_device over
 ROLLOUT_STEPS open-loop steps with every contact active and no touchdown impulse, rollout_footholds the same schedule through
 idocp_rbd_rollout_footholds_device (one latch launch more per step); both carry ms_per_step.
@@ -237,6 +237,91 @@ def score_rows(args, wanted, lib, rt, h, stream, m, n, host, measure, res):
         lib.idocp_rbd_objective_destroy(o)
 
 
+FDD_ROWS = ("fdd_fd_stage_a_f", "fdd_batch_scratch", "fdd_all", "fdd_A_B", "fdd_all_but_A", "fdd_fd_impulse", "fdd_batch_impulse_scratch", "fdd_impulse_all",
+            "fdd_linearize_s16")
+FDD_STEPS = 16
+
+
+def fdd_rows(wanted, lib, h, m, n, dev, active, measure, res):
+    """the fdd_* rows: idocp_rbd_forward_dynamics_derivatives_batch_device with every output and with A, B alone, beside the two launches it is
+    made of in the SAME run -- the forward call (a, f out) and the inverse call with the five scratch outputs -- and a 16-step
+    idocp_rbd_linearize_rollout_device on the same slices repeated (no touchdown: the status is constant).  fdd_ratio_*: the whole call over
+    the sum of its two existing launches; what is above 1 is the new kernel.  Three rows take the new kernel's serial sections apart: fdd_all_but_A
+    skips the lane-0 retraction Jacobians (they run for A alone); the IMPULSE call (fdd_impulse_all beside fdd_fd_impulse and
+    fdd_batch_impulse_scratch) has neither them nor the 36-lane correction sweep, only the product loop and the stores."""
+    nv, nq, nu, nf, nx = m.nv, m.nq, m.nu, 3 * m.ncontacts, 2 * m.nv
+    own = {}
+
+    def room(name, doubles):
+        own[name] = C.c_void_p()
+        capi.check(lib.idocp_device_alloc(C.byref(own[name]), 8 * doubles), "alloc")
+        return own[name]
+
+    def want(name):
+        return not wanted or name in wanted
+
+    fd = capi.RbdFdIO()
+    for k in capi.RbdFdIO.INPUTS:
+        setattr(fd, k, dev[k])
+    fd.a, fd.f = dev["fd_a"], dev["fd_f"]
+    if want("fdd_fd_stage_a_f"):
+        measure("fdd_fd_stage_a_f", lambda: capi.check(lib.idocp_rbd_forward_dynamics_batch_device(h, capi.RBD_STAGE, n, active, 0.05, 0.01, C.byref(fd)), "fd"))
+    if want("fdd_batch_scratch"):
+        io = capi.RbdIO()
+        for k in capi.RbdIO.INPUTS + ("dtau_dq", "dtau_dv", "dCdq", "dCdv", "MJtJinv"):
+            setattr(io, k, dev[k])
+        measure("fdd_batch_scratch", lambda: capi.check(lib.idocp_rbd_contact_dynamics_batch_device(h, capi.RBD_STAGE, n, active, 0.05, C.byref(io)), "batch"))
+    sizes = {"a": nv, "f": nf, "da_dq": nv * nv, "da_dv": nv * nv, "da_du": nv * nu, "df_dq": nf * nv, "df_dv": nf * nv, "df_du": nf * nu, "A": nx * nx, "B": nx * nu}
+    if want("fdd_fd_impulse"):
+        fi = capi.RbdFdIO()
+        fi.q, fi.v, fi.a, fi.f = dev["q"], dev["v"], dev["fd_a"], dev["fd_f"]
+        measure("fdd_fd_impulse", lambda: capi.check(lib.idocp_rbd_forward_dynamics_batch_device(h, capi.RBD_IMPULSE, n, active, 0.05, 0.01, C.byref(fi)), "fd"))
+    if want("fdd_batch_impulse_scratch"):
+        bi = capi.RbdIO()
+        for k in ("q", "v", "a", "f", "dtau_dq", "dtau_dv", "dCdq", "dCdv", "MJtJinv"):
+            setattr(bi, k, dev[k])
+        measure("fdd_batch_impulse_scratch", lambda: capi.check(lib.idocp_rbd_contact_dynamics_batch_device(h, capi.RBD_IMPULSE, n, active, 0.05, C.byref(bi)), "batch"))
+    no_torque = tuple(k for k in capi.RbdFddIO.OUTPUTS if k not in ("da_du", "df_du", "B"))
+    for name, mode, outputs in (("fdd_all", capi.RBD_STAGE, capi.RbdFddIO.OUTPUTS), ("fdd_A_B", capi.RBD_STAGE, ("A", "B")),
+                                ("fdd_all_but_A", capi.RBD_STAGE, tuple(k for k in capi.RbdFddIO.OUTPUTS if k != "A")),
+                                ("fdd_impulse_all", capi.RBD_IMPULSE, no_torque)):
+        if not want(name):
+            continue
+        io = capi.RbdFddIO()
+        for k in ("q", "v") if mode == capi.RBD_IMPULSE else capi.RbdFddIO.INPUTS:
+            setattr(io, k, dev[k])
+        for k in outputs:
+            setattr(io, k, own[k] if k in own else room(k, sizes[k] * n))
+        measure(name, lambda io=io, mode=mode: capi.check(lib.idocp_rbd_forward_dynamics_derivatives_batch_device(h, mode, n, active, 0.05, 0.01, C.byref(io)), name))
+    if want("fdd_linearize_s16"):
+        S = FDD_STEPS
+        slices = {"q": (S + 1, nq), "v": (S + 1, nv), "u": (S, nu), "contact_points": (S, nf)}
+        traj = {}
+        for k, (count, width) in slices.items():
+            traj[k] = room("traj_" + k, count * n * width)
+            for i in range(count):
+                capi.check(lib.idocp_device_copy(C.c_void_p(traj[k].value + 8 * i * n * width), dev[k], 8 * n * width), "copy")
+        At, Bt = room("A_traj", S * n * nx * nx), room("B_traj", S * n * nx * nu)
+        act = (C.c_int * (4 * S))(*([1] * (4 * S)))
+        measure("fdd_linearize_s16", lambda: capi.check(lib.idocp_rbd_linearize_rollout_device(h, n, S, act, 0.05, 0.01, traj["u"], traj["contact_points"], traj["q"],
+                                                                                                 traj["v"], At, Bt, 1), "linearize"))
+    parts = [res.get("fdd_fd_stage_a_f"), res.get("fdd_batch_scratch")]
+    if all(parts):
+        both = sum(x["ms_median"] for x in parts)
+        for name in ("fdd_all", "fdd_A_B"):
+            if name in res:
+                res["fdd_ratio_" + name[4:]] = round(res[name]["ms_median"] / both, 3)
+        if "fdd_all_but_A" in res:
+            res["fdd_ratio_all_but_A"] = round(res["fdd_all_but_A"]["ms_median"] / both, 3)
+        if "fdd_linearize_s16" in res:
+            res["fdd_ratio_linearize_per_step"] = round(res["fdd_linearize_s16"]["ms_median"] / FDD_STEPS / both, 3)
+    parts = [res.get("fdd_fd_impulse"), res.get("fdd_batch_impulse_scratch")]
+    if all(parts) and "fdd_impulse_all" in res:
+        res["fdd_ratio_impulse_all"] = round(res["fdd_impulse_all"]["ms_median"] / sum(x["ms_median"] for x in parts), 3)
+    for d in own.values():
+        lib.idocp_device_free(d)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--n", type=int, default=122880)
@@ -341,6 +426,8 @@ def main():
         sample_rows(wanted, lib, rt, h, stream, m, n, measure, res)
     if not wanted or set(wanted) & set(KIN_ROWS):
         kin_rows(wanted, lib, rt, h, stream, m, n, host, measure, res)
+    if not wanted or set(wanted) & set(FDD_ROWS):
+        fdd_rows(wanted, lib, h, m, n, dev, active, measure, res)
     ran = [k for k in res if isinstance(res[k], dict)]
     for key, src, width, rows in (("tau_finite", "tau", nv, ("stage_", "impulse_")), ("fd_a_finite", "fd_a", nv, ("fd_",)),
                                   ("policy_u_finite", "u_out", m.nu, ("policy_", "fd_step_closed_loop"))):
