@@ -619,6 +619,7 @@ static int setStageField(SplitSolutionC& x, const Robot& robot, const char* name
   else if (n == "beta") x.beta = toVec(value, nv);
   else if (n == "f") for (int c = 0; c < nc; ++c) x.f[c] = toVec(value + 3 * c, 3);
   else if (n == "mu") for (int c = 0; c < nc; ++c) x.mu[c] = toVec(value + 3 * c, 3);
+  else if (n == "xi") x.xi = toVec(value, 3 * nc);      // the multiplier of the switching constraint (tests/test_ocp_lqr_stage_host.py sets it back to zero)
   else return -1;
   return 0;
 }
