@@ -20,6 +20,7 @@
 #include "host_util.hpp"
 #include "idocp_hip.h"
 #include "model_shapes.hpp"
+#include "ocp_forms.hpp"
 #include "ocp_launch.hpp"
 
 using namespace idocp_dev;
@@ -78,18 +79,16 @@ struct idocp_ocp {
   std::vector<std::vector<std::pair<double, double>>> filters;
   OcpNode* d_nodes_ls = nullptr;
   double* ext_try = nullptr;
-  int fused_forward_mode = -1;        // idocp_ocp_set_fused_forward: -1 by batch size, 0 S4 + K6, 1 the fused forward sweep
-  int riccati_sweep_mode = -1;        // idocp_ocp_set_riccati_sweep: -1 by batch size, 0 one wavefront per instance (register-resident), 1 eight per instance
+  OcpForms forms;                     // which form of a kernel this handle runs (ocp_forms.hpp); idocp_ocp_clone copies the record
   // staging of the per-stage setters (idocp_ocp_set_solution_stages / _chain, the aux-matrix setters): an MPC loop warm-starts every tick, so
   // the device scratch and its pinned host twin are kept (grown on demand) and the setter returns without a stream synchronisation -- the
   // copy and the fill kernel are stream-ordered in front of whatever the caller launches next; fill_done guards the reuse of the host twin
   double *d_fill = nullptr, *h_fill = nullptr;
   size_t fill_cap = 0;
   hipEvent_t fill_done = nullptr;
-  // fork / join inside an iteration (round 6): the switching-constraint kernel K5s -- one latency-bound wavefront per stage that carries a
-  // switching constraint, 0.09 ms on configs[2] with most of the chip idle -- runs on a stream of its own NEXT TO the nominal sweeps K5n (both
-  // read the iterate only and write records of their own); the condensation launches wait for both.  IDOCP_SIDE_STREAM=0 keeps everything on
-  // the handle's stream.
+  // fork / join inside an iteration (round 6): the switching-constraint kernel K5s runs on a stream of its own NEXT TO the nominal sweeps K5n
+  // (both read the iterate only and write records of their own); the condensation launches wait for both.  Present where
+  // useSideStream(forms, ...) says so (ocp_forms.hpp, idocp_ocp_set_side_stream); every entry point joins an open fork first (enterO).
   hipStream_t side = nullptr;
   hipEvent_t ev_fork = nullptr, ev_join = nullptr;
   bool side_pending = false;          // a kernel is in flight on `side` that the next condensation launch has to wait for
@@ -104,6 +103,40 @@ int allocBufO(idocp_ocp* h, double** p, size_t n) {
   return IDOCP_OK;
 }
 int setDev(const idocp_ocp* h) { HIP_TRY(hipSetDevice(h->device)); return IDOCP_OK; }
+// a fork opened by launchSwitchO is closed here: the handle's stream waits for what is in flight on the side stream
+int joinSideO(idocp_ocp* h) {
+  if (h->side_pending) { HIP_TRY(hipStreamWaitEvent(h->stream, h->ev_join, 0)); h->side_pending = false; }
+  return IDOCP_OK;
+}
+// The head of every entry point that launches on or reads through h->stream: the handle's device, and no fork left open
+// (idocp_ocp_launch_kernel id 0 alone leaves one for ids 7, 8, 1, 2 -- or whatever entry comes next -- to close).
+int enterO(idocp_ocp* h) {
+  int rc = setDev(h); if (rc) return rc;
+  return joinSideO(h);
+}
+void dropSideO(idocp_ocp* h) {
+  if (h->side) { (void)hipStreamDestroy(h->side); h->side = nullptr; }
+  if (h->ev_fork) { (void)hipEventDestroy(h->ev_fork); h->ev_fork = nullptr; }
+  if (h->ev_join) { (void)hipEventDestroy(h->ev_join); h->ev_join = nullptr; }
+}
+// The side stream and its two events exist exactly while the handle's forms ask for them (creation, idocp_ocp_set_side_stream).  Both
+// streams are drained first: nothing is in flight on a stream that goes away, and nothing that was forked stays unjoined.
+int applySideStreamO(idocp_ocp* h) {
+  const bool want = useSideStream(h->forms, h->batch, h->parnmpc);
+  if (want == (h->side != nullptr)) return IDOCP_OK;
+  HIP_TRY(hipStreamSynchronize(h->stream));
+  if (h->side) HIP_TRY(hipStreamSynchronize(h->side));
+  h->side_pending = false;
+  if (!want) { dropSideO(h); return IDOCP_OK; }
+  if (hipStreamCreateWithFlags(&h->side, hipStreamNonBlocking) != hipSuccess || hipEventCreateWithFlags(&h->ev_fork, hipEventDisableTiming) != hipSuccess ||
+      hipEventCreateWithFlags(&h->ev_join, hipEventDisableTiming) != hipSuccess) {
+    (void)hipGetLastError();
+    dropSideO(h);
+    set_last_error("side stream: hipStreamCreate / hipEventCreate failed");
+    return IDOCP_E_DEVICE;
+  }
+  return IDOCP_OK;
+}
 
 using idocp_host::qRefAt;        // the reference of a stage time: cost_reference.hpp, shared with the rollout scoring
 using idocp_host::vRefOnAt;
@@ -265,7 +298,7 @@ static int checkTaskExtras(const idocp_cost_t* cost) {
 }
 
 static int createOcpImpl(const idocp_model_t* model, const idocp_cost_t* cost, const idocp_constraints_t* constraints, double T,
-                         int N, int max_num_impulse, int batch, int device, bool parnmpc, idocp_ocp_t** out) {
+                         int N, int max_num_impulse, int batch, int device, bool parnmpc, idocp_ocp_t** out, const OcpForms* forms = nullptr) {
   if (!model || !cost || !constraints || !out) { set_last_error("idocp_ocp_create: null argument"); return IDOCP_E_ARG; }
   if (!(T > 0)) { set_last_error("invalid value: T must be positive!"); return IDOCP_E_ARG; }       // ocp_solver.cpp:27-44
   if (N <= 0) { set_last_error("invalid value: N must be positive!"); return IDOCP_E_ARG; }
@@ -308,16 +341,10 @@ static int createOcpImpl(const idocp_model_t* model, const idocp_cost_t* cost, c
   h->NS = N + 1 + 3 * max_num_impulse;
   auto fail = [&](int code) { (void)hipGetLastError(); idocp_ocp_destroy(h); return code; };      // (clears HIP's sticky last error: see HIP_TRY)
   if (hipSetDevice(device) != hipSuccess || hipStreamCreate(&h->stream) != hipSuccess) { set_last_error("hipStreamCreate failed"); return fail(IDOCP_E_DEVICE); }
-  {
-    // (a batch of instances only: at batch 1 the two event hand-offs cost more than the 9 wavefronts of K5s -- 1.09 against 1.06 ms per iteration)
-    // (read at every creation, not once per process: tests/test_forward_expand_gpu.py runs the oracle parity tests with the side stream forced on small batches)
-    const bool use_side = !(getenv("IDOCP_SIDE_STREAM") && atoi(getenv("IDOCP_SIDE_STREAM")) == 0);
-    const int side_min_batch = getenv("IDOCP_SIDE_STREAM_MIN_BATCH") ? atoi(getenv("IDOCP_SIDE_STREAM_MIN_BATCH")) : 128;
-    if (use_side && !parnmpc && batch >= side_min_batch) {
-      if (hipStreamCreateWithFlags(&h->side, hipStreamNonBlocking) != hipSuccess || hipEventCreateWithFlags(&h->ev_fork, hipEventDisableTiming) != hipSuccess ||
-          hipEventCreateWithFlags(&h->ev_join, hipEventDisableTiming) != hipSuccess) { set_last_error("side stream: hipStreamCreate / hipEventCreate failed"); return fail(IDOCP_E_DEVICE); }
-    }
-  }
+  h->parnmpc = parnmpc;
+  if (forms) h->forms = *forms;      // idocp_ocp_clone: the source's record
+  else { const idocp_host::EnvSettings env = idocp_host::envSettings(); h->forms.prof_dimf = env.prof_dimf; h->forms.general_axes = env.general_axes ? 1 : 0; }
+  { const int rc_s = applySideStreamO(h); if (rc_s) return fail(rc_s); }
   const size_t ns = (size_t)batch * h->NS;
   OcpBuffers& B = h->B;
   int rc;
@@ -334,7 +361,6 @@ static int createOcpImpl(const idocp_model_t* model, const idocp_cost_t* cost, c
   if ((rc = allocBufO(h, &B.ric, ns * LQ::RIC))) return fail(rc);
   if ((rc = allocBufO(h, &B.gain, ns * LQ::GAIN))) return fail(rc);
   if ((rc = allocBufO(h, &B.swc, max_num_impulse > 0 ? ns * LQ::SWC : 16))) return fail(rc);
-  h->parnmpc = parnmpc;
   if (parnmpc) {
     if ((rc = allocBufO(h, &B.snew, ns * LQ::SNEW))) return fail(rc);
     if ((rc = allocBufO(h, &B.kinv, ns * LQ::KINV))) return fail(rc);
@@ -370,7 +396,7 @@ static int createOcpImpl(const idocp_model_t* model, const idocp_cost_t* cost, c
   B.status = reinterpret_cast<int*>(tmp);
   if ((rc = allocBufO(h, &tmp, 64))) return fail(rc);
   B.prof = reinterpret_cast<long long*>(tmp);
-  B.prof_dimf = getenv("IDOCP_PROF_DIMF") ? atoi(getenv("IDOCP_PROF_DIMF")) : 12;
+  B.prof_dimf = h->forms.prof_dimf;
   if ((rc = allocBufO(h, &tmp, ((size_t)h->NS * sizeof(OcpNode) + 7) / 8))) return fail(rc);
   h->d_nodes = reinterpret_cast<OcpNode*>(tmp);
   B.nodes = h->d_nodes;
@@ -402,7 +428,7 @@ static int createOcpImpl(const idocp_model_t* model, const idocp_cost_t* cost, c
     const double I3[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1};
     for (int k = 0; k < 9; ++k) if (model->contact_R[c][k] != I3[k]) B.leg_axes_xyy = 0;
   }
-  if (std::getenv("IDOCP_GENERAL_AXES")) B.leg_axes_xyy = 0;      // tests: the general instantiations on a model that qualifies for the special ones
+  if (h->forms.general_axes) B.leg_axes_xyy = 0;      // tests: the general instantiations on a model that qualifies for the special ones
   DevModel dm; idocp_host::toDevModel(*model, dm);
   OcpProblem& p = h->prob;
   std::memset(&p, 0, sizeof(p));
@@ -463,9 +489,8 @@ void idocp_ocp_destroy(idocp_ocp_t* h) {
   if (h->graph_exec) (void)hipGraphExecDestroy(h->graph_exec);
   if (h->graph) (void)hipGraphDestroy(h->graph);
   for (void* p : h->allocs) (void)hipFree(p);
-  if (h->side) { (void)hipStreamSynchronize(h->side); (void)hipStreamDestroy(h->side); }
-  if (h->ev_fork) (void)hipEventDestroy(h->ev_fork);
-  if (h->ev_join) (void)hipEventDestroy(h->ev_join);
+  if (h->side) (void)hipStreamSynchronize(h->side);
+  dropSideO(h);
   if (h->d_fill) (void)hipFree(h->d_fill);
   if (h->h_fill) (void)hipHostFree(h->h_fill);
   if (h->fill_done) (void)hipEventDestroy(h->fill_done);
@@ -498,7 +523,7 @@ int idocp_ocp_pop_front_contact_status(idocp_ocp_t* h) { return h ? sequenceChan
 
 int idocp_ocp_get_chain(idocp_ocp_t* h, double t, int capacity, int* kind, int* index, int* slot, double* dt, int* dimf, int* sw_dimi) {
   if (!h) return IDOCP_E_ARG;
-  int rc = setDev(h); if (rc) return rc;
+  int rc = enterO(h); if (rc) return rc;
   if ((rc = discretize(h, t, true))) return rc;
   const int M = h->M();
   if (capacity < M) { set_last_error("idocp_ocp_get_chain: capacity too small"); return IDOCP_E_ARG; }
@@ -516,7 +541,7 @@ int idocp_ocp_get_chain(idocp_ocp_t* h, double t, int capacity, int* kind, int* 
 
 int idocp_ocp_get_chain_times(idocp_ocp_t* h, double t, int capacity, double* times) {
   if (!h || !times) return IDOCP_E_ARG;
-  int rc = setDev(h); if (rc) return rc;
+  int rc = enterO(h); if (rc) return rc;
   // (the chain's shape and times do not depend on the reference poses: a TimeVarying task cost without poses yet must not stop the
   //  discretisation that tells the caller where to evaluate them)
   if ((rc = discretize(h, t, true))) return rc;
@@ -536,7 +561,7 @@ int idocp_ocp_set_task_refs(idocp_ocp_t* h, double t, int M, const double* refs)
   if (!h->seq_dirty && h->disc_time == t && M == h->M()) {
     // the chain is the current one (idocp_ocp_get_chain_times has just discretised at t, the facade's order of calls): the table
     // goes straight to the device -- no second discretisation with its host-synchronous uploads in the MPC loop
-    int rc = setDev(h); if (rc) return rc;
+    int rc = enterO(h); if (rc) return rc;
     HIP_TRY(hipMemcpyAsync(h->d_taskref, h->task_refs_host.data(), sizeof(double) * (size_t)M * 12, hipMemcpyHostToDevice, h->stream));
     HIP_TRY(hipStreamSynchronize(h->stream));
     h->task_refs_stale = false;
@@ -554,7 +579,7 @@ static int setSolutionO(idocp_ocp_t* h, const char* name, const double* values, 
     set_last_error("invalid arugment: name must be q, v, a, f, or u!");
     return IDOCP_E_ARG;
   }
-  int rc = setDev(h); if (rc) return rc;
+  int rc = enterO(h); if (rc) return rc;
   const int dim = (n == "f") ? 3 : f.dim, repeat = (n == "f") ? DQ::NC : 1;
   const size_t cnt = (size_t)(per_instance ? h->batch : 1) * dim;
   HIP_TRY(hipMemcpyAsync(h->d_tmp, values, cnt * sizeof(double), hipMemcpyHostToDevice, h->stream));
@@ -592,13 +617,13 @@ int idocp_ocp_set_solution_stages(idocp_ocp_t* h, const char* name, int nstages,
   if (!solFieldO(name, f)) { set_last_error(std::string("unknown field name: ") + name); return IDOCP_E_ARG; }
   const int nmax = h->parnmpc ? h->N : h->N + f.extra;        // grid stages that carry the field (the terminal stage: lmd gmm q v)
   if (nstages <= 0 || nstages > nmax) { set_last_error("idocp_ocp_set_solution_stages: nstages out of range"); return IDOCP_E_ARG; }
-  int rc = setDev(h); if (rc) return rc;
+  int rc = enterO(h); if (rc) return rc;
   return fillStagesO(h, h->B.sol, LQ::SOL, f.offset, f.dim, nstages, values);
 }
 int idocp_parnmpc_set_aux_mat(idocp_ocp_t* h, int nstages, const double* values) {
   if (!h || !values || !h->parnmpc) { set_last_error("idocp_parnmpc_set_aux_mat: not a ParNMPC handle"); return IDOCP_E_ARG; }
   if (nstages <= 0 || nstages > h->N) { set_last_error("idocp_parnmpc_set_aux_mat: nstages out of range"); return IDOCP_E_ARG; }
-  int rc = setDev(h); if (rc) return rc;
+  int rc = enterO(h); if (rc) return rc;
   return fillStagesO(h, h->B.aux, LQ::AUX, 0, DQ::NX * DQ::NX, nstages, values);
 }
 // warm start along the CHAIN of the current discretisation (event stages included): values[M][dim] in the order of idocp_ocp_get_chain
@@ -611,13 +636,13 @@ int idocp_ocp_set_solution_chain(idocp_ocp_t* h, const char* name, int M, const 
   if (!h || !name || !values) return IDOCP_E_ARG;
   Field f;
   if (!solFieldO(name, f)) { set_last_error(std::string("unknown field name: ") + name); return IDOCP_E_ARG; }
-  int rc = setDev(h); if (rc) return rc;
+  int rc = enterO(h); if (rc) return rc;
   if ((rc = chainLength(h, M))) return rc;
   return fillStagesO(h, h->B.sol, LQ::SOL, f.offset, f.dim, M, values, true);
 }
 int idocp_parnmpc_set_aux_mat_chain(idocp_ocp_t* h, int M, const double* values) {
   if (!h || !values || !h->parnmpc) { set_last_error("idocp_parnmpc_set_aux_mat_chain: not a ParNMPC handle"); return IDOCP_E_ARG; }
-  int rc = setDev(h); if (rc) return rc;
+  int rc = enterO(h); if (rc) return rc;
   if ((rc = chainLength(h, M))) return rc;
   return fillStagesO(h, h->B.aux, LQ::AUX, 0, DQ::NX * DQ::NX, M, values, true);
 }
@@ -625,7 +650,7 @@ int idocp_ocp_set_solution_batch(idocp_ocp_t* h, const char* name, const double*
 
 int idocp_ocp_init_constraints(idocp_ocp_t* h, double t) {
   if (!h) return IDOCP_E_ARG;
-  int rc = setDev(h); if (rc) return rc;
+  int rc = enterO(h); if (rc) return rc;
   if ((rc = discretize(h, t))) return rc;                 // ocp_solver.cpp:60-64
   OcpLaunch<DQ>::initConstraints(h->B, h->batch, h->NS, h->stream);
   OcpLaunch<DQ>::extInit(h->B, h->batch, h->NS, h->stream);      // ContactDistance rows
@@ -640,29 +665,12 @@ static void launchCondenseO(idocp_ocp_t* h, int M, const double* d_q, int part =
   else OcpLaunch<DQ>::condenseMixed(h->B, h->batch, M, h->plan.cond_n, d_q, h->stream, part, st_imp);
 }
 
-// The forward sweep that expands as it walks (ocp_forward_expand_kernel) pays when the stage-parallel expansion it absorbs is bandwidth: a
-// batch of instances.  A few instances are the opposite case -- K6 spreads their stages over the whole chip while the fused walk strings the
-// expansion of all stages of an instance onto one wavefront's chain -- so small batches keep S4 + K6 (latency mode).  IDOCP_FUSED_FORWARD=0 / 1
-// forces one or the other; IDOCP_FUSED_FORWARD_MIN_BATCH moves the threshold.
-static bool fusedForward(const idocp_ocp_t* h) {
-  static const int forced = getenv("IDOCP_FUSED_FORWARD") ? atoi(getenv("IDOCP_FUSED_FORWARD")) : -1;
-  static const int min_batch = getenv("IDOCP_FUSED_FORWARD_MIN_BATCH") ? atoi(getenv("IDOCP_FUSED_FORWARD_MIN_BATCH")) : 192;      // measured on configs[2]: S4 + K6 0.315 / 0.405 / 0.587 ms at batch 128 / 256 / 512, the fused walk 0.346 / 0.356 / 0.447
-  if (h->M() > OcpForwardExpandMaxChain) return false;             // the walk keeps the chain in LDS
-  if (h->fused_forward_mode >= 0) return h->fused_forward_mode != 0;
-  if (forced >= 0) return forced != 0;
-  return h->batch >= min_batch;
-}
-// The backward sweep of a handful of instances (latency mode: one reference solver object is batch 1) runs eight wavefronts per instance --
-// measured on configs[2]: 0.79 / 0.83 against 0.855 / 0.858 ms at batch 1 / 16, 0.88 against 0.86 at 64.  IDOCP_RICCATI_WIDE_MAX_BATCH moves
-// the threshold, IDOCP_RICCATI_NT (ocp_riccati_kernel.hip) overrides everything.
-static bool wideSweep(const idocp_ocp_t* h) {
-  static const int max_batch = getenv("IDOCP_RICCATI_WIDE_MAX_BATCH") ? atoi(getenv("IDOCP_RICCATI_WIDE_MAX_BATCH")) : 16;
-  if (h->riccati_sweep_mode >= 0) return h->riccati_sweep_mode != 0;
-  return h->batch <= max_batch;
-}
+// the rules and the measurements behind them: ocp_forms.hpp
+static bool fusedForward(const idocp_ocp_t* h) { return useFusedForward(h->forms, h->batch, h->M()); }
+static bool wideSweep(const idocp_ocp_t* h) { return useWideSweep(h->forms, h->batch); }
 int idocp_ocp_set_riccati_sweep(idocp_ocp_t* h, int mode) {
   if (!h || h->parnmpc || mode < -1 || mode > 1) return IDOCP_E_ARG;
-  h->riccati_sweep_mode = mode;
+  h->forms.riccati_wide = mode;
   ++h->disc_epoch;                      // a captured hipGraph holds the other kernel
   return IDOCP_OK;
 }
@@ -670,12 +678,24 @@ int idocp_ocp_riccati_sweep(idocp_ocp_t* h) { return (h && !h->parnmpc && wideSw
 // per handle: mode -1 = by batch size (the default), 0 = S4 + K6 + reduction, 1 = the fused forward sweep
 int idocp_ocp_set_fused_forward(idocp_ocp_t* h, int mode) {
   if (!h || h->parnmpc || mode < -1 || mode > 1) return IDOCP_E_ARG;
-  h->fused_forward_mode = mode;
+  h->forms.fused_forward = mode;
   ++h->disc_epoch;                      // a captured hipGraph holds the other kernels
   return IDOCP_OK;
 }
 // 1 when the forward sweep and the primal expansion of this OCPSolver handle run as one kernel, 0 when they are S4, K6 and the reduction
 int idocp_ocp_fused_forward(idocp_ocp_t* h) { return (h && !h->parnmpc && fusedForward(h)) ? 1 : 0; }
+// per handle: mode -1 = by batch size (the default), 0 = everything on the handle's stream, 1 = K5s and K7b on a stream of their own
+int idocp_ocp_set_side_stream(idocp_ocp_t* h, int mode) {
+  if (!h || h->parnmpc || mode < -1 || mode > 1) return IDOCP_E_ARG;
+  int rc = setDev(h); if (rc) return rc;
+  const int before = h->forms.side_stream;
+  h->forms.side_stream = mode;
+  if ((rc = applySideStreamO(h))) { h->forms.side_stream = before; return rc; }
+  ++h->disc_epoch;                      // a captured hipGraph holds the other fork / join structure
+  return IDOCP_OK;
+}
+// 1 when this OCPSolver handle runs K5s (and K7b) on a stream of their own, 0 when everything runs on the handle's stream
+int idocp_ocp_side_stream(idocp_ocp_t* h) { return (h && !h->parnmpc && h->side) ? 1 : 0; }
 static void launchForwardO(idocp_ocp_t* h, int M, const double* d_q, const double* d_v) {
   if (fusedForward(h)) { OcpLaunch<DQ>::forwardExpand(h->B, h->batch, M, d_q, d_v, h->stream); return; }
   OcpLaunch<DQ>::riccatiForward(h->B, h->batch, M, d_q, d_v, h->stream);
@@ -702,10 +722,6 @@ static int launchNominalO(idocp_ocp_t* h, int M, const double* d_q) {
   if (h->side_pending) HIP_TRY(hipEventRecord(h->ev_join, h->side));
   return IDOCP_OK;
 }
-static int joinSideO(idocp_ocp_t* h) {
-  if (h->side_pending) { HIP_TRY(hipStreamWaitEvent(h->stream, h->ev_join, 0)); h->side_pending = false; }
-  return IDOCP_OK;
-}
 // K7 and, independent of it, the base poses K7b: beside each other where the handle has a side stream (joined at once: the next iteration
 // reads both)
 static int launchIntegrateO(idocp_ocp_t* h, int M) {
@@ -717,23 +733,12 @@ static int launchIntegrateO(idocp_ocp_t* h, int M) {
   HIP_TRY(hipStreamWaitEvent(h->stream, h->ev_join, 0));
   return IDOCP_OK;
 }
-// the condensation launches proper: on a chain with several stage classes the largest class on the handle's stream and the others beside it on
-// the side stream (their tails blend instead of adding up); joined before the external Hessian / the Riccati sweep
+// the condensation launches proper, behind K5s and the nominal sweeps (two different instantiations of the 57 kB condensation kernel resident
+// together on two streams were measured slower, profiles/experiments/r06_side_stream.md: the classes go one behind the other)
 static int launchCondenseClassesO(idocp_ocp_t* h, int M, const double* d_q) {
   int rc;
   if ((rc = joinSideO(h))) return rc;
-  const bool mixed = !(h->plan.uniform_dimf == DQ::NF || h->plan.cond_n[0] + h->plan.cond_n[1] + h->plan.cond_n[3] + h->plan.cond_n[4] == 0);
-  // OFF by default: measured (round 6, profiles/experiments/r06_side_stream.md) -- two different instantiations of the 57 kB condensation kernel
-  // resident together take 3.2 instead of 2.24 ms (configs[2]); IDOCP_SIDE_STREAM_K5=1 repeats the experiment
-  static const bool split = getenv("IDOCP_SIDE_STREAM_K5") && atoi(getenv("IDOCP_SIDE_STREAM_K5")) != 0;
-  if (!mixed || !h->side || !split || h->plan.cond_n[1] == 0) { launchCondenseO(h, M, d_q, 2); return IDOCP_OK; }
-  HIP_TRY(hipEventRecord(h->ev_fork, h->stream));
-  HIP_TRY(hipStreamWaitEvent(h->side, h->ev_fork, 0));
-  OcpLaunch<DQ>::condenseMixed(h->B, h->batch, M, h->plan.cond_n, d_q, h->stream, 3);
-  OcpLaunch<DQ>::condenseMixed(h->B, h->batch, M, h->plan.cond_n, d_q, h->side, 4);
-  HIP_TRY(hipEventRecord(h->ev_join, h->side));
-  HIP_TRY(hipStreamWaitEvent(h->stream, h->ev_join, 0));
-  OcpLaunch<DQ>::condenseMixed(h->B, h->batch, M, h->plan.cond_n, d_q, h->stream, 5);
+  launchCondenseO(h, M, d_q, 2);
   return IDOCP_OK;
 }
 static int launchUpdateO(idocp_ocp_t* h, int M, const double* d_q, const double* d_v) {
@@ -752,6 +757,8 @@ static int launchUpdateO(idocp_ocp_t* h, int M, const double* d_q, const double*
 int idocp_ocp_launch_kernel(idocp_ocp_t* h, int kernel_id, const double* d_q, const double* d_v) {
   if (!h || kernel_id < 0 || kernel_id > 8 || !d_q || !d_v) return IDOCP_E_ARG;
   int rc = setDev(h); if (rc) return rc;
+  // ids 0, 7 and 1 run beside an open fork (1 closes it between its halves); every other id starts behind it
+  if (kernel_id != 0 && kernel_id != 7 && kernel_id != 1 && (rc = joinSideO(h))) return rc;
   if ((rc = ensureDiscretized(h))) return rc;
   const int M = h->M();
   switch (kernel_id) {
@@ -759,10 +766,9 @@ int idocp_ocp_launch_kernel(idocp_ocp_t* h, int kernel_id, const double* d_q, co
     case 1: if ((rc = launchNominalO(h, M, d_q))) return rc; if ((rc = launchCondenseClassesO(h, M, d_q))) return rc; break;
     case 7: if ((rc = launchNominalO(h, M, d_q))) return rc; break;      // the two halves of 1: the nominal rigid-body sweeps (+ external rows) ...
     case 8: if ((rc = launchCondenseClassesO(h, M, d_q))) return rc; break;      // ... and the condensation launches proper
-    case 2: if ((rc = joinSideO(h))) return rc;      // (a caller that skips the condensation ids still gets K5s in front of the sweep)
-            OcpLaunch<DQ>::riccatiBackward(h->B, h->batch, M, h->plan.has_switch, h->stream, wideSweep(h)); break;
+    case 2: OcpLaunch<DQ>::riccatiBackward(h->B, h->batch, M, h->plan.has_switch, h->stream, wideSweep(h)); break;
     // 3: the forward sweep.  Since round 5 it expands as it walks (S4 + K6 + the step-size reduction in one kernel, ocp_forward_expand_kernel);
-    // ids 4 and 5 are then empty.  IDOCP_FUSED_FORWARD=0 restores the three kernels behind ids 3, 4, 5.
+    // ids 4 and 5 are then empty.  idocp_ocp_set_fused_forward(h, 0) restores the three kernels behind ids 3, 4, 5.
     case 3: if (fusedForward(h)) OcpLaunch<DQ>::forwardExpand(h->B, h->batch, M, d_q, d_v, h->stream); else OcpLaunch<DQ>::riccatiForward(h->B, h->batch, M, d_q, d_v, h->stream); break;
     case 4: case 5: if (!fusedForward(h)) OcpLaunch<DQ>::single(kernel_id, h->B, h->batch, M, h->stream); break;
     case 6: if ((rc = launchIntegrateO(h, M))) return rc; break;
@@ -775,7 +781,7 @@ int idocp_ocp_launch_kernel(idocp_ocp_t* h, int kernel_id, const double* d_q, co
 int idocp_ocp_update_solution_device(idocp_ocp_t* h, double t, const double* d_q, const double* d_v) {
   if (!h || !d_q || !d_v) return IDOCP_E_ARG;
   if (!h->seq.status_set) { set_last_error("idocp_ocp_update_solution: call setContactStatusUniformly first"); return IDOCP_E_ARG; }
-  int rc = setDev(h); if (rc) return rc;
+  int rc = enterO(h); if (rc) return rc;
   if ((rc = discretize(h, t))) return rc;                 // ocp_.discretize(contact_sequence_, t) (ocp_solver.cpp:72)
   const int M = h->M();
   if ((rc = launchUpdateO(h, M, d_q, d_v))) return rc;
@@ -789,7 +795,7 @@ int idocp_ocp_update_solution_device(idocp_ocp_t* h, double t, const double* d_q
 int idocp_ocp_update_solution_graph(idocp_ocp_t* h, double t, const double* d_q, const double* d_v) {
   if (!h || !d_q || !d_v) return IDOCP_E_ARG;
   if (!h->seq.status_set) { set_last_error("idocp_ocp_update_solution: call setContactStatusUniformly first"); return IDOCP_E_ARG; }
-  int rc = setDev(h); if (rc) return rc;
+  int rc = enterO(h); if (rc) return rc;
   if (!h->launched_eagerly) return idocp_ocp_update_solution_device(h, t, d_q, d_v);      // first call: plain launches (one-time kernel attributes)
   if ((rc = discretize(h, t))) return rc;
   if (!h->graph_exec || h->graph_epoch != h->disc_epoch || h->graph_q != d_q || h->graph_v != d_v) {
@@ -798,7 +804,12 @@ int idocp_ocp_update_solution_graph(idocp_ocp_t* h, double t, const double* d_q,
     HIP_TRY(hipStreamBeginCapture(h->stream, hipStreamCaptureModeThreadLocal));
     rc = launchUpdateO(h, h->M(), d_q, d_v);
     const hipError_t e = hipStreamEndCapture(h->stream, &h->graph);
-    if (rc) return rc;
+    if (rc) {      // the capture is over either way; what it recorded -- an open fork included -- is dropped with it
+      h->side_pending = false;
+      if (h->graph) { (void)hipGraphDestroy(h->graph); h->graph = nullptr; }
+      (void)hipGetLastError();
+      return rc;
+    }
     HIP_TRY(e);
     HIP_TRY(hipGraphInstantiate(&h->graph_exec, h->graph, nullptr, nullptr, 0));
     h->graph_epoch = h->disc_epoch; h->graph_q = d_q; h->graph_v = d_v;
@@ -809,7 +820,7 @@ int idocp_ocp_update_solution_graph(idocp_ocp_t* h, double t, const double* d_q,
 
 int idocp_ocp_synchronize(idocp_ocp_t* h) {
   if (!h) return IDOCP_E_ARG;
-  int rc = setDev(h); if (rc) return rc;
+  int rc = enterO(h); if (rc) return rc;
   HIP_TRY(hipStreamSynchronize(h->stream));
   if (h->side) HIP_TRY(hipStreamSynchronize(h->side));      // (a fork left open by idocp_ocp_launch_kernel id 0 alone)
   return IDOCP_OK;
@@ -910,7 +921,7 @@ static int runLineSearchO(idocp_ocp_t* h, const double* d_q) {
 int idocp_ocp_compute_direction(idocp_ocp_t* h, double t, const double* q, const double* v) {
   if (!h || !q || !v) return IDOCP_E_ARG;
   if (!h->seq.status_set) { set_last_error("idocp_ocp_update_solution: call setContactStatusUniformly first"); return IDOCP_E_ARG; }
-  int rc = setDev(h); if (rc) return rc;
+  int rc = enterO(h); if (rc) return rc;
   HIP_TRY(hipMemcpyAsync(h->d_q0, q, sizeof(double) * h->batch * DQ::NQ, hipMemcpyHostToDevice, h->stream));
   HIP_TRY(hipMemcpyAsync(h->d_v0, v, sizeof(double) * h->batch * DQ::NV, hipMemcpyHostToDevice, h->stream));
   if ((rc = discretize(h, t))) return rc;
@@ -928,7 +939,7 @@ int idocp_ocp_compute_direction(idocp_ocp_t* h, double t, const double* q, const
 // (total cost, total constraint violation) of s (+) alpha[b] d for every instance (alpha = 0: the iterate itself, current slacks)
 int idocp_ocp_line_search_eval(idocp_ocp_t* h, const double* alpha, double* cost, double* violation) {
   if (!h || !alpha || !cost || !violation) return IDOCP_E_ARG;
-  int rc = setDev(h); if (rc) return rc;
+  int rc = enterO(h); if (rc) return rc;
   if (h->parnmpc && (rc = parnmpcLineSearchSupported(h))) return rc;
   std::vector<double> a(alpha, alpha + h->batch), cv;
   if ((rc = lineSearchEvalO(h, a, h->d_q0, cv))) return rc;
@@ -943,7 +954,7 @@ int idocp_ocp_clear_line_search_filter(idocp_ocp_t* h) {
 
 int idocp_ocp_update_solution(idocp_ocp_t* h, double t, const double* q, const double* v, int line_search) {
   if (!h || !q || !v) return IDOCP_E_ARG;
-  int rc = setDev(h); if (rc) return rc;
+  int rc = enterO(h); if (rc) return rc;
   HIP_TRY(hipMemcpyAsync(h->d_q0, q, sizeof(double) * h->batch * DQ::NQ, hipMemcpyHostToDevice, h->stream));
   HIP_TRY(hipMemcpyAsync(h->d_v0, v, sizeof(double) * h->batch * DQ::NV, hipMemcpyHostToDevice, h->stream));
   if (line_search) {
@@ -973,7 +984,7 @@ int idocp_ocp_update_solution(idocp_ocp_t* h, double t, const double* q, const d
 
 int idocp_ocp_compute_kkt_residual(idocp_ocp_t* h, double t, const double* q, const double* v) {
   if (!h || !q || !v) return IDOCP_E_ARG;
-  int rc = setDev(h); if (rc) return rc;
+  int rc = enterO(h); if (rc) return rc;
   if ((rc = discretize(h, t))) return rc;
   const int M = h->M();
   HIP_TRY(hipMemcpyAsync(h->d_q0, q, sizeof(double) * h->batch * DQ::NQ, hipMemcpyHostToDevice, h->stream));
@@ -987,7 +998,7 @@ int idocp_ocp_compute_kkt_residual(idocp_ocp_t* h, double t, const double* q, co
 }
 int idocp_ocp_kkt_error(idocp_ocp_t* h, double* kkt_error) {
   if (!h || !kkt_error) return IDOCP_E_ARG;
-  int rc = setDev(h); if (rc) return rc;
+  int rc = enterO(h); if (rc) return rc;
   HIP_TRY(hipMemcpyAsync(kkt_error, h->B.err, sizeof(double) * h->batch, hipMemcpyDeviceToHost, h->stream));
   HIP_TRY(hipStreamSynchronize(h->stream));
   return IDOCP_OK;
@@ -998,7 +1009,7 @@ int idocp_ocp_get_solution(idocp_ocp_t* h, const char* name, int instance, doubl
   if (!h || !name || !out || instance < 0 || instance >= h->batch) return IDOCP_E_ARG;
   Field f;
   if (!solFieldO(name, f)) { set_last_error(std::string("unknown field name: ") + name); return IDOCP_E_ARG; }
-  int rc = setDev(h); if (rc) return rc;
+  int rc = enterO(h); if (rc) return rc;
   return copyField(h, h->B.sol + (size_t)instance * h->NS * LQ::SOL, LQ::SOL, h->parnmpc ? h->N : h->plan.Ngrid + f.extra, f, out);
 }
 // OCPSolver::getSolution(stage) (ocp_solver.hpp:97): the whole split solution of ONE grid stage in one device-to-host copy --
@@ -1006,7 +1017,7 @@ int idocp_ocp_get_solution(idocp_ocp_t* h, const char* name, int instance, doubl
 // (split_solution.hxx:10-31); on the terminal stage only lmd gmm q v are meaningful.
 int idocp_ocp_get_split_solution(idocp_ocp_t* h, int instance, int stage, double* out) {
   if (!h || !out || instance < 0 || instance >= h->batch || stage < 0 || stage > (h->parnmpc ? h->N - 1 : h->plan.Ngrid)) return IDOCP_E_ARG;
-  int rc = setDev(h); if (rc) return rc;
+  int rc = enterO(h); if (rc) return rc;
   static_assert(LQ::S_LMD == 0 && LQ::S_NUP > LQ::S_MU, "record order = output order");
   const size_t n = LQ::S_NUP + 6;
   HIP_TRY(hipMemcpyAsync(out, h->B.sol + ((size_t)instance * h->NS + stage) * LQ::SOL, n * sizeof(double), hipMemcpyDeviceToHost, h->stream));
@@ -1042,7 +1053,7 @@ int idocp_ocp_get_direction(idocp_ocp_t* h, const char* name, int instance, doub
   if (!h || !name || !out || instance < 0 || instance >= h->batch) return IDOCP_E_ARG;
   Field f;
   if (!dirFieldO(name, f)) { set_last_error(std::string("unknown field name: ") + name); return IDOCP_E_ARG; }
-  int rc = setDev(h); if (rc) return rc;
+  int rc = enterO(h); if (rc) return rc;
   const size_t nrec = h->parnmpc ? h->N : h->plan.Ngrid + f.extra;
   rc = copyField(h, h->B.dir + (size_t)instance * h->NS * LQ::DIR, LQ::DIR, nrec, f, out);
   if (rc) return rc;
@@ -1056,7 +1067,7 @@ int idocp_ocp_get_direction(idocp_ocp_t* h, const char* name, int instance, doub
 // the same fields for every stage of the chain, in chain order: out[M][dim] (rows of stages that do not carry the
 // field, e.g. "u" on an impulse stage, hold whatever the slot holds)
 static int getChainField(idocp_ocp_t* h, const double* base, size_t stride, const Field& f, int instance, double* out) {
-  int rc = setDev(h); if (rc) return rc;
+  int rc = enterO(h); if (rc) return rc;
   const int M = h->M();
   std::vector<double> all((size_t)h->NS * stride);
   HIP_TRY(hipMemcpyAsync(all.data(), base + (size_t)instance * h->NS * stride, all.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream));
@@ -1108,7 +1119,7 @@ int idocp_ocp_get_direction_chain(idocp_ocp_t* h, const char* name, int instance
 
 int idocp_ocp_get_step_sizes(idocp_ocp_t* h, double* primal, double* dual) {
   if (!h || !primal || !dual) return IDOCP_E_ARG;
-  int rc = setDev(h); if (rc) return rc;
+  int rc = enterO(h); if (rc) return rc;
   std::vector<double> st((size_t)h->batch * 2);
   HIP_TRY(hipMemcpyAsync(st.data(), h->B.step, sizeof(double) * st.size(), hipMemcpyDeviceToHost, h->stream));
   HIP_TRY(hipStreamSynchronize(h->stream));
@@ -1119,7 +1130,7 @@ int idocp_ocp_get_step_sizes(idocp_ocp_t* h, double* primal, double* dual) {
 // chain != 0: one entry per stage of the chain (P, s: M entries; K, k: M - 1); chain == 0: grid stages 0..N
 static int getRiccati(idocp_ocp_t* h, int instance, int chain, double* P, double* s, double* K, double* k) {
   if (!h || instance < 0 || instance >= h->batch) return IDOCP_E_ARG;
-  int rc = setDev(h); if (rc) return rc;
+  int rc = enterO(h); if (rc) return rc;
   const int nv = DQ::NV, nx = DQ::NX, nu = DQ::NU;
   const int n = chain ? h->M() : h->plan.Ngrid + 1;
   std::vector<double> ric((size_t)h->NS * LQ::RIC), gain((size_t)h->NS * LQ::GAIN);
@@ -1152,7 +1163,7 @@ int idocp_ocp_get_riccati_chain(idocp_ocp_t* h, int instance, double* P, double*
 
 int idocp_ocp_get_state_feedback_gain(idocp_ocp_t* h, int instance, int stage, double* Kq, double* Kv) {
   if (!h || instance < 0 || instance >= h->batch || stage < 0 || stage >= h->plan.Ngrid || !Kq || !Kv) return IDOCP_E_ARG;
-  int rc = setDev(h); if (rc) return rc;
+  int rc = enterO(h); if (rc) return rc;
   std::vector<double> g(LQ::GAIN);
   HIP_TRY(hipMemcpyAsync(g.data(), h->B.gain + ((size_t)instance * h->NS + stage) * LQ::GAIN, g.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream));
   HIP_TRY(hipStreamSynchronize(h->stream));
@@ -1168,7 +1179,7 @@ int idocp_ocp_get_state_feedback_gain(idocp_ocp_t* h, int instance, int stage, d
 // stage in the reference's order (stages, impulses, aux, lifts), -1 if none.
 int idocp_ocp_is_current_solution_feasible(idocp_ocp_t* h, int* feasible, int* where) {
   if (!h || !feasible) return IDOCP_E_ARG;
-  int rc = setDev(h); if (rc) return rc;
+  int rc = enterO(h); if (rc) return rc;
   if ((rc = ensureDiscretized(h))) return rc;
   const int M = h->M(), nu = DQ::NU;
   const OcpProblem& P = h->prob;
@@ -1229,7 +1240,7 @@ int idocp_ocp_dimc(const idocp_ocp_t* h) {
 
 int idocp_ocp_get_constraint_data(idocp_ocp_t* h, int instance, double* slack, double* dual) {
   if (!h || instance < 0 || instance >= h->batch) return IDOCP_E_ARG;
-  int rc = setDev(h); if (rc) return rc;
+  int rc = enterO(h); if (rc) return rc;
   const int N = h->plan.Ngrid, dimc = idocp_ocp_dimc(h);
   std::vector<double> sl((size_t)N * LQ::CON), du((size_t)N * LQ::CON);
   HIP_TRY(hipMemcpyAsync(sl.data(), h->B.slack + (size_t)instance * h->NS * LQ::CON, sl.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream));
@@ -1260,7 +1271,7 @@ int idocp_ocp_get_constraint_data(idocp_ocp_t* h, int instance, double* slack, d
 
 int idocp_ocp_get_profile(idocp_ocp_t* h, long long* out, int n) {
   if (!h || !out || n <= 0 || n > 64) return IDOCP_E_ARG;
-  int rc = setDev(h); if (rc) return rc;
+  int rc = enterO(h); if (rc) return rc;
   HIP_TRY(hipMemcpy(out, h->B.prof, sizeof(long long) * n, hipMemcpyDeviceToHost));
   return IDOCP_OK;
 }
@@ -1273,7 +1284,7 @@ int idocp_ocp_set_lqr_stage(idocp_ocp_t* h, int stage, int terminal, const doubl
                             const double* Fx) {
   if (!h || !Qxx || !lx || stage < 0 || stage > h->plan.Ngrid) return IDOCP_E_ARG;
   if (!terminal && (!Qxu || !Quu || !Fqq6 || !Fqv6 || !Fvq || !Fvv || !Fvu || !lu || !Fx)) return IDOCP_E_ARG;
-  int rc = setDev(h); if (rc) return rc;
+  int rc = enterO(h); if (rc) return rc;
   const int nv = DQ::NV, nx = DQ::NX, nu = DQ::NU;
   std::vector<double> k(LQ::KKT, 0.0);
   for (int c = 0; c < nx; ++c) for (int r = 0; r <= c; ++r) k[LQ::K_QXX + LQ::xsym(r, c)] = Qxx[c * nx + r];
@@ -1315,7 +1326,7 @@ int idocp_ocp_get_contact_dynamics_chain(idocp_ocp_t* h, int instance, int posit
   return getContactDynamics(h, instance, nd.slot, nd.dimf, MJtJinv, MJtJinv_dIDCdqv, MJtJinv_IDC);
 }
 static int getContactDynamics(idocp_ocp_t* h, int instance, int stage, int dimf, double* MJtJinv, double* MJtJinv_dIDCdqv, double* MJtJinv_IDC) {
-  int rc = setDev(h); if (rc) return rc;
+  int rc = enterO(h); if (rc) return rc;
   std::vector<double> e(LQ::EXP);
   HIP_TRY(hipMemcpyAsync(e.data(), h->B.exp + ((size_t)instance * h->NS + stage) * LQ::EXP, e.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream));
   HIP_TRY(hipStreamSynchronize(h->stream));
@@ -1329,7 +1340,7 @@ static int getContactDynamics(idocp_ocp_t* h, int instance, int stage, int dimf,
 int idocp_ocp_get_lqr_stage(idocp_ocp_t* h, int instance, int stage, double* Qxx, double* Qxu, double* Quu, double* A, double* Bm,
                             double* lx, double* lu, double* Fx) {
   if (!h || instance < 0 || instance >= h->batch || stage < 0 || stage >= h->plan.Ngrid) return IDOCP_E_ARG;
-  int rc = setDev(h); if (rc) return rc;
+  int rc = enterO(h); if (rc) return rc;
   const int nv = DQ::NV, nx = DQ::NX, nu = DQ::NU;
   std::vector<double> k(LQ::KKT);
   HIP_TRY(hipMemcpyAsync(k.data(), h->B.kkt + ((size_t)instance * h->NS + stage) * LQ::KKT, k.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream));
@@ -1372,7 +1383,7 @@ int idocp_parnmpc_create_hybrid(const idocp_model_t* model, const idocp_cost_t* 
 // ParNMPCSolver::initBackwardCorrection (parnmpc_solver.cpp:66-70)
 int idocp_parnmpc_init_backward_correction(idocp_ocp_t* h, double t) {
   if (!h || !h->parnmpc) return IDOCP_E_ARG;
-  int rc = setDev(h); if (rc) return rc;
+  int rc = enterO(h); if (rc) return rc;
   if ((rc = discretize(h, t))) return rc;
   OcpLaunch<DQ>::parnmpcPhase(4, h->B, h->batch, h->M(), h->plan.has_terminal, h->d_q0, h->d_v0, h->stream);
   HIP_TRY(hipGetLastError());
@@ -1381,12 +1392,12 @@ int idocp_parnmpc_init_backward_correction(idocp_ocp_t* h, double t) {
 }
 
 // phases of ParNMPCSolver::updateSolution (parnmpc_solver.cpp:73-103), separately launchable (bench, tests):
-// 0 K5a tangent RNEA, 1 K9a backward-Euler condensation, 2 K9b KKT inverse + coarse update, 3 S5 backward serial,
+// 0 K5a tangent RNEA, 1 K9a backward-Euler condensation, 2 K9w KKT inverse + coarse update, 3 S5 backward serial,
 // 4 K10a backward parallel, 5 S6 forward serial, 6 K10b forward parallel + direction, 7 K6 expansion + step sizes,
 // 8 step-size reduction, 9 K7 dual expansion + integration
 int idocp_parnmpc_launch_phase(idocp_ocp_t* h, int phase, const double* d_q, const double* d_v) {
   if (!h || !h->parnmpc || phase < 0 || phase > 9 || !d_q || !d_v) return IDOCP_E_ARG;
-  int rc = setDev(h); if (rc) return rc;
+  int rc = enterO(h); if (rc) return rc;
   if ((rc = ensureDiscretized(h))) return rc;
   const int M = h->M();
   switch (phase) {
@@ -1412,7 +1423,7 @@ int idocp_parnmpc_launch_phase(idocp_ocp_t* h, int phase, const double* d_q, con
 int idocp_parnmpc_update_solution_device(idocp_ocp_t* h, double t, const double* d_q, const double* d_v) {
   if (!h || !h->parnmpc || !d_q || !d_v) return IDOCP_E_ARG;
   if (!h->seq.status_set) { set_last_error("idocp_parnmpc_update_solution: call setContactStatusUniformly first"); return IDOCP_E_ARG; }
-  int rc = setDev(h); if (rc) return rc;
+  int rc = enterO(h); if (rc) return rc;
   if ((rc = discretize(h, t))) return rc;
   HIP_TRY(hipMemsetAsync(h->B.status, 0, sizeof(int) * h->batch, h->stream));
   for (int phase = 0; phase <= 9; ++phase) if ((rc = idocp_parnmpc_launch_phase(h, phase, d_q, d_v))) return rc;
@@ -1424,7 +1435,7 @@ int idocp_parnmpc_update_solution_device(idocp_ocp_t* h, double t, const double*
 int idocp_parnmpc_compute_direction(idocp_ocp_t* h, double t, const double* q, const double* v) {
   if (!h || !h->parnmpc || !q || !v) return IDOCP_E_ARG;
   if (!h->seq.status_set) { set_last_error("idocp_parnmpc_update_solution: call setContactStatusUniformly first"); return IDOCP_E_ARG; }
-  int rc = setDev(h); if (rc) return rc;
+  int rc = enterO(h); if (rc) return rc;
   HIP_TRY(hipMemcpyAsync(h->d_q0, q, sizeof(double) * h->batch * DQ::NQ, hipMemcpyHostToDevice, h->stream));
   HIP_TRY(hipMemcpyAsync(h->d_v0, v, sizeof(double) * h->batch * DQ::NV, hipMemcpyHostToDevice, h->stream));
   if ((rc = discretize(h, t))) return rc;
@@ -1436,7 +1447,7 @@ int idocp_parnmpc_compute_direction(idocp_ocp_t* h, double t, const double* q, c
 
 int idocp_parnmpc_update_solution(idocp_ocp_t* h, double t, const double* q, const double* v, int line_search) {
   if (!h || !h->parnmpc || !q || !v) return IDOCP_E_ARG;
-  int rc = setDev(h); if (rc) return rc;
+  int rc = enterO(h); if (rc) return rc;
   if (line_search) {
     // ParNMPCSolver::updateSolution(t, q, v, true) (parnmpc_solver.cpp:73-103): direction, filter line search on the primal step, integration
     // (the support check needs the chain of this t; nothing has touched the direction / Riccati records when it refuses)
@@ -1461,7 +1472,7 @@ int idocp_parnmpc_update_solution(idocp_ocp_t* h, double t, const double* q, con
 
 int idocp_parnmpc_compute_kkt_residual(idocp_ocp_t* h, double t, const double* q, const double* v) {
   if (!h || !h->parnmpc || !q || !v) return IDOCP_E_ARG;
-  int rc = setDev(h); if (rc) return rc;
+  int rc = enterO(h); if (rc) return rc;
   if ((rc = discretize(h, t))) return rc;
   const int M = h->M();
   HIP_TRY(hipMemcpyAsync(h->d_q0, q, sizeof(double) * h->batch * DQ::NQ, hipMemcpyHostToDevice, h->stream));
@@ -1514,7 +1525,7 @@ int idocp_parnmpc_halo_size(int kind) {
 // *_device entry points otherwise take as d_q, d_v): use idocp_parnmpc_prev_state to get those pointers.
 static int haloImpl(idocp_ocp_t* h, int kind, bool do_import, double* d_buf, bool sync) {
   if (!h || !h->parnmpc || !d_buf || idocp_parnmpc_halo_size(kind) < 0) return IDOCP_E_ARG;
-  int rc = setDev(h); if (rc) return rc;
+  int rc = enterO(h); if (rc) return rc;
   if ((rc = ensureDiscretized(h))) return rc;
   OcpLaunch<DQ>::parnmpcHalo(h->B, h->batch, kind, do_import, d_buf, h->d_q0, h->d_v0, h->stream);
   HIP_TRY(hipGetLastError());
@@ -1544,7 +1555,7 @@ int idocp_parnmpc_set_line_search_hooks(idocp_ocp_t* h, int (*pre)(idocp_ocp_t*)
 // the shard's first stage (d_buf[batch][idocp_parnmpc_halo_size(0)], enqueued on the handle's stream)
 int idocp_parnmpc_trial_halo_async(idocp_ocp_t* h, int do_import, double* d_buf) {
   if (!h || !h->parnmpc || !d_buf) return IDOCP_E_ARG;
-  int rc = setDev(h); if (rc) return rc;
+  int rc = enterO(h); if (rc) return rc;
   OcpBuffers Bt = h->B;
   if (!do_import) Bt.sol = h->B.sol_try;
   OcpLaunch<DQ>::parnmpcHalo(Bt, h->batch, 0, do_import != 0, d_buf, h->d_qtry, h->d_vtry, h->stream);
@@ -1561,7 +1572,7 @@ int idocp_parnmpc_merit_device(idocp_ocp_t* h, double** d_merit) {
 // accepted primal steps
 int idocp_parnmpc_line_search(idocp_ocp_t* h) {
   if (!h || !h->parnmpc) return IDOCP_E_ARG;
-  int rc = setDev(h); if (rc) return rc;
+  int rc = enterO(h); if (rc) return rc;
   if ((rc = parnmpcLineSearchSupported(h))) return rc;
   return runLineSearchO(h, h->d_q0);
 }
@@ -1574,7 +1585,7 @@ int idocp_parnmpc_step_sizes_device(idocp_ocp_t* h, double** d_steps) {
 // discretise at time t (uploads the stage references) without running anything: call before the first phase of an iteration
 int idocp_parnmpc_discretize(idocp_ocp_t* h, double t) {
   if (!h || !h->parnmpc) return IDOCP_E_ARG;
-  int rc = setDev(h); if (rc) return rc;
+  int rc = enterO(h); if (rc) return rc;
   HIP_TRY(hipMemsetAsync(h->B.status, 0, sizeof(int) * h->batch, h->stream));
   return discretize(h, t);
 }
@@ -1583,7 +1594,7 @@ int idocp_parnmpc_discretize(idocp_ocp_t* h, double t) {
 // error of the shard's stages is then d_err2[batch]
 int idocp_parnmpc_kkt_error_squared_device(idocp_ocp_t* h, double t, double* d_err2) {
   if (!h || !h->parnmpc || !d_err2) return IDOCP_E_ARG;
-  int rc = setDev(h); if (rc) return rc;
+  int rc = enterO(h); if (rc) return rc;
   if ((rc = discretize(h, t))) return rc;
   const int M = h->M();
   OcpLaunch<DQ>::rnea(h->B, h->batch, M, h->plan.n_impulse(), h->stream);
@@ -1600,7 +1611,7 @@ int idocp_ocp_batch(idocp_ocp_t* h) { return h ? h->batch : 0; }
 int idocp_ocp_set_riccati_storage(idocp_ocp_t* h, int bits) {
   if (!h || (bits != 32 && bits != 64)) return IDOCP_E_ARG;
   if (h->parnmpc) { set_last_error("idocp_ocp_set_riccati_storage: the Riccati sweep belongs to OCPSolver"); return IDOCP_E_UNSUPPORTED; }
-  int rc = setDev(h); if (rc) return rc;
+  int rc = enterO(h); if (rc) return rc;
   h->prob.ric_fp32 = bits == 32 ? 1 : 0;
   HIP_TRY(hipMemcpyAsync(h->d_prob, &h->prob, sizeof(OcpProblem), hipMemcpyHostToDevice, h->stream));
   HIP_TRY(hipStreamSynchronize(h->stream));
@@ -1665,6 +1676,7 @@ int idocp_ocp_set_cost(idocp_ocp_t* h, const idocp_cost_t* cost) {
   }
   if (cost->task_dim != 0 && (cost->task_dim != 3 && cost->task_dim != 6)) { set_last_error("invalid value: task_dim must be 0, 3 or 6"); return IDOCP_E_ARG; }
   { const int rc_t = checkTaskExtras(cost); if (rc_t) return rc_t; }
+  { const int rc_e = enterO(h); if (rc_e) return rc_e; }
   h->cost = *cost;
   fillCostFields(h->prob, *cost);
   h->seq_dirty = true;              // the problem block and the per-stage reference table are uploaded with the next discretisation
@@ -1672,9 +1684,9 @@ int idocp_ocp_set_cost(idocp_ocp_t* h, const idocp_cost_t* cost) {
 }
 int idocp_ocp_clone(idocp_ocp_t* src, idocp_ocp_t** out) {
   if (!src || !out) return IDOCP_E_ARG;
-  int rc = setDev(src); if (rc) return rc;
+  int rc = enterO(src); if (rc) return rc;      // (the copies below read through the source's stream)
   idocp_ocp_t* h = nullptr;
-  if ((rc = createOcpImpl(&src->model, &src->cost, &src->cons, src->T, src->N, src->E, src->batch, src->device, src->parnmpc, &h))) return rc;
+  if ((rc = createOcpImpl(&src->model, &src->cost, &src->cons, src->T, src->N, src->E, src->batch, src->device, src->parnmpc, &h, &src->forms))) return rc;
   auto fail = [&](int code) { (void)hipGetLastError(); idocp_ocp_destroy(h); return code; };      // (clears HIP's sticky last error: see HIP_TRY)
   if (h->allocs.size() != src->allocs.size()) { set_last_error("idocp_ocp_clone: allocation tables differ"); return fail(IDOCP_E_DEVICE); }
   if (hipStreamSynchronize(src->stream) != hipSuccess) return fail(IDOCP_E_DEVICE);
@@ -1686,8 +1698,6 @@ int idocp_ocp_clone(idocp_ocp_t* src, idocp_ocp_t** out) {
   h->task_refs_host = src->task_refs_host; h->task_refs_t = src->task_refs_t;
   h->seq = src->seq; h->stage_offset = src->stage_offset; h->plan.has_terminal = src->plan.has_terminal; h->plan.has_prev = src->plan.has_prev;
   h->slice_begin = src->slice_begin; h->slice_end = src->slice_end;
-  h->fused_forward_mode = src->fused_forward_mode;
-  h->riccati_sweep_mode = src->riccati_sweep_mode;
   h->filters = src->filters;                 // the line-search filter is part of the solver's state (LineSearch is a member of the reference's solvers)
   h->prob = src->prob;
   h->seq_dirty = true;                       // the chain is rebuilt (and uploaded) on first use

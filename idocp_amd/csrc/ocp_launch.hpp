@@ -5,11 +5,9 @@
 #include <hip/hip_runtime.h>
 
 #include "ocp_device.hpp"
+#include "ocp_forms.hpp"      // OcpForwardExpandMaxChain
 
 namespace idocp_dev {
-
-// longest chain ocp_forward_expand_kernel keeps in LDS (slot, status word, two time steps per node); longer chains run S4 + K6
-constexpr int OcpForwardExpandMaxChain = 320;
 
 template <typename D>
 struct OcpLaunch {
@@ -19,9 +17,7 @@ struct OcpLaunch {
   // q0_lie != nullptr: with the Lie-group tasks of the forward-Euler stages (else the caller launches a lie kernel itself)
   static void nominal(const OcpBuffers& B, long batch, int M, hipStream_t st, const double* q0_lie = nullptr, hipStream_t st_imp = nullptr);      // st_imp: the launch over the impulse stages of a forward-Euler chain on a stream of its own      // K5n: nominal Newton-Euler sweeps -> nom record (every K5 / K8 / merit launch is preceded by it)
   static void condense(const OcpBuffers& B, long batch, int M, int dimf, const double* q0, hipStream_t st, int part = 0);   // K5b (+ terminal); dimf = -1: mixed chain
-  // part 0: everything; 1: the nominal sweeps + external rows; 2: the class launches + external Hessian; 3: the LARGEST class only; 4: the other
-  // classes only (parts 3 and 4 let the caller put them on two streams: the launches are independent, every stage writes its own records);
-  // 5: the external Hessian only
+  // part 0: everything; 1: the nominal sweeps + external rows; 2: the class launches + external Hessian
   static void condenseMixed(const OcpBuffers& B, long batch, int M, const int n[5], const double* q0, hipStream_t st, int part = 0, hipStream_t st_imp = nullptr);   // K5b on a chain with events, per stage class
   static void residual(const OcpBuffers& B, long batch, int M, const double* q0, hipStream_t st);   // K8
   static void condenseBackwardEuler(const OcpBuffers& B, long batch, int M, const double* q0, const double* v0, bool residual,
@@ -30,8 +26,7 @@ struct OcpLaunch {
   // sweep of one wavefront per instance
   static void riccatiBackward(const OcpBuffers& B, long batch, int M, bool hybrid, hipStream_t st, bool wide = false);
   static void riccatiForward(const OcpBuffers& B, long batch, int M, const double* q0, const double* v0, hipStream_t st);  // S4
-  static void parnmpcInverse(const OcpBuffers& B, long batch, int M, hipStream_t st);            // K9w, or K9b with IDOCP_K9_WAVE=0
-  static void parnmpcInverseWave(const OcpBuffers& B, long batch, int M, hipStream_t st);        // K9w (parnmpc_kkt_wave_kernel.hip)
+  static void parnmpcInverse(const OcpBuffers& B, long batch, int M, hipStream_t st);            // K9w (parnmpc_kkt_wave_kernel.hip)
   // terms with frame Jacobians of their own (ocp_ext_kernel.hip): no-ops when B.ext == nullptr
   static void extRows(const OcpBuffers& B, long batch, int M, bool residual, hipStream_t st);
   static void extHessian(const OcpBuffers& B, long batch, int M, hipStream_t st);
@@ -39,8 +34,7 @@ struct OcpLaunch {
   static void parnmpcImpulseMerit(const OcpBuffers& Btry, long batch, int n_impulse, const double* q0, const double* v0, hipStream_t st);      // line search on the impulse stages
   static void parnmpcImpulseCondense(const OcpBuffers& B, long batch, int n_impulse, bool residual, const double* q0, const double* v0,
                                      hipStream_t st);                                               // K9i: impulse stages of a ParNMPC chain
-  static void parnmpcEventInverse(const OcpBuffers& B, long batch, int n_general, hipStream_t st); // aux (switching rows) and impulse stages: K9w's general instantiation, or K9g with IDOCP_K9_WAVE=0
-  static void parnmpcEventInverseWave(const OcpBuffers& B, long batch, int n_general, hipStream_t st);
+  static void parnmpcEventInverse(const OcpBuffers& B, long batch, int n_general, hipStream_t st); // aux (switching rows) and impulse stages: K9w's general instantiation
   static void parnmpcPhase(int phase, const OcpBuffers& B, long batch, int M, bool has_terminal, const double* q0, const double* v0,
                            hipStream_t st);                                                       // 0 S5, 1 K10a, 2 S6, 3 K10b, 4 init aux_mat
   static void parnmpcHalo(const OcpBuffers& B, long batch, int kind, bool do_import, double* buf, double* q0, double* v0, hipStream_t st);

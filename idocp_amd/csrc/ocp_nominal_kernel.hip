@@ -12,7 +12,6 @@
 // record the tangent items of the condensation kernel read as LDS broadcasts (OcpLayout::O_JOINT .. O_IDC, 5.2 kB, copied into
 // its LDS scratch in 16-byte pieces; dev_rnea_tangent.hpp RneaScratch).
 #include <hip/hip_runtime.h>
-#include <cstdlib>
 
 #include "dev_dense.hpp"
 #include "dev_lie.hpp"
@@ -300,16 +299,15 @@ template <typename D>
 void OcpLaunch<D>::nominal(const OcpBuffers& B, long batch, int M, hipStream_t st, const double* q0_lie, hipStream_t st_imp) {
   const unsigned ntask = 2 * D::NL + 1 + (q0_lie ? 3 : 0);
   const unsigned groups = (unsigned)((batch * M + 63) / 64), blocks = ((groups + 7) / 8) * 8 * ntask;
-  static const int dbg = getenv("IDOCP_NOM_DBG") ? atoi(getenv("IDOCP_NOM_DBG")) : 0;
-  if (B.leg_axes_xyy) hipLaunchKernelGGL((ocp_nominal_kernel<D, true, false>), dim3(blocks), dim3(64), 0, st, B, dbg, 0, q0_lie);
-  else hipLaunchKernelGGL((ocp_nominal_kernel<D, false, false>), dim3(blocks), dim3(64), 0, st, B, dbg, 0, q0_lie);
+  if (B.leg_axes_xyy) hipLaunchKernelGGL((ocp_nominal_kernel<D, true, false>), dim3(blocks), dim3(64), 0, st, B, 0, 0, q0_lie);
+  else hipLaunchKernelGGL((ocp_nominal_kernel<D, false, false>), dim3(blocks), dim3(64), 0, st, B, 0, 0, q0_lie);
   // the impulse stages of a forward-Euler chain (ParNMPC's go through K5a / K9i)
   if (B.n_impulse_fe > 0) {
     const unsigned gi = (unsigned)((batch * B.n_impulse_fe + 63) / 64), bi = ((gi + 7) / 8) * 8 * (2 * D::NL + 1);
     const double* none = nullptr;
     hipStream_t si = st_imp ? st_imp : st;      // (impulse stages have records of their own: independent of the launch above)
-    if (B.leg_axes_xyy) hipLaunchKernelGGL((ocp_nominal_kernel<D, true, true>), dim3(bi), dim3(64), 0, si, B, dbg, B.n_impulse_fe, none);
-    else hipLaunchKernelGGL((ocp_nominal_kernel<D, false, true>), dim3(bi), dim3(64), 0, si, B, dbg, B.n_impulse_fe, none);
+    if (B.leg_axes_xyy) hipLaunchKernelGGL((ocp_nominal_kernel<D, true, true>), dim3(bi), dim3(64), 0, si, B, 0, B.n_impulse_fe, none);
+    else hipLaunchKernelGGL((ocp_nominal_kernel<D, false, true>), dim3(bi), dim3(64), 0, si, B, 0, B.n_impulse_fe, none);
   }
 }
 

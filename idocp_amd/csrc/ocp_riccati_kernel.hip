@@ -13,7 +13,6 @@
 // S3: one 256-thread workgroup per OCP instance walks the horizon backwards with
 // P_{i+1} and the stage's LQR blocks resident in LDS (~52 kB -> three instances per CU).
 #include <hip/hip_runtime.h>
-#include <cstdlib>
 #include <type_traits>
 
 #include "dev_dense.hpp"
@@ -1574,60 +1573,28 @@ __global__ __launch_bounds__(64) void ocp_riccati_forward_kernel(OcpBuffers B, c
 template <typename D>
 void OcpLaunch<D>::riccatiBackward(const OcpBuffers& B, long batch, int M, bool hybrid, hipStream_t st, bool wide) {
   (void)M;
-  const size_t smem = RiccatiSmem<D>::TOTAL * sizeof(double), smem_h = smem;      // the Schur blocks alias dead ones
+  const size_t smem = RiccatiSmem<D>::TOTAL * sizeof(double);      // (the Schur blocks of the hybrid instantiation alias dead ones)
+  const size_t rs = RiccatiRegSmem<D>::BYTES;
   static bool configured = false;
-  if (!configured) {
-    (void)hipFuncSetAttribute((const void*)ocp_riccati_backward_kernel<D, 256, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-    (void)hipFuncSetAttribute((const void*)ocp_riccati_backward_kernel<D, 128, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-    (void)hipFuncSetAttribute((const void*)ocp_riccati_backward_kernel<D, 64, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-    (void)hipFuncSetAttribute((const void*)ocp_riccati_backward_kernel<D, 128, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem_h);
-    (void)hipFuncSetAttribute((const void*)ocp_riccati_backward_kernel<D, 256, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem_h);
-    (void)hipFuncSetAttribute((const void*)ocp_riccati_backward_kernel<D, 64, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem_h);
-    (void)hipFuncSetAttribute((const void*)ocp_riccati_backward_kernel<D, 512, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem_h);
+  if (!configured) {      // both forms on the first call, whichever it launches: a later call may be inside a stream capture
+    (void)hipFuncSetAttribute((const void*)ocp_riccati_backward_kernel<D, 512, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
     (void)hipFuncSetAttribute((const void*)ocp_riccati_backward_kernel<D, 512, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
+    (void)hipFuncSetAttribute((const void*)ocp_riccati_backward_reg_kernel<D, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)rs);
+    (void)hipFuncSetAttribute((const void*)ocp_riccati_backward_reg_kernel<D, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)rs);
     configured = true;
   }
-  static const int nt_env = getenv("IDOCP_RICCATI_NT") ? atoi(getenv("IDOCP_RICCATI_NT")) : 0;
-  // round 4: the register-resident sweep (one wavefront per instance at every batch size); IDOCP_RICCATI_REG=0 selects the round-2 kernels
-  static const int reg_env = getenv("IDOCP_RICCATI_REG") ? atoi(getenv("IDOCP_RICCATI_REG")) : 1;
+  // A chain with switching constraints takes the HYBRID instantiation of either kernel.
   // Latency mode (a handful of instances, idocp_ocp_set_riccati_sweep): EIGHT wavefronts per instance on the LDS-staged kernel -- the tile
   // products of a phase run side by side on the four matrix cores of a CU instead of one behind the other on one (batch 1: 0.79 against
   // 0.855 ms per sweep; from 64 instances on the register-resident sweep wins: 0.884 against 0.859 ms)
-  if (nt_env == 512 || (nt_env == 0 && wide)) {
-    if (hybrid) hipLaunchKernelGGL((ocp_riccati_backward_kernel<D, 512, true>), dim3((unsigned)batch), dim3(512), smem_h, st, B);
+  if (wide) {
+    if (hybrid) hipLaunchKernelGGL((ocp_riccati_backward_kernel<D, 512, true>), dim3((unsigned)batch), dim3(512), smem, st, B);
     else hipLaunchKernelGGL((ocp_riccati_backward_kernel<D, 512, false>), dim3((unsigned)batch), dim3(512), smem, st, B);
     return;
   }
-  if (reg_env && nt_env == 0) {
-    const size_t rs = RiccatiRegSmem<D>::BYTES;
-    static bool reg_configured = false;
-    if (!reg_configured) {
-      (void)hipFuncSetAttribute((const void*)ocp_riccati_backward_reg_kernel<D, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)rs);
-      (void)hipFuncSetAttribute((const void*)ocp_riccati_backward_reg_kernel<D, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)rs);
-      reg_configured = true;
-    }
-    if (hybrid) hipLaunchKernelGGL((ocp_riccati_backward_reg_kernel<D, true>), dim3((unsigned)batch), dim3(64), rs, st, B);
-    else hipLaunchKernelGGL((ocp_riccati_backward_reg_kernel<D, false>), dim3((unsigned)batch), dim3(64), rs, st, B);
-    return;
-  }
-  // A chain with switching constraints takes the HYBRID instantiation (same LDS footprint).
-  if (hybrid) {
-    // measured on the trotting / running chains: four instances per CU (batch 1024) are fastest with ONE wavefront each (512 registers,
-    // nothing spilled, no wavefront waits for another: 2.02 vs 2.15 ms), two per CU with two wavefronts each (4.08 vs 4.43 ms)
-    if (nt_env == 64 || (nt_env == 0 && batch >= 1024)) hipLaunchKernelGGL((ocp_riccati_backward_kernel<D, 64, true>), dim3((unsigned)batch), dim3(64), smem_h, st, B);
-    else if (nt_env == 256 || (nt_env == 0 && batch < 512)) hipLaunchKernelGGL((ocp_riccati_backward_kernel<D, 256, true>), dim3((unsigned)batch), dim3(256), smem_h, st, B);
-    else hipLaunchKernelGGL((ocp_riccati_backward_kernel<D, 128, true>), dim3((unsigned)batch), dim3(128), smem_h, st, B);
-    return;
-  }
-  // Throughput mode (many instances): two wavefronts per instance, four instances per CU (39.8 kB
-  // of LDS each) -- measured best at batch 1024 (2.48 ms vs 3.22 ms with one and 2.96 ms with four
-  // wavefronts).  Latency mode (few instances): four wavefronts per instance.
-  // IDOCP_RICCATI_NT={64,128,256} overrides the choice (tuning aid).
-  if (nt_env == 128) hipLaunchKernelGGL((ocp_riccati_backward_kernel<D, 128, false>), dim3((unsigned)batch), dim3(128), smem, st, B);
-  else if (nt_env == 256) hipLaunchKernelGGL((ocp_riccati_backward_kernel<D, 256, false>), dim3((unsigned)batch), dim3(256), smem, st, B);
-  else if (nt_env == 64) hipLaunchKernelGGL((ocp_riccati_backward_kernel<D, 64, false>), dim3((unsigned)batch), dim3(64), smem, st, B);
-  else if (batch >= 512) hipLaunchKernelGGL((ocp_riccati_backward_kernel<D, 128, false>), dim3((unsigned)batch), dim3(128), smem, st, B);
-  else hipLaunchKernelGGL((ocp_riccati_backward_kernel<D, 256, false>), dim3((unsigned)batch), dim3(256), smem, st, B);
+  // round 4: the register-resident sweep, one wavefront per instance at every batch size
+  if (hybrid) hipLaunchKernelGGL((ocp_riccati_backward_reg_kernel<D, true>), dim3((unsigned)batch), dim3(64), rs, st, B);
+  else hipLaunchKernelGGL((ocp_riccati_backward_reg_kernel<D, false>), dim3((unsigned)batch), dim3(64), rs, st, B);
 }
 template <typename D>
 void OcpLaunch<D>::riccatiForward(const OcpBuffers& B, long batch, int M, const double* q0, const double* v0, hipStream_t st) {

@@ -1,26 +1,24 @@
 // ParNMPC: the event stages of a horizon with discrete events (ParNMPCDiscretizer chain, see ocp_capi.hip).
 //
-//   lift stage      an ordinary backward-Euler stage with its own time step: K5a / K5b<BWD> / K9b as they are
+//   lift stage      an ordinary backward-Euler stage with its own time step: K5a / K5b<BWD> / K9w as they are
 //   aux stage       ordinary stage + the switching constraint P(q) = 0 of the impulse that follows (switching_constraint.hxx:
 //                   8-21): K5s produces P, Pq; K5b<BWD> adds Pq^T xi; its KKT matrix has dimi more constraint rows
-//                   (SplitKKTMatrixInverter::invert with Pq, split_kkt_matrix_inverter.hxx:110-166)  -> K9g below
+//                   (SplitKKTMatrixInverter::invert with Pq, split_kkt_matrix_inverter.hxx:110-166)  -> K9w's general instantiation (parnmpc_kkt_wave_kernel.hip)
 //   impulse stage   ImpulseSplitParNMPC::linearizeOCP (impulse_split_parnmpc.hxx:33-60): impulse cost + impulse friction cone,
 //                   linearizeImpulseBackwardEuler / condenseImpulseBackwardEuler (impulse_state_equation.hxx:59-111),
 //                   ImpulseDynamicsBackwardEuler::linearizeImpulseDynamics / condenseImpulseDynamics
 //                   (impulse_dynamics_backward_euler.hxx:20-97)                                  -> K9i below
 //                   and its KKT matrix in (lmd, gmm, mu | f, q, v) (ImpulseSplitKKTMatrixInverter::invert,
-//                   impulse_split_kkt_matrix_inverter.hxx:34-80)                                  -> K9g below
+//                   impulse_split_kkt_matrix_inverter.hxx:34-80)                                  -> K9w's general instantiation
 //
 // K9i writes the impulse stage into the SAME records as a regular stage, re-using their blocks
 //   kkt:  K_QXX = Qxx, K_QXU = [Qqf; 0] (NX x ni), K_QUU = Qff (ni x ni), K_FQQ = Fqq6, K_FVQ = Fvq, K_FVV = -I,
 //         K_FVU = Fvf (NV x ni), K_LX = (lq, lv), K_LU = lf, K_FX = (Fq, Fv)
 //   swc:  W_P = V (contact-velocity residual), W_PHIX = [Vq Vv]
 //   exp:  what K6 / K7 need for computeCondensed{Primal,Dual}Direction of the impulse stage
-// so that K9g treats aux and impulse stages alike:  J = [F ; C], C = the W_PHIX rows on the (q, v) columns,
+// so that the general inverse treats aux and impulse stages alike:  J = [F ; C], C = the W_PHIX rows on the (q, v) columns,
 // Q over (w, q, v) with w = u (aux) or f (impulse).
 #include <hip/hip_runtime.h>
-
-#include <cstdlib>
 
 #include "dev_dense.hpp"
 #include "dev_lie.hpp"
@@ -28,11 +26,6 @@
 #include "ocp_launch.hpp"
 
 namespace idocp_dev {
-
-namespace {
-
-
-}  // namespace
 
 // ---------------------------------------------------------------------------------------------------- K9i ----
 // MERIT (with RESIDUAL): the line search's evaluation of a trial iterate on the impulse stage -- ImpulseSplitParNMPC::stageCost and
@@ -295,219 +288,6 @@ __global__ __launch_bounds__(256) void parnmpc_impulse_condense_kernel(OcpBuffer
   if (tid == 0 && !s_ok && B.status[b] == 0) B.status[b] = 2000 + pos;
 }
 
-// ---------------------------------------------------------------------------------------------------- K9g ----
-// KKT inverse + coarse update of an aux stage (switching rows) or an impulse stage, on the 3 x 3 register tiles of K9b.
-// The stage's matrices are PADDED to fixed sizes so that every loop bound is a compile-time constant:
-//   variables  (w, q, v) with w = u or f padded to NU entries (identity on the padding)      -> Q is NQ x NQ, NQ = NU + NX = 48
-//   constraints [F (NX rows); C (ni rows); zero rows up to NR = NX + NF = 48]; S = J Q^-1 J^T gets 1 on the padded diagonal
-// Padded rows / columns of the inverse are never written out; the kinv record holds the true layout
-//   lmd gmm | xi or mu (ni) | u or f (nw) | q v     with leading dimension NKG.
-template <typename D>
-struct KktInvEventSmem {
-  static constexpr int NX = D::NX, NU = D::NU, NF = D::NF, NQ_ = NU + NX, NR = NX + NF;
-  static_assert(NQ_ == NR && NR % 3 == 0 && (NR / 3) * (NR / 3) <= 256, "square 48 x 48 tiles, one per thread");
-  //   A : Q^-1 -> JQ = J Q^-1 -> BR[:, NU:] (NQ x NX) ;  B : J -> S^-1 -> TR = S^-1 JQ
-  static constexpr int A = 0, B = A + NQ_ * NQ_, PV = B + NR * NQ_,
-                       R1 = PV + 2 * (2 * NQ_ + 2), R2 = R1 + NR, T1 = R2 + NQ_, W = T1 + NR, DIR = W + NQ_, TOTAL = DIR + NR + NQ_ + 4;
-};
-
-template <typename D>
-__global__ __launch_bounds__(256) void parnmpc_kkt_inverse_general_kernel(OcpBuffers B) {
-  using L = OcpLayout<D>;
-  using S = KktInvEventSmem<D>;
-  constexpr int NV = D::NV, NX = D::NX, NU = D::NU, NF = D::NF, NC = D::NC, NQ = S::NQ_, NR = S::NR;
-  constexpr int TQ = NQ / 3;                       // 16 tiles per side of every matrix
-  extern __shared__ __attribute__((aligned(16))) double sm[];
-  __shared__ int s_ok;
-  const OcpProblem* __restrict__ P = B.prob;
-  const int M = B.M;
-  const int tid = threadIdx.x, nt = 256;
-  const long b = blockIdx.x;
-  const int pos = B.general_pos[blockIdx.y];
-  const OcpNode* __restrict__ nd = B.nodes + pos;
-  const ParnmpcShape sh = parnmpcShape<L>(*nd);
-  const int ni = sh.ni, nw = sh.nw, nr = NX + ni, nK = sh.nk;
-  const bool impulse = sh.impulse;
-  const bool last = P->has_terminal && (pos == M - 2);
-  const double dt = nd->dt;
-  const long rec = b * B.NS + nd->slot;
-  const double* __restrict__ kk = B.kkt + rec * L::KKT;
-  const double* __restrict__ Wc = B.swc + rec * L::SWC;
-  const double* __restrict__ aux = B.aux + (b * B.NS + nd->next) * L::AUX;
-  double* __restrict__ ki = B.kinv + rec * L::KINV;
-  if (tid == 0) s_ok = 1;
-  // ---- Q over (w, q, v), padded, straight into the register tiles ----
-  double qinv[3][3];
-  const int ti = tid % TQ, tj = tid / TQ;          // tile (ti, tj) of a 48 x 48 matrix
-#pragma unroll
-  for (int tr = 0; tr < 3; ++tr)
-#pragma unroll
-    for (int tc = 0; tc < 3; ++tc) {
-      const int r = 3 * ti + tr, c = 3 * tj + tc;
-      double v;
-      if (r < NU && c < NU) v = (r < nw && c < nw) ? kk[L::K_QUU + r + NU * c] : (r == c ? 1.0 : 0.0);
-      else if (r < NU) v = r < nw ? kk[L::K_QXU + (c - NU) + NX * r] : 0.0;
-      else if (c < NU) v = c < nw ? kk[L::K_QXU + (r - NU) + NX * c] : 0.0;
-      else {
-        int rr = r - NU, cc = c - NU;
-        const double ax = last ? 0.0 : aux[rr + NX * cc];
-        if (rr > cc) { const int t = rr; rr = cc; cc = t; }      // K5 writes the triangle on and above the diagonal (Qxx symmetric, Qvq = Qqv^T)
-        v = kk[L::K_QXX + L::xsym(rr, cc)] + ax;
-      }
-      qinv[tr][tc] = v;
-    }
-  // ---- J = [0 Fqq Fqv; Fvw Fvq Fvv; 0 Cq Cv; 0] (NR x NQ) -> region B ----
-  for (int e = tid; e < NR * NQ; e += nt) {
-    const int c = e / NR, r = e - c * NR;
-    double v = 0.0;
-    if (r < NV) {
-      if (c >= NU && c < NU + NV) { const int cq = c - NU; v = (r < 6 && cq < 6) ? kk[L::K_FQQ + r + 6 * cq] : ((r >= 6 && r == cq) ? -1.0 : 0.0); }
-      else if (c >= NU + NV && !impulse) { const int cv = c - NU - NV; v = (r < 6 && cv < 6) ? kk[L::K_FQV + r + 6 * cv] : ((r >= 6 && r == cv) ? dt : 0.0); }
-    } else if (r < NX) {
-      const int rv = r - NV;
-      if (c < NU) v = c < nw ? kk[L::K_FVU + rv + NV * c] : 0.0;
-      else if (c < NU + NV) v = kk[L::K_FVQ + rv + NV * (c - NU)];
-      else v = kk[L::K_FVV + rv + NV * (c - NU - NV)];
-    } else if (r < nr && c >= NU) {
-      v = Wc[L::W_PHIX + (r - NX) + NF * (c - NU)];
-    }
-    sm[S::B + e] = v;
-  }
-  if (tid < NR) sm[S::R1 + tid] = tid < NX ? kk[L::K_FX + tid] : (tid < nr ? Wc[L::W_P + tid - NX] : 0.0);
-  if (tid >= 64 && tid < 64 + NQ) { const int r = tid - 64; sm[S::R2 + r] = r < NU ? (r < nw ? kk[L::K_LU + r] : 0.0) : kk[L::K_LX + r - NU]; }
-  blockLdsSync();
-  // ---- Q^-1 ----
-  gaussJordanTiles<NQ>(qinv, true, ti, tj, &sm[S::PV], &s_ok);
-#pragma unroll
-  for (int tr = 0; tr < 3; ++tr)
-#pragma unroll
-    for (int tc = 0; tc < 3; ++tc) sm[S::A + 3 * ti + tr + NQ * (3 * tj + tc)] = qinv[tr][tc];
-  blockLdsSync();
-  // ---- JQ = J Q^-1 (all 256 tiles), then w = Q^-1 r2 ----
-  double acc[3][3] = {{0.0, 0.0, 0.0}, {0.0, 0.0, 0.0}, {0.0, 0.0, 0.0}};
-  tileMM<NQ>(acc, [&](int r, int m) { return sm[S::B + 3 * ti + r + NR * m]; },
-             [&](int m, int c) { return sm[S::A + m + NQ * (3 * tj + c)]; });
-  if (tid < NQ) {
-    double w = 0.0;
-    for (int m = 0; m < NQ; ++m) w += sm[S::A + tid + NQ * m] * sm[S::R2 + m];
-    sm[S::W + tid] = w;
-  }
-  blockLdsSync();                                   // Q^-1 is dead in LDS: JQ takes its place
-#pragma unroll
-  for (int tr = 0; tr < 3; ++tr)
-#pragma unroll
-    for (int tc = 0; tc < 3; ++tc) sm[S::A + 3 * ti + tr + NR * (3 * tj + tc)] = acc[tr][tc];
-  blockLdsSync();
-  // ---- S = J JQ^T (+ 1 on the padded diagonal) into register tiles, S^-1 ----
-  double sinv[3][3] = {{0.0, 0.0, 0.0}, {0.0, 0.0, 0.0}, {0.0, 0.0, 0.0}};
-  tileMM<NQ>(sinv, [&](int r, int m) { return sm[S::B + 3 * ti + r + NR * m]; },
-             [&](int m, int c) { return sm[S::A + 3 * tj + c + NR * m]; });
-  if (ti == tj) {
-#pragma unroll
-    for (int t3 = 0; t3 < 3; ++t3) if (3 * ti + t3 >= nr) sinv[t3][t3] = 1.0;
-  }
-  gaussJordanTiles<NR>(sinv, true, ti, tj, &sm[S::PV], &s_ok);      // its first barrier also ends the reads of J
-#pragma unroll
-  for (int tr = 0; tr < 3; ++tr)
-#pragma unroll
-    for (int tc = 0; tc < 3; ++tc) sm[S::B + 3 * ti + tr + NR * (3 * tj + tc)] = sinv[tr][tc];
-  blockLdsSync();
-  // ---- TR = S^-1 JQ ; t1 = r1 - JQ r2 ; what else reads S^-1: TL = -S^-1[:, 0:NX] and -S^-1 r1 ----
-#pragma unroll
-  for (int tr = 0; tr < 3; ++tr)
-#pragma unroll
-    for (int tc = 0; tc < 3; ++tc) acc[tr][tc] = 0.0;
-  tileMM<NR>(acc, [&](int r, int m) { return sm[S::B + 3 * ti + r + NR * m]; },
-             [&](int m, int c) { return sm[S::A + m + NR * (3 * tj + c)]; });
-  if (tid < NR) {
-    const int r = tid;
-    double t = sm[S::R1 + r];
-    for (int m = 0; m < NQ; ++m) t -= sm[S::A + r + NR * m] * sm[S::R2 + m];
-    sm[S::T1 + r] = t;
-    double d = 0.0;
-    for (int m = 0; m < NR; ++m) d -= sm[S::B + r + NR * m] * sm[S::R1 + m];
-    sm[S::DIR + r] = d;
-  }
-  for (int e = tid; e < nr * NX; e += nt) {
-    const int c = e / nr, r = e - c * nr;
-    ki[L::I_C0 + r + L::NKG * c] = -sm[S::B + r + NR * c];
-  }
-  blockLdsSync();                                   // S^-1 is dead: TR takes its place
-#pragma unroll
-  for (int tr = 0; tr < 3; ++tr)
-#pragma unroll
-    for (int tc = 0; tc < 3; ++tc) sm[S::B + 3 * ti + tr + NR * (3 * tj + tc)] = acc[tr][tc];
-  blockLdsSync();
-  // ---- BR[:, NU:] = Q^-1[:, NU:] - TR^T JQ[:, NU:] by the threads that hold those tiles of Q^-1 ; coarse direction ----
-  const bool b_on = tj >= NU / 3;
-  if (b_on) {
-#pragma unroll
-    for (int tr = 0; tr < 3; ++tr)
-#pragma unroll
-      for (int tc = 0; tc < 3; ++tc) acc[tr][tc] = 0.0;
-    tileMM<NR>(acc, [&](int r, int m) { return sm[S::B + m + NR * (3 * ti + r)]; },
-               [&](int m, int c) { return sm[S::A + m + NR * (3 * tj + c)]; });
-  } else if (tid < NR) {
-    double d = sm[S::DIR + tid];
-    for (int m = 0; m < NQ; ++m) d += sm[S::B + tid + NR * m] * sm[S::R2 + m];
-    sm[S::DIR + tid] = d;
-  }
-  if (tid >= 256 - NQ) {
-    const int r = tid - (256 - NQ);
-    double d = sm[S::W + r];
-    for (int m = 0; m < NR; ++m) d += sm[S::B + m + NR * r] * sm[S::T1 + m];
-    sm[S::DIR + NR + r] = d;
-  }
-  blockLdsSync();                                   // JQ is dead: BR[:, NU:] takes its place (NQ x NX)
-  if (b_on) {
-#pragma unroll
-    for (int tr = 0; tr < 3; ++tr)
-#pragma unroll
-      for (int tc = 0; tc < 3; ++tc) sm[S::A + 3 * ti + tr + NQ * (3 * (tj - NU / 3) + tc)] = qinv[tr][tc] - acc[tr][tc];
-  }
-  blockLdsSync();
-  // ---- column blocks of the inverse in the true row layout: C0 = KKT_inv[:, 0:NX] (top part written above),
-  //      C1 = KKT_inv[:, nK-NX : nK] ----
-  for (int e = tid; e < nK * NX; e += nt) {
-    const int c = e / nK, r = e - c * nK;
-    if (r < nr) {
-      ki[L::I_C1G + r + L::NKG * c] = sm[S::B + r + NR * (NU + c)];
-    } else {
-      const int rt = r - nr;                                   // true variable row: w (nw), then q, v
-      const int rq = rt < nw ? rt : NU + (rt - nw);            // padded variable row
-      ki[L::I_C0 + r + L::NKG * c] = sm[S::B + c + NR * rq];
-      ki[L::I_C1G + r + L::NKG * c] = sm[S::A + rq + NQ * c];
-    }
-  }
-  // ---- s_new = s - direction (split_backward_correction.hxx:49-63, impulse_split_backward_correction.hxx:43-55) ----
-  const double* __restrict__ s = B.sol + rec * L::SOL;
-  double* __restrict__ sn = B.snew + rec * L::SNEW;
-  const double* dir = &sm[S::DIR];          // padded: [lmd gmm | extra (NF) ] | [w (NU) | dq dv]
-  const double* dw = dir + NR;
-  if (tid < NV) {
-    sn[L::N_LMD + tid] = s[L::S_LMD + tid] - dir[tid];
-    sn[L::N_GMM + tid] = s[L::S_GMM + tid] - dir[NV + tid];
-    sn[L::N_V + tid] = s[L::S_V + tid] - dw[NU + NV + tid];
-    if (tid >= 6) sn[L::N_Q + tid + 1] = s[L::S_Q + tid + 1] - dw[NU + tid];
-  }
-  if (!impulse) {
-    if (tid >= 64 && tid < 64 + NU) sn[L::N_U + tid - 64] = s[L::S_U + tid - 64] - dw[tid - 64];
-    if (tid >= 96 && tid < 96 + ni) sn[L::N_XI + tid - 96] = s[L::S_XI + tid - 96] - dir[NX + tid - 96];
-  } else if (tid >= 64 && tid < 64 + NC && nd->active[tid - 64]) {
-    const int c = tid - 64, row = nd->row_of[c];
-    for (int k = 0; k < 3; ++k) {
-      sn[L::N_U + row + k] = s[L::S_F + 3 * c + k] - dw[row + k];             // f, packed rows
-      sn[L::N_XI + row + k] = s[L::S_MU + 3 * c + k] - dir[NX + row + k];     // mu, packed rows
-    }
-  }
-  if (tid == 128) {
-    double qn[7];
-    lieIntegrateBase(s + L::S_Q, dw + NU, -1.0, qn);
-    for (int k = 0; k < 7; ++k) sn[L::N_Q + k] = qn[k];
-  }
-  if (tid == 0 && !s_ok && B.status[b] == 0) B.status[b] = 1000 + pos;
-}
-
 template <typename D>
 void OcpLaunch<D>::parnmpcImpulseCondense(const OcpBuffers& B, long batch, int n_impulse, bool residual, const double* q0, const double* v0,
                                           hipStream_t st) {
@@ -524,23 +304,7 @@ void OcpLaunch<D>::parnmpcImpulseMerit(const OcpBuffers& Btry, long batch, int n
   hipLaunchKernelGGL((parnmpc_impulse_condense_kernel<D, true, true>), dim3((unsigned)batch, (unsigned)n_impulse), dim3(256), 0, st, Btry, q0, v0);
 }
 
-template <typename D>
-void OcpLaunch<D>::parnmpcEventInverse(const OcpBuffers& B, long batch, int n_general, hipStream_t st) {
-  if (n_general <= 0) return;
-  // K9w's general instantiation (one wavefront per stage, parnmpc_kkt_wave_kernel.hip) unless IDOCP_K9G_WAVE=0 / IDOCP_K9_WAVE=0 ask for K9g below
-  static const bool wave = [] { const char* e = getenv("IDOCP_K9G_WAVE"); const char* e2 = getenv("IDOCP_K9_WAVE"); return !((e && e[0] == '0') || (e2 && e2[0] == '0')); }();
-  if (wave) { parnmpcEventInverseWave(B, batch, n_general, st); return; }
-  const size_t smem = KktInvEventSmem<D>::TOTAL * sizeof(double);
-  static bool configured = false;
-  if (!configured) {
-    (void)hipFuncSetAttribute((const void*)parnmpc_kkt_inverse_general_kernel<D>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-    configured = true;
-  }
-  hipLaunchKernelGGL((parnmpc_kkt_inverse_general_kernel<D>), dim3((unsigned)batch, (unsigned)n_general), dim3(256), smem, st, B);
-}
-
 template void OcpLaunch<LeggedDims<4, 3>>::parnmpcImpulseCondense(const OcpBuffers&, long, int, bool, const double*, const double*, hipStream_t);
 template void OcpLaunch<LeggedDims<4, 3>>::parnmpcImpulseMerit(const OcpBuffers&, long, int, const double*, const double*, hipStream_t);
-template void OcpLaunch<LeggedDims<4, 3>>::parnmpcEventInverse(const OcpBuffers&, long, int, hipStream_t);
 
 }  // namespace idocp_dev

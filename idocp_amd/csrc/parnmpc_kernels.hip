@@ -1,22 +1,17 @@
-// ParNMPC: per-stage KKT inverse, coarse update and the correction sweeps.
+// ParNMPC: the correction sweeps behind the per-stage KKT inverse and coarse update (K9w, parnmpc_kkt_wave_kernel.hip).
 //
-// Replaces, for horizons without discrete events,
-//   SplitKKTMatrixInverter::invert            (include/idocp/ocp/split_kkt_matrix_inverter.hxx:44-80)
-//   SplitBackwardCorrection::coarseUpdate ... forwardCorrectionParallel, computeDirection
-//                                             (include/idocp/ocp/split_backward_correction.hxx:30-155)
+// Replaces
+//   SplitBackwardCorrection::backwardCorrectionSerial ... forwardCorrectionParallel, computeDirection
+//                                             (include/idocp/ocp/split_backward_correction.hxx:60-155)
 //   BackwardCorrectionSolver                  (src/ocp/backward_correction_solver.cpp:54-490)
 // The stage linearisation itself is K5a + K5b<BWD> (ocp_rnea_kernel.hip, ocp_condense_kernel.hip).
 //
-// K9b  parnmpc_kkt_inverse_kernel   one 256-thread workgroup per stage: Qss^-1 (48 x 48) and (F Qss^-1 F^T)^-1 (36 x 36) by
-//                                   Gauss-Jordan on 3 x 3 register tiles, the two column blocks of the KKT inverse the sweeps
-//                                   need, the coarse direction and the coarse iterate s_new
 // S5   parnmpc_backward_serial      one wavefront per instance walks the stages backwards (lmd, gmm corrections)
 // K10a parnmpc_backward_parallel    one wavefront per stage (u, q, v corrections)
 // S6   parnmpc_forward_serial       one wavefront per instance walks forwards (q, v corrections)
 // K10b parnmpc_forward_parallel     one wavefront per stage (lmd, gmm, u corrections), aux_mat, Newton direction s_new - s
 #include <hip/hip_runtime.h>
 
-#include <cstdlib>
 #include <type_traits>
 
 #include "dev_dense.hpp"
@@ -25,221 +20,6 @@
 #include "ocp_launch.hpp"
 
 namespace idocp_dev {
-
-template <typename D>
-struct KktInvSmem {
-  static constexpr int NX = D::NX, NU = D::NU, NQ_ = NU + NX;       // NQ_ = dim of (u, q, v)
-  // Two matrix regions reused by lifetime (36 kB in all, four workgroups per CU):
-  //   A : Q^-1 (NQ x NQ) -> FQ = F Q^-1 (NX x NQ) -> BR[:, NU:] (NQ x NX)
-  //   B : F (NX x NQ)    -> S^-1 (NX x NX)        -> TR = S^-1 FQ (NX x NQ)
-  // then the pivot rows / columns of the Gauss-Jordan steps and the vectors.
-  static constexpr int A = 0, B = A + NQ_ * NQ_, PV = B + NX * NQ_,
-                       R1 = PV + 2 * (2 * NQ_ + 2), R2 = R1 + NX, T1 = R2 + NQ_, W = T1 + NQ_, DIR = W + NQ_, TOTAL = DIR + NX + NQ_ + 4;
-  static_assert(NX % 3 == 0 && NQ_ % 3 == 0 && NU % 3 == 0, "3 x 3 tiles");
-  static_assert((NQ_ / 3) * (NQ_ / 3) <= 256, "one tile per thread");
-  static_assert((NQ_ / 3) * (NX / 3) + NQ_ <= 256 && (NQ_ / 3) * (NX / 3) + NX <= 256, "side jobs next to the NX x NQ tiles");
-};
-
-template <typename D>
-__global__ __launch_bounds__(256) void parnmpc_kkt_inverse_kernel(OcpBuffers B) {
-  using L = OcpLayout<D>;
-  using S = KktInvSmem<D>;
-  constexpr int NV = D::NV, NQc = D::NQ, NX = D::NX, NU = D::NU, NQ = S::NQ_, NK = L::NK;
-  constexpr int TQ = NQ / 3, TX = NX / 3, TU = NU / 3;        // tiles per side of Q (16), of S (12), of the u block (4)
-  extern __shared__ __attribute__((aligned(16))) double sm[];
-  __shared__ int s_ok;
-  const OcpProblem* __restrict__ P = B.prob;
-  const int M = B.M;
-  const int tid = threadIdx.x, nt = 256;
-  const long unit = blockIdx.x;
-  const long b = unit / (M - 1);
-  const int pos = (int)(unit - b * (M - 1));
-  const OcpNode* __restrict__ nd = B.nodes + pos;
-  if (parnmpcShape<L>(*nd).general) return;        // aux stages with switching rows and impulse stages: parnmpc_event_kernels.hip
-  const bool last = P->has_terminal && (pos == M - 2);
-  const double dt = nd->dt;
-  const long rec = b * B.NS + nd->slot;
-  const double* __restrict__ kk = B.kkt + rec * L::KKT;
-  const double* __restrict__ aux = B.aux + (b * B.NS + nd->next) * L::AUX;
-  double* __restrict__ ki = B.kinv + rec * L::KINV;
-  if (tid == 0) s_ok = 1;
-  // ---- Qss in the order (u, q, v) (SplitBackwardCorrection::coarseUpdate: Qxx += aux_mat_next, Qvq = Qqv^T, Qux = Qxu^T):
-  //      straight into the register tiles ----
-  double qinv[3][3];
-  const int qi = tid % TQ, qj = tid / TQ;
-  const bool q_on = tid < TQ * TQ;
-#pragma unroll
-  for (int tr = 0; tr < 3; ++tr)
-#pragma unroll
-    for (int tc = 0; tc < 3; ++tc) {
-      const int r = 3 * qi + tr, c = 3 * qj + tc;
-      double v = 0.0;
-      if (q_on) {
-        if (r < NU && c < NU) v = kk[L::K_QUU + r + NU * c];
-        else if (r < NU) v = kk[L::K_QXU + (c - NU) + NX * r];
-        else if (c < NU) v = kk[L::K_QXU + (r - NU) + NX * c];
-        else {
-          int rr = r - NU, cc = c - NU;
-          const double ax = last ? 0.0 : aux[rr + NX * cc];
-          if (rr > cc) { const int t = rr; rr = cc; cc = t; }      // K5 writes the triangle on and above the diagonal (Qxx symmetric, Qvq = Qqv^T)
-          v = kk[L::K_QXX + L::xsym(rr, cc)] + ax;
-        }
-      }
-      qinv[tr][tc] = v;
-    }
-  // ---- F = [0 Fqq Fqv; Fvu Fvq Fvv] (NX x NQ): backward Euler has Fqq = -I, Fqv = dt I outside the base blocks ----
-  for (int e = tid; e < NX * NQ; e += nt) {
-    const int c = e / NX, r = e - c * NX;
-    double v = 0.0;
-    if (r < NV) {
-      if (c >= NU && c < NU + NV) { const int cq = c - NU; v = (r < 6 && cq < 6) ? kk[L::K_FQQ + r + 6 * cq] : ((r >= 6 && r == cq) ? -1.0 : 0.0); }
-      else if (c >= NU + NV) { const int cv = c - NU - NV; v = (r < 6 && cv < 6) ? kk[L::K_FQV + r + 6 * cv] : ((r >= 6 && r == cv) ? dt : 0.0); }
-    } else {
-      const int rv = r - NV;
-      if (c < NU) v = kk[L::K_FVU + rv + NV * c];
-      else if (c < NU + NV) v = kk[L::K_FVQ + rv + NV * (c - NU)];
-      else v = kk[L::K_FVV + rv + NV * (c - NU - NV)];
-    }
-    sm[S::B + e] = v;
-  }
-  // residual (split_kkt_residual.hxx): r1 = [Fq; Fv], r2 = [lu; lq; lv]
-  if (tid < NX) sm[S::R1 + tid] = kk[L::K_FX + tid];
-  if (tid >= 64 && tid < 64 + NU) sm[S::R2 + tid - 64] = kk[L::K_LU + tid - 64];
-  if (tid >= 128 && tid < 128 + NX) sm[S::R2 + NU + tid - 128] = kk[L::K_LX + tid - 128];
-  blockLdsSync();                                   // s_ok
-  // ---- Q^-1 (llt_Q_.solve(I), split_kkt_matrix_inverter.hxx:55-58); the tiles stay in registers for BR ----
-  gaussJordanTiles<NQ>(qinv, q_on, qi, qj, &sm[S::PV], &s_ok);
-  if (q_on) {
-#pragma unroll
-    for (int tr = 0; tr < 3; ++tr)
-#pragma unroll
-      for (int tc = 0; tc < 3; ++tc) sm[S::A + 3 * qi + tr + NQ * (3 * qj + tc)] = qinv[tr][tc];
-  }
-  blockLdsSync();
-  // ---- FQ = F Q^-1 (multiplyF, :60): TX x TQ tiles ; w = Q^-1 r2 ----
-  const int fi = tid % TX, fj = tid / TX;            // tile of an NX x NQ matrix
-  const bool f_on = tid < TX * TQ;
-  double acc[3][3] = {{0.0, 0.0, 0.0}, {0.0, 0.0, 0.0}, {0.0, 0.0, 0.0}};
-  if (f_on) {
-    tileMM<NQ>(acc, [&](int r, int m) { return sm[S::B + 3 * fi + r + NX * m]; },
-               [&](int m, int c) { return sm[S::A + m + NQ * (3 * fj + c)]; });
-  } else if (tid < TX * TQ + NQ) {
-    const int r = tid - TX * TQ;
-    double w = 0.0;
-    for (int m = 0; m < NQ; ++m) w += sm[S::A + r + NQ * m] * sm[S::R2 + m];
-    sm[S::W + r] = w;
-  }
-  blockLdsSync();                                   // Q^-1 is dead in LDS: FQ takes its place
-  if (f_on) {
-#pragma unroll
-    for (int tr = 0; tr < 3; ++tr)
-#pragma unroll
-      for (int tc = 0; tc < 3; ++tc) sm[S::A + 3 * fi + tr + NX * (3 * fj + tc)] = acc[tr][tc];
-  }
-  blockLdsSync();
-  // ---- S = F FQ^T (:61) into register tiles, S^-1 (:62-66) ----
-  const bool s_on = tid < TX * TX;                   // (fi, fj) is then a tile of an NX x NX matrix as well
-  double sinv[3][3] = {{0.0, 0.0, 0.0}, {0.0, 0.0, 0.0}, {0.0, 0.0, 0.0}};
-  if (s_on)
-    tileMM<NQ>(sinv, [&](int r, int m) { return sm[S::B + 3 * fi + r + NX * m]; },
-               [&](int m, int c) { return sm[S::A + 3 * fj + c + NX * m]; });
-  gaussJordanTiles<NX>(sinv, s_on, fi, fj, &sm[S::PV], &s_ok);      // its first barrier also ends the reads of F
-  if (s_on) {
-#pragma unroll
-    for (int tr = 0; tr < 3; ++tr)
-#pragma unroll
-      for (int tc = 0; tc < 3; ++tc) sm[S::B + 3 * fi + tr + NX * (3 * fj + tc)] = sinv[tr][tc];
-  }
-  blockLdsSync();
-  // ---- TR = S^-1 FQ  (= - topLeft * Jac_Qinv, :67-69) ; t1 = r1 - FQ r2 ; what else reads S^-1: TL = -S^-1 (the top
-  //      of C0) and the first half of the top of the coarse direction, -S^-1 r1 ----
-#pragma unroll
-  for (int tr = 0; tr < 3; ++tr)
-#pragma unroll
-    for (int tc = 0; tc < 3; ++tc) acc[tr][tc] = 0.0;
-  if (f_on) {
-    tileMM<NX>(acc, [&](int r, int m) { return sm[S::B + 3 * fi + r + NX * m]; },
-               [&](int m, int c) { return sm[S::A + m + NX * (3 * fj + c)]; });
-  } else if (tid < TX * TQ + NX) {
-    const int r = tid - TX * TQ;
-    double t = sm[S::R1 + r];
-    for (int m = 0; m < NQ; ++m) t -= sm[S::A + r + NX * m] * sm[S::R2 + m];
-    sm[S::T1 + r] = t;
-    double d = 0.0;
-    for (int m = 0; m < NX; ++m) d -= sm[S::B + r + NX * m] * sm[S::R1 + m];
-    sm[S::DIR + r] = d;
-  }
-  for (int e = tid; e < NX * NX; e += nt) {
-    const int c = e / NX, r = e - c * NX;
-    ki[L::I_C0 + r + NK * c] = -sm[S::B + e];
-  }
-  blockLdsSync();                                   // S^-1 is dead: TR takes its place
-  if (f_on) {
-#pragma unroll
-    for (int tr = 0; tr < 3; ++tr)
-#pragma unroll
-      for (int tc = 0; tc < 3; ++tc) sm[S::B + 3 * fi + tr + NX * (3 * fj + tc)] = acc[tr][tc];
-  }
-  blockLdsSync();
-  // ---- BR[:, NU:] = Q^-1[:, NU:] - TR^T FQ[:, NU:] (:70-78) by the threads that hold those tiles of Q^-1 ;
-  //      coarse direction = KKT_inv * [r1; r2]: top = -S^-1 r1 + TR r2 ; bottom = Q^-1 r2 + TR^T (r1 - FQ r2) ----
-  const bool b_on = q_on && qj >= TU;
-  if (b_on) {
-#pragma unroll
-    for (int tr = 0; tr < 3; ++tr)
-#pragma unroll
-      for (int tc = 0; tc < 3; ++tc) acc[tr][tc] = 0.0;
-    tileMM<NX>(acc, [&](int r, int m) { return sm[S::B + m + NX * (3 * qi + r)]; },
-               [&](int m, int c) { return sm[S::A + m + NX * (3 * qj + c)]; });
-  } else if (tid < NX) {
-    double d = sm[S::DIR + tid];
-    for (int m = 0; m < NQ; ++m) d += sm[S::B + tid + NX * m] * sm[S::R2 + m];
-    sm[S::DIR + tid] = d;
-  }
-  if (tid >= 256 - NQ) {                             // after its tile: the bottom of the direction
-    const int r = tid - (256 - NQ);
-    double d = sm[S::W + r];
-    for (int m = 0; m < NX; ++m) d += sm[S::B + m + NX * r] * sm[S::T1 + m];
-    sm[S::DIR + NX + r] = d;
-  }
-  blockLdsSync();                                   // FQ is dead: BR[:, NU:] takes its place (NQ x NX)
-  if (b_on) {
-#pragma unroll
-    for (int tr = 0; tr < 3; ++tr)
-#pragma unroll
-      for (int tc = 0; tc < 3; ++tc) sm[S::A + 3 * qi + tr + NQ * (3 * (qj - TU) + tc)] = qinv[tr][tc] - acc[tr][tc];
-  }
-  blockLdsSync();
-  // ---- the column blocks of the inverse: C0 = [TL; TR^T] with TL = -S^-1 (above) ; C1 = [TR[:, NU:]; BR[:, NU:]] ----
-  for (int e = tid; e < NK * NX; e += nt) {
-    const int c = e / NK, r = e - c * NK;
-    if (r < NX) {
-      ki[L::I_C1 + e] = sm[S::B + r + NX * (NU + c)];
-    } else {
-      const int rq = r - NX;
-      ki[L::I_C0 + e] = sm[S::B + c + NX * rq];
-      ki[L::I_C1 + e] = sm[S::A + rq + NQ * c];
-    }
-  }
-  // ---- s_new = s - direction (split_backward_correction.hxx:49-58) ----
-  const double* __restrict__ s = B.sol + rec * L::SOL;
-  double* __restrict__ sn = B.snew + rec * L::SNEW;
-  const double* dir = &sm[S::DIR];          // dlmd dgmm | du dq dv
-  if (tid < NV) {
-    sn[L::N_LMD + tid] = s[L::S_LMD + tid] - dir[tid];
-    sn[L::N_GMM + tid] = s[L::S_GMM + tid] - dir[NV + tid];
-    sn[L::N_V + tid] = s[L::S_V + tid] - dir[NX + NU + NV + tid];
-    if (tid >= 6) sn[L::N_Q + tid + 1] = s[L::S_Q + tid + 1] - dir[NX + NU + tid];
-  }
-  if (tid >= 64 && tid < 64 + NU) sn[L::N_U + tid - 64] = s[L::S_U + tid - 64] - dir[NX + tid - 64];
-  if (tid == 128) {
-    double qn[7];
-    lieIntegrateBase(s + L::S_Q, dir + NX + NU, -1.0, qn);
-    for (int k = 0; k < 7; ++k) sn[L::N_Q + k] = qn[k];
-  }
-  (void)NQc;
-  if (tid == 0 && !s_ok && B.status[b] == 0) B.status[b] = 1000 + pos;
-}
 
 // y[0:rows] = A[r0 : r0 + rows, 0 : NX] x  for a column block A (ld NK) in global memory; one lane per row
 template <int NX>
@@ -726,43 +506,25 @@ void OcpLaunch<D>::parnmpcHalo(const OcpBuffers& B, long batch, int kind, bool d
 }
 
 template <typename D>
-void OcpLaunch<D>::parnmpcInverse(const OcpBuffers& B, long batch, int M, hipStream_t st) {
-  // K9w (one wavefront per stage on the matrix cores, parnmpc_kkt_wave_kernel.hip) unless IDOCP_K9_WAVE=0 asks for the round-1 kernel below
-  static const bool wave = [] { const char* e = getenv("IDOCP_K9_WAVE"); return !(e && e[0] == '0'); }();
-  if (wave) { parnmpcInverseWave(B, batch, M, st); return; }
-  const size_t smem = KktInvSmem<D>::TOTAL * sizeof(double);
-  static bool configured = false;
-  if (!configured) {
-    (void)hipFuncSetAttribute((const void*)parnmpc_kkt_inverse_kernel<D>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-    configured = true;
-  }
-  hipLaunchKernelGGL((parnmpc_kkt_inverse_kernel<D>), dim3((unsigned)(batch * (M - 1))), dim3(256), smem, st, B);
-}
-template <typename D>
 void OcpLaunch<D>::parnmpcPhase(int phase, const OcpBuffers& B, long batch, int M, bool has_terminal, const double* q0, const double* v0,
                                 hipStream_t st) {
   const int nbp = has_terminal ? M - 2 : M - 1;      // stages of the backward parallel correction
   switch (phase) {
-    case 0: {
-      // S5 with the rows requested two stages ahead (round 4) unless the chain is longer than its LDS tables or IDOCP_S5_DEPTH=1 asks for the old one
-      static const bool deep = [] { const char* e = getenv("IDOCP_S5_DEPTH"); return !(e && e[0] == '1'); }();
-      if (deep && M <= 1024) hipLaunchKernelGGL((parnmpc_backward_serial2_kernel<D>), dim3((unsigned)batch), dim3(64), 0, st, B);
+    case 0:
+      // S5 with the rows requested two stages ahead (round 4) unless the chain is longer than its LDS tables
+      if (M <= 1024) hipLaunchKernelGGL((parnmpc_backward_serial2_kernel<D>), dim3((unsigned)batch), dim3(64), 0, st, B);
       else hipLaunchKernelGGL((parnmpc_backward_serial_kernel<D>), dim3((unsigned)batch), dim3(64), 0, st, B);
       break;
-    }
     case 1: if (nbp > 0) hipLaunchKernelGGL((parnmpc_backward_parallel_kernel<D>), dim3((unsigned)(batch * nbp)), dim3(64), 0, st, B); break;
-    case 2: {
-      static const bool deep = [] { const char* e = getenv("IDOCP_S6_DEPTH"); return !(e && e[0] == '1'); }();
-      if (deep && M <= 1024) hipLaunchKernelGGL((parnmpc_forward_serial2_kernel<D>), dim3((unsigned)batch), dim3(64), 0, st, B, q0, v0);
+    case 2:
+      if (M <= 1024) hipLaunchKernelGGL((parnmpc_forward_serial2_kernel<D>), dim3((unsigned)batch), dim3(64), 0, st, B, q0, v0);
       else hipLaunchKernelGGL((parnmpc_forward_serial_kernel<D>), dim3((unsigned)batch), dim3(64), 0, st, B, q0, v0);
       break;
-    }
     case 3: hipLaunchKernelGGL((parnmpc_forward_parallel_kernel<D>), dim3((unsigned)(batch * (M - 1))), dim3(64), 0, st, B); break;
     default: hipLaunchKernelGGL((parnmpc_init_aux_kernel<D>), dim3((unsigned)batch), dim3(64), 0, st, B); break;
   }
 }
 
-template void OcpLaunch<LeggedDims<4, 3>>::parnmpcInverse(const OcpBuffers&, long, int, hipStream_t);
 template void OcpLaunch<LeggedDims<4, 3>>::parnmpcHalo(const OcpBuffers&, long, int, bool, double*, double*, double*, hipStream_t);
 template void OcpLaunch<LeggedDims<4, 3>>::parnmpcPhase(int, const OcpBuffers&, long, int, bool, const double*, const double*, hipStream_t);
 

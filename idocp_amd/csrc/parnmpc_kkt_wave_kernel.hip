@@ -1,9 +1,9 @@
 // K9w: the KKT inverse of a regular ParNMPC stage on ONE wavefront, register-resident, on the matrix cores (round 4).
 //
-// Replaces (like K9b, parnmpc_kernels.hip, which stays as the fallback IDOCP_K9_WAVE=0)
+// Replaces
 //   SplitKKTMatrixInverter::invert            (include/idocp/ocp/split_kkt_matrix_inverter.hxx:44-108)
 //   SplitBackwardCorrection::coarseUpdate     (include/idocp/ocp/split_backward_correction.hxx:30-58)
-// for the stages without switching rows / impulses (those: K9g, parnmpc_event_kernels.hip).
+// for the stages without switching rows / impulses (those: the general instantiation further down).
 //
 //   KKT = [0 F; F^T Q],  Q (48 x 48, order u q v) = Qss + aux_mat_next,  F (36 x 48) = [0 Fqq Fqv; Fvu Fvq Fvv]
 //   KKT^-1 = [-S^-1, S^-1 F Q^-1; . , Q^-1 - Q^-1 F^T S^-1 F Q^-1],  S = F Q^-1 F^T
@@ -23,8 +23,8 @@
 // The coarse direction KKT^-1 [r1; r2] is four matrix-vector products that contract over the ROWS of accumulator-layout tiles.
 // One wavefront per stage, no workgroup barrier, TWO wavefronts per SIMD (<= 256 registers, 19.5 kB LDS: what does not fit waits in LDS --
 // FQ during the factorisation of S -- or in the stage's dead lin record -- Q^-1 until BR is formed); every global access is a 16-byte piece
-// of a 1 kB run (loads requested at once at the top, output staged in LDS by blocks of 16 columns).  Against K9b's 256 threads with 84
-// barriers and ~10^4 vector instructions per thread: 4.45 -> 2.2 ms (with the list of what the compiler had to be talked out of).
+// of a 1 kB run (loads requested at once at the top, output staged in LDS by blocks of 16 columns).  Against the 256 threads with 84
+// barriers of the round-1 kernel it replaced (K9b) and ~10^4 vector instructions per thread: 4.45 -> 2.2 ms (with the list of what the compiler had to be talked out of).
 #include <hip/hip_runtime.h>
 
 #include <type_traits>
@@ -1155,7 +1155,7 @@ __global__ __launch_bounds__(64, 2) void parnmpc_kkt_inverse_wave_general_kernel
 }
 
 template <typename D>
-void OcpLaunch<D>::parnmpcInverseWave(const OcpBuffers& B, long batch, int M, hipStream_t st) {
+void OcpLaunch<D>::parnmpcInverse(const OcpBuffers& B, long batch, int M, hipStream_t st) {
   const size_t smem = KktWaveSmem<D>::TOTAL * sizeof(double);
   static bool configured = false;
   if (!configured) {
@@ -1165,10 +1165,10 @@ void OcpLaunch<D>::parnmpcInverseWave(const OcpBuffers& B, long batch, int M, hi
   hipLaunchKernelGGL((parnmpc_kkt_inverse_wave_kernel<D>), dim3((unsigned)(batch * (M - 1))), dim3(64), smem, st, B);
 }
 
-template void OcpLaunch<LeggedDims<4, 3>>::parnmpcInverseWave(const OcpBuffers&, long, int, hipStream_t);
+template void OcpLaunch<LeggedDims<4, 3>>::parnmpcInverse(const OcpBuffers&, long, int, hipStream_t);
 
 template <typename D>
-void OcpLaunch<D>::parnmpcEventInverseWave(const OcpBuffers& B, long batch, int n_general, hipStream_t st) {
+void OcpLaunch<D>::parnmpcEventInverse(const OcpBuffers& B, long batch, int n_general, hipStream_t st) {
   if (n_general <= 0) return;
   const size_t smem = KktWaveSmemG<D>::TOTAL * sizeof(double);
   static bool configured = false;
@@ -1178,8 +1178,6 @@ void OcpLaunch<D>::parnmpcEventInverseWave(const OcpBuffers& B, long batch, int 
   }
   hipLaunchKernelGGL((parnmpc_kkt_inverse_wave_general_kernel<D>), dim3((unsigned)batch, (unsigned)n_general), dim3(64), smem, st, B);
 }
-template void OcpLaunch<LeggedDims<4, 3>>::parnmpcEventInverseWave(const OcpBuffers&, long, int, hipStream_t);
-
-
+template void OcpLaunch<LeggedDims<4, 3>>::parnmpcEventInverse(const OcpBuffers&, long, int, hipStream_t);
 
 }  // namespace idocp_dev

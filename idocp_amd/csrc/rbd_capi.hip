@@ -587,8 +587,7 @@ int idocp_rbd_create(const idocp_model_t* model, int device, idocp_rbd_t** out) 
   if (device < 0 || device >= ndev) { set_last_error("invalid device ordinal"); return IDOCP_E_ARG; }
   idocp_rbd* h = new idocp_rbd();
   h->model = *model; h->device = device; h->quadruped = quad;
-  h->zaxes = true;      // (the instantiation of the chain sweep the solvers and idocp_rnea_derivatives choose for +z axes)
-  for (int i = 0; i < model->njoints; ++i) if (!(model->axis[i][0] == 0.0 && model->axis[i][1] == 0.0 && model->axis[i][2] == 1.0)) h->zaxes = false;
+  h->zaxes = idocp_host::allAxesZ(*model);      // (the instantiation of the chain sweep the solvers and idocp_rnea_derivatives choose for +z axes)
   auto fail = [&](const char* what) { set_last_error(what); (void)hipGetLastError(); idocp_rbd_destroy(h); return IDOCP_E_DEVICE; };
   if (hipSetDevice(device) != hipSuccess || hipStreamCreate(&h->stream) != hipSuccess) return fail("hipStreamCreate failed");
   if (hipMalloc(&h->d_model, MODEL_BYTES + sizeof(RbdFrames)) != hipSuccess) return fail("hipMalloc of the model failed");

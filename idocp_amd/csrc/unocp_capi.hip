@@ -309,9 +309,7 @@ static int createImpl(const idocp_model_t* model, const idocp_cost_t* cost, cons
     if (hipMemcpyAsync(B.task_ref, refs.data(), refs.size() * sizeof(double), hipMemcpyHostToDevice, h->stream) != hipSuccess ||
         hipStreamSynchronize(h->stream) != hipSuccess) { set_last_error("hipMemcpy failed"); return fail(IDOCP_E_DEVICE); }
   }
-  B.zaxes = 1;
-  for (int i = 0; i < model->njoints; ++i) if (!(model->axis[i][0] == 0.0 && model->axis[i][1] == 0.0 && model->axis[i][2] == 1.0)) B.zaxes = 0;
-  if (std::getenv("IDOCP_GENERAL_AXES")) B.zaxes = 0;      // tests: the general instantiation on a chain that qualifies for the special one
+  B.zaxes = idocp_host::allAxesZ(*model) && !idocp_host::envSettings().general_axes;      // (tests: the general instantiation on a chain that qualifies for the special one)
   DevModel dm; toDevModel(*model, dm);
   UnProblem up;
   fillUnProblem(*model, *cost, *constraints, T, N, batch, bwd, dt, stage_offset, has_terminal, has_prev, up);
@@ -981,8 +979,7 @@ int idocp_rnea_derivatives(const idocp_model_t* model, int n, const double* q, c
   HIP_TRY(hipMemcpy(d_q, q, sizeof(double) * n * nv, hipMemcpyHostToDevice));
   HIP_TRY(hipMemcpy(d_v, v, sizeof(double) * n * nv, hipMemcpyHostToDevice));
   HIP_TRY(hipMemcpy(d_a, a, sizeof(double) * n * nv, hipMemcpyHostToDevice));
-  bool zaxes = !std::getenv("IDOCP_GENERAL_AXES");      // (the same choice of the sweep's instantiation as the solvers make)
-  for (int i = 0; i < model->njoints; ++i) if (!(model->axis[i][0] == 0.0 && model->axis[i][1] == 0.0 && model->axis[i][2] == 1.0)) zaxes = false;
+  const bool zaxes = idocp_host::allAxesZ(*model) && !idocp_host::envSettings().general_axes;      // (the same choice of the sweep's instantiation as the solvers make)
   unImplFor(nv)->rneaDerivatives(d_m, n, d_q, d_v, d_a, d_tau, d_dq, d_dv, d_da, zaxes, nullptr);
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipDeviceSynchronize());

@@ -3,8 +3,8 @@
 // Same constructor signature and methods as the reference class
 // (include/idocp/ocp/parnmpc_solver.hpp; src/ocp/parnmpc_solver.cpp).  Every method forwards to
 // the C ABI (include/idocp_hip.h: idocp_parnmpc_* and the shared idocp_ocp_* entry points); the
-// arithmetic runs in the HIP kernels K5a / K5b<BWD> / K9b / S5 / K10a / S6 / K10b / K6 / K7 and, for
-// contact sequences with discrete events (pushBackContactStatus; max_num_impulse > 0), K5s / K9i / K9g
+// arithmetic runs in the HIP kernels K5a / K5b<BWD> / K9w / S5 / K10a / S6 / K10b / K6 / K7 and, for
+// contact sequences with discrete events (pushBackContactStatus; max_num_impulse > 0), K5s / K9i / K9w's general instantiation
 // for the aux and impulse stages of the ParNMPCDiscretizer chain.
 //
 // A FIXED-BASE robot without contact frames (examples/iiwa14/parnmpc_benchmark.cpp of the reference) is bound to the kernels of

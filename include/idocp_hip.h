@@ -748,7 +748,7 @@ int idocp_device_copy(void* d_dst, const void* d_src, unsigned long nbytes);
  * launches), so that a profiler of the caller can bracket them apart.
  * Since round 5 the forward sweep of a BATCH of instances expands as it walks (riccati_recursion_solver.cpp:129-251 in one kernel): id 3
  * is then the whole of 3 + 4 + 5 and ids 4, 5 launch nothing; idocp_ocp_fused_forward(h) says which form the handle runs (small batches
- * keep the three kernels: latency mode; IDOCP_FUSED_FORWARD=0 / 1 forces one, IDOCP_FUSED_FORWARD_MIN_BATCH moves the threshold). */
+ * keep the three kernels: latency mode, below batch 192; idocp_ocp_set_fused_forward forces one form). */
 int idocp_ocp_launch_kernel(idocp_ocp_t* h, int kernel_id, const double* d_q,
                             const double* d_v);
 int idocp_ocp_fused_forward(idocp_ocp_t* h);
@@ -758,9 +758,17 @@ int idocp_ocp_set_fused_forward(idocp_ocp_t* h, int mode);
 /* The backward Riccati sweep S3 (riccati_recursion_solver.cpp:48-107) has two forms: one wavefront per instance with P in registers (batches:
  * the throughput form) and eight wavefronts per instance with P staged in LDS (a handful of instances: the latency form, 8 % faster at batch
  * 1).  idocp_ocp_riccati_sweep(h): 1 when the handle runs the latency form.  set: mode -1 by batch size (default: batch <= 16 ->
- * latency form; IDOCP_RICCATI_WIDE_MAX_BATCH moves the threshold), 0 throughput form, 1 latency form -- per handle, copied by clone. */
+ * latency form), 0 throughput form, 1 latency form -- per handle, copied by clone. */
 int idocp_ocp_riccati_sweep(idocp_ocp_t* h);
 int idocp_ocp_set_riccati_sweep(idocp_ocp_t* h, int mode);
+
+/* Fork / join inside an iteration of an OCPSolver handle: the switching-constraint kernel K5s (next to the nominal sweeps) and the base poses
+ * K7b (next to K7) run on a stream of the handle's own; every entry point joins before it reads or launches.  idocp_ocp_side_stream(h): 1
+ * when the handle has that stream.  set: mode -1 by batch size (default: from batch 128), 0 everything on the handle's stream, 1 the side
+ * stream -- per handle, copied by clone; the call waits for the handle's work, then creates or destroys the stream.  The answers are bitwise
+ * the same in both forms. */
+int idocp_ocp_side_stream(idocp_ocp_t* h);
+int idocp_ocp_set_side_stream(idocp_ocp_t* h, int mode);
 
 /* ---- Batched rigid-body terms on plain arrays: what Robot::RNEA, RNEADerivatives, setContactForces,
  * computeBaumgarteResidual / Derivatives, RNEAImpulse(+Derivatives), computeImpulseVelocityResidual / Derivatives and computeMJtJinv

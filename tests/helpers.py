@@ -15,10 +15,12 @@ from idocp_amd.workloads import P, arr, dp, ROOT, GOLDEN
 _oracles = {}
 
 
-def force_forms(monkeypatch, fused=None, sweep=None):
-    """Every OCPSolver handle created during this test runs the forward sweep (fused: 1 = ocp_forward_expand_kernel, 0 = S4 + K6) and / or the
-    backward sweep (sweep: 0 = one wavefront per instance, register-resident; 1 = eight per instance) in the given form instead of the one its
-    batch size would pick -- idocp_ocp_set_fused_forward / idocp_ocp_set_riccati_sweep on the new handle.  Scoped to the test by monkeypatch."""
+def force_forms(monkeypatch, fused=None, sweep=None, side=None):
+    """Every OCPSolver handle created during this test runs the forward sweep (fused: 1 = ocp_forward_expand_kernel, 0 = S4 + K6), the
+    backward sweep (sweep: 0 = one wavefront per instance, register-resident; 1 = eight per instance) and / or the fork of K5s / K7b onto a
+    side stream (side: 1 = with the side stream, 0 = everything on the handle's stream) in the given form instead of the one its batch size
+    would pick -- idocp_ocp_set_fused_forward / idocp_ocp_set_riccati_sweep / idocp_ocp_set_side_stream on the new handle.  Scoped to the
+    test by monkeypatch."""
     def hook(solver):
         lib = solver.lib
         if fused is not None:
@@ -27,6 +29,9 @@ def force_forms(monkeypatch, fused=None, sweep=None):
         if sweep is not None:
             lib.idocp_ocp_set_riccati_sweep.argtypes = [C.c_void_p, C.c_int]
             capi.check(lib.idocp_ocp_set_riccati_sweep(solver.h, int(sweep)), "set_riccati_sweep")
+        if side is not None:
+            lib.idocp_ocp_set_side_stream.argtypes = [C.c_void_p, C.c_int]
+            capi.check(lib.idocp_ocp_set_side_stream(solver.h, int(side)), "set_side_stream")
     monkeypatch.setattr(HipOCP, "_post_create", list(HipOCP._post_create) + [hook])
 
 ORACLE_PATH_OVERRIDE = None       # bench.py's cpu_baseline leg points this at the natively built library

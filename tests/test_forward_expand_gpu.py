@@ -160,10 +160,11 @@ def test_chains_longer_than_the_walk_keeps_in_lds_fall_back_to_s4_k6():
 def test_side_stream_iteration_equals_the_single_stream_one_and_survives_graph_capture(monkeypatch):
     """Round 6: handles of >= 128 instances run the switching-constraint kernel, the impulse stages' nominal launch and the base-pose update
     on a side stream beside their independent neighbours (fork / join with events; ocp_capi.hip launchSwitchO / launchNominalO / joinSideO /
-    launchIntegrateO).  (i) A handle created with IDOCP_SIDE_STREAM_MIN_BATCH above its batch (everything on one stream) and one with the
-    side stream step the same trotting chain to BITWISE the same iterate -- the kernels and their inputs are the same, only the order in
-    which independent launches start differs.  (ii) The fork / join is captured into the hipGraph of idocp_ocp_update_solution_graph:
-    a clone stepping through the graph stays bitwise on the eager handle."""
+    launchIntegrateO).  (i) A clone stepped kernel by kernel with a synchronisation after every launch (nothing can overlap), a clone
+    switched to a single stream (idocp_ocp_set_side_stream(.., 0)) and the handle with the side stream step the same trotting chain to BITWISE
+    the same iterate -- the kernels and their inputs are the same, only the order in which independent launches start differs.  (ii) The
+    fork / join is captured into the hipGraph of idocp_ocp_update_solution_graph: a clone stepping through the graph stays bitwise on the
+    eager handle."""
     import copy
     torch = pytest.importorskip("torch")
     lib = capi.lib()
@@ -186,10 +187,12 @@ def test_side_stream_iteration_equals_the_single_stream_one_and_survives_graph_c
         g.init_constraints(0.0)
         return g
 
+    lib.idocp_ocp_side_stream.argtypes = [C.c_void_p]
+    lib.idocp_ocp_set_side_stream.argtypes = [C.c_void_p, C.c_int]
     side = handle()                                   # (the default: a side stream from batch 128 on)
-    # the switch is read once per process: a handle WITHOUT a side stream is one below the threshold -- here made by a batch-127 twin would change
-    # the problem, so the single-stream reference runs kernel by kernel through idocp_ocp_launch_kernel on a clone, ids in the plain order, with a
-    # stream synchronisation after every launch (nothing can overlap)
+    assert lib.idocp_ocp_side_stream(side.h) == 1
+    # one single-stream reference runs kernel by kernel through idocp_ocp_launch_kernel on a clone, ids in the plain order, with a stream
+    # synchronisation after every launch (nothing can overlap); the other is a clone told to keep everything on its own stream, stepped eagerly
     h2 = C.c_void_p()
     capi.check(lib.idocp_ocp_clone(side.h, C.byref(h2)), "clone")
     plain = copy.copy(side)
@@ -198,18 +201,25 @@ def test_side_stream_iteration_equals_the_single_stream_one_and_survives_graph_c
     capi.check(lib.idocp_ocp_clone(side.h, C.byref(h3)), "clone")
     graph = copy.copy(side)
     graph.h = h3
+    h4 = C.c_void_p()
+    capi.check(lib.idocp_ocp_clone(side.h, C.byref(h4)), "clone")
+    single = copy.copy(side)
+    single.h = h4
+    capi.check(lib.idocp_ocp_set_side_stream(single.h, 0), "set_side_stream")
+    assert lib.idocp_ocp_side_stream(single.h) == 0 and lib.idocp_ocp_side_stream(plain.h) == 1 and lib.idocp_ocp_side_stream(graph.h) == 1
     lib.idocp_ocp_fused_forward.argtypes = [C.c_void_p]
     kids = [0, 7, 8, 2, 3, 6] if lib.idocp_ocp_fused_forward(side.h) else [0, 7, 8, 2, 3, 4, 5, 6]
     for it in range(3):
         capi.check(lib.idocp_ocp_update_solution_device(side.h, *args), "eager, side stream")
         capi.check(lib.idocp_ocp_update_solution_graph(graph.h, *args), "graph")      # (first call eager, second captures, third replays)
+        capi.check(lib.idocp_ocp_update_solution_device(single.h, *args), "eager, single stream")
         if it == 0:
             capi.check(lib.idocp_ocp_update_solution_device(plain.h, *args), "first iteration of the serialised clone: discretises and uploads")
         else:
             for kid in kids:
                 capi.check(lib.idocp_ocp_launch_kernel(plain.h, kid, args[1], args[2]), "kernel %d" % kid)
                 capi.check(lib.idocp_ocp_synchronize(plain.h))
-    for s_ in (side, plain, graph):
+    for s_ in (side, plain, graph, single):
         capi.check(lib.idocp_ocp_synchronize(s_.h))
     M = len(side.chain(0.0))
     for f in ("q", "v", "a", "u", "f", "lmd", "gmm", "beta", "mu"):
@@ -218,13 +228,20 @@ def test_side_stream_iteration_equals_the_single_stream_one_and_survives_graph_c
             assert np.isfinite(ref).all()
             assert np.array_equal(plain.get_chain(f, M, inst), ref), ("serialised", f, inst)
             assert np.array_equal(graph.get_chain(f, M, inst), ref), ("graph", f, inst)
+            assert np.array_equal(single.get_chain(f, M, inst), ref), ("single stream", f, inst)
 
 
 def test_oracle_parity_with_the_side_stream_forced_on_small_batches(monkeypatch):
     """The parity tests of the other files run small batches, i.e. handles WITHOUT a side stream (it starts at 128 instances); here the chains with
-    switching constraints, impulse stages and lift stages, the MPC loop and the full-size configs run with IDOCP_SIDE_STREAM_MIN_BATCH=1: every
-    handle forks K5s / the impulse stages' nominal launch / the base poses onto its side stream and joins them, under the same oracle bars."""
-    monkeypatch.setenv("IDOCP_SIDE_STREAM_MIN_BATCH", "1")
+    switching constraints, impulse stages and lift stages, the MPC loop and the full-size configs run with the side stream forced on every
+    handle (idocp_ocp_set_side_stream through helpers.force_forms): every handle forks K5s / the impulse stages' nominal launch / the base
+    poses onto its side stream and joins them, under the same oracle bars."""
+    force_forms(monkeypatch, side=1)
+    lib = capi.lib()
+    lib.idocp_ocp_side_stream.argtypes = [C.c_void_p]
+    m = anymal_model()
+    small = HipOCP(m, *anymal_problem(m), 0.5, 10, batch=2)
+    assert lib.idocp_ocp_side_stream(small.h) == 1      # (the forcing reaches the handles made below; their batch sizes alone would say 0)
     import test_hybrid_gpu as H
     H.test_first_iteration_direction_parity_along_the_chain(False, 31, 1.55, 1e-10)
     H.test_flight_phase_sequence_parity()
@@ -233,3 +250,113 @@ def test_oracle_parity_with_the_side_stream_forced_on_small_batches(monkeypatch)
     H.test_full_size_c3_from_three_perturbed_states()
     import test_golden_kkt as K
     K.test_hip_direction_is_the_dense_newton_direction()
+
+
+def _small_trotting_handle(m, batch=2):
+    """batch 2 on the shortest chain of the suite that has switching constraints, impulse stages and lift stages"""
+    cost, cons = anymal_problem(m, trotting_ref=True)
+    g = HipOCP(m, cost, cons, 1.55, 31, batch=batch, max_num_impulse=3)
+    trotting_sequence(g, m, 2)
+    g.set_solution("q", ANYMAL_Q_STANDING)
+    g.set_solution("v", np.zeros(m.nv))
+    g.set_solution("f", [0, 0, 0.25 * (-m.total_mass * m.gravity[2])])
+    g.init_constraints(0.0)
+    return g
+
+
+def _side_lib():
+    lib = capi.lib()
+    lib.idocp_ocp_side_stream.argtypes = [C.c_void_p]
+    lib.idocp_ocp_set_side_stream.argtypes = [C.c_void_p, C.c_int]
+    return lib
+
+
+def _clone_of(g):
+    import copy
+    h = C.c_void_p()
+    capi.check(capi.lib().idocp_ocp_clone(g.h, C.byref(h)), "clone")
+    c = copy.copy(g)
+    c.h = h
+    return c
+
+
+CHAIN_FIELDS = ("q", "v", "a", "u", "f", "lmd", "gmm", "beta", "mu") + tuple(OCP_DIR_FIELDS) + ("dxi",)
+
+
+def test_side_stream_setter_contract_and_switching_between_iterations():
+    """idocp_ocp_set_side_stream has the contract of the other two form setters: modes -1 / 0 / 1 only, OCPSolver handles only, the getter
+    follows, a clone inherits the mode.  The setter takes effect between two iterations -- it drains both streams, creates or destroys the side
+    stream and invalidates a captured graph: a handle switched on -> off -> on stays BITWISE on a twin left on, both stepped through
+    idocp_ocp_update_solution_graph (the twin: eager, captured, replayed)."""
+    from helpers import HipParNMPC
+    torch = pytest.importorskip("torch")
+    lib = _side_lib()
+    m = anymal_model()
+    a = _small_trotting_handle(m)
+    assert lib.idocp_ocp_side_stream(a.h) == 0                                                 # batch 2: below the threshold
+    assert lib.idocp_ocp_set_side_stream(a.h, 2) != 0 and lib.idocp_ocp_set_side_stream(a.h, -2) != 0
+    assert lib.idocp_ocp_side_stream(a.h) == 0
+    assert lib.idocp_ocp_set_side_stream(a.h, 1) == 0 and lib.idocp_ocp_side_stream(a.h) == 1
+    assert lib.idocp_ocp_set_side_stream(a.h, -1) == 0 and lib.idocp_ocp_side_stream(a.h) == 0
+    assert lib.idocp_ocp_set_side_stream(a.h, 0) == 0 and lib.idocp_ocp_side_stream(a.h) == 0
+    assert lib.idocp_ocp_set_side_stream(a.h, 1) == 0 and lib.idocp_ocp_side_stream(a.h) == 1
+    cost, cons = anymal_problem(m)
+    p = HipParNMPC(m, cost, cons, 0.5, 10, batch=2)
+    assert lib.idocp_ocp_set_side_stream(p.h, 1) != 0 and lib.idocp_ocp_side_stream(p.h) == 0
+    b = _clone_of(a)
+    assert lib.idocp_ocp_side_stream(b.h) == 1                                                 # inherited: its batch size alone would say 0
+    q = np.tile(ANYMAL_Q_STANDING, (2, 1))
+    q[:, 7:] += 0.01 * np.random.default_rng(5).uniform(-1, 1, (2, 12))
+    dq = torch.tensor(q, dtype=torch.float64, device="cuda")
+    dv = torch.zeros((2, m.nv), dtype=torch.float64, device="cuda")
+    args = (C.c_double(0.0), C.c_void_p(dq.data_ptr()), C.c_void_p(dv.data_ptr()))
+    for mode_after in (0, 1, None):
+        capi.check(lib.idocp_ocp_update_solution_graph(a.h, *args), "switched handle")
+        capi.check(lib.idocp_ocp_update_solution_graph(b.h, *args), "twin")
+        if mode_after is not None:
+            capi.check(lib.idocp_ocp_set_side_stream(a.h, mode_after), "set_side_stream between two iterations")
+            assert lib.idocp_ocp_side_stream(a.h) == mode_after
+    for s_ in (a, b):
+        capi.check(lib.idocp_ocp_synchronize(s_.h))
+    M = len(a.chain(0.0))
+    for f in CHAIN_FIELDS:
+        for inst in (0, 1):
+            ref = b.get_chain(f, M, inst)
+            assert f.startswith("d") or np.isfinite(ref).all()
+            assert np.array_equal(a.get_chain(f, M, inst), ref), (f, inst)
+
+
+def test_entries_behind_an_open_fork_join_it():
+    """idocp_ocp_launch_kernel id 0 alone leaves K5s in flight on the side stream.  Whatever entry point comes next -- here the KKT residual,
+    whose own K5s writes the same records on the handle's stream, and a clone, which copies them -- joins the fork first: the answers are
+    bitwise those of a twin that synchronised in between.  (A test cannot prove the absence of a race; this one holds the join in place.)"""
+    torch = pytest.importorskip("torch")
+    lib = _side_lib()
+    m = anymal_model()
+    a = _small_trotting_handle(m)
+    capi.check(lib.idocp_ocp_set_side_stream(a.h, 1), "set_side_stream")
+    q = np.tile(ANYMAL_Q_STANDING, (2, 1))
+    q[:, 7:] += 0.01 * np.random.default_rng(9).uniform(-1, 1, (2, 12))
+    v = np.zeros((2, m.nv))
+    dq = torch.tensor(q, dtype=torch.float64, device="cuda")
+    dv = torch.zeros((2, m.nv), dtype=torch.float64, device="cuda")
+    capi.check(lib.idocp_ocp_update_solution_device(a.h, C.c_double(0.0), C.c_void_p(dq.data_ptr()), C.c_void_p(dv.data_ptr())), "one iteration")
+    capi.check(lib.idocp_ocp_synchronize(a.h))
+    b = _clone_of(a)
+    assert lib.idocp_ocp_side_stream(a.h) == 1 and lib.idocp_ocp_side_stream(b.h) == 1
+    out = {}
+    for name, g, sync in (("open", a, False), ("closed", b, True)):
+        capi.check(lib.idocp_ocp_launch_kernel(g.h, 0, C.c_void_p(dq.data_ptr()), C.c_void_p(dv.data_ptr())), "kernel 0")
+        if sync:
+            capi.check(lib.idocp_ocp_synchronize(g.h))
+        err = g.kkt_error(0.0, q, v)
+        capi.check(lib.idocp_ocp_launch_kernel(g.h, 0, C.c_void_p(dq.data_ptr()), C.c_void_p(dv.data_ptr())), "kernel 0")
+        if sync:
+            capi.check(lib.idocp_ocp_synchronize(g.h))
+        c = _clone_of(g)
+        M = len(c.chain(0.0))
+        out[name] = (err, {f: np.stack([c.get_chain(f, M, inst) for inst in (0, 1)]) for f in CHAIN_FIELDS})
+    assert np.isfinite(out["open"][0]).all() and (out["open"][0] > 0).all()
+    assert np.array_equal(out["open"][0], out["closed"][0])
+    for f in CHAIN_FIELDS:
+        assert np.array_equal(out["open"][1][f], out["closed"][1][f]), f
