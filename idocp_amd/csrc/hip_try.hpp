@@ -18,3 +18,13 @@
       return IDOCP_E_DEVICE;                                                                  \
     }                                                                                         \
   } while (0)
+
+// A host temporary (a stack object, a local vector) to the device, complete on return: the stream is synchronised even when the copy call itself
+// reports an error, so no way out of the caller leaves a copy in flight from a frame that is gone.
+inline int uploadTemporary(void* d_dst, const void* h_src, size_t bytes, hipStream_t stream) {
+  const hipError_t copied = hipMemcpyAsync(d_dst, h_src, bytes, hipMemcpyHostToDevice, stream);
+  const hipError_t waited = hipStreamSynchronize(stream);
+  HIP_TRY(copied);
+  HIP_TRY(waited);
+  return IDOCP_OK;
+}

@@ -19,6 +19,7 @@
 #include "hip_try.hpp"
 #include "host_util.hpp"
 #include "idocp_hip.h"
+#include "line_search_filter.hpp"
 #include "model_shapes.hpp"
 #include "ocp_forms.hpp"
 #include "ocp_launch.hpp"
@@ -76,7 +77,7 @@ struct idocp_ocp {
   const double *graph_q = nullptr, *graph_v = nullptr;
   bool launched_eagerly = false;
   // filter line search (LineSearchFilter, src/line_search/line_search_filter.cpp): one filter per instance
-  std::vector<std::vector<std::pair<double, double>>> filters;
+  std::vector<idocp_host::LineSearchFilter> filters;
   OcpNode* d_nodes_ls = nullptr;
   double* ext_try = nullptr;
   OcpForms forms;                     // which form of a kernel this handle runs (ocp_forms.hpp); idocp_ocp_clone copies the record
@@ -113,6 +114,12 @@ int joinSideO(idocp_ocp* h) {
 int enterO(idocp_ocp* h) {
   int rc = setDev(h); if (rc) return rc;
   return joinSideO(h);
+}
+// the measured state of a host-pointer entry point, into the handle's staging buffers (v == nullptr: the configuration alone)
+int uploadStateO(idocp_ocp* h, const double* q, const double* v) {
+  HIP_TRY(hipMemcpyAsync(h->d_q0, q, sizeof(double) * h->batch * DQ::NQ, hipMemcpyHostToDevice, h->stream));
+  if (v) HIP_TRY(hipMemcpyAsync(h->d_v0, v, sizeof(double) * h->batch * DQ::NV, hipMemcpyHostToDevice, h->stream));
+  return IDOCP_OK;
 }
 void dropSideO(idocp_ocp* h) {
   if (h->side) { (void)hipStreamDestroy(h->side); h->side = nullptr; }
@@ -841,7 +848,7 @@ static int parnmpcLineSearchSupported(const idocp_ocp_t* h) {
 }
 static int lineSearchEvalO(idocp_ocp_t* h, const std::vector<double>& alpha, const double* d_q, std::vector<double>& out) {
   const int M = h->M();
-  HIP_TRY(hipMemcpyAsync(h->B.ls_alpha, alpha.data(), sizeof(double) * h->batch, hipMemcpyHostToDevice, h->stream));
+  { const int rca = uploadTemporary(h->B.ls_alpha, alpha.data(), sizeof(double) * h->batch, h->stream); if (rca) return rca; }
   OcpLaunch<DQ>::trialIterate(h->B, h->batch, M, h->stream);
   OcpBuffers Bt = h->B;
   Bt.sol = h->B.sol_try;
@@ -874,45 +881,34 @@ static int lineSearchEvalO(idocp_ocp_t* h, const std::vector<double>& alpha, con
   HIP_TRY(hipStreamSynchronize(h->stream));
   return IDOCP_OK;
 }
-// LineSearch::computeStepSize (include/idocp/line_search/line_search.hpp:62-92) for every instance of the batch; the filter
-// (line_search_filter.cpp:33-63, defaults line_search_filter.hpp:16-17, line_search.hpp:25-26) runs on the host.  On return
-// B.step holds the accepted primal step of every instance.
+// LineSearch::computeStepSize (include/idocp/line_search/line_search.hpp:62-92) for every instance of the batch; the filter logic runs on the
+// host (line_search_filter.hpp).  On return B.step holds the accepted primal step of every instance.
 static int runLineSearchO(idocp_ocp_t* h, const double* d_q) {
-  const double cost_rate = 0.005, con_rate = 0.005, reduction = 0.75, min_step = 0.05;
-  const int B = h->batch;
-  auto accepted = [](const std::vector<std::pair<double, double>>& f, double c, double v) {
-    for (const auto& p : f) if (c >= p.first && v >= p.second) return false;
-    return true;
-  };
-  auto augment = [&](std::vector<std::pair<double, double>>& f, double c, double v) {
-    for (auto it = f.begin(); it != f.end();) { if (c <= it->first && v <= it->second) it = f.erase(it); else ++it; }
-    f.push_back({c - cost_rate * v, (1 - con_rate) * v});
-  };
-  std::vector<double> step((size_t)B * 2), alpha(B, 0.0), cv;
-  int rc;
-  bool any_empty = false;
-  for (int b = 0; b < B; ++b) any_empty = any_empty || h->filters[b].empty();
-  if (any_empty) {                                  // "if filter is empty, augment the current solution to the filter"
-    if ((rc = lineSearchEvalO(h, alpha, d_q, cv))) return rc;
-    for (int b = 0; b < B; ++b) if (h->filters[b].empty()) augment(h->filters[b], cv[2 * b], cv[2 * b + 1]);
-  }
+  std::vector<double> step((size_t)h->batch * 2);
   HIP_TRY(hipMemcpyAsync(step.data(), h->B.step, sizeof(double) * step.size(), hipMemcpyDeviceToHost, h->stream));
   HIP_TRY(hipStreamSynchronize(h->stream));
-  std::vector<char> done(B, 0);
-  int open = 0;
-  for (int b = 0; b < B; ++b) { alpha[b] = step[2 * b]; if (!(alpha[b] > min_step)) done[b] = 1; else ++open; }
-  while (open > 0) {
-    if ((rc = lineSearchEvalO(h, alpha, d_q, cv))) return rc;
-    for (int b = 0; b < B; ++b) {
-      if (done[b]) continue;
-      if (accepted(h->filters[b], cv[2 * b], cv[2 * b + 1])) { augment(h->filters[b], cv[2 * b], cv[2 * b + 1]); done[b] = 1; --open; continue; }
-      alpha[b] *= reduction;
-      if (!(alpha[b] > min_step)) { done[b] = 1; --open; }
-    }
-  }
-  for (int b = 0; b < B; ++b) step[2 * b] = alpha[b] > min_step ? alpha[b] : min_step;
-  HIP_TRY(hipMemcpyAsync(h->B.step, step.data(), sizeof(double) * step.size(), hipMemcpyHostToDevice, h->stream));
-  HIP_TRY(hipStreamSynchronize(h->stream));         // `step` is a stack temporary
+  const int rc = idocp_host::filterLineSearch(h->filters, step.data(), 2, [&](const std::vector<double>& alpha, std::vector<double>& cv) { return lineSearchEvalO(h, alpha, d_q, cv); });
+  return rc ? rc : uploadTemporary(h->B.step, step.data(), sizeof(double) * step.size(), h->stream);
+}
+// kernels 0 .. 5 with the uploaded state, all on the handle's stream (launchUpdateO alone forks K5s onto the side stream)
+static int launchDirectionO(idocp_ocp_t* h) {
+  const int M = h->M();
+  HIP_TRY(hipMemsetAsync(h->B.status, 0, sizeof(int) * h->batch, h->stream));
+  OcpLaunch<DQ>::rnea(h->B, h->batch, M, h->plan.n_impulse(), h->stream);
+  if (h->plan.has_switch) OcpLaunch<DQ>::switching(h->B, h->batch, M, h->stream);
+  launchCondenseO(h, M, h->d_q0);
+  OcpLaunch<DQ>::riccatiBackward(h->B, h->batch, M, h->plan.has_switch, h->stream, wideSweep(h));
+  launchForwardO(h, M, h->d_q0, h->d_v0);
+  HIP_TRY(hipGetLastError());
+  return IDOCP_OK;
+}
+// the status words of the iteration; `what` failed, and the message names the first instance it failed in
+static int statusOfO(idocp_ocp_t* h, const char* what) {
+  std::vector<int> st(h->batch);
+  HIP_TRY(hipMemcpyAsync(st.data(), h->B.status, sizeof(int) * h->batch, hipMemcpyDeviceToHost, h->stream));
+  HIP_TRY(hipStreamSynchronize(h->stream));
+  for (int b = 0; b < h->batch; ++b)
+    if (st[b] != 0) { set_last_error(std::string(what) + ", instance " + std::to_string(b)); return st[b]; }
   return IDOCP_OK;
 }
 
@@ -922,17 +918,9 @@ int idocp_ocp_compute_direction(idocp_ocp_t* h, double t, const double* q, const
   if (!h || !q || !v) return IDOCP_E_ARG;
   if (!h->seq.status_set) { set_last_error("idocp_ocp_update_solution: call setContactStatusUniformly first"); return IDOCP_E_ARG; }
   int rc = enterO(h); if (rc) return rc;
-  HIP_TRY(hipMemcpyAsync(h->d_q0, q, sizeof(double) * h->batch * DQ::NQ, hipMemcpyHostToDevice, h->stream));
-  HIP_TRY(hipMemcpyAsync(h->d_v0, v, sizeof(double) * h->batch * DQ::NV, hipMemcpyHostToDevice, h->stream));
+  if ((rc = uploadStateO(h, q, v))) return rc;
   if ((rc = discretize(h, t))) return rc;
-  const int M = h->M();
-  HIP_TRY(hipMemsetAsync(h->B.status, 0, sizeof(int) * h->batch, h->stream));
-  OcpLaunch<DQ>::rnea(h->B, h->batch, M, h->plan.n_impulse(), h->stream);
-  if (h->plan.has_switch) OcpLaunch<DQ>::switching(h->B, h->batch, M, h->stream);
-  launchCondenseO(h, M, h->d_q0);
-  OcpLaunch<DQ>::riccatiBackward(h->B, h->batch, M, h->plan.has_switch, h->stream, wideSweep(h));
-  launchForwardO(h, M, h->d_q0, h->d_v0);
-  HIP_TRY(hipGetLastError());
+  if ((rc = launchDirectionO(h))) return rc;
   HIP_TRY(hipStreamSynchronize(h->stream));
   return IDOCP_OK;
 }
@@ -955,31 +943,18 @@ int idocp_ocp_clear_line_search_filter(idocp_ocp_t* h) {
 int idocp_ocp_update_solution(idocp_ocp_t* h, double t, const double* q, const double* v, int line_search) {
   if (!h || !q || !v) return IDOCP_E_ARG;
   int rc = enterO(h); if (rc) return rc;
-  HIP_TRY(hipMemcpyAsync(h->d_q0, q, sizeof(double) * h->batch * DQ::NQ, hipMemcpyHostToDevice, h->stream));
-  HIP_TRY(hipMemcpyAsync(h->d_v0, v, sizeof(double) * h->batch * DQ::NV, hipMemcpyHostToDevice, h->stream));
+  if ((rc = uploadStateO(h, q, v))) return rc;      // (in front of the status_set check, which the other branch makes behind it too)
   if (line_search) {
     // OCPSolver::updateSolution(t, q, v, true) (ocp_solver.cpp:67-92): direction, filter line search on the primal step, integration
     if (!h->seq.status_set) { set_last_error("idocp_ocp_update_solution: call setContactStatusUniformly first"); return IDOCP_E_ARG; }
     if ((rc = discretize(h, t))) return rc;
-    const int M = h->M();
-    HIP_TRY(hipMemsetAsync(h->B.status, 0, sizeof(int) * h->batch, h->stream));
-    OcpLaunch<DQ>::rnea(h->B, h->batch, M, h->plan.n_impulse(), h->stream);
-    if (h->plan.has_switch) OcpLaunch<DQ>::switching(h->B, h->batch, M, h->stream);
-    launchCondenseO(h, M, h->d_q0);
-    OcpLaunch<DQ>::riccatiBackward(h->B, h->batch, M, h->plan.has_switch, h->stream, wideSweep(h));
-    launchForwardO(h, M, h->d_q0, h->d_v0);
-    HIP_TRY(hipGetLastError());
+    if ((rc = launchDirectionO(h))) return rc;
     if ((rc = runLineSearchO(h, h->d_q0))) return rc;
-    OcpLaunch<DQ>::expandDualIntegrate(h->B, h->batch, M, h->stream);
+    OcpLaunch<DQ>::expandDualIntegrate(h->B, h->batch, h->M(), h->stream);      // (K7 and K7b on the handle's stream: no fork on this path)
     HIP_TRY(hipGetLastError());
   } else
   if ((rc = idocp_ocp_update_solution_device(h, t, h->d_q0, h->d_v0))) return rc;
-  std::vector<int> st(h->batch);
-  HIP_TRY(hipMemcpyAsync(st.data(), h->B.status, sizeof(int) * h->batch, hipMemcpyDeviceToHost, h->stream));
-  HIP_TRY(hipStreamSynchronize(h->stream));
-  for (int b = 0; b < h->batch; ++b)
-    if (st[b] != 0) { set_last_error("factorisation failed (M, J M^-1 J^T, Quu or the switching-constraint Schur complement not positive definite), instance " + std::to_string(b)); return st[b]; }
-  return IDOCP_OK;
+  return statusOfO(h, "factorisation failed (M, J M^-1 J^T, Quu or the switching-constraint Schur complement not positive definite)");
 }
 
 int idocp_ocp_compute_kkt_residual(idocp_ocp_t* h, double t, const double* q, const double* v) {
@@ -987,7 +962,7 @@ int idocp_ocp_compute_kkt_residual(idocp_ocp_t* h, double t, const double* q, co
   int rc = enterO(h); if (rc) return rc;
   if ((rc = discretize(h, t))) return rc;
   const int M = h->M();
-  HIP_TRY(hipMemcpyAsync(h->d_q0, q, sizeof(double) * h->batch * DQ::NQ, hipMemcpyHostToDevice, h->stream));
+  if ((rc = uploadStateO(h, q, nullptr))) return rc;      // (this residual reads no measured velocity: d_v0 keeps what it held)
   OcpLaunch<DQ>::rnea(h->B, h->batch, M, h->plan.n_impulse(), h->stream);
   if (h->plan.has_switch) OcpLaunch<DQ>::switching(h->B, h->batch, M, h->stream);
   OcpLaunch<DQ>::residual(h->B, h->batch, M, h->d_q0, h->stream);
@@ -1436,8 +1411,7 @@ int idocp_parnmpc_compute_direction(idocp_ocp_t* h, double t, const double* q, c
   if (!h || !h->parnmpc || !q || !v) return IDOCP_E_ARG;
   if (!h->seq.status_set) { set_last_error("idocp_parnmpc_update_solution: call setContactStatusUniformly first"); return IDOCP_E_ARG; }
   int rc = enterO(h); if (rc) return rc;
-  HIP_TRY(hipMemcpyAsync(h->d_q0, q, sizeof(double) * h->batch * DQ::NQ, hipMemcpyHostToDevice, h->stream));
-  HIP_TRY(hipMemcpyAsync(h->d_v0, v, sizeof(double) * h->batch * DQ::NV, hipMemcpyHostToDevice, h->stream));
+  if ((rc = uploadStateO(h, q, v))) return rc;
   if ((rc = discretize(h, t))) return rc;
   HIP_TRY(hipMemsetAsync(h->B.status, 0, sizeof(int) * h->batch, h->stream));
   for (int phase = 0; phase <= 8; ++phase) if ((rc = idocp_parnmpc_launch_phase(h, phase, h->d_q0, h->d_v0))) return rc;
@@ -1458,31 +1432,29 @@ int idocp_parnmpc_update_solution(idocp_ocp_t* h, double t, const double* q, con
     if ((rc = runLineSearchO(h, h->d_q0))) return rc;
     if ((rc = idocp_parnmpc_launch_phase(h, 9, h->d_q0, h->d_v0))) return rc;
   } else {
-    HIP_TRY(hipMemcpyAsync(h->d_q0, q, sizeof(double) * h->batch * DQ::NQ, hipMemcpyHostToDevice, h->stream));
-    HIP_TRY(hipMemcpyAsync(h->d_v0, v, sizeof(double) * h->batch * DQ::NV, hipMemcpyHostToDevice, h->stream));
+    if ((rc = uploadStateO(h, q, v))) return rc;
     if ((rc = idocp_parnmpc_update_solution_device(h, t, h->d_q0, h->d_v0))) return rc;
   }
-  std::vector<int> st(h->batch);
-  HIP_TRY(hipMemcpyAsync(st.data(), h->B.status, sizeof(int) * h->batch, hipMemcpyDeviceToHost, h->stream));
-  HIP_TRY(hipStreamSynchronize(h->stream));
-  for (int b = 0; b < h->batch; ++b)
-    if (st[b] != 0) { set_last_error("factorisation failed (a stage matrix is not positive definite), instance " + std::to_string(b)); return st[b]; }
-  return IDOCP_OK;
+  return statusOfO(h, "factorisation failed (a stage matrix is not positive definite)");
 }
 
-int idocp_parnmpc_compute_kkt_residual(idocp_ocp_t* h, double t, const double* q, const double* v) {
-  if (!h || !h->parnmpc || !q || !v) return IDOCP_E_ARG;
-  int rc = enterO(h); if (rc) return rc;
-  if ((rc = discretize(h, t))) return rc;
+// the KKT residual of the chain against the state in d_q0, d_v0; d_err2 (device, [batch]): the squared error goes there too, on the stream
+static int launchParnmpcResidualO(idocp_ocp_t* h, double* d_err2 = nullptr) {
   const int M = h->M();
-  HIP_TRY(hipMemcpyAsync(h->d_q0, q, sizeof(double) * h->batch * DQ::NQ, hipMemcpyHostToDevice, h->stream));
-  HIP_TRY(hipMemcpyAsync(h->d_v0, v, sizeof(double) * h->batch * DQ::NV, hipMemcpyHostToDevice, h->stream));
   OcpLaunch<DQ>::rnea(h->B, h->batch, M, h->plan.n_impulse(), h->stream);
   if (h->plan.has_switch) OcpLaunch<DQ>::switching(h->B, h->batch, M, h->stream);
   OcpLaunch<DQ>::condenseBackwardEuler(h->B, h->batch, M, h->d_q0, h->d_v0, true, h->stream);
   OcpLaunch<DQ>::parnmpcImpulseCondense(h->B, h->batch, h->plan.n_impulse(), true, h->d_q0, h->d_v0, h->stream);
-  ocpKktErrorReduce(h->B, h->batch, h->stream);
+  ocpKktErrorReduce(h->B, h->batch, h->stream, d_err2);
   HIP_TRY(hipGetLastError());
+  return IDOCP_OK;
+}
+int idocp_parnmpc_compute_kkt_residual(idocp_ocp_t* h, double t, const double* q, const double* v) {
+  if (!h || !h->parnmpc || !q || !v) return IDOCP_E_ARG;
+  int rc = enterO(h); if (rc) return rc;
+  if ((rc = discretize(h, t))) return rc;
+  if ((rc = uploadStateO(h, q, v))) return rc;
+  if ((rc = launchParnmpcResidualO(h))) return rc;
   HIP_TRY(hipStreamSynchronize(h->stream));
   return IDOCP_OK;
 }
@@ -1596,14 +1568,7 @@ int idocp_parnmpc_kkt_error_squared_device(idocp_ocp_t* h, double t, double* d_e
   if (!h || !h->parnmpc || !d_err2) return IDOCP_E_ARG;
   int rc = enterO(h); if (rc) return rc;
   if ((rc = discretize(h, t))) return rc;
-  const int M = h->M();
-  OcpLaunch<DQ>::rnea(h->B, h->batch, M, h->plan.n_impulse(), h->stream);
-  if (h->plan.has_switch) OcpLaunch<DQ>::switching(h->B, h->batch, M, h->stream);
-  OcpLaunch<DQ>::condenseBackwardEuler(h->B, h->batch, M, h->d_q0, h->d_v0, true, h->stream);
-  OcpLaunch<DQ>::parnmpcImpulseCondense(h->B, h->batch, h->plan.n_impulse(), true, h->d_q0, h->d_v0, h->stream);
-  ocpKktErrorReduce(h->B, h->batch, h->stream, d_err2);      // stays on the device and on the stream
-  HIP_TRY(hipGetLastError());
-  return IDOCP_OK;
+  return launchParnmpcResidualO(h, d_err2);      // stays on the device and on the stream: no synchronisation here
 }
 int idocp_ocp_batch(idocp_ocp_t* h) { return h ? h->batch : 0; }
 // Storage precision of the Riccati factorisation P, s (64 = default; 32 = rounded to single precision after every stage of the

@@ -14,12 +14,12 @@
 #include <cmath>
 #include <cstring>
 #include <string>
-#include <utility>
 #include <vector>
 
 #include "hip_try.hpp"
 #include "host_util.hpp"
 #include "idocp_hip.h"
+#include "line_search_filter.hpp"
 #include "model_shapes.hpp"
 #include "unocp_launch.hpp"
 
@@ -94,7 +94,7 @@ struct idocp_unocp {
   int level_offset = 0;         // constraint time step of local stage i = i + level_offset
   int shard = 0;                // 1: a horizon shard of UnParNMPC (idocp_unparnmpc_create_shard)
   // filter line search (LineSearchFilter, src/line_search/line_search_filter.cpp): one filter per instance
-  std::vector<std::vector<std::pair<double, double>>> filters;
+  std::vector<idocp_host::LineSearchFilter> filters;
 };
 
 namespace {
@@ -367,16 +367,14 @@ int idocp_unocp_set_cost(idocp_unocp_t* h, const idocp_cost_t* cost) {
   int rc = setDevice(h); if (rc) return rc;
   UnProblem up;
   fillUnProblem(h->model, *cost, h->cons, h->T, h->N, h->batch, h->bwd, h->shard_dt, h->shard_offset, h->shard_terminal, h->shard_prev, up);
-  // (the block is read by kernels already queued on the stream: the copy is ordered behind them; `up` must outlive the asynchronous copy)
-  HIP_TRY(hipMemcpyAsync(const_cast<UnProblem*>(h->B.prob), &up, sizeof(up), hipMemcpyHostToDevice, h->stream));
+  // (the block is read by kernels already queued on the stream: the copy is ordered behind them)
+  if ((rc = uploadTemporary(const_cast<UnProblem*>(h->B.prob), &up, sizeof(up), h->stream))) return rc;
   if (cost->task_dim != 0 && !cost->task_time_varying) {      // the constant reference pose of every stage (time-varying: idocp_unocp_set_task_refs)
     std::vector<double> refs((size_t)(h->N + 1) * 12);
     for (int i = 0; i <= h->N; ++i) std::memcpy(&refs[12 * i], cost->task_ref, sizeof(double) * 12);
-    HIP_TRY(hipMemcpyAsync(h->B.task_ref, refs.data(), refs.size() * sizeof(double), hipMemcpyHostToDevice, h->stream));
-    HIP_TRY(hipStreamSynchronize(h->stream));
+    if ((rc = uploadTemporary(h->B.task_ref, refs.data(), refs.size() * sizeof(double), h->stream))) return rc;
   }
-  HIP_TRY(hipStreamSynchronize(h->stream));
-  h->cost = *cost;
+  h->cost = *cost;      // only behind both copies: a failure leaves the host with the cost it had
   return IDOCP_OK;
 }
 
@@ -534,11 +532,10 @@ int idocp_unocp_init_constraints(idocp_unocp_t* h) {
 }
 
 // UnLineSearch::computeStepSize (include/idocp/line_search/unline_search.hpp:62-92) for every instance of the batch: the
-// trial iterates are evaluated on the device (un_line_search_kernel), the filter logic (line_search_filter.cpp:33-63,
-// defaults line_search_filter.hpp:16-17, line_search.hpp:25-26) runs here.  On return B.step holds the accepted primal
-// step of every instance.  d_q, d_v: the measured state of the update (device).
+// trial iterates are evaluated on the device (un_line_search_kernel), the filter logic runs on the host (line_search_filter.hpp).
+// On return B.step holds the accepted primal step of every instance.  d_q, d_v: the measured state of the update (device).
 static int lineSearchEval(idocp_unocp_t* h, const std::vector<double>& alpha, const double* d_q, const double* d_v, std::vector<double>& out) {
-  HIP_TRY(hipMemcpyAsync(h->B.ls_alpha, alpha.data(), sizeof(double) * h->batch, hipMemcpyHostToDevice, h->stream));
+  int rc = uploadTemporary(h->B.ls_alpha, alpha.data(), sizeof(double) * h->batch, h->stream); if (rc) return rc;
   h->impl->lineSearchEval(h->B, h->batch, h->N, h->bwd != 0, d_q, d_v, h->stream);
   HIP_TRY(hipGetLastError());
   out.resize((size_t)h->batch * 2);
@@ -548,42 +545,11 @@ static int lineSearchEval(idocp_unocp_t* h, const std::vector<double>& alpha, co
 }
 static int runLineSearch(idocp_unocp_t* h, const double* d_q, const double* d_v) {
   if (h->shard) { set_last_error("line_search=true is not supported on a horizon shard"); return IDOCP_E_UNSUPPORTED; }
-  const double cost_rate = 0.005, con_rate = 0.005, reduction = 0.75, min_step = 0.05;
-  const int B = h->batch;
-  auto accepted = [](const std::vector<std::pair<double, double>>& f, double c, double v) {
-    for (const auto& p : f) if (c >= p.first && v >= p.second) return false;
-    return true;
-  };
-  auto augment = [&](std::vector<std::pair<double, double>>& f, double c, double v) {
-    for (auto it = f.begin(); it != f.end();) { if (c <= it->first && v <= it->second) it = f.erase(it); else ++it; }
-    f.push_back({c - cost_rate * v, (1 - con_rate) * v});
-  };
-  std::vector<double> step((size_t)B * 2), alpha(B, 0.0), cv;
-  int rc;
-  bool any_empty = false;
-  for (int b = 0; b < B; ++b) any_empty = any_empty || h->filters[b].empty();
-  if (any_empty) {                                  // "if filter is empty, augment the current solution to the filter"
-    if ((rc = lineSearchEval(h, alpha, d_q, d_v, cv))) return rc;
-    for (int b = 0; b < B; ++b) if (h->filters[b].empty()) augment(h->filters[b], cv[2 * b], cv[2 * b + 1]);
-  }
+  std::vector<double> step((size_t)h->batch * 2);
   HIP_TRY(hipMemcpyAsync(step.data(), h->B.step, sizeof(double) * step.size(), hipMemcpyDeviceToHost, h->stream));
   HIP_TRY(hipStreamSynchronize(h->stream));
-  std::vector<char> done(B, 0);
-  int open = 0;
-  for (int b = 0; b < B; ++b) { alpha[b] = step[2 * b]; if (!(alpha[b] > min_step)) done[b] = 1; else ++open; }
-  while (open > 0) {
-    if ((rc = lineSearchEval(h, alpha, d_q, d_v, cv))) return rc;
-    for (int b = 0; b < B; ++b) {
-      if (done[b]) continue;
-      if (accepted(h->filters[b], cv[2 * b], cv[2 * b + 1])) { augment(h->filters[b], cv[2 * b], cv[2 * b + 1]); done[b] = 1; --open; continue; }
-      alpha[b] *= reduction;
-      if (!(alpha[b] > min_step)) { done[b] = 1; --open; }
-    }
-  }
-  for (int b = 0; b < B; ++b) step[2 * b] = alpha[b] > min_step ? alpha[b] : min_step;
-  HIP_TRY(hipMemcpyAsync(h->B.step, step.data(), sizeof(double) * step.size(), hipMemcpyHostToDevice, h->stream));
-  HIP_TRY(hipStreamSynchronize(h->stream));         // `step` is a stack temporary
-  return IDOCP_OK;
+  const int rc = idocp_host::filterLineSearch(h->filters, step.data(), 2, [&](const std::vector<double>& alpha, std::vector<double>& cv) { return lineSearchEval(h, alpha, d_q, d_v, cv); });
+  return rc ? rc : uploadTemporary(h->B.step, step.data(), sizeof(double) * step.size(), h->stream);
 }
 
 static int wrongKind(const idocp_unocp_t* h, int want_bwd) {
@@ -593,27 +559,48 @@ static int wrongKind(const idocp_unocp_t* h, int want_bwd) {
   return IDOCP_E_ARG;
 }
 
+// the measured state of a host-pointer entry point, into the handle's staging buffers
+static int uploadState(idocp_unocp_t* h, const double* q, const double* v) {
+  HIP_TRY(hipMemcpyAsync(h->d_q0, q, sizeof(double) * h->batch * h->model.nq, hipMemcpyHostToDevice, h->stream));
+  HIP_TRY(hipMemcpyAsync(h->d_v0, v, sizeof(double) * h->batch * h->model.nv, hipMemcpyHostToDevice, h->stream));
+  return IDOCP_OK;
+}
+// what an iteration runs in front of its integration.  UnOCPSolver: linearize, Riccati, expand + step sizes ...
+static int launchDirection(idocp_unocp_t* h, const double* d_q, const double* d_v) {
+  HIP_TRY(hipMemsetAsync(h->B.status, 0, sizeof(int) * h->batch, h->stream));
+  h->impl->linearize(h->B, h->batch, h->N, h->stream);
+  h->impl->riccati(h->B, h->batch, h->N, d_q, d_v, h->stream);
+  h->impl->expand(h->B, h->batch, h->N, h->stream);
+  HIP_TRY(hipGetLastError());
+  return IDOCP_OK;
+}
+// ... UnParNMPCSolver: phases 0 .. 5
+static int launchParnmpcDirection(idocp_unocp_t* h, const double* d_q, const double* d_v) {
+  HIP_TRY(hipMemsetAsync(h->B.status, 0, sizeof(int) * h->batch, h->stream));
+  for (int phase = 0; phase <= 5; ++phase) h->impl->parnmpcPhase(phase, h->B, h->batch, h->N, d_q, d_v, h->stream);
+  HIP_TRY(hipGetLastError());
+  return IDOCP_OK;
+}
+
 int idocp_unocp_update_solution_device(idocp_unocp_t* h, double t, const double* d_q, const double* d_v) {
   if (!h || !d_q || !d_v) return IDOCP_E_ARG;
   if (wrongKind(h, 0)) return IDOCP_E_ARG;
   (void)t;   // ConfigurationSpaceCost is time-invariant
   int rc = setDevice(h); if (rc) return rc;
-  HIP_TRY(hipMemsetAsync(h->B.status, 0, sizeof(int) * h->batch, h->stream));
-  h->impl->linearize(h->B, h->batch, h->N, h->stream);
-  h->impl->riccati(h->B, h->batch, h->N, d_q, d_v, h->stream);
-  h->impl->expand(h->B, h->batch, h->N, h->stream);
+  if ((rc = launchDirection(h, d_q, d_v))) return rc;
   h->impl->integrate(h->B, h->batch, h->N, h->stream);
   HIP_TRY(hipGetLastError());
-  h->has_direction = true;
+  h->has_direction = true;      // (behind the integration, here and in every branch below: the launchers above leave it alone)
   return IDOCP_OK;
 }
 
-static int statusOf(idocp_unocp_t* h) {
+// the status words of the last direction; the message names the first instance that failed, between `before` and `after`
+static int statusOf(idocp_unocp_t* h, const char* before, const char* after) {
   std::vector<int> st(h->batch);
   HIP_TRY(hipMemcpyAsync(st.data(), h->B.status, sizeof(int) * h->batch, hipMemcpyDeviceToHost, h->stream));
   HIP_TRY(hipStreamSynchronize(h->stream));
   for (int b = 0; b < h->batch; ++b)
-    if (st[b] != 0) { set_last_error("Riccati: Qaa not positive definite (instance " + std::to_string(b) + ")"); return st[b]; }
+    if (st[b] != 0) { set_last_error(before + std::to_string(b) + after); return st[b]; }
   return IDOCP_OK;
 }
 
@@ -630,24 +617,16 @@ int idocp_unocp_update_solution(idocp_unocp_t* h, double t, const double* q, con
   if (!h || !q || !v) return IDOCP_E_ARG;
   if (wrongKind(h, 0)) return IDOCP_E_ARG;
   int rc = setDevice(h); if (rc) return rc;
-  HIP_TRY(hipMemcpyAsync(h->d_q0, q, sizeof(double) * h->batch * h->model.nq, hipMemcpyHostToDevice, h->stream));
-  HIP_TRY(hipMemcpyAsync(h->d_v0, v, sizeof(double) * h->batch * h->model.nv, hipMemcpyHostToDevice, h->stream));
-  if (!line_search) {
-    rc = idocp_unocp_update_solution_device(h, t, h->d_q0, h->d_v0);
-    if (rc) return rc;
-    return statusOf(h);
-  }
+  if ((rc = uploadState(h, q, v))) return rc;
   // unocp_solver.cpp:116-120: the filter line search sits between the direction and the update
-  HIP_TRY(hipMemsetAsync(h->B.status, 0, sizeof(int) * h->batch, h->stream));
-  h->impl->linearize(h->B, h->batch, h->N, h->stream);
-  h->impl->riccati(h->B, h->batch, h->N, h->d_q0, h->d_v0, h->stream);
-  h->impl->expand(h->B, h->batch, h->N, h->stream);
-  HIP_TRY(hipGetLastError());
-  if ((rc = statusOf(h))) return rc;
+  if ((rc = line_search ? launchDirection(h, h->d_q0, h->d_v0) : idocp_unocp_update_solution_device(h, t, h->d_q0, h->d_v0))) return rc;
+  // (with a line search the status is read in front of it -- this solver alone: the other three read it behind the integration)
+  rc = statusOf(h, "Riccati: Qaa not positive definite (instance ", ")");
+  if (rc || !line_search) return rc;
   if ((rc = runLineSearch(h, h->d_q0, h->d_v0))) return rc;
   h->impl->integrate(h->B, h->batch, h->N, h->stream);
   HIP_TRY(hipGetLastError());
-  HIP_TRY(hipStreamSynchronize(h->stream));
+  HIP_TRY(hipStreamSynchronize(h->stream));      // (the line-search path waits for the integration; the *_device entries return with it in flight)
   h->has_direction = true;
   return IDOCP_OK;
 }
@@ -754,8 +733,8 @@ int idocp_unparnmpc_update_solution_device(idocp_unocp_t* h, double t, const dou
   if (wrongKind(h, 1)) return IDOCP_E_ARG;
   (void)t;
   int rc = setDevice(h); if (rc) return rc;
-  HIP_TRY(hipMemsetAsync(h->B.status, 0, sizeof(int) * h->batch, h->stream));
-  for (int phase = 0; phase <= 6; ++phase) h->impl->parnmpcPhase(phase, h->B, h->batch, h->N, d_q, d_v, h->stream);
+  if ((rc = launchParnmpcDirection(h, d_q, d_v))) return rc;
+  h->impl->parnmpcPhase(6, h->B, h->batch, h->N, d_q, d_v, h->stream);
   HIP_TRY(hipGetLastError());
   h->has_direction = true;
   return IDOCP_OK;
@@ -764,33 +743,24 @@ int idocp_unparnmpc_update_solution(idocp_unocp_t* h, double t, const double* q,
   if (!h || !q || !v) return IDOCP_E_ARG;
   if (wrongKind(h, 1)) return IDOCP_E_ARG;
   int rc = setDevice(h); if (rc) return rc;
-  HIP_TRY(hipMemcpyAsync(h->d_q0, q, sizeof(double) * h->batch * h->model.nq, hipMemcpyHostToDevice, h->stream));
-  HIP_TRY(hipMemcpyAsync(h->d_v0, v, sizeof(double) * h->batch * h->model.nv, hipMemcpyHostToDevice, h->stream));
+  if ((rc = uploadState(h, q, v))) return rc;
   if (!line_search) {
     if ((rc = idocp_unparnmpc_update_solution_device(h, t, h->d_q0, h->d_v0))) return rc;
   } else {                                           // unparnmpc_solver.cpp:81-86
-    HIP_TRY(hipMemsetAsync(h->B.status, 0, sizeof(int) * h->batch, h->stream));
-    for (int phase = 0; phase <= 5; ++phase) h->impl->parnmpcPhase(phase, h->B, h->batch, h->N, h->d_q0, h->d_v0, h->stream);
-    HIP_TRY(hipGetLastError());
+    if ((rc = launchParnmpcDirection(h, h->d_q0, h->d_v0))) return rc;
     if ((rc = runLineSearch(h, h->d_q0, h->d_v0))) return rc;
     h->impl->parnmpcPhase(6, h->B, h->batch, h->N, h->d_q0, h->d_v0, h->stream);
     HIP_TRY(hipGetLastError());
     h->has_direction = true;
   }
-  std::vector<int> st(h->batch);
-  HIP_TRY(hipMemcpyAsync(st.data(), h->B.status, sizeof(int) * h->batch, hipMemcpyDeviceToHost, h->stream));
-  HIP_TRY(hipStreamSynchronize(h->stream));
-  for (int b = 0; b < h->batch; ++b)
-    if (st[b] != 0) { set_last_error("UnParNMPC: stage KKT matrix not invertible (Q or F Q^-1 F^T not positive definite), instance " + std::to_string(b)); return st[b]; }
-  return IDOCP_OK;
+  return statusOf(h, "UnParNMPC: stage KKT matrix not invertible (Q or F Q^-1 F^T not positive definite), instance ", "");
 }
 int idocp_unparnmpc_compute_kkt_residual(idocp_unocp_t* h, double t, const double* q, const double* v) {
   if (!h || !q || !v) return IDOCP_E_ARG;
   if (wrongKind(h, 1)) return IDOCP_E_ARG;
   (void)t;
   int rc = setDevice(h); if (rc) return rc;
-  HIP_TRY(hipMemcpyAsync(h->d_q0, q, sizeof(double) * h->batch * h->model.nq, hipMemcpyHostToDevice, h->stream));
-  HIP_TRY(hipMemcpyAsync(h->d_v0, v, sizeof(double) * h->batch * h->model.nv, hipMemcpyHostToDevice, h->stream));
+  if ((rc = uploadState(h, q, v))) return rc;
   h->impl->parnmpcResidual(h->B, h->batch, h->N, h->d_q0, h->d_v0, h->stream);
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipStreamSynchronize(h->stream));

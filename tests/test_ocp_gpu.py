@@ -289,3 +289,47 @@ def test_line_search_accepted_steps_follow_the_oracle():
         for f in ("q", "v", "a", "u", "f"):
             assert rel_err(g.get(f, 1), o.get(f)) < 1e-8, (it, f)
     capi.check(g.lib.idocp_ocp_clear_line_search_filter(g.h))
+
+
+def test_line_search_of_a_heterogeneous_batch_follows_one_oracle_per_instance():
+    """The part of the filter line search that belongs to a batch (idocp_amd/csrc/line_search_filter.hpp: one filter per instance, every probe
+    evaluates all of them, an instance that has finished waits for the slowest): three instances with three measured states against three
+    oracle objects, six iterations with line_search = 1 on the event-free horizon of _ls_pair(20, 1.0, 0).
+
+    The states were chosen with the oracle alone.  Tried: the standing pose with the joints moved by +0.05 (the neighbouring test's), -0.05,
+    +0.1, +0.2, two random joint offsets (up to 0.1 / 0.3, the latter with random joint velocities), +0.05 with joint velocities 1, and the
+    standing pose with a base velocity of 0.5.  Every one backtracks; kept are +0.05, +0.2 and +0.05 with velocities 1, whose maximum steps
+    (1, 0.28 .. 0.13, 0.45 .. 0.28) and accepted steps (0.05 .. 0.133, 0.05 .. 0.054, 0.05 .. 0.066) differ, so that the instances stop at
+    different probes of the same search."""
+    lib_o, m, o0, g, q0, v0 = _ls_pair(20, 1.0, 0, batch=3)
+    oracles = [o0]
+    for _ in range(2):                                   # (the oracle half of _ls_pair)
+        o = OracleOCP(m, *anymal_problem(m, trotting_ref=True), 1.0, 20)
+        o.set_contact_status([1, 1, 1, 1], anymal_contact_points(m))
+        o.set_solution("q", ANYMAL_Q_STANDING)
+        o.set_solution("v", np.zeros(m.nv))
+        o.set_solution("f", [0, 0, 0.25 * (-m.total_mass * m.gravity[2])])
+        o.init_constraints(0.0)
+        oracles.append(o)
+    q, v = np.tile(q0, (3, 1)), np.tile(v0, (3, 1))
+    q[1, 7:] += 0.15                                     # joints at +0.2
+    v[2, 6:] = 1.0
+    differed = below = False
+    for it in range(6):
+        amax, acc = np.zeros(3), np.zeros(3)
+        for b, o in enumerate(oracles):
+            assert lib_o.oracle_ocp_compute_direction(o.h, 0.0, P(q[b]), P(v[b])) == 0      # (the maximum step; the update below starts over from the iterate)
+            amax[b] = o.step_sizes()[0]
+            assert lib_o.oracle_ocp_update_solution_ls(o.h, 0.0, P(q[b]), P(v[b])) == 0
+        assert g.lib.idocp_ocp_update_solution(g.h, 0.0, P(g._bc(q, g.nq)), P(g._bc(v, g.nv)), 1) == 0
+        ag, bg = g.step_sizes()
+        for b, o in enumerate(oracles):
+            acc[b], bo = o.step_sizes()
+            print("iteration %d instance %d: maximum step %.6g, accepted %.6g (GPU %.6g), dual %.6g (GPU %.6g)" % (it, b, amax[b], acc[b], ag[b], bo, bg[b]))
+            assert abs(ag[b] - acc[b]) < 1e-12 and abs(bg[b] - bo) < 1e-9, (it, b, ag[b], acc[b])
+            for f in ("q", "v", "a", "u", "f"):
+                assert rel_err(g.get(f, b), o.get(f)) < 1e-8, (it, b, f)
+        differed = differed or len(set(acc)) > 1
+        below = below or bool(np.any(acc < amax))
+    assert differed, "no two instances accepted different primal steps in any iteration"
+    assert below, "no instance accepted a step below its maximum step"
