@@ -146,6 +146,13 @@ class RbdFootholdRollout(C.Structure):
     _fields_ = [("u", C.c_void_p), ("policy", C.POINTER(RbdPolicy))] + [(name, C.c_void_p) for name in ARRAYS]
 
 
+class RbdLqrIO(C.Structure):
+    """idocp_rbd_lqr_io_t: the arrays of idocp_rbd_lqr_backward(_device); a pointer left at None is NULL"""
+    INPUTS = ("A_traj", "B_traj", "x_weight", "u_weight", "xf_weight", "lx_traj", "lu_traj")
+    OUTPUTS = ("K_traj", "k_traj", "P0", "p0", "expected", "status")
+    _fields_ = [(name, C.c_void_p) for name in INPUTS] + [("regularization", C.c_double)] + [(name, C.c_void_p) for name in OUTPUTS]
+
+
 RBD_STAGE, RBD_IMPULSE = 0, 1
 RBD_SCORE_MAX_WINDOW = 1024
 RBD_REDUCE_CHUNK = 1024      # IDOCP_RBD_REDUCE_CHUNK: samples per chunk of the fixed-order sums
@@ -379,6 +386,10 @@ def _proto(lib):
             f = getattr(lib, name + form)
             f.argtypes = args
             f.restype = ci
+    for form in ("", "_device"):
+        f = getattr(lib, "idocp_rbd_lqr_backward" + form)
+        f.argtypes = [vp, ci, ci, P(RbdLqrIO)]
+        f.restype = ci
     for name, args in [
         ("idocp_ocp_set_contact_status_uniformly", [vp, P(ci), c_double_p]),
         ("idocp_ocp_set_solution", [vp, cs, c_double_p]),

@@ -789,6 +789,41 @@ __device__ __forceinline__ void mfmaTilePairTN4(const double* X0, int xr0, const
   }
 }
 
+// NT tiles of ONE block column on v_mfma_f64_16x16x4_f64: tile t holds C(16 t + i, j) = sum_k X[k + ldx (16 t + i)] Y[k + ldy j], i.e. rows
+// 16 t .. 16 t + 15 of X^T Y for the 16 columns of Y given.  The Y operand is read once for all the tiles, every operand read is issued before
+// the first multiply, and the NT accumulation chains alternate on the matrix core.  m = number of valid rows of X^T (columns of X), yc = valid
+// columns of Y (lanes beyond re-read the last valid one; their results are never stored), k is masked against KMAX's padding: the operands
+// must be READABLE up to 8 ceil(KMAX / 8) entries behind the start of every column.
+template <int KMAX, int NT>
+__device__ __forceinline__ void mfmaTileColumnTN(const double* X, int m, const double* Y, int yc, int ldx, int ldy, int k, int lane, mfma_d4 (&acc)[NT]) {
+  typedef double d2 __attribute__((ext_vector_type(2)));
+  constexpr int KS = (KMAX + 7) / 8;
+  const int li = lane & 15, g = lane >> 4;
+  const double* yp = Y + ldy * (li < yc ? li : yc - 1) + 2 * g;
+  d2 ya[KS], xa[NT][KS];
+#pragma unroll
+  for (int s = 0; s < KS; ++s) ya[s] = *reinterpret_cast<const d2*>(yp + 8 * s);
+#pragma unroll
+  for (int t = 0; t < NT; ++t) {
+    const int r = 16 * t + li;
+    const double* xp = X + ldx * (r < m ? r : m - 1) + 2 * g;
+#pragma unroll
+    for (int s = 0; s < KS; ++s) xa[t][s] = *reinterpret_cast<const d2*>(xp + 8 * s);
+  }
+#pragma unroll
+  for (int t = 0; t < NT; ++t) acc[t] = mfma_d4{0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+  for (int s = 0; s < KS; ++s) {
+    const int kk = 8 * s + 2 * g;
+    const bool v0 = kk < k, v1 = kk + 1 < k;
+    const double y0 = v0 ? ya[s].x : 0.0, y1 = v1 ? ya[s].y : 0.0;
+#pragma unroll
+    for (int t = 0; t < NT; ++t) acc[t] = __builtin_amdgcn_mfma_f64_16x16x4f64(y0, v0 ? xa[t][s].x : 0.0, acc[t], 0, 0, 0);
+#pragma unroll
+    for (int t = 0; t < NT; ++t) acc[t] = __builtin_amdgcn_mfma_f64_16x16x4f64(y1, v1 ? xa[t][s].y : 0.0, acc[t], 0, 0, 0);
+  }
+}
+
 // store(r, c, value) for the elements of a tile at (r0, c0) that lie inside m x n
 template <typename Store>
 __device__ __forceinline__ void mfmaTileStore(const mfma_d4& acc, int r0, int c0, int m, int n, int lane, Store store) {

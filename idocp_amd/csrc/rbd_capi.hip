@@ -566,6 +566,45 @@ int linearizeDevice(idocp_rbd* h, int n, int steps, const int* active, double ti
   return IDOCP_OK;
 }
 
+// ---- time-varying LQR gains about a linearised rollout ----
+
+// host: the weight arrays are host memory and can be looked at
+int checkLqr(const char* who, const idocp_rbd* h, int n, int steps, const idocp_rbd_lqr_io_t* io, bool host) {
+  const std::string w(who);
+  if (!h || !io) { set_last_error(w + ": null handle or io"); return IDOCP_E_ARG; }
+  if (n <= 0) { set_last_error(w + ": n must be positive"); return IDOCP_E_ARG; }
+  if (steps < 1) { set_last_error(w + ": steps must be at least 1"); return IDOCP_E_ARG; }
+  if (!io->A_traj || !io->B_traj) { set_last_error(w + ": A_traj and B_traj are needed"); return IDOCP_E_ARG; }
+  if (!io->x_weight || !io->u_weight || !io->xf_weight) { set_last_error(w + ": x_weight, u_weight and xf_weight are needed"); return IDOCP_E_ARG; }
+  if ((io->lx_traj != nullptr) != (io->lu_traj != nullptr)) { set_last_error(w + ": lx_traj and lu_traj come together (both or neither)"); return IDOCP_E_ARG; }
+  if (!io->lx_traj && (io->k_traj || io->expected)) { set_last_error(w + ": k_traj and expected need the gradients lx_traj and lu_traj"); return IDOCP_E_ARG; }
+  if (!io->K_traj && !io->k_traj && !io->P0 && !io->p0 && !io->expected && !io->status) { set_last_error(w + ": no output was asked for"); return IDOCP_E_ARG; }
+  if (!std::isfinite(io->regularization) || io->regularization < 0.0) {
+    set_last_error(w + ": regularization must be finite and non-negative"); return IDOCP_E_ARG;
+  }
+  if (!host) return IDOCP_OK;
+  const int nx = 2 * h->model.nv, nu = h->model.nu;
+  auto weights = [&](const char* name, const double* x, int m) {
+    for (int j = 0; j < m; ++j)
+      if (!std::isfinite(x[j]) || x[j] < 0.0) { set_last_error(w + ": " + name + "[" + std::to_string(j) + "] must be finite and non-negative"); return false; }
+    return true;
+  };
+  if (!weights("x_weight", io->x_weight, nx) || !weights("u_weight", io->u_weight, nu) || !weights("xf_weight", io->xf_weight, nx)) return IDOCP_E_ARG;
+  return IDOCP_OK;
+}
+
+// io: device pointers
+int launchLqr(idocp_rbd* h, int n, int steps, const idocp_rbd_lqr_io_t& io) {
+  RbdLqrArgs a;
+  a.A = io.A_traj; a.B = io.B_traj; a.x_weight = io.x_weight; a.u_weight = io.u_weight; a.xf_weight = io.xf_weight;
+  a.lx = io.lx_traj; a.lu = io.lu_traj; a.regularization = io.regularization;
+  a.K = io.K_traj; a.k = io.k_traj; a.P0 = io.P0; a.p0 = io.p0; a.expected = io.expected; a.status = io.status;
+  a.n = n; a.steps = steps; a.nx = 2 * h->model.nv; a.nu = h->model.nu;
+  rbdLqrBackward(h->quadruped, a, h->stream);
+  HIP_TRY(hipGetLastError());
+  return IDOCP_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -1050,6 +1089,39 @@ int idocp_rbd_weighted_mean(idocp_rbd_t* h, int n, int rows, int m, const double
   p.out(mean, (size_t)rows * m, &d_mean);
   rc = stageIn(h, p); if (rc) return rc;
   rc = launchMean(h, n, rows, m, d_weights, d_x, d_mean); if (rc) return rc;
+  return stageOut(h, p);
+}
+
+int idocp_rbd_lqr_backward_device(idocp_rbd_t* h, int n, int steps, const idocp_rbd_lqr_io_t* io) {
+  int rc = checkLqr("idocp_rbd_lqr_backward_device", h, n, steps, io, false); if (rc) return rc;
+  HIP_TRY(hipSetDevice(h->device));
+  return launchLqr(h, n, steps, *io);
+}
+
+int idocp_rbd_lqr_backward(idocp_rbd_t* h, int n, int steps, const idocp_rbd_lqr_io_t* io) {
+  int rc = checkLqr("idocp_rbd_lqr_backward", h, n, steps, io, true); if (rc) return rc;
+  HIP_TRY(hipSetDevice(h->device));
+  const size_t nx = 2 * (size_t)h->model.nv, nu = h->model.nu, N = (size_t)n, S = (size_t)steps;
+  StagePlan p;
+  idocp_rbd_lqr_io_t d = *io;
+  double* d_status = nullptr;
+  p.in(io->A_traj, S * N * nx * nx, &d.A_traj);
+  p.in(io->B_traj, S * N * nx * nu, &d.B_traj);
+  p.in(io->x_weight, nx, &d.x_weight);
+  p.in(io->u_weight, nu, &d.u_weight);
+  p.in(io->xf_weight, nx, &d.xf_weight);
+  p.in(io->lx_traj, (S + 1) * N * nx, &d.lx_traj);
+  p.in(io->lu_traj, S * N * nu, &d.lu_traj);
+  p.out(io->K_traj, S * N * nx * nu, &d.K_traj);
+  p.out(io->k_traj, S * N * nu, &d.k_traj);
+  p.out(io->P0, N * nx * nx, &d.P0);
+  p.out(io->p0, N * nx, &d.p0);
+  p.out(io->expected, N * 2, &d.expected);
+  if (io->status) p.deviceOnly((N + 1) / 2, &d_status);      // (n ints in a slot of doubles; they come down by a copy of their own, in front of stageOut's wait)
+  rc = stageIn(h, p); if (rc) return rc;
+  d.status = reinterpret_cast<int*>(d_status);
+  rc = launchLqr(h, n, steps, d); if (rc) return rc;
+  if (io->status) HIP_TRY(hipMemcpyAsync(io->status, d_status, sizeof(int) * N, hipMemcpyDeviceToHost, h->stream));
   return stageOut(h, p);
 }
 

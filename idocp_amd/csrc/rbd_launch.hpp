@@ -106,5 +106,18 @@ void rbdFddChain(int nv, const RbdFddArgs& a, int n, hipStream_t st);
 // column-major, nx <= 36, nu <= 12; A or B may be NULL.  One wavefront per sample, fixed order of summation.  One launch.
 void rbdFddImpulseProduct(int nx, int nu, const double* E, double* A, double* B, int n, hipStream_t st);
 
+// The backward pass of time-varying LQR over a linearised rollout (rbd_lqr_kernel.hip; the arrays of idocp_rbd_lqr_io_t).  Every pointer: DEVICE
+// memory.  nx = 2 nv, nu: 36, 12 on the quadruped, at most 16, 8 on a chain.  lx and lu: both or neither; an output that is NULL is not stored.
+// One wavefront per sample, RBD_LQR_WAVES samples per workgroup, any n.  One launch.
+constexpr int RBD_LQR_WAVES = 1;
+struct RbdLqrArgs {
+  const double *A, *B, *x_weight, *u_weight, *xf_weight, *lx, *lu;
+  double regularization;
+  double *K, *k, *P0, *p0, *expected;
+  int* status;
+  int n, steps, nx, nu;
+};
+void rbdLqrBackward(bool quadruped, const RbdLqrArgs& a, hipStream_t st);
+
 }  // namespace idocp_dev
 #endif  // IDOCP_RBD_LAUNCH_HPP_

@@ -313,6 +313,49 @@ class Robot {
     idocp_rbd_objective_destroy(objective);
     ok(rc);
   }
+  // Time-varying LQR gains about ONE linearised trajectory, an ADDITION like forwardDynamicsDerivatives, whose A and B it takes per step: the
+  // backward pass of idocp_rbd_lqr_backward (idocp_hip.h has the recursion) with the diagonal stage weights x_weight (2 nv, on [dq; dv]),
+  // u_weight (nu) and the terminal weight xf_weight (2 nv), already scaled by the caller (dt included), the optional cost gradients lx (N + 1
+  // vectors of 2 nv) and lu (N of nu) -- both empty or both given -- and a regularisation of Quu.  K[k] is nu x 2 nv = [Kq | Kv] in the convention
+  // of stateFeedbackTorques (u = u_ff + K [q (-) q_ref; v - v_ref]); k[k] is the feed-forward step, zero without gradients.  Returns false, with
+  // NaN from the failing step down, where Quu is not positive definite or an input is not finite.  ONE n = 1 call on the same lazily created handle.
+  bool lqrGains(const std::vector<Eigen::MatrixXd>& A, const std::vector<Eigen::MatrixXd>& B, const Eigen::VectorXd& x_weight,
+                const Eigen::VectorXd& u_weight, const Eigen::VectorXd& xf_weight, const std::vector<Eigen::VectorXd>& lx,
+                const std::vector<Eigen::VectorXd>& lu, const double regularization, std::vector<Eigen::MatrixXd>& K, std::vector<Eigen::VectorXd>& k) {
+    const int steps = (int)A.size(), nx = 2 * model_.nv, nu = model_.nu;
+    const bool grad = !lx.empty() || !lu.empty();
+    if (steps < 1 || (int)B.size() != steps || (grad && ((int)lx.size() != steps + 1 || (int)lu.size() != steps))) {
+      std::cerr << "invalid size: N steps have N of A, B and, if given, N + 1 of lx and N of lu!" << '\n'; std::exit(EXIT_FAILURE);
+    }
+    sized(x_weight, nx, "x_weight"); sized(u_weight, nu, "u_weight"); sized(xf_weight, nx, "xf_weight");
+    const size_t nxx = (size_t)nx * nx, nxu = (size_t)nx * nu;
+    std::vector<double> As(steps * nxx), Bs(steps * nxu), lxs, lus, Ks(steps * nxu), ks;
+    for (int s = 0; s < steps; ++s) {
+      if (A[s].rows() != nx || A[s].cols() != nx || B[s].rows() != nx || B[s].cols() != nu) {
+        std::cerr << "invalid size: A must be " << nx << " x " << nx << " and B " << nx << " x " << nu << "!" << '\n'; std::exit(EXIT_FAILURE);
+      }
+      for (int c = 0; c < nx; ++c) for (int r = 0; r < nx; ++r) As[s * nxx + (size_t)c * nx + r] = A[s](r, c);
+      for (int c = 0; c < nu; ++c) for (int r = 0; r < nx; ++r) Bs[s * nxu + (size_t)c * nx + r] = B[s](r, c);
+    }
+    if (grad) {
+      lxs.resize((size_t)(steps + 1) * nx); lus.resize((size_t)steps * nu); ks.resize((size_t)steps * nu);
+      for (int s = 0; s <= steps; ++s) { sized(lx[s], nx, "lx"); for (int j = 0; j < nx; ++j) lxs[(size_t)s * nx + j] = lx[s][j]; }
+      for (int s = 0; s < steps; ++s) { sized(lu[s], nu, "lu"); for (int j = 0; j < nu; ++j) lus[(size_t)s * nu + j] = lu[s][j]; }
+    }
+    int status = -1;
+    idocp_rbd_lqr_io_t io = idocp_rbd_lqr_io_t();
+    io.A_traj = As.data(); io.B_traj = Bs.data(); io.x_weight = x_weight.data(); io.u_weight = u_weight.data(); io.xf_weight = xf_weight.data();
+    io.lx_traj = grad ? lxs.data() : nullptr; io.lu_traj = grad ? lus.data() : nullptr; io.regularization = regularization;
+    io.K_traj = Ks.data(); io.k_traj = grad ? ks.data() : nullptr; io.status = &status;
+    if (!rbd_.h) ok(idocp_rbd_create(&model_, 0, &rbd_.h));
+    ok(idocp_rbd_lqr_backward(rbd_.h, 1, steps, &io));
+    K.assign(steps, Eigen::MatrixXd(nu, nx)); k.assign(steps, Eigen::VectorXd::Zero(nu));
+    for (int s = 0; s < steps; ++s) {
+      for (int c = 0; c < nx; ++c) for (int r = 0; r < nu; ++r) K[s](r, c) = Ks[s * nxu + (size_t)c * nu + r];
+      if (grad) for (int j = 0; j < nu; ++j) k[s][j] = ks[(size_t)s * nu + j];
+    }
+    return status < 0;
+  }
   // Robot::framePosition / frameRotation / framePlacement (robot.hxx:206-233): of any frame of the URDF (pinocchio's frame numbering, as the
   // contact frames and the task-space costs use it), at the configuration of the last updateFrameKinematics / updateKinematics
   Eigen::Vector3d framePosition(const int frame_id) const { return framePlacement(frame_id).translation(); }

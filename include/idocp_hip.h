@@ -938,6 +938,43 @@ int idocp_rbd_rollout_policy_device(idocp_rbd_t* h, int n, int steps, const int*
                                     const idocp_rbd_policy_t* policy, const double* contact_points, double* q_traj, double* v_traj, double* u_traj,
                                     double* a_traj, double* f_traj, int touchdown_impulse);
 
+/* ---- Time-varying LQR gains about a linearised rollout: the backward pass of LQR / iLQR per sample, on the GPU (rbd_lqr_kernel.hip; an ADDITION
+ * like the rest of this block, the reference has no counterpart).  It consumes what idocp_rbd_linearize_rollout writes and produces gains in
+ * exactly the layout idocp_rbd_policy_t reads, so that rollout, linearisation, gains, policy rollout and score run on the handle's stream with no
+ * host round trip.  With W* = diag(*_weight), the recursion -- this is the definition -- is
+ *   P = Wxf, p = lx[steps];   for k = steps - 1 .. 0, with A = A_traj[k], B = B_traj[k]:
+ *     Qx = lx[k] + A^T p,  Qu = lu[k] + B^T p,
+ *     Qxx = Wx + A^T P A,  Qux = B^T P A,  Quu = Wu + regularization I + B^T P B,
+ *     K_k = -Quu^-1 Qux,  k_k = -Quu^-1 Qu   (Cholesky),
+ *     P <- (X + X^T) / 2 with X = Qxx + Qux^T K_k,   p <- Qx + Qux^T k_k.
+ * The sign is the policy's, u = u_ff + K e: a caller sets u_ff = u_traj (+ alpha k_traj), q_ref = q_traj, v_ref = v_traj with shared_ref = 0, and
+ * K = K_traj, unchanged.  The weights are diagonal and already scaled by the caller (dt included); the a_weight and f_weight terms of
+ * idocp_cost_t have no place in a diagonal x_weight / u_weight.  Both model kinds are taken (quadruped: 2 nv = 36, nu = 12; chains of 2 .. 8
+ * joints).  An output that is NULL is not stored; a sample's bits depend neither on n, nor on the outputs asked for, nor on the form of the call.
+ * Failure is per sample: a sample fails at step k if a pivot of Quu at step k is not positive or an entry the step reads from that sample is not
+ * finite.  K_traj and k_traj of the steps <= k, P0, p0 and expected of that sample are then NaN and status = k; the steps > k keep their valid
+ * values, and no other sample is touched. */
+typedef struct idocp_rbd_lqr_io {
+  const double *A_traj, *B_traj;   /* [steps][n][2nv*2nv], [steps][n][2nv*nu]: exactly what idocp_rbd_linearize_rollout writes */
+  const double *x_weight;          /* [2nv] stage weight on [dq; dv], diagonal, >= 0, already scaled by the caller (dt included) */
+  const double *u_weight;          /* [nu]  stage weight on du, >= 0 */
+  const double *xf_weight;         /* [2nv] terminal weight, >= 0 */
+  const double *lx_traj, *lu_traj; /* optional cost gradients [steps + 1][n][2nv], [steps][n][nu]; both or neither; NULL = 0 */
+  double regularization;           /* >= 0, added to the diagonal of Quu */
+  double *K_traj;                  /* [steps][n][nu * 2nv], column-major nu x 2nv, columns [dq | dv]: the K of idocp_rbd_policy_t */
+  double *k_traj;                  /* [steps][n][nu] feed-forward step; only with gradients */
+  double *P0, *p0;                 /* [n][2nv*2nv], [n][2nv]: value function at slice 0 */
+  double *expected;                /* [n][2]: {sum_k k_k^T Qu_k, 1/2 sum_k k_k^T Quu_k k_k}; only with gradients */
+  int *status;                     /* [n]: -1, or the largest step index at which the sample failed */
+} idocp_rbd_lqr_io_t;
+/* Host pointers; stages through the handle's buffer like the other host forms and returns when the outputs are in place.  IDOCP_E_ARG (the text
+ * of idocp_last_error names the call) for n <= 0, steps < 1, a NULL handle, io, A_traj, B_traj or weight array, only one of lx_traj / lu_traj,
+ * k_traj or expected without gradients, no output at all, a negative or non-finite regularization, and a negative or non-finite weight. */
+int idocp_rbd_lqr_backward(idocp_rbd_t* h, int n, int steps, const idocp_rbd_lqr_io_t* io);
+/* Device pointers for everything, the weights and status included; asynchronous on idocp_rbd_stream(h); allocates nothing.  The weights are
+ * NOT checked (they are device memory). */
+int idocp_rbd_lqr_backward_device(idocp_rbd_t* h, int n, int steps, const idocp_rbd_lqr_io_t* io);
+
 /* ---- Contact-frame kinematics for n states (rbd_kinematics_kernel.hip): the batched counterpart of Robot::updateFrameKinematics with
  * getContactPoints, frameRotation and getFrameJacobian, which idocp_model_contact_positions / idocp_model_frame_world_placement give one state
  * on the host.  Quadrupeds only (a fixed-base chain has no contact frames: IDOCP_E_UNSUPPORTED).  Per sample i and contact c:

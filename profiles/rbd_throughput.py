@@ -14,7 +14,8 @@ copy of that array -- and sample_weights (idocp_rbd_importance_weights_device: c
 those three arrays.  The fdd_* rows are the forward-dynamics derivatives (fdd_rows has their description).  The kin_* rows are idocp_rbd_contact_kinematics_batch_device: kin_points (q in, points out) and kin_all (q and v in, all four
 outputs), each against kin_*_copy, a device-to-device copy of the bytes the call reads and writes.  rollout is idocp_rbd_rollout_device over
 ROLLOUT_STEPS open-loop steps with every contact active and no touchdown impulse, rollout_footholds the same schedule through
-idocp_rbd_rollout_footholds_device (one latch launch more per step); both carry ms_per_step.
+idocp_rbd_rollout_footholds_device (one latch launch more per step); both carry ms_per_step.  The lqr_* rows are idocp_rbd_lqr_backward_device over
+16 steps (lqr_rows has their description); run with fdd_linearize_s16 they also carry their ratio to the linearisation that feeds them.
 
     python profiles/rbd_throughput.py [--n 122880] [--launches 20] [--warmup 5] [--rows name,name,...]
 """
@@ -322,6 +323,69 @@ def fdd_rows(wanted, lib, h, m, n, dev, active, measure, res):
         lib.idocp_device_free(d)
 
 
+LQR_ROWS = ("lqr_gains_copy", "lqr_gains", "lqr_gains_ilqr_copy", "lqr_gains_ilqr")
+LQR_STEPS = 16
+LQR_FLOP_PER_STEP = 2.7e5      # per sample and step on the quadruped: P A, A^T (P A), B^T (P A), Qux^T K and the small rest
+
+
+def lqr_rows(wanted, lib, rt, h, stream, m, n, measure, res):
+    """the lqr_* rows: idocp_rbd_lqr_backward_device over 16 steps of A = I + 0.1 N(0, 1), B = 0.1 N(0, 1) (one block of 1 024 samples repeated
+    over the batch and the steps) -- lqr_gains writes K_traj and status alone, lqr_gains_ilqr takes the gradients and writes every output --, each
+    against a device-to-device copy of the bytes it reads and writes, and with the FP64 rate it reaches on the 2.7e5 FLOP per sample and step."""
+    rt.hipMemcpyAsync.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p]
+    nx, nu, S, block = 2 * m.nv, m.nu, LQR_STEPS, min(n, 1024)
+    rng = np.random.default_rng(5)
+    sizes = {"A_traj": S * n * nx * nx, "B_traj": S * n * nx * nu, "lx_traj": (S + 1) * n * nx, "lu_traj": S * n * nu, "K_traj": S * n * nx * nu,
+             "k_traj": S * n * nu, "P0": n * nx * nx, "p0": n * nx, "expected": 2 * n, "status": (n + 1) // 2, "x_weight": nx, "u_weight": nu, "xf_weight": nx}
+    dev = {}
+    for key, size in list(sizes.items()) + [("copy", sum(sizes.values()))]:
+        dev[key] = C.c_void_p()
+        capi.check(lib.idocp_device_alloc(C.byref(dev[key]), 8 * size), "alloc")
+    for key, x in (("x_weight", rng.uniform(0.5, 2, nx)), ("u_weight", rng.uniform(0.5, 2, nu)), ("xf_weight", rng.uniform(0.5, 2, nx))):
+        capi.check(lib.idocp_device_upload(dev[key], x.ctypes.data, x.nbytes), "upload")
+    for key, width, x in (("A_traj", nx * nx, np.eye(nx) + 0.1 * rng.normal(size=(block, nx, nx))), ("B_traj", nx * nu, 0.1 * rng.normal(size=(block, nu, nx))),
+                          ("lx_traj", nx, rng.normal(size=(block, nx))), ("lu_traj", nu, rng.normal(size=(block, nu)))):
+        x = np.ascontiguousarray(x)
+        capi.check(lib.idocp_device_upload(dev[key], x.ctypes.data, x.nbytes), "upload")
+        at, total = block * width, sizes[key]
+        while at < total:      # (doubling: the filled front copied behind itself)
+            count = min(at, total - at)
+            capi.check(lib.idocp_device_copy(C.c_void_p(dev[key].value + 8 * at), dev[key], 8 * count), "copy")
+            at += count
+    selections = {"lqr_gains": ("A_traj", "B_traj", "K_traj", "status"), "lqr_gains_ilqr": tuple(k for k in sizes if not k.endswith("weight"))}
+    for name, keys in selections.items():
+        io = capi.RbdLqrIO()
+        for key in keys + ("x_weight", "u_weight", "xf_weight"):
+            setattr(io, key, dev[key])
+        io.regularization = 0.1
+        nbytes = 8 * sum(sizes[key] for key in keys)
+
+        def copy(keys=keys):
+            at = 0
+            for key in keys:      # the very bytes the call reads and writes, array by array
+                assert rt.hipMemcpyAsync(C.c_void_p(dev["copy"].value + at), dev[key], 8 * sizes[key], 3, stream) == 0
+                at += 8 * sizes[key]
+
+        for row, launch in ((name + "_copy", copy), (name, lambda io=io: capi.check(lib.idocp_rbd_lqr_backward_device(h, n, S, C.byref(io)), "lqr"))):
+            if wanted and row not in wanted:
+                continue
+            measure(row, launch)
+            res[row].update({"steps": S, "bytes": nbytes, "GB_per_s": round(nbytes / res[row]["ms_median"] / 1e6, 1)})
+        if name in res:
+            res[name]["ms_per_step"] = round(res[name]["ms_median"] / S, 4)
+            res[name]["fp64_TFLOP_per_s"] = round(LQR_FLOP_PER_STEP * n * S / res[name]["ms_median"] / 1e9, 2)
+            if name + "_copy" in res:
+                res[name]["ratio_to_copy"] = round(res[name]["ms_median"] / res[name + "_copy"]["ms_median"], 3)
+            if "fdd_linearize_s16" in res:      # the call that produces its input, same shapes, same run
+                res[name]["ratio_to_linearize"] = round(res[name]["ms_median"] / res["fdd_linearize_s16"]["ms_median"], 3)
+    status = np.zeros((n + 1) // 2)
+    capi.check(lib.idocp_rbd_synchronize(h), "synchronize")
+    capi.check(lib.idocp_device_download(status.ctypes.data, dev["status"], status.nbytes), "download")
+    res["lqr_all_solved"] = bool((status.view(np.int32)[:n] == -1).all())
+    for d in dev.values():
+        lib.idocp_device_free(d)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--n", type=int, default=122880)
@@ -428,6 +492,8 @@ def main():
         kin_rows(wanted, lib, rt, h, stream, m, n, host, measure, res)
     if not wanted or set(wanted) & set(FDD_ROWS):
         fdd_rows(wanted, lib, h, m, n, dev, active, measure, res)
+    if not wanted or set(wanted) & set(LQR_ROWS):
+        lqr_rows(wanted, lib, rt, h, stream, m, n, measure, res)
     ran = [k for k in res if isinstance(res[k], dict)]
     for key, src, width, rows in (("tau_finite", "tau", nv, ("stage_", "impulse_")), ("fd_a_finite", "fd_a", nv, ("fd_",)),
                                   ("policy_u_finite", "u_out", m.nu, ("policy_", "fd_step_closed_loop"))):
