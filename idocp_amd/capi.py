@@ -153,6 +153,31 @@ class RbdLqrIO(C.Structure):
     _fields_ = [(name, C.c_void_p) for name in INPUTS] + [("regularization", C.c_double)] + [(name, C.c_void_p) for name in OUTPUTS]
 
 
+class RbdGradientIO(C.Structure):
+    """idocp_rbd_gradient_io_t: the slices and requested outputs of idocp_rbd_objective_gradients(_device); a pointer left at None is NULL"""
+    INPUTS = ("q_traj", "v_traj", "u_traj")
+    OUTPUTS = ("lx_traj", "lu_traj")
+    _fields_ = [(name, C.c_void_p) for name in INPUTS + OUTPUTS]
+
+
+class RbdIlqrAcceptIO(C.Structure):
+    """idocp_rbd_ilqr_accept_io_t: the arrays and constants of idocp_rbd_ilqr_accept(_device); a pointer left at None is NULL"""
+    CURRENT = ("q_traj", "v_traj", "u_traj", "a_traj", "f_traj", "cost", "violation")
+    TRIAL = ("trial_q", "trial_v", "trial_u", "trial_a", "trial_f", "trial_cost", "trial_violation")
+    STATE = ("expected", "alpha", "done", "alpha_accepted")
+    CONSTANTS = ("penalty", "armijo", "shrink", "alpha_min")
+    _fields_ = [(name, C.c_void_p) for name in CURRENT + TRIAL + STATE] + [(name, C.c_double) for name in CONSTANTS]
+
+
+class RbdIlqrIO(C.Structure):
+    """idocp_rbd_ilqr_io_t: the arrays and constants of idocp_rbd_ilqr_iterate(_device); a pointer left at None is NULL"""
+    CURRENT = ("q_traj", "v_traj", "u_traj", "a_traj", "f_traj", "cost", "violation", "u_min", "u_max")
+    CONSTANTS = ("regularization", "armijo", "shrink", "alpha_min", "penalty")
+    OUTPUTS = ("alpha_accepted", "lqr_status", "expected")
+    _fields_ = ([(name, C.c_void_p) for name in CURRENT] + [(name, C.c_double) for name in CONSTANTS] + [("trials", C.c_int)] +
+                [(name, C.c_void_p) for name in OUTPUTS] + [("workspace", C.c_void_p)])
+
+
 RBD_STAGE, RBD_IMPULSE = 0, 1
 RBD_SCORE_MAX_WINDOW = 1024
 RBD_REDUCE_CHUNK = 1024      # IDOCP_RBD_REDUCE_CHUNK: samples per chunk of the fixed-order sums
@@ -390,6 +415,20 @@ def _proto(lib):
         f = getattr(lib, "idocp_rbd_lqr_backward" + form)
         f.argtypes = [vp, ci, ci, P(RbdLqrIO)]
         f.restype = ci
+    for form in ("", "_device"):
+        for name, args in (("idocp_rbd_objective_gradients", [vp, vp, ci, ci, ci, ci, P(RbdGradientIO)]),
+                           ("idocp_rbd_ilqr_step_torques", [vp, ci, ci, vp, vp, vp, vp]),
+                           ("idocp_rbd_ilqr_accept", [vp, ci, ci, P(RbdIlqrAcceptIO)]),
+                           ("idocp_rbd_ilqr_iterate", [vp, vp, ci, ci, c_int_p, cd, cd, vp, P(RbdIlqrIO), ci])):
+            f = getattr(lib, name + form)
+            f.argtypes = args
+            f.restype = ci
+    lib.idocp_rbd_objective_lqr_weights_device.argtypes = [vp, P(vp), P(vp), P(vp)]
+    lib.idocp_rbd_objective_lqr_weights_device.restype = ci
+    lib.idocp_rbd_objective_get_lqr_weights.argtypes = [vp, vp, vp, vp]
+    lib.idocp_rbd_objective_get_lqr_weights.restype = ci
+    lib.idocp_rbd_ilqr_workspace_bytes.argtypes = [vp, ci, ci]
+    lib.idocp_rbd_ilqr_workspace_bytes.restype = C.c_ulonglong
     for name, args in [
         ("idocp_ocp_set_contact_status_uniformly", [vp, P(ci), c_double_p]),
         ("idocp_ocp_set_solution", [vp, cs, c_double_p]),

@@ -7,8 +7,10 @@
 
 #include <climits>
 #include <cmath>
+#include <cstdint>
 #include <cstring>
 #include <string>
+#include <vector>
 
 #include "hip_try.hpp"
 #include "host_util.hpp"
@@ -61,6 +63,8 @@ struct idocp_rbd_objective {
   idocp_host::RbdObjectivePlan plan;
   double *d_q_ref = nullptr, *d_v_ref = nullptr;      // [steps + 1][nq], [steps + 1][nv]
   idocp_host::RbdScoreBlock* d_block = nullptr;
+  std::vector<double> lqr_weights;                    // idocp_host::lqrWeights: [x_weight | u_weight | xf_weight], and the same bits behind the block
+  double* d_lqr_weights = nullptr;
 };
 
 namespace {
@@ -605,6 +609,167 @@ int launchLqr(idocp_rbd* h, int n, int steps, const idocp_rbd_lqr_io_t& io) {
   return IDOCP_OK;
 }
 
+// ---- gradients of an objective, the line-search step of iLQR, one iteration ----
+
+// everything that is refused, and the kernel's arguments but for the five array pointers of io
+int checkGradients(const char* who, const idocp_rbd* h, const idocp_rbd_objective* o, int n, int first_step, int steps, int terminal,
+                   const idocp_rbd_gradient_io_t* io, RbdGradientArgs* a) {
+  const std::string w(who);
+  if (!h || !o || !io) { set_last_error(w + ": null handle, objective or io"); return IDOCP_E_ARG; }
+  if (o->owner != h) { set_last_error(w + ": the objective was created on another handle"); return IDOCP_E_ARG; }
+  const idocp_host::RbdGradientCall c = idocp_host::planGradientCall(who, o->plan, n, first_step, steps, terminal, io->q_traj, io->v_traj, io->u_traj,
+                                                                     io->lx_traj, io->lu_traj);
+  if (c.rc) { set_last_error(c.error); return c.rc; }
+  a->q_ref = o->d_q_ref + (size_t)first_step * o->plan.nq;
+  a->v_ref = o->d_v_ref + (size_t)first_step * o->plan.nv;
+  a->block = o->d_block;
+  a->n = n; a->steps = steps; a->terminal = terminal != 0;
+  return IDOCP_OK;
+}
+
+int checkLqrWeights(const char* who, const idocp_rbd_objective* o) {
+  const std::string w(who);
+  if (!o) { set_last_error(w + ": null objective"); return IDOCP_E_ARG; }
+  const std::string unsupported = idocp_host::gradientUnsupported(o->plan);
+  if (!unsupported.empty()) { set_last_error(w + ": " + unsupported); return IDOCP_E_UNSUPPORTED; }
+  return IDOCP_OK;
+}
+
+int checkStepTorques(const char* who, const idocp_rbd* h, int n, int steps, const double* u, const double* k, const double* alpha, const double* out) {
+  const std::string w(who);
+  if (!h) { set_last_error(w + ": null handle"); return IDOCP_E_ARG; }
+  if (n <= 0) { set_last_error(w + ": n must be positive"); return IDOCP_E_ARG; }
+  if (steps < 1) { set_last_error(w + ": steps must be at least 1"); return IDOCP_E_ARG; }
+  if (!u || !k || !alpha || !out) { set_last_error(w + ": u_traj, k_traj, alpha and u_ff are needed"); return IDOCP_E_ARG; }
+  return IDOCP_OK;
+}
+
+int checkAccept(const char* who, const idocp_rbd* h, int n, int steps, const idocp_rbd_ilqr_accept_io_t* io) {
+  const std::string w(who);
+  if (!h || !io) { set_last_error(w + ": null handle or io"); return IDOCP_E_ARG; }
+  if (n <= 0) { set_last_error(w + ": n must be positive"); return IDOCP_E_ARG; }
+  if (steps < 1) { set_last_error(w + ": steps must be at least 1"); return IDOCP_E_ARG; }
+  if (!io->q_traj || !io->v_traj || !io->u_traj || !io->trial_q || !io->trial_v || !io->trial_u) {
+    set_last_error(w + ": q_traj, v_traj, u_traj and their trial arrays are needed"); return IDOCP_E_ARG;
+  }
+  if (!io->cost || !io->violation || !io->trial_cost || !io->trial_violation) {
+    set_last_error(w + ": cost, violation, trial_cost and trial_violation are needed"); return IDOCP_E_ARG;
+  }
+  if (!io->expected || !io->alpha || !io->done || !io->alpha_accepted) { set_last_error(w + ": expected, alpha, done and alpha_accepted are needed"); return IDOCP_E_ARG; }
+  const double values[4] = {io->penalty, io->armijo, io->shrink, io->alpha_min};
+  const char* const names[4] = {"penalty", "armijo", "shrink", "alpha_min"};
+  for (int i = 0; i < 4; ++i)
+    if (!std::isfinite(values[i]) || values[i] < 0.0) { set_last_error(w + ": " + names[i] + " must be finite and non-negative"); return IDOCP_E_ARG; }
+  return IDOCP_OK;
+}
+
+// io: device pointers
+int launchAccept(idocp_rbd* h, int n, int steps, const idocp_rbd_ilqr_accept_io_t& io) {
+  RbdIlqrAcceptArgs a;
+  double* const dst[5] = {io.q_traj, io.v_traj, io.u_traj, io.a_traj, io.f_traj};
+  const double* const src[5] = {io.trial_q, io.trial_v, io.trial_u, io.trial_a, io.trial_f};
+  const int width[5] = {h->model.nq, h->model.nv, h->model.nu, h->model.nv, 3 * h->model.ncontacts};
+  for (int c = 0; c < 5; ++c) { a.dst[c] = dst[c]; a.src[c] = src[c]; a.width[c] = width[c]; }
+  a.cost = io.cost; a.violation = io.violation; a.alpha = io.alpha; a.alpha_accepted = io.alpha_accepted;
+  a.trial_cost = io.trial_cost; a.trial_violation = io.trial_violation; a.expected = io.expected; a.done = io.done;
+  a.penalty = io.penalty; a.armijo = io.armijo; a.shrink = io.shrink; a.alpha_min = io.alpha_min;
+  a.n = n; a.steps = steps; a.wide = 0;
+  rbdIlqrAccept(a, h->stream);
+  HIP_TRY(hipGetLastError());
+  return IDOCP_OK;
+}
+
+// The workspace of one iteration (include/idocp_hip.h names the order): offsets in doubles, each piece at an even number of doubles.
+struct IlqrWorkspace {
+  size_t A, B, lx, lu, K, k, u_ff, q, v, u, a, f, cost, violation, alpha, done, total;
+};
+IlqrWorkspace ilqrWorkspace(const idocp_rbd* h, int n, int steps) {
+  const size_t nq = h->model.nq, nv = h->model.nv, nu = h->model.nu, nf = 3 * (size_t)h->model.ncontacts, N = (size_t)n, S = (size_t)steps, nx = 2 * nv;
+  IlqrWorkspace w;
+  size_t at = 0;
+  auto piece = [&](size_t doubles) { const size_t here = at; at += (doubles + 1) / 2 * 2; return here; };
+  w.A = piece(S * N * nx * nx); w.B = piece(S * N * nx * nu); w.lx = piece((S + 1) * N * nx); w.lu = piece(S * N * nu);
+  w.K = piece(S * N * nx * nu); w.k = piece(S * N * nu); w.u_ff = piece(S * N * nu);
+  w.q = piece((S + 1) * N * nq); w.v = piece((S + 1) * N * nv); w.u = piece(S * N * nu); w.a = piece(S * N * nv); w.f = piece(S * N * nf);
+  w.cost = piece(N); w.violation = piece(N); w.alpha = piece(N); w.done = piece((N + 1) / 2);
+  w.total = at;
+  return w;
+}
+
+int checkIterate(const char* who, const idocp_rbd* h, const idocp_rbd_objective* o, int n, int steps, const idocp_rbd_ilqr_io_t* io, bool host) {
+  const std::string w(who);
+  if (!h || !o || !io) { set_last_error(w + ": null handle, objective or io"); return IDOCP_E_ARG; }
+  if (o->owner != h) { set_last_error(w + ": the objective was created on another handle"); return IDOCP_E_ARG; }
+  int rc = checkLqrWeights(who, o); if (rc) return rc;
+  if (n <= 0) { set_last_error(w + ": n must be positive"); return IDOCP_E_ARG; }
+  if (steps < 1) { set_last_error(w + ": steps must be at least 1"); return IDOCP_E_ARG; }
+  if (steps > o->plan.steps) { set_last_error(w + ": steps must lie within the objective's " + std::to_string(o->plan.steps) + " steps"); return IDOCP_E_ARG; }
+  if (!io->q_traj || !io->v_traj || !io->u_traj) { set_last_error(w + ": q_traj, v_traj and u_traj are needed"); return IDOCP_E_ARG; }
+  if (!io->cost || !io->violation) { set_last_error(w + ": cost and violation are needed"); return IDOCP_E_ARG; }
+  if (!io->alpha_accepted || !io->lqr_status || !io->expected) { set_last_error(w + ": alpha_accepted, lqr_status and expected are needed"); return IDOCP_E_ARG; }
+  if (io->trials < 1) { set_last_error(w + ": trials must be at least 1"); return IDOCP_E_ARG; }
+  const double values[5] = {io->regularization, io->armijo, io->shrink, io->alpha_min, io->penalty};
+  const char* const names[5] = {"regularization", "armijo", "shrink", "alpha_min", "penalty"};
+  for (int i = 0; i < 5; ++i)
+    if (!std::isfinite(values[i]) || values[i] < 0.0) { set_last_error(w + ": " + names[i] + " must be finite and non-negative"); return IDOCP_E_ARG; }
+  if (!host && !io->workspace) { set_last_error(w + ": the workspace is needed (idocp_rbd_ilqr_workspace_bytes)"); return IDOCP_E_ARG; }
+  if (!host && (reinterpret_cast<uintptr_t>(io->workspace) & 15u)) { set_last_error(w + ": the workspace must be 16-byte aligned"); return IDOCP_E_ARG; }
+  return IDOCP_OK;
+}
+
+// io: device pointers; ws: the workspace.  The chain of include/idocp_hip.h; every call on the handle's stream, no synchronisation, no host read.
+int iterateDevice(idocp_rbd* h, const idocp_rbd_objective* o, int n, int steps, const int* active, double time_step, double dt,
+                  const double* contact_points, const idocp_rbd_ilqr_io_t& io, double* ws, int touchdown_impulse) {
+  const size_t nq = h->model.nq, nv = h->model.nv, nu = h->model.nu, nf = 3 * (size_t)h->model.ncontacts, N = (size_t)n;
+  const IlqrWorkspace w = ilqrWorkspace(h, n, steps);
+  double *A = ws + w.A, *B = ws + w.B, *lx = ws + w.lx, *lu = ws + w.lu, *K = ws + w.K, *kff = ws + w.k, *u_ff = ws + w.u_ff;
+  double *qt = ws + w.q, *vt = ws + w.v, *ut = ws + w.u, *at = ws + w.a, *ft = nf ? ws + w.f : nullptr;
+  double *cost_t = ws + w.cost, *violation_t = ws + w.violation, *alpha = ws + w.alpha;
+  int* done = reinterpret_cast<int*>(ws + w.done);
+  int rc = idocp_rbd_linearize_rollout_device(h, n, steps, active, time_step, dt, io.u_traj, contact_points, io.q_traj, io.v_traj, A, B, touchdown_impulse);
+  if (rc) return rc;
+  idocp_rbd_gradient_io_t g = idocp_rbd_gradient_io_t();
+  g.q_traj = io.q_traj; g.v_traj = io.v_traj; g.u_traj = io.u_traj; g.lx_traj = lx; g.lu_traj = lu;
+  rc = idocp_rbd_objective_gradients_device(h, o, n, 0, steps, 1, &g); if (rc) return rc;
+  idocp_rbd_lqr_io_t lqr = idocp_rbd_lqr_io_t();
+  lqr.A_traj = A; lqr.B_traj = B; lqr.lx_traj = lx; lqr.lu_traj = lu; lqr.regularization = io.regularization;
+  rc = idocp_rbd_objective_lqr_weights_device(o, &lqr.x_weight, &lqr.u_weight, &lqr.xf_weight); if (rc) return rc;
+  lqr.K_traj = K; lqr.k_traj = kff; lqr.expected = io.expected; lqr.status = io.lqr_status;
+  rc = idocp_rbd_lqr_backward_device(h, n, steps, &lqr); if (rc) return rc;
+  rbdIlqrInit(alpha, done, io.alpha_accepted, n, h->stream);
+  HIP_TRY(hipGetLastError());
+  // every trial starts from the state the rollout started from
+  HIP_TRY(hipMemcpyAsync(qt, io.q_traj, sizeof(double) * N * nq, hipMemcpyDeviceToDevice, h->stream));
+  HIP_TRY(hipMemcpyAsync(vt, io.v_traj, sizeof(double) * N * nv, hipMemcpyDeviceToDevice, h->stream));
+  idocp_rbd_policy_t pol = idocp_rbd_policy_t();
+  pol.u_ff = u_ff; pol.K = K; pol.q_ref = io.q_traj; pol.v_ref = io.v_traj; pol.u_min = io.u_min; pol.u_max = io.u_max;
+  idocp_rbd_ilqr_accept_io_t acc = idocp_rbd_ilqr_accept_io_t();
+  acc.q_traj = io.q_traj; acc.v_traj = io.v_traj; acc.u_traj = io.u_traj; acc.a_traj = io.a_traj; acc.f_traj = io.f_traj;
+  acc.cost = io.cost; acc.violation = io.violation;
+  acc.trial_q = qt; acc.trial_v = vt; acc.trial_u = ut; acc.trial_a = at; acc.trial_f = ft;
+  acc.trial_cost = cost_t; acc.trial_violation = violation_t; acc.expected = io.expected; acc.alpha = alpha; acc.done = done;
+  acc.alpha_accepted = io.alpha_accepted;
+  acc.penalty = io.penalty; acc.armijo = io.armijo; acc.shrink = io.shrink; acc.alpha_min = io.alpha_min;
+  // A sample accepted in an early round is rolled out again in the later rounds, about the trajectory it now holds, and that trial is ignored
+  // (done[i] != 0): simpler than compacting the batch, and the stream stays free of host decisions.
+  for (int round = 0; round < io.trials; ++round) {
+    rc = idocp_rbd_ilqr_step_torques_device(h, n, steps, io.u_traj, kff, alpha, u_ff); if (rc) return rc;
+    rc = idocp_rbd_rollout_policy_device(h, n, steps, active, time_step, dt, &pol, contact_points, qt, vt, ut, at, ft, touchdown_impulse); if (rc) return rc;
+    for (int first = 0; first < steps; first += IDOCP_RBD_SCORE_MAX_WINDOW) {      // (the windows of the header, with accumulate)
+      const int window = steps - first < IDOCP_RBD_SCORE_MAX_WINDOW ? steps - first : IDOCP_RBD_SCORE_MAX_WINDOW;
+      idocp_rbd_score_io_t sc = idocp_rbd_score_io_t();
+      sc.q_traj = qt + first * N * nq; sc.v_traj = vt + first * N * nv; sc.u_traj = ut + first * N * nu; sc.a_traj = at + first * N * nv;
+      sc.f_traj = ft ? ft + first * N * nf : nullptr;
+      sc.cost = cost_t; sc.violation = violation_t;
+      rc = idocp_rbd_score_rollout_device(h, o, n, first, window, active ? active + (size_t)first * h->model.ncontacts : nullptr,
+                                          first + window == steps, first > 0, &sc);
+      if (rc) return rc;
+    }
+    rc = launchAccept(h, n, steps, acc); if (rc) return rc;
+  }
+  return IDOCP_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -953,13 +1118,18 @@ int idocp_rbd_objective_create(idocp_rbd_t* h, const idocp_cost_t* cost, const i
   const size_t nq_tab = (o->plan.q_ref.size() + 1) / 2 * 2, nv_tab = (o->plan.v_ref.size() + 1) / 2 * 2;      // (16-byte pieces)
   auto fail = [&](const char* what) { set_last_error(what); (void)hipGetLastError(); idocp_rbd_objective_destroy(o); return IDOCP_E_DEVICE; };
   if (hipSetDevice(h->device) != hipSuccess) return fail("idocp_rbd_objective_create: hipSetDevice failed");
-  if (hipMalloc(reinterpret_cast<void**>(&o->d_q_ref), sizeof(double) * (nq_tab + nv_tab) + sizeof(idocp_host::RbdScoreBlock)) != hipSuccess)
+  o->lqr_weights.resize((size_t)idocp_host::lqrWeightDoubles(o->plan));
+  idocp_host::lqrWeights(o->plan, o->lqr_weights.data());
+  const size_t block_bytes = (sizeof(idocp_host::RbdScoreBlock) + 15) / 16 * 16;
+  if (hipMalloc(reinterpret_cast<void**>(&o->d_q_ref), sizeof(double) * (nq_tab + nv_tab + o->lqr_weights.size()) + block_bytes) != hipSuccess)
     return fail("idocp_rbd_objective_create: hipMalloc of the objective failed");
   o->d_v_ref = o->d_q_ref + nq_tab;
   o->d_block = reinterpret_cast<idocp_host::RbdScoreBlock*>(o->d_v_ref + nv_tab);
+  o->d_lqr_weights = reinterpret_cast<double*>(reinterpret_cast<char*>(o->d_block) + block_bytes);
   if (hipMemcpyAsync(o->d_q_ref, o->plan.q_ref.data(), sizeof(double) * o->plan.q_ref.size(), hipMemcpyHostToDevice, h->stream) != hipSuccess ||
       hipMemcpyAsync(o->d_v_ref, o->plan.v_ref.data(), sizeof(double) * o->plan.v_ref.size(), hipMemcpyHostToDevice, h->stream) != hipSuccess ||
       hipMemcpyAsync(o->d_block, &o->plan.block, sizeof(idocp_host::RbdScoreBlock), hipMemcpyHostToDevice, h->stream) != hipSuccess ||
+      hipMemcpyAsync(o->d_lqr_weights, o->lqr_weights.data(), sizeof(double) * o->lqr_weights.size(), hipMemcpyHostToDevice, h->stream) != hipSuccess ||
       hipStreamSynchronize(h->stream) != hipSuccess) return fail("idocp_rbd_objective_create: upload of the objective failed");
   *out = o;
   return IDOCP_OK;
@@ -1122,6 +1292,168 @@ int idocp_rbd_lqr_backward(idocp_rbd_t* h, int n, int steps, const idocp_rbd_lqr
   d.status = reinterpret_cast<int*>(d_status);
   rc = launchLqr(h, n, steps, d); if (rc) return rc;
   if (io->status) HIP_TRY(hipMemcpyAsync(io->status, d_status, sizeof(int) * N, hipMemcpyDeviceToHost, h->stream));
+  return stageOut(h, p);
+}
+
+int idocp_rbd_objective_gradients_device(idocp_rbd_t* h, const idocp_rbd_objective_t* o, int n, int first_step, int steps, int terminal,
+                                         const idocp_rbd_gradient_io_t* io) {
+  RbdGradientArgs a;
+  int rc = checkGradients("idocp_rbd_objective_gradients_device", h, o, n, first_step, steps, terminal, io, &a); if (rc) return rc;
+  HIP_TRY(hipSetDevice(h->device));
+  a.q = io->q_traj; a.v = io->v_traj; a.u = io->u_traj; a.lx = io->lx_traj; a.lu = io->lu_traj;
+  rbdGradient(h->model.nv, h->quadruped, a, h->stream);
+  HIP_TRY(hipGetLastError());
+  return IDOCP_OK;
+}
+
+int idocp_rbd_objective_gradients(idocp_rbd_t* h, const idocp_rbd_objective_t* o, int n, int first_step, int steps, int terminal,
+                                  const idocp_rbd_gradient_io_t* io) {
+  RbdGradientArgs a;
+  int rc = checkGradients("idocp_rbd_objective_gradients", h, o, n, first_step, steps, terminal, io, &a); if (rc) return rc;
+  HIP_TRY(hipSetDevice(h->device));
+  const size_t nq = h->model.nq, nv = h->model.nv, nu = h->model.nu, N = (size_t)n, S = (size_t)steps, slices = S + (terminal ? 1 : 0);
+  StagePlan p;
+  p.in(io->q_traj, slices * N * nq, &a.q);
+  p.in(io->v_traj, slices * N * nv, &a.v);
+  p.in(io->u_traj, S * N * nu, &a.u);
+  p.out(io->lx_traj, slices * N * 2 * nv, &a.lx);
+  p.out(io->lu_traj, S * N * nu, &a.lu);
+  rc = stageIn(h, p); if (rc) return rc;
+  rbdGradient(h->model.nv, h->quadruped, a, h->stream);
+  HIP_TRY(hipGetLastError());
+  return stageOut(h, p);
+}
+
+int idocp_rbd_objective_lqr_weights_device(const idocp_rbd_objective_t* o, const double** d_x_weight, const double** d_u_weight,
+                                           const double** d_xf_weight) {
+  int rc = checkLqrWeights("idocp_rbd_objective_lqr_weights_device", o); if (rc) return rc;
+  if (d_x_weight) *d_x_weight = o->d_lqr_weights;
+  if (d_u_weight) *d_u_weight = o->d_lqr_weights + idocp_host::lqrWeightOffsetU(o->plan);
+  if (d_xf_weight) *d_xf_weight = o->d_lqr_weights + idocp_host::lqrWeightOffsetXf(o->plan);
+  return IDOCP_OK;
+}
+
+int idocp_rbd_objective_get_lqr_weights(const idocp_rbd_objective_t* o, double* x_weight, double* u_weight, double* xf_weight) {
+  int rc = checkLqrWeights("idocp_rbd_objective_get_lqr_weights", o); if (rc) return rc;
+  const double* w = o->lqr_weights.data();
+  if (x_weight) std::memcpy(x_weight, w, sizeof(double) * 2 * o->plan.nv);
+  if (u_weight) std::memcpy(u_weight, w + idocp_host::lqrWeightOffsetU(o->plan), sizeof(double) * o->plan.nu);
+  if (xf_weight) std::memcpy(xf_weight, w + idocp_host::lqrWeightOffsetXf(o->plan), sizeof(double) * 2 * o->plan.nv);
+  return IDOCP_OK;
+}
+
+int idocp_rbd_ilqr_step_torques_device(idocp_rbd_t* h, int n, int steps, const double* u_traj, const double* k_traj, const double* alpha,
+                                       double* u_ff) {
+  int rc = checkStepTorques("idocp_rbd_ilqr_step_torques_device", h, n, steps, u_traj, k_traj, alpha, u_ff); if (rc) return rc;
+  HIP_TRY(hipSetDevice(h->device));
+  rbdIlqrStepTorques(u_traj, k_traj, alpha, u_ff, n, steps, h->model.nu, h->stream);
+  HIP_TRY(hipGetLastError());
+  return IDOCP_OK;
+}
+
+int idocp_rbd_ilqr_step_torques(idocp_rbd_t* h, int n, int steps, const double* u_traj, const double* k_traj, const double* alpha, double* u_ff) {
+  int rc = checkStepTorques("idocp_rbd_ilqr_step_torques", h, n, steps, u_traj, k_traj, alpha, u_ff); if (rc) return rc;
+  HIP_TRY(hipSetDevice(h->device));
+  const size_t count = (size_t)steps * n * h->model.nu;
+  StagePlan p;
+  const double *d_u, *d_k, *d_alpha;
+  double* d_out;
+  p.in(u_traj, count, &d_u);
+  p.in(k_traj, count, &d_k);
+  p.in(alpha, (size_t)n, &d_alpha);
+  p.out(u_ff, count, &d_out);
+  rc = stageIn(h, p); if (rc) return rc;
+  rbdIlqrStepTorques(d_u, d_k, d_alpha, d_out, n, steps, h->model.nu, h->stream);
+  HIP_TRY(hipGetLastError());
+  return stageOut(h, p);
+}
+
+int idocp_rbd_ilqr_accept_device(idocp_rbd_t* h, int n, int steps, const idocp_rbd_ilqr_accept_io_t* io) {
+  int rc = checkAccept("idocp_rbd_ilqr_accept_device", h, n, steps, io); if (rc) return rc;
+  HIP_TRY(hipSetDevice(h->device));
+  return launchAccept(h, n, steps, *io);
+}
+
+int idocp_rbd_ilqr_accept(idocp_rbd_t* h, int n, int steps, const idocp_rbd_ilqr_accept_io_t* io) {
+  int rc = checkAccept("idocp_rbd_ilqr_accept", h, n, steps, io); if (rc) return rc;
+  HIP_TRY(hipSetDevice(h->device));
+  const size_t nq = h->model.nq, nv = h->model.nv, nu = h->model.nu, nf = 3 * (size_t)h->model.ncontacts, N = (size_t)n, S = (size_t)steps;
+  StagePlan p;
+  idocp_rbd_ilqr_accept_io_t d = *io;
+  double* d_done = nullptr;
+  const bool with_a = io->a_traj && io->trial_a, with_f = io->f_traj && io->trial_f;
+  p.update(io->q_traj, (S + 1) * N * nq, &d.q_traj);
+  p.update(io->v_traj, (S + 1) * N * nv, &d.v_traj);
+  p.update(io->u_traj, S * N * nu, &d.u_traj);
+  p.update(with_a ? io->a_traj : nullptr, S * N * nv, &d.a_traj);
+  p.update(with_f ? io->f_traj : nullptr, S * N * nf, &d.f_traj);
+  p.update(io->cost, N, &d.cost);
+  p.update(io->violation, N, &d.violation);
+  p.in(io->trial_q, (S + 1) * N * nq, &d.trial_q);
+  p.in(io->trial_v, (S + 1) * N * nv, &d.trial_v);
+  p.in(io->trial_u, S * N * nu, &d.trial_u);
+  p.in(with_a ? io->trial_a : nullptr, S * N * nv, &d.trial_a);
+  p.in(with_f ? io->trial_f : nullptr, S * N * nf, &d.trial_f);
+  p.in(io->trial_cost, N, &d.trial_cost);
+  p.in(io->trial_violation, N, &d.trial_violation);
+  p.in(io->expected, 2 * N, &d.expected);
+  p.update(io->alpha, N, &d.alpha);
+  p.update(io->alpha_accepted, N, &d.alpha_accepted);
+  p.deviceOnly((N + 1) / 2, &d_done);      // (n ints in a slot of doubles; they travel by copies of their own)
+  rc = stageIn(h, p); if (rc) return rc;
+  d.done = reinterpret_cast<int*>(d_done);
+  HIP_TRY(hipMemcpyAsync(d.done, io->done, sizeof(int) * N, hipMemcpyHostToDevice, h->stream));
+  rc = launchAccept(h, n, steps, d); if (rc) return rc;
+  HIP_TRY(hipMemcpyAsync(io->done, d.done, sizeof(int) * N, hipMemcpyDeviceToHost, h->stream));
+  return stageOut(h, p);
+}
+
+unsigned long long idocp_rbd_ilqr_workspace_bytes(const idocp_rbd_t* h, int n, int steps) {
+  if (!h || n <= 0 || steps < 1) return 0;
+  return sizeof(double) * (unsigned long long)ilqrWorkspace(h, n, steps).total;
+}
+
+int idocp_rbd_ilqr_iterate_device(idocp_rbd_t* h, const idocp_rbd_objective_t* o, int n, int steps, const int* active, double time_step, double dt,
+                                  const double* contact_points, const idocp_rbd_ilqr_io_t* io, int touchdown_impulse) {
+  int rc = checkIterate("idocp_rbd_ilqr_iterate_device", h, o, n, steps, io, false); if (rc) return rc;
+  HIP_TRY(hipSetDevice(h->device));
+  return iterateDevice(h, o, n, steps, active, time_step, dt, contact_points, *io, static_cast<double*>(io->workspace), touchdown_impulse);
+}
+
+int idocp_rbd_ilqr_iterate(idocp_rbd_t* h, const idocp_rbd_objective_t* o, int n, int steps, const int* active, double time_step, double dt,
+                           const double* contact_points, const idocp_rbd_ilqr_io_t* io, int touchdown_impulse) {
+  const char* who = "idocp_rbd_ilqr_iterate";
+  int rc = checkIterate(who, h, o, n, steps, io, true); if (rc) return rc;
+  {      // (the bounds are host memory here and can be looked at)
+    idocp_rbd_policy_t bounds = idocp_rbd_policy_t();
+    bounds.u_min = io->u_min; bounds.u_max = io->u_max;
+    rc = checkPolicy(who, h, &bounds, true); if (rc) return rc;
+  }
+  if (h->quadruped && !contact_points) { set_last_error(std::string(who) + ": contact_points are needed"); return IDOCP_E_ARG; }
+  HIP_TRY(hipSetDevice(h->device));
+  const size_t nq = h->model.nq, nv = h->model.nv, nu = h->model.nu, nf = 3 * (size_t)h->model.ncontacts, N = (size_t)n, S = (size_t)steps;
+  StagePlan p;
+  idocp_rbd_ilqr_io_t d = *io;
+  const double* d_points;
+  double *d_status = nullptr, *d_ws = nullptr;
+  p.update(io->q_traj, (S + 1) * N * nq, &d.q_traj);
+  p.update(io->v_traj, (S + 1) * N * nv, &d.v_traj);
+  p.update(io->u_traj, S * N * nu, &d.u_traj);
+  p.update(io->a_traj, S * N * nv, &d.a_traj);
+  p.update(io->f_traj, S * N * nf, &d.f_traj);
+  p.update(io->cost, N, &d.cost);
+  p.update(io->violation, N, &d.violation);
+  p.in(io->u_min, nu, &d.u_min);
+  p.in(io->u_max, nu, &d.u_max);
+  p.in(contact_points, S * N * nf, &d_points);
+  p.out(io->alpha_accepted, N, &d.alpha_accepted);
+  p.out(io->expected, 2 * N, &d.expected);
+  p.deviceOnly((N + 1) / 2, &d_status);
+  p.deviceOnly(ilqrWorkspace(h, n, steps).total, &d_ws);
+  rc = stageIn(h, p); if (rc) return rc;
+  d.lqr_status = reinterpret_cast<int*>(d_status);
+  rc = iterateDevice(h, o, n, steps, active, time_step, dt, d_points, d, d_ws, touchdown_impulse); if (rc) return rc;
+  HIP_TRY(hipMemcpyAsync(io->lqr_status, d_status, sizeof(int) * N, hipMemcpyDeviceToHost, h->stream));
   return stageOut(h, p);
 }
 

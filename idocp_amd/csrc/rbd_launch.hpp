@@ -119,5 +119,40 @@ struct RbdLqrArgs {
 };
 void rbdLqrBackward(bool quadruped, const RbdLqrArgs& a, hipStream_t st);
 
+// Gradients of an objective along a rollout (rbd_gradient_kernel.hip; the arrays of idocp_rbd_gradient_io_t).  Every pointer: DEVICE memory;
+// q, v [steps (+ 1 if terminal)][n][..], u [steps][n][nu] or NULL, q_ref / v_ref the objective's tables AT the window's first step, block its
+// weights; lx [steps (+ 1)][n][2 nv] and lu [steps][n][nu], either may be NULL.  (steps + 1) * n fits an int.  One wavefront per
+// RBD_GRADIENT_ITEMS consecutive (slice, sample) pairs, any n.  One launch.
+constexpr int RBD_GRADIENT_ITEMS = 64;
+struct RbdGradientArgs {
+  const double *q, *v, *u, *q_ref, *v_ref;
+  const idocp_host::RbdScoreBlock* block;
+  double *lx, *lu;
+  int n, steps, terminal;
+};
+void rbdGradient(int nv, bool quadruped, const RbdGradientArgs& a, hipStream_t st);
+
+// The line-search step of iLQR (rbd_ilqr_kernel.hip).  Every pointer: DEVICE memory.
+// out [steps][n][nu] = u + alpha[i] k, alpha [n]; alpha[i] == 0 gives u bit for bit.  One launch.
+void rbdIlqrStepTorques(const double* u, const double* k, const double* alpha, double* out, int n, int steps, int nu, hipStream_t st);
+// The acceptance test per sample and the copy of the accepted samples' slices (idocp_rbd_ilqr_accept_io_t).  dst / src / width: the current and
+// the trial array and the doubles per sample and slice of q, v (steps + 1 slices), u, a, f (steps slices); a pair with a NULL pointer or width 0 is
+// left out.  A workgroup owns RBD_ILQR_GROUP consecutive samples.  One launch.
+constexpr int RBD_ILQR_GROUP = 32;
+struct RbdIlqrAcceptArgs {
+  double* dst[5];
+  const double* src[5];
+  int width[5];
+  double *cost, *violation, *alpha, *alpha_accepted;
+  const double *trial_cost, *trial_violation, *expected;
+  int* done;
+  double penalty, armijo, shrink, alpha_min;
+  int n, steps;
+  int wide;      // set by the launcher: bit c = both pointers of pair c are 16-byte aligned
+};
+void rbdIlqrAccept(RbdIlqrAcceptArgs a, hipStream_t st);
+// alpha [n] = 1, done [n] = 0, alpha_accepted [n] = 0: the start of the rounds of one iteration.  One launch.
+void rbdIlqrInit(double* alpha, int* done, double* alpha_accepted, int n, hipStream_t st);
+
 }  // namespace idocp_dev
 #endif  // IDOCP_RBD_LAUNCH_HPP_

@@ -2,7 +2,8 @@
 // configuration-space reference of every step by the solvers' own rules (cost_reference.hpp), the packed block of weights, bounds and switches the
 // kernel reads (rbd_score_kernel.hip), the per-step contact masks of a call, and every refusal.  Plain C++17: this header includes no HIP runtime
 // header (a CPU program defines IDOCP_NO_HIP_RUNTIME so that dev_lie.hpp brings none either; tests/cpp/rbd_objective_plan.cpp), rbd_capi.hip
-// uploads what it plans.
+// uploads what it plans.  The same objective serves idocp_rbd_objective_gradients and the LQR weight tables (planGradientCall, lqrWeights, at the
+// end; tests/cpp/rbd_gradient_plan.cpp).
 #ifndef IDOCP_RBD_OBJECTIVE_HPP_
 #define IDOCP_RBD_OBJECTIVE_HPP_
 
@@ -159,6 +160,56 @@ inline RbdScoreCall planScoreCall(const char* who_, const RbdObjectivePlan& o, i
     c.masks[k / 8] |= m << (4 * (k % 8));
   }
   return c;
+}
+
+// What idocp_rbd_objective_gradients and the LQR weights cannot carry (include/idocp_hip.h says why): "" when the objective is fine, else the
+// text that names the term.
+inline std::string gradientUnsupported(const RbdObjectivePlan& o) {
+  using namespace rbd_objective_detail;
+  if (anyNonZero(o.block.a_weight, o.nv))
+    return "a non-zero a_weight: the gradient of the acceleration term needs da/dx, and its Hessian does not fit a diagonal x_weight / u_weight";
+  if (o.ncontacts && anyNonZero(&o.block.f_weight[0][0], 3 * IDOCP_MAX_CONTACTS))
+    return "a non-zero f_weight: the gradient of the contact-force term needs df/dx, and its Hessian does not fit a diagonal x_weight / u_weight";
+  return "";
+}
+
+// One call of the gradients against a planned objective: everything that can be refused without looking at device memory.
+struct RbdGradientCall {
+  int rc = IDOCP_OK;
+  std::string error;
+};
+// have_*: the caller's pointer is not null
+inline RbdGradientCall planGradientCall(const char* who_, const RbdObjectivePlan& o, int n, int first_step, int steps, int terminal, bool have_q,
+                                        bool have_v, bool have_u, bool have_lx, bool have_lu) {
+  using namespace rbd_objective_detail;
+  RbdGradientCall c;
+  const std::string who = std::string(who_) + ": ";
+  auto refuse = [&](int rc, const std::string& what) { c.rc = rc; c.error = who + what; return c; };
+  const std::string unsupported = gradientUnsupported(o);
+  if (!unsupported.empty()) return refuse(IDOCP_E_UNSUPPORTED, unsupported);
+  if (n <= 0) return refuse(IDOCP_E_ARG, "n must be positive");
+  if (steps < 1) return refuse(IDOCP_E_ARG, "steps must be at least 1");
+  if (first_step < 0 || first_step > o.steps - steps)
+    return refuse(IDOCP_E_ARG, "first_step + steps must lie within the objective's " + std::to_string(o.steps) + " steps");
+  if (((long long)steps + (terminal ? 1 : 0)) * n > 2147483647LL) return refuse(IDOCP_E_ARG, "(steps + 1) * n must fit an int");
+  if (!have_q || !have_v) return refuse(IDOCP_E_ARG, "q_traj and v_traj are needed");
+  if (!have_u && anyNonZero(o.block.u_weight, o.nu)) return refuse(IDOCP_E_ARG, "u_traj is NULL but a non-zero u_weight reads it");
+  if (!have_lx && !have_lu) return refuse(IDOCP_E_ARG, "no output was asked for (lx_traj, lu_traj)");
+  return c;
+}
+
+// x_weight [2 nv] = dt [q_weight; v_weight], u_weight [nu] = dt u_weight, xf_weight [2 nv] = [qf_weight; vf_weight]: the diagonal weights
+// idocp_rbd_lqr_io_t reads, behind one another in `out` (lqrWeightDoubles of them), each piece at an even number of doubles
+inline int lqrWeightOffsetU(const RbdObjectivePlan& o) { return 2 * o.nv; }
+inline int lqrWeightOffsetXf(const RbdObjectivePlan& o) { return 2 * o.nv + (o.nu + 1) / 2 * 2; }
+inline int lqrWeightDoubles(const RbdObjectivePlan& o) { return lqrWeightOffsetXf(o) + 2 * o.nv; }
+inline void lqrWeights(const RbdObjectivePlan& o, double* out) {
+  const RbdScoreBlock& b = o.block;
+  const int nv = o.nv, nu = o.nu, iu = lqrWeightOffsetU(o), ixf = lqrWeightOffsetXf(o);
+  for (int i = 0; i < lqrWeightDoubles(o); ++i) out[i] = 0.0;
+  for (int r = 0; r < nv; ++r) { out[r] = b.dt * b.q_weight[r]; out[nv + r] = b.dt * b.v_weight[r]; }
+  for (int j = 0; j < nu; ++j) out[iu + j] = b.dt * b.u_weight[j];
+  for (int r = 0; r < nv; ++r) { out[ixf + r] = b.qf_weight[r]; out[ixf + nv + r] = b.vf_weight[r]; }
 }
 
 }  // namespace idocp_host

@@ -12,7 +12,7 @@ namespace idocp_host {
 
 struct StagePlan {
   struct Copy { double* host; size_t offset, count; };      // `count` doubles between host memory and base + offset
-  static constexpr int MAX_SLOTS = 16;                      // (the largest call, idocp_rbd_contact_dynamics_batch, declares 14)
+  static constexpr int MAX_SLOTS = 24;                      // (the largest call, idocp_rbd_ilqr_accept, declares 19)
   Copy up[MAX_SLOTS], down[MAX_SLOTS], zero[MAX_SLOTS];     // host to device; device to host; zero-filled before the launch (host: null)
   int n_up = 0, n_down = 0, n_zero = 0, n_slots = 0;
 

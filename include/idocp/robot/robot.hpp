@@ -356,6 +356,91 @@ class Robot {
     }
     return status < 0;
   }
+  // The gradients lx (N + 1 vectors of 2 nv, the last one of the terminal cost) and lu (N of nu) of the cost scoreTrajectory sums, along ONE stored
+  // trajectory, in the tangent [dq; dv] of forwardDynamicsDerivatives: what lqrGains takes as lx and lu.  An ADDITION: ONE n = 1 call of
+  // idocp_rbd_objective_gradients (idocp_hip.h has the definition) on the same lazily created handle.  The cost's a_weight and f_weight must be zero
+  // (the call says so otherwise); the constraints are not differentiated.
+  template <class CostFunctionT>
+  void costGradients(const CostFunctionT& cost, const double t0, const double dt, const std::vector<Eigen::VectorXd>& q,
+                     const std::vector<Eigen::VectorXd>& v, const std::vector<Eigen::VectorXd>& u, std::vector<Eigen::VectorXd>& lx,
+                     std::vector<Eigen::VectorXd>& lu) {
+    const int steps = (int)u.size(), nx = 2 * model_.nv;
+    if (steps < 1 || (int)q.size() != steps + 1 || (int)v.size() != steps + 1) {
+      std::cerr << "invalid size: a trajectory of N stages has N + 1 states q, v and N of u!" << '\n'; std::exit(EXIT_FAILURE);
+    }
+    const size_t nq = model_.nq, nv = model_.nv, nu = model_.nu;
+    std::vector<double> qs((steps + 1) * nq), vs((steps + 1) * nv), us(steps * nu), lxs((size_t)(steps + 1) * nx), lus(steps * nu);
+    for (int k = 0; k <= steps; ++k) {
+      sized(q[k], model_.nq, "q"); sized(v[k], model_.nv, "v");
+      for (size_t j = 0; j < nq; ++j) qs[k * nq + j] = q[k][j];
+      for (size_t j = 0; j < nv; ++j) vs[k * nv + j] = v[k][j];
+      if (k == steps) break;
+      sized(u[k], model_.nu, "u");
+      for (size_t j = 0; j < nu; ++j) us[k * nu + j] = u[k][j];
+    }
+    const idocp_cost_t c = cost.native();
+    if (!rbd_.h) ok(idocp_rbd_create(&model_, 0, &rbd_.h));
+    idocp_rbd_objective_t* objective = nullptr;
+    ok(idocp_rbd_objective_create(rbd_.h, &c, nullptr, t0, dt, steps, &objective));
+    idocp_rbd_gradient_io_t io = idocp_rbd_gradient_io_t();
+    io.q_traj = qs.data(); io.v_traj = vs.data(); io.u_traj = us.data(); io.lx_traj = lxs.data(); io.lu_traj = lus.data();
+    const int rc = idocp_rbd_objective_gradients(rbd_.h, objective, 1, 0, steps, 1, &io);
+    idocp_rbd_objective_destroy(objective);
+    ok(rc);
+    lx.assign(steps + 1, Eigen::VectorXd(nx)); lu.assign(steps, Eigen::VectorXd(model_.nu));
+    for (int k = 0; k <= steps; ++k) for (int j = 0; j < nx; ++j) lx[k][j] = lxs[(size_t)k * nx + j];
+    for (int k = 0; k < steps; ++k) for (size_t j = 0; j < nu; ++j) lu[k][j] = lus[k * nu + j];
+  }
+  // ONE iLQR iteration on ONE stored trajectory, in place, an ADDITION: idocp_rbd_ilqr_iterate with n = 1 (idocp_hip.h has the chain: linearise,
+  // gradients, backward pass with the cost's own weights and `regularization`, then up to `trials` closed-loop rollouts with the step alpha halved
+  // until the Armijo test with the factor `armijo` passes).  q, v (N + 1) and u (N) are the rollout of u from (q[0], v[0]) under contact_status with
+  // the contacts held at contact_points (idocp_rbd_rollout's convention: N entries of ncontacts points; empty on a fixed base), total_cost its score
+  // (scoreTrajectory).  Returns the step taken: 0 if none was accepted or the backward pass failed, and the trajectory is then left as it was.
+  template <class CostFunctionT>
+  double ilqrIterate(const CostFunctionT& cost, const double t0, const double dt, const double time_step, const std::vector<ContactStatus>& contact_status,
+                     const std::vector<std::vector<Eigen::Vector3d>>& contact_points, std::vector<Eigen::VectorXd>& q, std::vector<Eigen::VectorXd>& v,
+                     std::vector<Eigen::VectorXd>& u, double& total_cost, const double regularization = 1e-6, const double armijo = 1e-4,
+                     const int trials = 8) {
+    const int steps = (int)u.size(), nc = model_.ncontacts;
+    if (steps < 1 || (int)q.size() != steps + 1 || (int)v.size() != steps + 1 ||
+        (nc > 0 && ((int)contact_status.size() != steps || (int)contact_points.size() != steps))) {
+      std::cerr << "invalid size: a trajectory of N stages has N + 1 states q, v and N of u, contact_status and contact_points!" << '\n'; std::exit(EXIT_FAILURE);
+    }
+    const size_t nq = model_.nq, nv = model_.nv, nu = model_.nu;
+    std::vector<double> qs((steps + 1) * nq), vs((steps + 1) * nv), us(steps * nu), pts((size_t)steps * 3 * nc, 0.0);
+    std::vector<int> act((size_t)steps * nc, 0);
+    for (int k = 0; k <= steps; ++k) {
+      sized(q[k], model_.nq, "q"); sized(v[k], model_.nv, "v");
+      for (size_t j = 0; j < nq; ++j) qs[k * nq + j] = q[k][j];
+      for (size_t j = 0; j < nv; ++j) vs[k * nv + j] = v[k][j];
+      if (k == steps) break;
+      sized(u[k], model_.nu, "u");
+      for (size_t j = 0; j < nu; ++j) us[k * nu + j] = u[k][j];
+      for (int c = 0; c < nc; ++c) {
+        act[(size_t)k * nc + c] = contact_status[k].isContactActive(c) ? 1 : 0;
+        for (int x = 0; x < 3; ++x) pts[((size_t)k * nc + c) * 3 + x] = contact_points[k][c][x];
+      }
+    }
+    const idocp_cost_t c = cost.native();
+    if (!rbd_.h) ok(idocp_rbd_create(&model_, 0, &rbd_.h));
+    idocp_rbd_objective_t* objective = nullptr;
+    ok(idocp_rbd_objective_create(rbd_.h, &c, nullptr, t0, dt, steps, &objective));
+    double violation = 0.0, alpha = 0.0, expected[2] = {0.0, 0.0};
+    int status = -1;
+    idocp_rbd_ilqr_io_t io = idocp_rbd_ilqr_io_t();
+    io.q_traj = qs.data(); io.v_traj = vs.data(); io.u_traj = us.data(); io.cost = &total_cost; io.violation = &violation;
+    io.regularization = regularization; io.armijo = armijo; io.shrink = 0.5; io.alpha_min = 0.0; io.penalty = 0.0; io.trials = trials;
+    io.alpha_accepted = &alpha; io.lqr_status = &status; io.expected = expected;
+    const int rc = idocp_rbd_ilqr_iterate(rbd_.h, objective, 1, steps, nc > 0 ? act.data() : nullptr, time_step, dt, nc > 0 ? pts.data() : nullptr, &io, 0);
+    idocp_rbd_objective_destroy(objective);
+    ok(rc);
+    for (int k = 0; k <= steps; ++k) {
+      for (size_t j = 0; j < nq; ++j) q[k][j] = qs[k * nq + j];
+      for (size_t j = 0; j < nv; ++j) v[k][j] = vs[k * nv + j];
+      if (k < steps) for (size_t j = 0; j < nu; ++j) u[k][j] = us[k * nu + j];
+    }
+    return alpha;
+  }
   // Robot::framePosition / frameRotation / framePlacement (robot.hxx:206-233): of any frame of the URDF (pinocchio's frame numbering, as the
   // contact frames and the task-space costs use it), at the configuration of the last updateFrameKinematics / updateKinematics
   Eigen::Vector3d framePosition(const int frame_id) const { return framePlacement(frame_id).translation(); }

@@ -1087,6 +1087,112 @@ int idocp_rbd_score_rollout(idocp_rbd_t* h, const idocp_rbd_objective_t* o, int 
 int idocp_rbd_score_rollout_device(idocp_rbd_t* h, const idocp_rbd_objective_t* o, int n, int first_step, int steps, const int* active, int terminal,
                                    int accumulate, const idocp_rbd_score_io_t* io);
 
+/* ---- Gradients of an objective along a rollout (rbd_gradient_kernel.hip): the lx_traj, lu_traj that idocp_rbd_lqr_io_t reads.  An ADDITION.
+ * This is the definition: the derivative of what idocp_rbd_score_rollout sums as `cost`, taken in the tangent x = [dq; dv], q (+) eps e_r, the tangent
+ * of idocp_rbd_linearize_rollout.  With e = q (-) q_ref(t_k) and J = d e / d dq -- on the quadruped the base rows of J are the 6 x 6 Jlog6 of the
+ * relative base placement and J is the identity elsewhere, on a chain J is the identity --, slice k of the window:
+ *   lx[k][i][0:nv]   = dt J^T (q_weight o e)
+ *   lx[k][i][nv:2nv] = dt v_weight o (v - v_ref_k)
+ *   lu[k][i]         = dt u_weight o (u - u_ref)        (0 where u_traj is NULL)
+ * and the terminal slice the same with qf_weight, vf_weight and no dt.  The reference forms the same product in ConfigurationSpaceCost
+ * (configuration_space_cost.cpp:292-328: lq += dt J^T W diff with Robot::dSubtractdConfigurationPlus on a floating base).  The logarithm is the one
+ * the score takes (lieRelative, lieLog6 of dev_lie.hpp); J^T (W e) of the base rows is summed over the rows in index order.
+ * The gradient is of `cost`, NOT of `violation`: the constraint rows of the objective are not differentiated.  Refused with IDOCP_E_UNSUPPORTED, never
+ * dropped: an objective with a non-zero a_weight entry or a non-zero f_weight entry of any contact -- their gradients need da/dx and df/dx, and their
+ * Hessians are dense, which the diagonal x_weight / u_weight of idocp_rbd_lqr_backward cannot hold.
+ * n, first_step, steps and terminal mean what they mean for idocp_rbd_score_rollout; IDOCP_RBD_SCORE_MAX_WINDOW does not apply (the slices are
+ * independent), only (steps + 1) * n must fit an int.  A non-finite entry in what a slice reads of a sample (q, v, and u where given) makes that
+ * sample's lx and lu of that slice NaN and touches nothing else.  A sample's bits depend neither on n, nor on the outputs asked for, nor on the form
+ * of the call. */
+typedef struct idocp_rbd_gradient_io {
+  const double *q_traj, *v_traj;   /* [steps (+ 1 if terminal)][n][nq | nv] */
+  const double *u_traj;            /* [steps][n][nu]; NULL is allowed only when every u_weight is zero */
+  double *lx_traj;                 /* [steps (+ 1 if terminal)][n][2nv]; either output may be NULL */
+  double *lu_traj;                 /* [steps][n][nu] */
+} idocp_rbd_gradient_io_t;
+/* ADDITION.  Host pointers; stages through the handle's buffer and returns when the outputs are in place.  IDOCP_E_ARG (idocp_last_error names the
+ * call) for a NULL handle, objective or io, an objective of another handle, n <= 0, steps < 1, a window outside the objective, q_traj or v_traj
+ * missing, u_traj missing under a non-zero u_weight, and no output at all. */
+int idocp_rbd_objective_gradients(idocp_rbd_t* h, const idocp_rbd_objective_t* o, int n, int first_step, int steps, int terminal,
+                                  const idocp_rbd_gradient_io_t* io);
+/* ADDITION.  Device pointers; asynchronous on idocp_rbd_stream(h); one launch; allocates nothing. */
+int idocp_rbd_objective_gradients_device(idocp_rbd_t* h, const idocp_rbd_objective_t* o, int n, int first_step, int steps, int terminal,
+                                         const idocp_rbd_gradient_io_t* io);
+/* ADDITION.  The LQR weights of an objective as device tables that live as long as the objective (uploaded by idocp_rbd_objective_create), directly
+ * usable in idocp_rbd_lqr_io_t: x_weight [2nv] = dt [q_weight; v_weight], u_weight [nu] = dt u_weight, xf_weight [2nv] = [qf_weight; vf_weight].
+ * They are the diagonal Gauss-Newton approximation with J ~ I on the base rows: they approximate the HESSIAN only.  The gradients above are exact, so
+ * the fixed point of an iteration built on both is not moved.  Any of the three places may be NULL.  Refuses what the gradient call refuses. */
+int idocp_rbd_objective_lqr_weights_device(const idocp_rbd_objective_t* o, const double** d_x_weight, const double** d_u_weight,
+                                           const double** d_xf_weight);
+/* ADDITION.  The host twin: the same bits into x_weight [2nv], u_weight [nu], xf_weight [2nv] (any may be NULL). */
+int idocp_rbd_objective_get_lqr_weights(const idocp_rbd_objective_t* o, double* x_weight, double* u_weight, double* xf_weight);
+
+/* ---- The line-search step of iLQR (rbd_ilqr_kernel.hip).  ADDITIONS.
+ * idocp_rbd_ilqr_step_torques: u_ff[k][i][:] = u_traj[k][i][:] + alpha[i] * k_traj[k][i][:] (the product rounded, then the sum), all [steps][n][nu],
+ * alpha [n]; a sample whose alpha is 0 gets u_traj bit for bit, whatever k_traj holds.  One launch.  IDOCP_E_ARG for a NULL handle or array,
+ * n <= 0, steps < 1. */
+int idocp_rbd_ilqr_step_torques(idocp_rbd_t* h, int n, int steps, const double* u_traj, const double* k_traj, const double* alpha, double* u_ff);
+/* Device pointers; asynchronous on idocp_rbd_stream(h); allocates nothing. */
+int idocp_rbd_ilqr_step_torques_device(idocp_rbd_t* h, int n, int steps, const double* u_traj, const double* k_traj, const double* alpha,
+                                       double* u_ff);
+/* idocp_rbd_ilqr_accept: per sample, with merit = cost + penalty * violation (the combination of idocp_rbd_importance_weights), the trial is
+ * ACCEPTED if and only if done[i] == 0, trial_cost[i] and trial_violation[i] are finite, and
+ *   merit_trial <= merit + armijo * (alpha e0 + alpha^2 e1),   {e0, e1} = expected[i] of idocp_rbd_lqr_backward, alpha = alpha[i].
+ * (A NaN in expected or alpha rejects.)  An accepted sample copies its slices of the trial arrays over the current ones -- q, v
+ * [steps + 1][n][..], u [steps][n][nu], and a, f [steps][n][..] where both the current and the trial array are given --, overwrites cost[i] and
+ * violation[i], sets done[i] = 1 and writes alpha_accepted[i] = alpha[i].  A rejected sample does only this: alpha[i] *= shrink, and where
+ * alpha[i] < alpha_min afterwards, alpha[i] = 0; nothing else of it is touched.  A sample with done[i] != 0 is left alone entirely.  The copies are
+ * selects on whole slices, no arithmetic on the data.  One launch. */
+typedef struct idocp_rbd_ilqr_accept_io {
+  double *q_traj, *v_traj, *u_traj, *a_traj, *f_traj;   /* the current trajectory, in / out; a_traj, f_traj optional */
+  double *cost, *violation;                             /* [n] its scores, in / out */
+  const double *trial_q, *trial_v, *trial_u, *trial_a, *trial_f;
+  const double *trial_cost, *trial_violation;           /* [n] */
+  const double *expected;                               /* [n][2] */
+  double *alpha;                                        /* [n], in / out */
+  int *done;                                            /* [n], in / out */
+  double *alpha_accepted;                               /* [n]; written for the samples accepted by this call only */
+  double penalty, armijo, shrink, alpha_min;
+} idocp_rbd_ilqr_accept_io_t;
+/* Host pointers; returns when everything is in place.  IDOCP_E_ARG for a NULL handle, io or needed array, n <= 0, steps < 1, and a penalty, armijo,
+ * shrink or alpha_min that is negative or not finite. */
+int idocp_rbd_ilqr_accept(idocp_rbd_t* h, int n, int steps, const idocp_rbd_ilqr_accept_io_t* io);
+/* Device pointers, done included; asynchronous on idocp_rbd_stream(h); allocates nothing. */
+int idocp_rbd_ilqr_accept_device(idocp_rbd_t* h, int n, int steps, const idocp_rbd_ilqr_accept_io_t* io);
+
+/* ---- One iLQR iteration on the handle's stream.  ADDITION.  Chains, with no synchronisation and no host read in between:
+ *   idocp_rbd_linearize_rollout_device about (q_traj, v_traj, u_traj); idocp_rbd_objective_gradients_device (first_step 0, terminal);
+ *   idocp_rbd_lqr_backward_device with the objective's weights and `regularization`; then alpha = 1, done = 0, alpha_accepted = 0 and `trials`
+ *   rounds of: step torques; idocp_rbd_rollout_policy_device into the trial arrays with u_ff = u + alpha k, K = K_traj, q_ref = q_traj,
+ *   v_ref = v_traj, shared_ref = 0 and the caller's u_min, u_max; idocp_rbd_score_rollout_device with terminal = 1 (window by window with accumulate
+ *   beyond IDOCP_RBD_SCORE_MAX_WINDOW steps); accept.
+ * A sample accepted in an early round is simply rolled out again in the later rounds and that trial is ignored (done[i] != 0): simpler than
+ * compaction, and the stream stays free of host decisions.  A sample whose LQR status is not -1 has a NaN k_traj, hence a NaN trial: it is never
+ * accepted and keeps its trajectory, so failure stays per sample.  Quadrupeds roll out under the caller's FIXED contact_points (latching footholds is
+ * out of scope); chains pass active = contact_points = NULL.  The objective needs at least `steps` steps; step k of the rollout is its step k.
+ * The workspace is carved, in this order and each piece at an even number of doubles, into A_traj, B_traj, lx, lu, K_traj, k_traj, u_ff, the trial
+ * q, v, u, a, f, the trial cost and violation, alpha [n] and done [n ints]. */
+typedef struct idocp_rbd_ilqr_io {
+  double *q_traj, *v_traj, *u_traj;   /* [steps + 1][n][nq | nv], [steps][n][nu]: the current rollout, in / out */
+  double *a_traj, *f_traj;            /* [steps][n][nv | 3 ncontacts], in / out, optional (f_traj NULL on a chain) */
+  double *cost, *violation;           /* [n]: its score under the objective with terminal = 1, in / out (the caller scores the first rollout once) */
+  const double *u_min, *u_max;        /* [nu], either may be NULL */
+  double regularization, armijo, shrink, alpha_min, penalty;
+  int trials;                         /* >= 1 */
+  double *alpha_accepted;             /* [n]: the step taken, 0 = none */
+  int *lqr_status;                    /* [n]: status of idocp_rbd_lqr_backward */
+  double *expected;                   /* [n][2]: expected of idocp_rbd_lqr_backward */
+  void *workspace;                    /* DEVICE memory of idocp_rbd_ilqr_workspace_bytes(h, n, steps) bytes, 16-byte aligned; the host form ignores it */
+} idocp_rbd_ilqr_io_t;
+/* bytes of the workspace, 0 for a NULL handle, n <= 0 or steps < 1 */
+unsigned long long idocp_rbd_ilqr_workspace_bytes(const idocp_rbd_t* h, int n, int steps);
+/* Device pointers (the workspace included); asynchronous on idocp_rbd_stream(h); allocates nothing beyond what the calls it chains may allocate. */
+int idocp_rbd_ilqr_iterate_device(idocp_rbd_t* h, const idocp_rbd_objective_t* o, int n, int steps, const int* active, double time_step, double dt,
+                                  const double* contact_points, const idocp_rbd_ilqr_io_t* io, int touchdown_impulse);
+/* Host pointers; stages once, owns its workspace for the duration of the call (in the handle's staging buffer) and reads back once. */
+int idocp_rbd_ilqr_iterate(idocp_rbd_t* h, const idocp_rbd_objective_t* o, int n, int steps, const int* active, double time_step, double dt,
+                           const double* contact_points, const idocp_rbd_ilqr_io_t* io, int touchdown_impulse);
+
 /* ---- Sampling around a torque sequence: perturb, weigh, average (rbd_sample_kernel.hip).  Every call of this block is an ADDITION (the reference
  * has no counterpart).  With idocp_rbd_rollout_policy_device and idocp_rbd_score_rollout_device between the first and the second, one iteration of
  * a sampling-based refinement (the MPPI update: the softmin-weighted mean of the sampled torque sequences) runs on the handle's stream without a

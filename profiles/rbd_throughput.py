@@ -15,7 +15,8 @@ those three arrays.  The fdd_* rows are the forward-dynamics derivatives (fdd_ro
 outputs), each against kin_*_copy, a device-to-device copy of the bytes the call reads and writes.  rollout is idocp_rbd_rollout_device over
 ROLLOUT_STEPS open-loop steps with every contact active and no touchdown impulse, rollout_footholds the same schedule through
 idocp_rbd_rollout_footholds_device (one latch launch more per step); both carry ms_per_step.  The lqr_* rows are idocp_rbd_lqr_backward_device over
-16 steps (lqr_rows has their description); run with fdd_linearize_s16 they also carry their ratio to the linearisation that feeds them.
+16 steps (lqr_rows has their description); run with fdd_linearize_s16 they also carry their ratio to the linearisation that feeds them.  The grad_*,
+ilqr_accept and ilqr_iterate rows are the cost gradients, the acceptance step and one whole iLQR iteration (ilqr_rows has their description).
 
     python profiles/rbd_throughput.py [--n 122880] [--launches 20] [--warmup 5] [--rows name,name,...]
 """
@@ -385,6 +386,111 @@ def lqr_rows(wanted, lib, rt, h, stream, m, n, measure, res):
     for d in dev.values():
         lib.idocp_device_free(d)
 
+ILQR_ROWS = ("grad_s16_copy", "grad_s16", "ilqr_accept_copy", "ilqr_accept", "ilqr_iterate")
+ILQR_STEPS = 16
+
+
+def ilqr_rows(wanted, lib, rt, h, stream, m, n, measure, res):
+    """the grad_*, ilqr_accept and ilqr_iterate rows on 16 steps of ANYmal standing on four feet: grad_s16 is idocp_rbd_objective_gradients_device
+    (q, v, u in, lx with the terminal slice and lu out), ilqr_accept is idocp_rbd_ilqr_accept_device with EVERY sample accepted (done is cleared in
+    front of each launch, so q, v, u, a, f are copied in full), each against a device-to-device copy of the bytes the call moves; ilqr_iterate is one
+    idocp_rbd_ilqr_iterate_device with two trial rounds about a rollout of zero torques, to be read against fdd_linearize_s16 and lqr_gains_ilqr."""
+    rt.hipMemcpyAsync.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p]
+    rt.hipMemsetAsync.argtypes = [C.c_void_p, C.c_int, C.c_size_t, C.c_void_p]
+    nq, nv, nu, nf, S = m.nq, m.nv, m.nu, 3 * m.ncontacts, ILQR_STEPS
+    rng = np.random.default_rng(11)
+    cost = capi.Cost()
+    cost.set("q_ref", ANYMAL_Q_STANDING).set("q_weight", np.full(nv, 10.0)).set("v_weight", np.full(nv, 1.0)).set("u_weight", np.full(nu, 1e-3))
+    cost.set("qf_weight", np.full(nv, 10.0)).set("vf_weight", np.full(nv, 1.0)).set("a_weight", np.zeros(nv))
+    for c in range(4):
+        for x in range(3):
+            cost.f_weight[c][x] = 0.0
+    o = C.c_void_p()
+    capi.check(lib.idocp_rbd_objective_create(h, C.byref(cost), None, 0.0, 0.01, S, C.byref(o)), "objective")
+    want_iterate = not wanted or "ilqr_iterate" in wanted
+    sizes = {"q": (S + 1) * n * nq, "v": (S + 1) * n * nv, "u": S * n * nu, "a": S * n * nv, "f": S * n * nf, "lx": (S + 1) * n * 2 * nv, "lu": S * n * nu,
+             "tq": (S + 1) * n * nq, "tv": (S + 1) * n * nv, "tu": S * n * nu, "ta": S * n * nv, "tf": S * n * nf, "pts": S * n * nf,
+             "cost": n, "viol": n, "tcost": n, "tviol": n, "expected": 2 * n, "alpha": n, "alpha_accepted": n, "done": (n + 1) // 2, "status": (n + 1) // 2}
+    sizes["copy"] = 2 * sum(sizes[k] for k in ("q", "v", "u", "a", "f"))
+    if want_iterate:
+        sizes["work"] = lib.idocp_rbd_ilqr_workspace_bytes(h, n, S) // 8
+    dev = {}
+    for key, size in sizes.items():
+        dev[key] = C.c_void_p()
+        capi.check(lib.idocp_device_alloc(C.byref(dev[key]), 8 * size), "alloc")
+        assert rt.hipMemsetAsync(dev[key], 0, 8 * size, stream) == 0
+    q0 = np.tile(ANYMAL_Q_STANDING, (n, 1))
+    q0[:, 7:] += rng.uniform(-0.02, 0.02, (n, nv - 6))
+    feet = np.zeros(nf)
+    capi.check(lib.idocp_model_contact_positions(C.byref(m), np.ascontiguousarray(ANYMAL_Q_STANDING).ctypes.data, feet.ctypes.data), "feet")
+    pts = np.ascontiguousarray(np.broadcast_to(feet, (S, n, nf)))
+    ones = np.ones(n)
+    for key, x in (("q", q0), ("tq", q0), ("pts", pts), ("alpha", ones)):
+        capi.check(lib.idocp_device_upload(dev[key], x.ctypes.data, x.nbytes), "upload")
+    act = (C.c_int * (4 * S))(*([1] * (4 * S)))
+    ts, dt = 0.05, 0.01
+    # a real rollout (zero torques) in the current arrays and in the trial arrays, and its score
+    for pre in ("", "t"):
+        capi.check(lib.idocp_rbd_rollout_device(h, n, S, act, ts, dt, dev[pre + "u"], dev["pts"], dev[pre + "q"], dev[pre + "v"], dev[pre + "a"], dev[pre + "f"], 0), "rollout")
+    sc = capi.RbdScoreIO()
+    sc.q_traj, sc.v_traj, sc.u_traj, sc.a_traj, sc.f_traj, sc.cost, sc.violation = dev["q"], dev["v"], dev["u"], dev["a"], dev["f"], dev["cost"], dev["viol"]
+    capi.check(lib.idocp_rbd_score_rollout_device(h, o, n, 0, S, act, 1, 0, C.byref(sc)), "score")
+    assert rt.hipMemcpyAsync(dev["tcost"], dev["cost"], 8 * n, 3, stream) == 0
+
+    def copier(keys):
+        def copy():
+            at = 0
+            for key in keys:
+                assert rt.hipMemcpyAsync(C.c_void_p(dev["copy"].value + at), dev[key], 8 * sizes[key], 3, stream) == 0
+                at += 8 * sizes[key]
+        return copy
+
+    g = capi.RbdGradientIO()
+    g.q_traj, g.v_traj, g.u_traj, g.lx_traj, g.lu_traj = dev["q"], dev["v"], dev["u"], dev["lx"], dev["lu"]
+    grad_keys = ("q", "v", "u", "lx", "lu")
+    acc = capi.RbdIlqrAcceptIO()
+    for field, key in (("q_traj", "q"), ("v_traj", "v"), ("u_traj", "u"), ("a_traj", "a"), ("f_traj", "f"), ("cost", "cost"), ("violation", "viol"),
+                       ("trial_q", "tq"), ("trial_v", "tv"), ("trial_u", "tu"), ("trial_a", "ta"), ("trial_f", "tf"), ("trial_cost", "tcost"),
+                       ("trial_violation", "tviol"), ("expected", "expected"), ("alpha", "alpha"), ("done", "done"), ("alpha_accepted", "alpha_accepted")):
+        setattr(acc, field, dev[key])
+    acc.penalty, acc.armijo, acc.shrink, acc.alpha_min = 0.0, 1e-4, 0.5, 1e-3
+    acc_keys = ("q", "v", "u", "a", "f", "tq", "tv", "tu", "ta", "tf")      # (read the trial, write the current: a copy of the same bytes reads and writes both)
+
+    def accept():
+        assert rt.hipMemsetAsync(dev["done"], 0, 8 * sizes["done"], stream) == 0      # every sample is accepted again: merit_trial == merit, expected = 0
+        capi.check(lib.idocp_rbd_ilqr_accept_device(h, n, S, C.byref(acc)), "accept")
+
+    plan = (("grad_s16_copy", copier(grad_keys), grad_keys), ("grad_s16", lambda: capi.check(lib.idocp_rbd_objective_gradients_device(h, o, n, 0, S, 1, C.byref(g)), "gradients"), grad_keys),
+            ("ilqr_accept_copy", copier(("tq", "tv", "tu", "ta", "tf")), acc_keys), ("ilqr_accept", accept, acc_keys))
+    for row, launch, keys in plan:
+        if wanted and row not in wanted:
+            continue
+        measure(row, launch)
+        nbytes = 8 * sum(sizes[k] for k in keys)
+        res[row].update({"steps": S, "bytes": nbytes, "GB_per_s": round(nbytes / res[row]["ms_median"] / 1e6, 1)})
+    for name in ("grad_s16", "ilqr_accept"):
+        if name in res and name + "_copy" in res:
+            res[name]["ratio_to_copy"] = round(res[name]["ms_median"] / res[name + "_copy"]["ms_median"], 3)
+    if want_iterate:
+        io = capi.RbdIlqrIO()
+        for field, key in (("q_traj", "q"), ("v_traj", "v"), ("u_traj", "u"), ("a_traj", "a"), ("f_traj", "f"), ("cost", "cost"), ("violation", "viol"),
+                           ("alpha_accepted", "alpha_accepted"), ("lqr_status", "status"), ("expected", "expected"), ("workspace", "work")):
+            setattr(io, field, dev[key])
+        io.regularization, io.armijo, io.shrink, io.alpha_min, io.penalty, io.trials = 1e-6, 1e-4, 0.5, 1e-3, 0.0, 2
+        measure("ilqr_iterate", lambda: capi.check(lib.idocp_rbd_ilqr_iterate_device(h, o, n, S, act, ts, dt, dev["pts"], C.byref(io), 0), "iterate"))
+        res["ilqr_iterate"].update({"steps": S, "trials": 2})
+        status = np.zeros((n + 1) // 2)
+        capi.check(lib.idocp_rbd_synchronize(h), "synchronize")
+        capi.check(lib.idocp_device_download(status.ctypes.data, dev["status"], status.nbytes), "download")
+        res["ilqr_all_solved"] = bool((status.view(np.int32)[:n] == -1).all())
+        for part in ("fdd_linearize_s16", "lqr_gains_ilqr"):
+            if part in res:
+                res["ilqr_iterate"]["share_" + part] = round(res[part]["ms_median"] / res["ilqr_iterate"]["ms_median"], 3)
+    capi.check(lib.idocp_rbd_synchronize(h), "synchronize")
+    lib.idocp_rbd_objective_destroy(o)
+    for d in dev.values():
+        lib.idocp_device_free(d)
+
 
 def main():
     ap = argparse.ArgumentParser()
@@ -494,6 +600,8 @@ def main():
         fdd_rows(wanted, lib, h, m, n, dev, active, measure, res)
     if not wanted or set(wanted) & set(LQR_ROWS):
         lqr_rows(wanted, lib, rt, h, stream, m, n, measure, res)
+    if not wanted or set(wanted) & set(ILQR_ROWS):
+        ilqr_rows(wanted, lib, rt, h, stream, m, n, measure, res)
     ran = [k for k in res if isinstance(res[k], dict)]
     for key, src, width, rows in (("tau_finite", "tau", nv, ("stage_", "impulse_")), ("fd_a_finite", "fd_a", nv, ("fd_",)),
                                   ("policy_u_finite", "u_out", m.nu, ("policy_", "fd_step_closed_loop"))):
