@@ -1216,7 +1216,8 @@ int idocp_ocp_dimc(const idocp_ocp_t* h) {
 int idocp_ocp_get_constraint_data(idocp_ocp_t* h, int instance, double* slack, double* dual) {
   if (!h || instance < 0 || instance >= h->batch) return IDOCP_E_ARG;
   int rc = enterO(h); if (rc) return rc;
-  const int N = h->plan.Ngrid, dimc = idocp_ocp_dimc(h);
+  // (a ParNMPC plan counts its last stage apart: all N stages carry rows, stage i at constraint level i + 1)
+  const int N = h->parnmpc ? h->N : h->plan.Ngrid, dimc = idocp_ocp_dimc(h), level0 = h->parnmpc ? 1 + h->stage_offset : 0;
   std::vector<double> sl((size_t)N * LQ::CON), du((size_t)N * LQ::CON);
   HIP_TRY(hipMemcpyAsync(sl.data(), h->B.slack + (size_t)instance * h->NS * LQ::CON, sl.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream));
   HIP_TRY(hipMemcpyAsync(du.data(), h->B.dual + (size_t)instance * h->NS * LQ::CON, du.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream));
@@ -1232,7 +1233,8 @@ int idocp_ocp_get_constraint_data(idocp_ocp_t* h, int instance, double* slack, d
     for (int comp = 0; comp < 11; ++comp) {
       if (!use[comp]) continue;
       const int n = comp == 10 ? DQ::NC : (comp != 6 ? DQ::NU : cr * DQ::NC);
-      const bool valid = (comp < 2 || comp == 10) ? i >= 2 : (comp < 4 ? i >= 1 : true);
+      const int level = i + level0;
+      const bool valid = (comp < 2 || comp == 10) ? level >= 2 : (comp < 4 ? level >= 1 : true);
       for (int r = 0; r < n; ++r) {
         const int src = comp == 10 ? LQ::C_CD + r : (comp != 6 ? ipmCompRow<LQ>(comp) + r : LQ::C_FRIC + 5 * (r / cr) + r % cr);
         if (slack) slack[(size_t)i * dimc + off + r] = valid ? sl[(size_t)i * LQ::CON + src] : 0.0;
@@ -1310,6 +1312,32 @@ static int getContactDynamics(idocp_ocp_t* h, int instance, int stage, int dimf,
   for (int c = 0; c < DQ::NX; ++c) for (int r = 0; r < n; ++r) MJtJinv_dIDCdqv[r + n * c] = e[LQ::E_MJD + r + DQ::NVF * c];
   for (int r = 0; r < n; ++r) MJtJinv_IDC[r] = e[LQ::E_MJIDC + r];
   return dimf;
+}
+
+// The ext record of one chain position as ocp_ext_kernel left it (OcpLayout::EXT: the ContactDistance rows and the task-space components of a stage
+// BEFORE they are added into the kkt record), unpacked into the caller's arrays; every array may be null.  Reaches the node kinds
+// idocp_ocp_get_lqr_stage cannot: impulse, aux, lift, terminal, and ParNMPC's last stage.  No arithmetic, no launch: for tests.
+int idocp_ocp_get_ext_terms(idocp_ocp_t* h, int instance, int position, double* z, double* Jc, double* w, double* JJ, double* tw, double* lq,
+                            double* cost, double* violation, double* kkt_error) {
+  if (!h) return IDOCP_E_ARG;
+  if (!h->B.ext) { set_last_error("idocp_ocp_get_ext_terms: the handle has no ext record (no ContactDistance constraint, no task-space cost)"); return IDOCP_E_ARG; }
+  if (instance < 0 || instance >= h->batch) { set_last_error("idocp_ocp_get_ext_terms: instance out of range"); return IDOCP_E_ARG; }
+  if (position < 0 || position >= h->M()) { set_last_error("idocp_ocp_get_ext_terms: position out of range"); return IDOCP_E_ARG; }
+  if (h->parnmpc && position == h->M() - 1) { set_last_error("idocp_ocp_get_ext_terms: the placeholder behind ParNMPC's last stage has no terms"); return IDOCP_E_ARG; }
+  int rc = enterO(h); if (rc) return rc;
+  std::vector<double> x(LQ::EXT);
+  HIP_TRY(hipMemcpyAsync(x.data(), h->B.ext + ((size_t)instance * h->NS + h->plan.nodes[position].slot) * LQ::EXT, x.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  HIP_TRY(hipStreamSynchronize(h->stream));
+  if (z) std::memcpy(z, &x[LQ::X_Z], sizeof(double) * DQ::NC);
+  if (Jc) std::memcpy(Jc, &x[LQ::X_CDJ], sizeof(double) * DQ::NC * DQ::NV);
+  if (w) std::memcpy(w, &x[LQ::X_W], sizeof(double) * DQ::NC);
+  if (JJ) std::memcpy(JJ, &x[LQ::X_TJ], sizeof(double) * LQ::NT * 6 * DQ::NV);
+  if (tw) std::memcpy(tw, &x[LQ::X_TW], sizeof(double) * LQ::NT * 6);
+  if (lq) std::memcpy(lq, &x[LQ::X_LQ], sizeof(double) * DQ::NV);
+  if (cost) *cost = x[LQ::X_COST];
+  if (violation) *violation = x[LQ::X_VIOL];
+  if (kkt_error) *kkt_error = x[LQ::X_ERR];
+  return IDOCP_OK;
 }
 
 int idocp_ocp_get_lqr_stage(idocp_ocp_t* h, int instance, int stage, double* Qxx, double* Qxu, double* Quu, double* A, double* Bm,

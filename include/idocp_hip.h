@@ -569,6 +569,15 @@ int idocp_ocp_get_contact_dynamics(idocp_ocp_t* h, int instance, int stage, doub
  * include/idocp/impulse/impulse_dynamics_forward_euler_data.hxx -- MJtJinv over the impulse's contacts, the blocks of [ImD; V] in place of [ID; C]). */
 int idocp_ocp_get_contact_dynamics_chain(idocp_ocp_t* h, int instance, int position, double* MJtJinv, double* MJtJinv_dIDCdqv,
                                          double* MJtJinv_IDC);
+/* For tests: the terms of one chain position that carry frame Jacobians of their own (ContactDistance rows, TaskSpace3DCost / TaskSpace6DCost
+ * components), as the last linearisation left them BEFORE they were added into the stage -- any node kind, ParNMPC's last stage included.
+ * With nc = max_point_contacts, nt = 1 + IDOCP_MAX_EXTRA_TASKS, every array nullable: z[nc] world heights of the contact frames,
+ * Jc[nc][nv] the ContactDistance rows (zero on an active contact), w[nc] their Hessian weights, JJ[nt * 6][nv] the task rows (six per component,
+ * the last three zero for a 3D one; unused components zero), tw[nt * 6] their Hessian weights, lq[nv] the share of the gradient, and the scalars
+ * cost, violation, kkt_error of the stage's share.  IDOCP_E_ARG (with a text) for a handle without such terms, an instance or position
+ * out of range, and the placeholder behind ParNMPC's last stage.  One device-to-host copy; launches nothing. */
+int idocp_ocp_get_ext_terms(idocp_ocp_t* h, int instance, int position, double* z, double* Jc, double* w, double* JJ, double* tw, double* lq,
+                            double* cost, double* violation, double* kkt_error);
 int idocp_ocp_get_lqr_stage(idocp_ocp_t* h, int instance, int stage, double* Qxx, double* Qxu,
                             double* Quu, double* A, double* B, double* lx, double* lu,
                             double* Fx);

@@ -80,6 +80,59 @@ static void taskTerms(const Robot& task_robot, const RCost& cost, real t, const 
   }
 }
 
+// The un-condensed read of the terms with frame Jacobians of their own (ExtTermsC, ocp.hpp) of one node: the ContactDistance rows as
+// augmentDualResidual + condenseSlackAndDual + computePrimalAndDualResidual leave them TOGETHER (contact_distance.cpp:68-102, 132-146), the
+// task components row by row with the weights of the node's kind (kind_w: 0 stage, 1 impulse, 2 terminal; scale = dt on a stage;
+// add_terminal: ParNMPC's last stage, terminal_parnmpc.hxx).  rows = the slack / dual of component 10, or null where the node has none.
+static ExtTermsC extTermsOfNode(const Robot& robot_, const Robot& task_robot, const RCost& cost, real barrier, int nc, const SplitSolutionC& si,
+                                int kind_w, bool add_terminal, real t, real scale, const ContactStatus& cs, const IpmData* rows) {
+  Robot robot = robot_;
+  const int nv = robot.dimv(), NT = 1 + IDOCP_MAX_EXTRA_TASKS;
+  ExtTermsC x;
+  x.z = Mat(nc); x.Jc = Mat(nc, nv); x.w = Mat(nc); x.JJ = Mat(6 * NT, nv); x.tw = Mat(6 * NT); x.lq = Mat(nv);
+  x.slack = Mat(nc); x.dual = Mat(nc);
+  if (rows) {
+    robot.updateKinematics(si.q, si.v, si.a);
+    for (int cc = 0; cc < nc; ++cc) {
+      real pw[3]; robot.contactFrame(cc, pw, nullptr, nullptr, nullptr);
+      x.z[cc] = pw[2];                                   // setSlackAndDual takes the height of every frame
+      if (cs.active[cc]) continue;
+      Mat vdq, adq, adv, J;
+      robot.frameDerivatives(cc, vdq, adq, adv, J);      // LOCAL frame Jacobian, its row 2
+      const real sl = rows->slack[cc], du = rows->dual[cc];
+      x.slack[cc] = sl; x.dual[cc] = du;
+      const real residual = -pw[2] + sl, duality = sl * du - barrier;
+      const real g = scale * du + scale * (du * residual - duality) / sl;
+      x.w[cc] = scale * du / sl;
+      for (int col = 0; col < nv; ++col) { x.Jc(cc, col) = J(2, col); x.lq[col] -= g * J(2, col); }
+      x.violation += scale * std::fabs(residual);
+      x.kkt_error += residual * residual + duality * duality;
+    }
+  }
+  for (int e = 0; e < cost.taskCount(); ++e) {
+    RModel mt = task_robot.model();
+    if (e > 0) {
+      mt.contact_frame_id[0] = -1; mt.contact_joint[0] = cost.taskJoint(e);
+      for (int k2 = 0; k2 < 9; ++k2) mt.contact_R[0][k2] = cost.taskFrameR(e)[k2];
+      for (int k2 = 0; k2 < 3; ++k2) mt.contact_p[0][k2] = cost.taskFrameP(e)[k2];
+    }
+    Robot re(mt);
+    const int dim = e ? cost.taskDim(e) : cost.task_dim;
+    const real* ref = e ? cost.taskConstRef(e) : cost.taskRefAt(t);
+    const real* w = e ? cost.taskWeight(e, kind_w) : (kind_w == 0 ? cost.task_weight : (kind_w == 1 ? cost.task_weighti : cost.task_weightf));
+    const real* wf = e ? cost.taskWeight(e, 2) : cost.task_weightf;
+    real c; Mat g, H, JJ, diff;
+    re.taskSpaceTerms(dim, ref, w, si.q, c, g, H, &JJ, &diff);
+    for (int r = 0; r < dim; ++r) {
+      const real tw = scale * w[r] + (add_terminal ? wf[r] : real(0.0));
+      x.tw[6 * e + r] = tw;
+      for (int col = 0; col < nv; ++col) { x.JJ(6 * e + r, col) = JJ(r, col); x.lq[col] += JJ(r, col) * tw * diff[r]; }
+    }
+    x.cost += scale * c;                                 // (the merit takes the stage weight alone on ParNMPC's last stage: line_search.cpp:228-237)
+  }
+  return x;
+}
+
 OCPSolver::OCPSolver(const RModel& model, const RCost& cost_, const idocp_constraints_t& constraints, real T, int N,
                      int max_num_impulse)
     : robot(model), task_robot(makeTaskRobot(model, cost_)), cost(cost_), cons(constraints), N_ideal_(N), N_(N), nv_(model.nv), nu_(model.nu), nc_(model.ncontacts),
@@ -273,6 +326,14 @@ void OCPSolver::discretize(real t) {
 const ContactStatus& OCPSolver::nodeContacts(int p) const {
   const NodeC& nd = chain[p];
   return nd.kind == NodeC::Impulse ? seq.impulse_status[nd.phase] : seq.phases[nd.phase];
+}
+
+ExtTermsC OCPSolver::extTerms(int p) const {
+  const NodeC& nd = chain[p];
+  const bool impulse = nd.kind == NodeC::Impulse, terminal = nd.kind == NodeC::Terminal;
+  const bool rows = !impulse && !terminal && componentValid(10, nd);
+  return extTermsOfNode(robot, task_robot, cost, cons.barrier, nc_, s[nd.slot], impulse ? 1 : (terminal ? 2 : 0), false, nd.t,
+                        (impulse || terminal) ? real(1.0) : nd.dt, nodeContacts(p), rows ? &ipm[nd.slot][10] : nullptr);
 }
 
 // ------------------------------------------------------------ constraints ----
@@ -1511,6 +1572,14 @@ void ParNMPCSolver::discretize(real t) {
     has_terminal = hi >= N_;
   }
   discretized_ = true; disc_t_ = t;
+}
+
+ExtTermsC ParNMPCSolver::extTerms(int p) const {
+  const PNode& nd = chain[p];
+  const bool impulse = nd.kind == NodeC::Impulse;
+  const bool rows = !impulse && componentValid(10, nd);
+  return extTermsOfNode(robot, task_robot, cost, cons.barrier, nc_, s[nd.slot], impulse ? 1 : 0, nd.kind == NodeC::Terminal, nd.t,
+                        impulse ? real(1.0) : nd.dt, nodeContacts(nd), rows ? &ipm[nd.slot][10] : nullptr);
 }
 
 bool ParNMPCSolver::componentValid(int c, const PNode& nd) const {     // constraints_data.hpp:18-42

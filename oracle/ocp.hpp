@@ -130,6 +130,14 @@ struct UncondensedC {
   Mat aux_next;      // ParNMPC: what the coarse update adds to Qxx for the stage behind this one (BackwardCorrectionSolver::aux_mat_ of the next stage)
 };
 
+// The terms with frame Jacobians of their own of ONE node, row by row and un-condensed (test hook: oracle_ocp_get_ext_terms /
+// oracle_parnmpc_get_ext_terms): heights z [nc], ContactDistance rows Jc [nc x nv] and Hessian weights w [nc], task rows JJ [ncomp * 6 x nv]
+// and weights tw [ncomp * 6], their share lq [nv] of the gradient, and the three scalars the merit and the KKT error take from them.
+struct ExtTermsC {
+  Mat z, Jc, w, JJ, tw, lq;
+  Mat slack, dual;            // [nc]: the state of the ContactDistance rows the terms were formed with (zeros where the node has none)
+  real cost = 0, violation = 0, kkt_error = 0;
+};
 struct RiccatiC {
   Mat Pqq, Pqv, Pvv, sq, sv;
   explicit RiccatiC(int nv) : Pqq(nv, nv), Pqv(nv, nv), Pvv(nv, nv), sq(nv), sv(nv) {}
@@ -167,6 +175,7 @@ class OCPSolver {
   real stepDt() const { return dt_; }
   int dimc() const;
   const ContactStatus& nodeContacts(int p) const;     // contact (or impulse) status a node is linearised with
+  ExtTermsC extTerms(int p) const;                    // of chain position p at the current iterate, slack and dual
   Robot robot;
   Robot task_robot;                          // the robot with the task frame of a TaskSpace3D / 6D cost as its contact 0
   RCost cost;
@@ -275,6 +284,7 @@ class ParNMPCSolver {
   std::vector<PNode> chain;
   ContactSequenceC seq;
   const ContactStatus& nodeContacts(const PNode& nd) const { return nd.kind == NodeC::Impulse ? seq.impulse_status[nd.event] : seq.phases[nd.phase]; }
+  ExtTermsC extTerms(int p) const;          // of chain position p at the current iterate, slack and dual
   int slotOf(int kind, int index) const;
   int nslots() const { return N_ideal_ + 3 * max_events_; }
   Robot robot;

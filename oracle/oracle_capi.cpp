@@ -876,6 +876,40 @@ static int uncondensedField(const UncondensedC& U, const char* name, double* out
   if (out) for (int i = 0; i < m->size(); ++i) out[i] = (double)m->d[i];
   return m->size();
 }
+// ---- test hook: the terms with frame Jacobians of their own of chain position `pos`, un-condensed and row by row (ExtTermsC, ocp.hpp):
+//   z[nc], Jc[nc][nv], w[nc], JJ[(1 + IDOCP_MAX_EXTRA_TASKS) * 6][nv], tw[the same rows], lq[nv] row-major, out3 = cost, violation, kkt_error;
+//   cd_slack[nc], cd_dual[nc] = the slack and dual of the ContactDistance rows they were formed with (state); every array may be NULL;
+//   -1 for a position out of range
+static int writeExtTerms(const ExtTermsC& x, double* z, double* Jc, double* w, double* JJ, double* tw, double* lq, double* out3,
+                         double* cd_slack, double* cd_dual) {
+  const int nc = x.z.size(), nv = x.lq.size(), nr = x.tw.size();
+  for (int c = 0; c < nc; ++c) {
+    if (z) z[c] = (double)x.z[c];
+    if (w) w[c] = (double)x.w[c];
+    if (cd_slack) cd_slack[c] = (double)x.slack[c];
+    if (cd_dual) cd_dual[c] = (double)x.dual[c];
+    if (Jc) for (int k = 0; k < nv; ++k) Jc[(size_t)c * nv + k] = (double)x.Jc(c, k);
+  }
+  for (int r = 0; r < nr; ++r) {
+    if (tw) tw[r] = (double)x.tw[r];
+    if (JJ) for (int k = 0; k < nv; ++k) JJ[(size_t)r * nv + k] = (double)x.JJ(r, k);
+  }
+  if (lq) for (int k = 0; k < nv; ++k) lq[k] = (double)x.lq[k];
+  if (out3) { out3[0] = (double)x.cost; out3[1] = (double)x.violation; out3[2] = (double)x.kkt_error; }
+  return 0;
+}
+int oracle_ocp_get_ext_terms(void* h, int pos, double* z, double* Jc, double* w, double* JJ, double* tw, double* lq, double* out3,
+                         double* cd_slack, double* cd_dual) {
+  OCPSolver* s = static_cast<OCPSolver*>(h);
+  if (pos < 0 || pos >= s->M()) return -1;
+  try { return writeExtTerms(s->extTerms(pos), z, Jc, w, JJ, tw, lq, out3, cd_slack, cd_dual); } catch (...) { return -2; }
+}
+int oracle_parnmpc_get_ext_terms(void* h, int pos, double* z, double* Jc, double* w, double* JJ, double* tw, double* lq, double* out3,
+                         double* cd_slack, double* cd_dual) {
+  ParNMPCSolver* s = static_cast<ParNMPCSolver*>(h);
+  if (pos < 0 || pos >= s->M()) return -1;
+  try { return writeExtTerms(s->extTerms(pos), z, Jc, w, JJ, tw, lq, out3, cd_slack, cd_dual); } catch (...) { return -2; }
+}
 double oracle_ocp_bench(void* h, double t, const double* q, const double* v, int iters, double* riccati_seconds) {
   OCPSolver* s = static_cast<OCPSolver*>(h);
   Mat Q = toVec(q, s->robot.dimq()), V = toVec(v, s->robot.dimv());

@@ -499,7 +499,7 @@ void Robot::computeContactDerivative(const std::vector<bool>& active, Mat& Pq) c
 static void log3(const real* R, real* w, real* theta);
 static void VmatInv(const real* w, real* Vi);
 static void Jlog6(const real* R, const real* p, Mat& J);
-void Robot::taskSpaceTerms(int dim, const real* ref, const real* w, const Mat& q, real& cost, Mat& grad, Mat& hess) {
+void Robot::taskSpaceTerms(int dim, const real* ref, const real* w, const Mat& q, real& cost, Mat& grad, Mat& hess, Mat* rows_out, Mat* diff_out) {
   FLOP_REGION(R_COST_CONSTRAINTS);
   const int nv = m_.nv;
   const Mat zero(nv);
@@ -527,6 +527,8 @@ void Robot::taskSpaceTerms(int dim, const real* ref, const real* w, const Mat& q
     for (int col = 0; col < nv; ++col)
       for (int r = 0; r < 3; ++r) { real a = 0; for (int k = 0; k < 3; ++k) a += R[3 * r + k] * J(k, col); JJ(r, col) = a; }
   }
+  if (rows_out) *rows_out = JJ;
+  if (diff_out) *diff_out = diff;
   cost = 0;
   for (int r = 0; r < m; ++r) cost += 0.5 * w[r] * diff[r] * diff[r];
   grad = Mat(nv); hess = Mat(nv, nv);

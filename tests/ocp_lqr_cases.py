@@ -134,8 +134,14 @@ def jac_difference(q0, q1, arg, T=np.float64):
     """(d (q1 (-) q0) / d q_arg in the tangent of q_arg [nv x nv], its own error estimate): -I / +I on the joints; the 6 x 6 base block by central
     differences at h, h / 2, h / 4, h / 8 Romberg-extrapolated three times (error h^8), the estimate = the last correction of the table"""
     nv = len(q0) - 1
-    X0, X1 = _placement(np.asarray(q0), T), _placement(np.asarray(q1), T)
     J = np.eye(nv, dtype=T) * (1 if arg else -1)
+    J[:6, :6], worst = jac_log(_placement(np.asarray(q0), T), _placement(np.asarray(q1), T), arg, T)
+    return J, worst
+
+
+def jac_log(X0, X1, arg, T=np.float64):
+    """(d log(X0^-1 X1) / d (the own tangent of X_arg) [6 x 6], its error estimate) of two placements (R, p): the Romberg table of `jac_difference`"""
+    J = np.zeros((6, 6), dtype=T)
     h0, worst = T(0.05) if T is not np.float64 else 0.04, 0.0
     for k in range(6):
         tab = []
@@ -149,7 +155,7 @@ def jac_difference(q0, q1, arg, T=np.float64):
         for m in range(1, 4):
             new = [(4 ** m * tab[j + 1] - tab[j]) / (4 ** m - 1) for j in range(len(tab) - 1)]
             last, tab = tab[-1], new
-        J[:6, k] = tab[0]
+        J[:, k] = tab[0]
         worst = max(worst, float(np.abs(tab[0] - last).max()))
     return J, worst
 
@@ -303,7 +309,7 @@ def families(cons, nu):
     off, at = 0, {}
     for name, n, on in (("q", 2 * nu, cons.joint_position_limits), ("v", 2 * nu, cons.joint_velocity_limits), ("u", 2 * nu, cons.joint_torque_limits),
                         ("cone", 4 * cr, cons.linearized_friction_cone or cons.friction_cone), ("alo", nu, cons.joint_acceleration_lower_limit),
-                        ("ahi", nu, cons.joint_acceleration_upper_limit)):
+                        ("ahi", nu, cons.joint_acceleration_upper_limit), ("cd", 4, getattr(cons, "contact_distance", 0))):
         if on:
             at[name] = slice(off, off + n)
             off += n
@@ -393,10 +399,11 @@ def reference_at(M, cost, t, mutate=None):
     return q_ref, vt[0]
 
 
-def lqr_stage(m, M, cost, cons, rec, st, slack, dual, T=LD, mutate=None):
+def lqr_stage(m, M, cost, cons, rec, st, slack, dual, T=LD, mutate=None, ext=None):
     """The condensed stage (module docstring) as {name of QUANTITIES: float64 array}, "fd_error": the largest error estimate of the differenced
     Jacobians.  st: dict(dt, t, level, mask, q, v, a, f [4][3], u, beta, mu [4][3], q_next, v_next, q_prev, lmd, gmm, lmd_next, gmm_next); rec: the
-    referee_record of the stage; slack, dual: the stage's row of get_constraint_data.  T: the real type everything is formed in."""
+    referee_record of the stage; slack, dual: the stage's row of get_constraint_data.  T: the real type everything is formed in.  ext: the terms with frame
+    Jacobians of their own (ocp_ext_cases.ext_record: "lq" [nv] and "H" [nv][nv], dt and weights inside), added to the gradient and the Hessian of q."""
     nv, nu, nq = m.nv, m.nu, m.nq
     dt, mask = T(st["dt"]), tuple(int(x) for x in st["mask"])
     act = RC.rows_of(mask)
@@ -420,6 +427,8 @@ def lqr_stage(m, M, cost, cons, rec, st, slack, dual, T=LD, mutate=None):
     gv, ga, gu, gf = dt * wv * (v - c(v_ref)), dt * wa * a, dt * wu * (u - W("u_ref", nu)), dt * wf * (fa - f_ref)
     hv, ha, hu, Hff = dt * wv, dt * wa, dt * wu, np.diag(dt * wf)
     Hqq, Hff = Hqq.copy(), Hff.astype(T)
+    if ext is not None:
+        gq, Hqq = gq + c(ext["lq"]), Hqq + c(ext["H"])
     # ---- the inequality rows: dt grad g (z + (z (g + s) - (s z - eps)) / s) and dt (z / s) grad g grad g^T
     idx, dimc = row_index(cons, nu, mask, st["level"])
     assert len(slack) == len(dual) == dimc, (len(slack), dimc)
@@ -507,7 +516,7 @@ def lqr_stage(m, M, cost, cons, rec, st, slack, dual, T=LD, mutate=None):
     return out
 
 
-def terminal_stage(m, M, cost, st, T=LD):
+def terminal_stage(m, M, cost, st, T=LD, ext=None):
     """(Hessian, gradient) of the terminal node: 1/2 |q (-) q_ref|^2_Wqf + 1/2 |v - v_ref|^2_Wvf + lmd . Fq- + gmm . Fv-, Gauss-Newton; st: dict(t, q, v,
     q_prev, lmd, gmm)"""
     nv = m.nv
@@ -521,6 +530,9 @@ def terminal_stage(m, M, cost, st, T=LD):
     H[:nv, :nv] = Jq.T @ (wq[:, None] * Jq)
     H[nv:, nv:] = np.diag(wv)
     g = np.concatenate([Jq.T @ (wq * e) + Fqp.T @ c(st["lmd"]), wv * (c(st["v"]) - c(v_ref)) - c(st["gmm"])])
+    if ext is not None:      # (ocp_ext_cases.ext_record of the terminal node)
+        H[:nv, :nv] += c(ext["H"])
+        g[:nv] += c(ext["lq"])
     return H.astype(np.float64), g.astype(np.float64), max(e0, e1)
 
 

@@ -125,3 +125,9 @@ def test_acceleration_bound_errors():
     consa.a_max[0] = float("nan")
     assert lib.idocp_ocp_create(C.byref(ma), C.byref(costa), C.byref(consa), 1.0, 20, 1, 0, C.byref(h)) == -1
     assert b"must be finite" in lib.idocp_last_error()
+
+
+def test_get_ext_terms_is_declared_and_refuses_a_null_handle():
+    # the test-facing getter of the ext record (tests/test_ocp_ext_terms_gpu.py): declared, exported, IDOCP_E_ARG without a handle
+    assert "idocp_ocp_get_ext_terms" in declared_functions()
+    assert capi.lib().idocp_ocp_get_ext_terms(None, 0, 0, *[None] * 9) == -1
