@@ -178,6 +178,12 @@ class RbdIlqrIO(C.Structure):
                 [(name, C.c_void_p) for name in OUTPUTS] + [("workspace", C.c_void_p)])
 
 
+class RbdCostLinearizationIO(C.Structure):
+    """idocp_rbd_cost_linearization_io_t: the requested outputs of idocp_rbd_linearize_rollout_cost(_device); a pointer left at None is NULL"""
+    OUTPUTS = ("A_traj", "B_traj", "G_traj", "rho_traj", "lx_traj", "lu_traj")
+    _fields_ = [(name, C.c_void_p) for name in OUTPUTS]
+
+
 RBD_STAGE, RBD_IMPULSE = 0, 1
 RBD_SCORE_MAX_WINDOW = 1024
 RBD_REDUCE_CHUNK = 1024      # IDOCP_RBD_REDUCE_CHUNK: samples per chunk of the fixed-order sums
@@ -429,6 +435,17 @@ def _proto(lib):
     lib.idocp_rbd_objective_get_lqr_weights.restype = ci
     lib.idocp_rbd_ilqr_workspace_bytes.argtypes = [vp, ci, ci]
     lib.idocp_rbd_ilqr_workspace_bytes.restype = C.c_ulonglong
+    for form in ("", "_device"):
+        for name, args in (("idocp_rbd_linearize_rollout_cost", [vp, vp, ci, ci, c_int_p, cd, cd, vp, vp, vp, vp, P(RbdCostLinearizationIO), ci]),
+                           ("idocp_rbd_lqr_backward_gn", [vp, ci, ci, P(RbdLqrIO), ci, vp]),
+                           ("idocp_rbd_ilqr_iterate_gn", [vp, vp, ci, ci, c_int_p, cd, cd, vp, P(RbdIlqrIO), ci])):
+            f = getattr(lib, name + form)
+            f.argtypes = args
+            f.restype = ci
+    lib.idocp_rbd_objective_residual_rows.argtypes = [vp]
+    lib.idocp_rbd_objective_residual_rows.restype = ci
+    lib.idocp_rbd_ilqr_gn_workspace_bytes.argtypes = [vp, ci, ci]
+    lib.idocp_rbd_ilqr_gn_workspace_bytes.restype = C.c_ulonglong
     for name, args in [
         ("idocp_ocp_set_contact_status_uniformly", [vp, P(ci), c_double_p]),
         ("idocp_ocp_set_solution", [vp, cs, c_double_p]),

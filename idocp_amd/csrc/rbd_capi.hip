@@ -55,6 +55,7 @@ struct idocp_rbd {
   RbdBuffer fdd;                      // forward-dynamics derivatives: what one pass keeps between its launches (rbd_fdd_plan.hpp), at most 256 MiB
   int fdd_limit = 0;                  // idocp_rbd_set_derivatives_chunk (a test hook, not in idocp_hip.h): bound on the samples of a pass (0: none)
   RbdBuffer lin;                      // rollout linearisation at a touchdown: [v_pre [n][nv] | E [n][2 nv * 2 nv]]
+  RbdBuffer gn;                       // cost linearisation: a, f and the six derivative blocks of one pass (ResidualPlan), under the cap of `fdd`
 };
 
 // the objective of the rollout scoring: the plan of rbd_objective.hpp and its three pieces in ONE block of device memory
@@ -65,6 +66,7 @@ struct idocp_rbd_objective {
   idocp_host::RbdScoreBlock* d_block = nullptr;
   std::vector<double> lqr_weights;                    // idocp_host::lqrWeights: [x_weight | u_weight | xf_weight], and the same bits behind the block
   double* d_lqr_weights = nullptr;
+  double* d_residual = nullptr;                       // idocp_host::residualTable: [scales | references], 2 R doubles behind the weights
 };
 
 namespace {
@@ -538,11 +540,72 @@ int checkLinearize(const char* who, idocp_rbd* h, int n, int steps, const int* a
   return IDOCP_OK;
 }
 
-// every pointer: device memory
+// The scratch of the cost linearisation: a, f and the six derivative blocks of one pass, each piece [chunk][its size] at an even number of doubles.
+// The sample axis is cut by the rule of rbd_fdd_plan.hpp under the same cap, with an EVEN chunk (the runs of a workgroup of rbd_residual_kernel.hip
+// then start 16-byte aligned).
+struct ResidualPlan {
+  int chunk = 0;
+  size_t a, f, da_dq, da_dv, da_du, df_dq, df_dv, df_du, total;
+};
+ResidualPlan residualPlan(const idocp_rbd* h, int n) {
+  const size_t V = h->model.nv, U = h->model.nu, F = h->quadruped ? 3 * (size_t)h->model.ncontacts : 0;
+  const size_t sizes[8] = {V, F, V * V, V * V, V * U, F * V, F * V, F * U};
+  size_t per_sample = 0;
+  for (size_t s : sizes) per_sample += s;
+  size_t fit = idocp_host::FDD_SCRATCH_CAP_DOUBLES / (per_sample + 8) / 2 * 2;      // (+ 8: the rounding of the pieces)
+  if (fit < 2) fit = 2;
+  ResidualPlan p;
+  p.chunk = (size_t)n < fit ? n : (int)fit;
+  size_t* const offsets[8] = {&p.a, &p.f, &p.da_dq, &p.da_dv, &p.da_du, &p.df_dq, &p.df_dv, &p.df_du};
+  size_t at = 0;
+  for (int i = 0; i < 8; ++i) { *offsets[i] = at; at += ((size_t)p.chunk * sizes[i] + 1) / 2 * 2; }
+  p.total = at;
+  return p;
+}
+
+// what the cost form of the linearisation adds (idocp_rbd_linearize_rollout_cost): G, rho and the gradients lx, lu, which hold the diagonal part
+struct CostLinearization {
+  const double* table;      // idocp_host::residualTable of the objective, device memory
+  double *G, *rho, *lx, *lu;
+  int R;
+};
+
+// every pointer: device memory.  cost == nullptr: idocp_rbd_linearize_rollout.  With cost, step k takes the sample axis in the passes of
+// residualPlan: the derivative composition of the pass with a, f and the blocks into h->gn, then one launch of rbd_residual_kernel.hip.
 int linearizeDevice(idocp_rbd* h, int n, int steps, const int* active, double time_step, double dt, const double* u, const double* contact_points,
-                    const double* q_traj, const double* v_traj, double* A_traj, double* B_traj, int touchdown_impulse) {
+                    const double* q_traj, const double* v_traj, double* A_traj, double* B_traj, int touchdown_impulse,
+                    const CostLinearization* cost = nullptr) {
   const size_t nq = h->model.nq, nv = h->model.nv, nu = h->model.nu, nf = 3 * (size_t)h->model.ncontacts, N = (size_t)n, nx = 2 * nv;
-  if (!A_traj && !B_traj) return IDOCP_OK;
+  if (!cost && !A_traj && !B_traj) return IDOCP_OK;
+  if (cost) {
+    const ResidualPlan p = residualPlan(h, n);
+    int rc = h->gn.grow(p.total, h->stream); if (rc) return rc;
+    double* const S = h->gn.ptr;
+    const size_t R = (size_t)cost->R, nz = nx + nu;
+    auto at = [](double* x, size_t off) { return x ? x + off : nullptr; };
+    for (int k = 0; k < steps; ++k) {
+      const int mask = h->quadruped ? maskOf(h, active + (size_t)k * h->model.ncontacts) : 0;
+      for (int first = 0; first < n; first += p.chunk) {
+        const int cnt = n - first < p.chunk ? n - first : p.chunk;
+        const size_t F = (size_t)k * N + first;      // (slice k, sample `first`)
+        idocp_rbd_fdd_io_t io = idocp_rbd_fdd_io_t();
+        io.q = q_traj + F * nq; io.v = v_traj + F * nv; io.u = u ? u + F * nu : nullptr;
+        io.contact_points = contact_points ? contact_points + F * nf : nullptr;
+        io.A = at(A_traj, F * nx * nx); io.B = at(B_traj, F * nx * nu);
+        io.a = S + p.a; io.da_dq = S + p.da_dq; io.da_dv = S + p.da_dv; io.da_du = S + p.da_du;
+        if (h->quadruped) { io.f = S + p.f; io.df_dq = S + p.df_dq; io.df_dv = S + p.df_dv; io.df_du = S + p.df_du; }
+        rc = launchDerivatives(h, IDOCP_RBD_STAGE, cnt, mask, time_step, dt, io); if (rc) return rc;
+        RbdResidualArgs r;
+        r.a = io.a; r.f = io.f; r.da_dq = io.da_dq; r.da_dv = io.da_dv; r.da_du = io.da_du; r.df_dq = io.df_dq; r.df_dv = io.df_dv; r.df_du = io.df_du;
+        r.table = cost->table;
+        r.G = at(cost->G, F * R * nz); r.rho = at(cost->rho, F * R); r.lx = at(cost->lx, F * nx); r.lu = at(cost->lu, F * nu);
+        r.count = cnt; r.mask = mask;
+        if (!rbdResidual(h->model.nv, h->quadruped, r, h->stream)) { set_last_error("idocp_rbd_linearize_rollout_cost: no residual kernel for this model"); return IDOCP_E_UNSUPPORTED; }
+        HIP_TRY(hipGetLastError());
+      }
+    }
+    if (!A_traj && !B_traj) return IDOCP_OK;
+  }
   for (int k = 0; k < steps; ++k) {
     const int mask = h->quadruped ? maskOf(h, active + (size_t)k * h->model.ncontacts) : 0;
     const int next = (h->quadruped && k + 1 < steps) ? maskOf(h, active + (size_t)(k + 1) * h->model.ncontacts) : 0;
@@ -554,7 +617,8 @@ int linearizeDevice(idocp_rbd* h, int n, int steps, const int* active, double ti
     io.q = qk; io.v = vk; io.u = uk; io.contact_points = pk;
     io.A = A_traj ? A_traj + k * N * nx * nx : nullptr;
     io.B = B_traj ? B_traj + k * N * nx * nu : nullptr;
-    int rc = launchDerivatives(h, IDOCP_RBD_STAGE, n, mask, time_step, dt, io); if (rc) return rc;
+    int rc = IDOCP_OK;
+    if (!cost) { rc = launchDerivatives(h, IDOCP_RBD_STAGE, n, mask, time_step, dt, io); if (rc) return rc; }      // (with cost: A_k, B_k are in place)
     if (!touchdown) continue;
     rc = h->lin.grow(N * nv + N * nx * nx, h->stream); if (rc) return rc;
     double *v_pre = h->lin.ptr, *E = v_pre + N * nv;
@@ -635,6 +699,101 @@ int checkLqrWeights(const char* who, const idocp_rbd_objective* o) {
   return IDOCP_OK;
 }
 
+// ---- the cost linearisation and the backward pass with residual rows
+
+// what idocp_rbd_linearize_rollout_cost refuses beyond checkLinearize
+int checkLinearizeCost(const char* who, const idocp_rbd* h, const idocp_rbd_objective* o, int n, int steps, const double* u_traj,
+                       const idocp_rbd_cost_linearization_io_t* io) {
+  const std::string w(who);
+  if (!o || !io) { set_last_error(w + ": null objective or io"); return IDOCP_E_ARG; }
+  if (o->owner != h) { set_last_error(w + ": the objective was created on another handle"); return IDOCP_E_ARG; }
+  if (steps > o->plan.steps) { set_last_error(w + ": steps must lie within the objective's " + std::to_string(o->plan.steps) + " steps"); return IDOCP_E_ARG; }
+  const std::string unsupported = idocp_host::residualUnsupported(o->plan);
+  if (!unsupported.empty()) { set_last_error(w + ": " + unsupported); return IDOCP_E_UNSUPPORTED; }
+  if (!io->A_traj && !io->B_traj && !io->G_traj && !io->rho_traj && !io->lx_traj && !io->lu_traj) {
+    set_last_error(w + ": no output was asked for"); return IDOCP_E_ARG;
+  }
+  if (((long long)steps + 1) * n > 2147483647LL) { set_last_error(w + ": (steps + 1) * n must fit an int"); return IDOCP_E_ARG; }
+  if (!u_traj && (io->lx_traj || io->lu_traj) && idocp_host::rbd_objective_detail::anyNonZero(o->plan.block.u_weight, o->plan.nu)) {
+    set_last_error(w + ": u_traj is NULL but a non-zero u_weight reads it"); return IDOCP_E_ARG;
+  }
+  return IDOCP_OK;
+}
+
+// every pointer: device memory.  The diagonal part of the gradients first (rbd_gradient_kernel.hip, first_step 0, the terminal slice included),
+// then the linearisation with the residual rows on top.
+int linearizeCostDevice(idocp_rbd* h, const idocp_rbd_objective* o, int n, int steps, const int* active, double time_step, double dt, const double* u,
+                        const double* contact_points, const double* q_traj, const double* v_traj, const idocp_rbd_cost_linearization_io_t& io,
+                        int touchdown_impulse) {
+  // A_traj, B_traj alone: the plain linearisation (the same bits: a sample's do not depend on how the sample axis is cut), no rows formed
+  if (!io.G_traj && !io.rho_traj && !io.lx_traj && !io.lu_traj)
+    return linearizeDevice(h, n, steps, active, time_step, dt, u, contact_points, q_traj, v_traj, io.A_traj, io.B_traj, touchdown_impulse);
+  if (io.lx_traj || io.lu_traj) {
+    RbdGradientArgs g;
+    g.q = q_traj; g.v = v_traj; g.u = u; g.q_ref = o->d_q_ref; g.v_ref = o->d_v_ref; g.block = o->d_block;
+    g.lx = io.lx_traj; g.lu = io.lu_traj; g.n = n; g.steps = steps; g.terminal = 1;
+    rbdGradient(h->model.nv, h->quadruped, g, h->stream);
+    HIP_TRY(hipGetLastError());
+  }
+  CostLinearization c;
+  c.table = o->d_residual; c.G = io.G_traj; c.rho = io.rho_traj; c.lx = io.lx_traj; c.lu = io.lu_traj; c.R = idocp_host::residualRows(o->plan);
+  return linearizeDevice(h, n, steps, active, time_step, dt, u, contact_points, q_traj, v_traj, io.A_traj, io.B_traj, touchdown_impulse, &c);
+}
+
+int checkLqrGn(const char* who, const idocp_rbd* h, int g_rows, const double* G_traj) {
+  const std::string w(who);
+  if (!G_traj && g_rows == 0) return IDOCP_OK;
+  if (!G_traj || g_rows == 0) { set_last_error(w + ": G_traj and g_rows come together (NULL with 0, or both given)"); return IDOCP_E_ARG; }
+  if (g_rows < 4 || g_rows > 64 || g_rows % 4 != 0) { set_last_error(w + ": g_rows must be a multiple of 4 within 4 .. 64"); return IDOCP_E_ARG; }
+  (void)h;
+  return IDOCP_OK;
+}
+
+// io, G: device pointers
+int launchLqrGn(idocp_rbd* h, int n, int steps, const idocp_rbd_lqr_io_t& io, int g_rows, const double* G) {
+  if (!G) return launchLqr(h, n, steps, io);
+  RbdLqrGnArgs a;
+  a.A = io.A_traj; a.B = io.B_traj; a.x_weight = io.x_weight; a.u_weight = io.u_weight; a.xf_weight = io.xf_weight;
+  a.lx = io.lx_traj; a.lu = io.lu_traj; a.regularization = io.regularization;
+  a.K = io.K_traj; a.k = io.k_traj; a.P0 = io.P0; a.p0 = io.p0; a.expected = io.expected; a.status = io.status;
+  a.n = n; a.steps = steps; a.nx = 2 * h->model.nv; a.nu = h->model.nu;
+  a.G = G; a.g_rows = g_rows;
+  rbdLqrBackwardGn(h->quadruped, a, h->stream);
+  HIP_TRY(hipGetLastError());
+  return IDOCP_OK;
+}
+
+// the host form of both backward passes
+int lqrHost(const char* who, idocp_rbd* h, int n, int steps, const idocp_rbd_lqr_io_t* io, int g_rows, const double* G_traj) {
+  int rc = checkLqr(who, h, n, steps, io, true); if (rc) return rc;
+  rc = checkLqrGn(who, h, g_rows, G_traj); if (rc) return rc;
+  HIP_TRY(hipSetDevice(h->device));
+  const size_t nx = 2 * (size_t)h->model.nv, nu = h->model.nu, N = (size_t)n, S = (size_t)steps;
+  StagePlan p;
+  idocp_rbd_lqr_io_t d = *io;
+  double* d_status = nullptr;
+  const double* d_G = nullptr;
+  p.in(io->A_traj, S * N * nx * nx, &d.A_traj);
+  p.in(io->B_traj, S * N * nx * nu, &d.B_traj);
+  p.in(io->x_weight, nx, &d.x_weight);
+  p.in(io->u_weight, nu, &d.u_weight);
+  p.in(io->xf_weight, nx, &d.xf_weight);
+  p.in(io->lx_traj, (S + 1) * N * nx, &d.lx_traj);
+  p.in(io->lu_traj, S * N * nu, &d.lu_traj);
+  p.out(io->K_traj, S * N * nx * nu, &d.K_traj);
+  p.out(io->k_traj, S * N * nu, &d.k_traj);
+  p.out(io->P0, N * nx * nx, &d.P0);
+  p.out(io->p0, N * nx, &d.p0);
+  p.out(io->expected, N * 2, &d.expected);
+  if (io->status) p.deviceOnly((N + 1) / 2, &d_status);      // (n ints in a slot of doubles; they come down by a copy of their own, in front of stageOut's wait)
+  p.in(G_traj, S * N * (size_t)g_rows * (nx + nu), &d_G);
+  rc = stageIn(h, p); if (rc) return rc;
+  d.status = reinterpret_cast<int*>(d_status);
+  rc = launchLqrGn(h, n, steps, d, g_rows, d_G); if (rc) return rc;
+  if (io->status) HIP_TRY(hipMemcpyAsync(io->status, d_status, sizeof(int) * N, hipMemcpyDeviceToHost, h->stream));
+  return stageOut(h, p);
+}
+
 int checkStepTorques(const char* who, const idocp_rbd* h, int n, int steps, const double* u, const double* k, const double* alpha, const double* out) {
   const std::string w(who);
   if (!h) { set_last_error(w + ": null handle"); return IDOCP_E_ARG; }
@@ -681,9 +840,10 @@ int launchAccept(idocp_rbd* h, int n, int steps, const idocp_rbd_ilqr_accept_io_
 
 // The workspace of one iteration (include/idocp_hip.h names the order): offsets in doubles, each piece at an even number of doubles.
 struct IlqrWorkspace {
-  size_t A, B, lx, lu, K, k, u_ff, q, v, u, a, f, cost, violation, alpha, done, total;
+  size_t A, B, lx, lu, K, k, u_ff, q, v, u, a, f, cost, violation, alpha, done, G, total;
 };
-IlqrWorkspace ilqrWorkspace(const idocp_rbd* h, int n, int steps) {
+// g_rows: the rows of G_traj behind everything else (idocp_rbd_ilqr_iterate_gn), 0: none
+IlqrWorkspace ilqrWorkspace(const idocp_rbd* h, int n, int steps, int g_rows = 0) {
   const size_t nq = h->model.nq, nv = h->model.nv, nu = h->model.nu, nf = 3 * (size_t)h->model.ncontacts, N = (size_t)n, S = (size_t)steps, nx = 2 * nv;
   IlqrWorkspace w;
   size_t at = 0;
@@ -692,15 +852,21 @@ IlqrWorkspace ilqrWorkspace(const idocp_rbd* h, int n, int steps) {
   w.K = piece(S * N * nx * nu); w.k = piece(S * N * nu); w.u_ff = piece(S * N * nu);
   w.q = piece((S + 1) * N * nq); w.v = piece((S + 1) * N * nv); w.u = piece(S * N * nu); w.a = piece(S * N * nv); w.f = piece(S * N * nf);
   w.cost = piece(N); w.violation = piece(N); w.alpha = piece(N); w.done = piece((N + 1) / 2);
+  w.G = piece(S * N * (size_t)g_rows * (nx + nu));
   w.total = at;
   return w;
 }
 
-int checkIterate(const char* who, const idocp_rbd* h, const idocp_rbd_objective* o, int n, int steps, const idocp_rbd_ilqr_io_t* io, bool host) {
+// gn: the Gauss-Newton form takes every objective whose a_weight and f_weight have square roots
+int checkIterate(const char* who, const idocp_rbd* h, const idocp_rbd_objective* o, int n, int steps, const idocp_rbd_ilqr_io_t* io, bool host,
+                 bool gn = false) {
   const std::string w(who);
   if (!h || !o || !io) { set_last_error(w + ": null handle, objective or io"); return IDOCP_E_ARG; }
   if (o->owner != h) { set_last_error(w + ": the objective was created on another handle"); return IDOCP_E_ARG; }
-  int rc = checkLqrWeights(who, o); if (rc) return rc;
+  if (gn) {
+    const std::string unsupported = idocp_host::residualUnsupported(o->plan);
+    if (!unsupported.empty()) { set_last_error(w + ": " + unsupported); return IDOCP_E_UNSUPPORTED; }
+  } else { int rc = checkLqrWeights(who, o); if (rc) return rc; }
   if (n <= 0) { set_last_error(w + ": n must be positive"); return IDOCP_E_ARG; }
   if (steps < 1) { set_last_error(w + ": steps must be at least 1"); return IDOCP_E_ARG; }
   if (steps > o->plan.steps) { set_last_error(w + ": steps must lie within the objective's " + std::to_string(o->plan.steps) + " steps"); return IDOCP_E_ARG; }
@@ -712,30 +878,44 @@ int checkIterate(const char* who, const idocp_rbd* h, const idocp_rbd_objective*
   const char* const names[5] = {"regularization", "armijo", "shrink", "alpha_min", "penalty"};
   for (int i = 0; i < 5; ++i)
     if (!std::isfinite(values[i]) || values[i] < 0.0) { set_last_error(w + ": " + names[i] + " must be finite and non-negative"); return IDOCP_E_ARG; }
-  if (!host && !io->workspace) { set_last_error(w + ": the workspace is needed (idocp_rbd_ilqr_workspace_bytes)"); return IDOCP_E_ARG; }
+  if (!host && !io->workspace) { set_last_error(w + ": the workspace is needed (idocp_rbd_ilqr_workspace_bytes, idocp_rbd_ilqr_gn_workspace_bytes)"); return IDOCP_E_ARG; }
   if (!host && (reinterpret_cast<uintptr_t>(io->workspace) & 15u)) { set_last_error(w + ": the workspace must be 16-byte aligned"); return IDOCP_E_ARG; }
   return IDOCP_OK;
 }
 
 // io: device pointers; ws: the workspace.  The chain of include/idocp_hip.h; every call on the handle's stream, no synchronisation, no host read.
+// gn: the chain of idocp_rbd_ilqr_iterate_gn -- the cost linearisation and the backward pass with residual rows in place of the first three calls.
 int iterateDevice(idocp_rbd* h, const idocp_rbd_objective* o, int n, int steps, const int* active, double time_step, double dt,
-                  const double* contact_points, const idocp_rbd_ilqr_io_t& io, double* ws, int touchdown_impulse) {
+                  const double* contact_points, const idocp_rbd_ilqr_io_t& io, double* ws, int touchdown_impulse, bool gn = false) {
   const size_t nq = h->model.nq, nv = h->model.nv, nu = h->model.nu, nf = 3 * (size_t)h->model.ncontacts, N = (size_t)n;
-  const IlqrWorkspace w = ilqrWorkspace(h, n, steps);
+  const int g_rows = gn ? idocp_host::residualRows(o->plan) : 0;
+  const IlqrWorkspace w = ilqrWorkspace(h, n, steps, g_rows);
   double *A = ws + w.A, *B = ws + w.B, *lx = ws + w.lx, *lu = ws + w.lu, *K = ws + w.K, *kff = ws + w.k, *u_ff = ws + w.u_ff;
   double *qt = ws + w.q, *vt = ws + w.v, *ut = ws + w.u, *at = ws + w.a, *ft = nf ? ws + w.f : nullptr;
   double *cost_t = ws + w.cost, *violation_t = ws + w.violation, *alpha = ws + w.alpha;
   int* done = reinterpret_cast<int*>(ws + w.done);
-  int rc = idocp_rbd_linearize_rollout_device(h, n, steps, active, time_step, dt, io.u_traj, contact_points, io.q_traj, io.v_traj, A, B, touchdown_impulse);
-  if (rc) return rc;
-  idocp_rbd_gradient_io_t g = idocp_rbd_gradient_io_t();
-  g.q_traj = io.q_traj; g.v_traj = io.v_traj; g.u_traj = io.u_traj; g.lx_traj = lx; g.lu_traj = lu;
-  rc = idocp_rbd_objective_gradients_device(h, o, n, 0, steps, 1, &g); if (rc) return rc;
+  int rc = IDOCP_OK;
   idocp_rbd_lqr_io_t lqr = idocp_rbd_lqr_io_t();
   lqr.A_traj = A; lqr.B_traj = B; lqr.lx_traj = lx; lqr.lu_traj = lu; lqr.regularization = io.regularization;
-  rc = idocp_rbd_objective_lqr_weights_device(o, &lqr.x_weight, &lqr.u_weight, &lqr.xf_weight); if (rc) return rc;
   lqr.K_traj = K; lqr.k_traj = kff; lqr.expected = io.expected; lqr.status = io.lqr_status;
-  rc = idocp_rbd_lqr_backward_device(h, n, steps, &lqr); if (rc) return rc;
+  if (gn) {
+    idocp_rbd_cost_linearization_io_t c = idocp_rbd_cost_linearization_io_t();
+    c.A_traj = A; c.B_traj = B; c.G_traj = ws + w.G; c.lx_traj = lx; c.lu_traj = lu;
+    rc = idocp_rbd_linearize_rollout_cost_device(h, o, n, steps, active, time_step, dt, io.u_traj, contact_points, io.q_traj, io.v_traj, &c, touchdown_impulse);
+    if (rc) return rc;
+    lqr.x_weight = o->d_lqr_weights;      // (the tables of idocp_rbd_objective_lqr_weights_device, without its refusal)
+    lqr.u_weight = o->d_lqr_weights + idocp_host::lqrWeightOffsetU(o->plan);
+    lqr.xf_weight = o->d_lqr_weights + idocp_host::lqrWeightOffsetXf(o->plan);
+    rc = idocp_rbd_lqr_backward_gn_device(h, n, steps, &lqr, g_rows, c.G_traj); if (rc) return rc;
+  } else {
+    rc = idocp_rbd_linearize_rollout_device(h, n, steps, active, time_step, dt, io.u_traj, contact_points, io.q_traj, io.v_traj, A, B, touchdown_impulse);
+    if (rc) return rc;
+    idocp_rbd_gradient_io_t g = idocp_rbd_gradient_io_t();
+    g.q_traj = io.q_traj; g.v_traj = io.v_traj; g.u_traj = io.u_traj; g.lx_traj = lx; g.lu_traj = lu;
+    rc = idocp_rbd_objective_gradients_device(h, o, n, 0, steps, 1, &g); if (rc) return rc;
+    rc = idocp_rbd_objective_lqr_weights_device(o, &lqr.x_weight, &lqr.u_weight, &lqr.xf_weight); if (rc) return rc;
+    rc = idocp_rbd_lqr_backward_device(h, n, steps, &lqr); if (rc) return rc;
+  }
   rbdIlqrInit(alpha, done, io.alpha_accepted, n, h->stream);
   HIP_TRY(hipGetLastError());
   // every trial starts from the state the rollout started from
@@ -768,6 +948,43 @@ int iterateDevice(idocp_rbd* h, const idocp_rbd_objective* o, int n, int steps, 
     rc = launchAccept(h, n, steps, acc); if (rc) return rc;
   }
   return IDOCP_OK;
+}
+
+// the host form of both iterations: stages once, owns the workspace in the staging buffer, reads back once
+int iterateHost(const char* who, idocp_rbd* h, const idocp_rbd_objective* o, int n, int steps, const int* active, double time_step, double dt,
+                const double* contact_points, const idocp_rbd_ilqr_io_t* io, int touchdown_impulse, bool gn) {
+  int rc = checkIterate(who, h, o, n, steps, io, true, gn); if (rc) return rc;
+  {      // (the bounds are host memory here and can be looked at)
+    idocp_rbd_policy_t bounds = idocp_rbd_policy_t();
+    bounds.u_min = io->u_min; bounds.u_max = io->u_max;
+    rc = checkPolicy(who, h, &bounds, true); if (rc) return rc;
+  }
+  if (h->quadruped && !contact_points) { set_last_error(std::string(who) + ": contact_points are needed"); return IDOCP_E_ARG; }
+  HIP_TRY(hipSetDevice(h->device));
+  const size_t nq = h->model.nq, nv = h->model.nv, nu = h->model.nu, nf = 3 * (size_t)h->model.ncontacts, N = (size_t)n, S = (size_t)steps;
+  StagePlan p;
+  idocp_rbd_ilqr_io_t d = *io;
+  const double* d_points;
+  double *d_status = nullptr, *d_ws = nullptr;
+  p.update(io->q_traj, (S + 1) * N * nq, &d.q_traj);
+  p.update(io->v_traj, (S + 1) * N * nv, &d.v_traj);
+  p.update(io->u_traj, S * N * nu, &d.u_traj);
+  p.update(io->a_traj, S * N * nv, &d.a_traj);
+  p.update(io->f_traj, S * N * nf, &d.f_traj);
+  p.update(io->cost, N, &d.cost);
+  p.update(io->violation, N, &d.violation);
+  p.in(io->u_min, nu, &d.u_min);
+  p.in(io->u_max, nu, &d.u_max);
+  p.in(contact_points, S * N * nf, &d_points);
+  p.out(io->alpha_accepted, N, &d.alpha_accepted);
+  p.out(io->expected, 2 * N, &d.expected);
+  p.deviceOnly((N + 1) / 2, &d_status);
+  p.deviceOnly(ilqrWorkspace(h, n, steps, gn ? idocp_host::residualRows(o->plan) : 0).total, &d_ws);
+  rc = stageIn(h, p); if (rc) return rc;
+  d.lqr_status = reinterpret_cast<int*>(d_status);
+  rc = iterateDevice(h, o, n, steps, active, time_step, dt, d_points, d, d_ws, touchdown_impulse, gn); if (rc) return rc;
+  HIP_TRY(hipMemcpyAsync(io->lqr_status, d_status, sizeof(int) * N, hipMemcpyDeviceToHost, h->stream));
+  return stageOut(h, p);
 }
 
 }  // namespace
@@ -820,6 +1037,7 @@ void idocp_rbd_destroy(idocp_rbd_t* h) {
   h->reduce.release();
   h->fdd.release();
   h->lin.release();
+  h->gn.release();
   if (h->stream) (void)hipStreamDestroy(h->stream);
   delete h;
 }
@@ -1121,15 +1339,20 @@ int idocp_rbd_objective_create(idocp_rbd_t* h, const idocp_cost_t* cost, const i
   o->lqr_weights.resize((size_t)idocp_host::lqrWeightDoubles(o->plan));
   idocp_host::lqrWeights(o->plan, o->lqr_weights.data());
   const size_t block_bytes = (sizeof(idocp_host::RbdScoreBlock) + 15) / 16 * 16;
-  if (hipMalloc(reinterpret_cast<void**>(&o->d_q_ref), sizeof(double) * (nq_tab + nv_tab + o->lqr_weights.size()) + block_bytes) != hipSuccess)
+  const size_t weights_tab = (o->lqr_weights.size() + 1) / 2 * 2;
+  std::vector<double> residual((size_t)2 * idocp_host::residualRows(o->plan));
+  idocp_host::residualTable(o->plan, residual.data());      // (a negative weight leaves a NaN here; the calls that read the table refuse it)
+  if (hipMalloc(reinterpret_cast<void**>(&o->d_q_ref), sizeof(double) * (nq_tab + nv_tab + weights_tab + residual.size()) + block_bytes) != hipSuccess)
     return fail("idocp_rbd_objective_create: hipMalloc of the objective failed");
   o->d_v_ref = o->d_q_ref + nq_tab;
   o->d_block = reinterpret_cast<idocp_host::RbdScoreBlock*>(o->d_v_ref + nv_tab);
   o->d_lqr_weights = reinterpret_cast<double*>(reinterpret_cast<char*>(o->d_block) + block_bytes);
+  o->d_residual = o->d_lqr_weights + weights_tab;
   if (hipMemcpyAsync(o->d_q_ref, o->plan.q_ref.data(), sizeof(double) * o->plan.q_ref.size(), hipMemcpyHostToDevice, h->stream) != hipSuccess ||
       hipMemcpyAsync(o->d_v_ref, o->plan.v_ref.data(), sizeof(double) * o->plan.v_ref.size(), hipMemcpyHostToDevice, h->stream) != hipSuccess ||
       hipMemcpyAsync(o->d_block, &o->plan.block, sizeof(idocp_host::RbdScoreBlock), hipMemcpyHostToDevice, h->stream) != hipSuccess ||
       hipMemcpyAsync(o->d_lqr_weights, o->lqr_weights.data(), sizeof(double) * o->lqr_weights.size(), hipMemcpyHostToDevice, h->stream) != hipSuccess ||
+      hipMemcpyAsync(o->d_residual, residual.data(), sizeof(double) * residual.size(), hipMemcpyHostToDevice, h->stream) != hipSuccess ||
       hipStreamSynchronize(h->stream) != hipSuccess) return fail("idocp_rbd_objective_create: upload of the objective failed");
   *out = o;
   return IDOCP_OK;
@@ -1269,29 +1492,56 @@ int idocp_rbd_lqr_backward_device(idocp_rbd_t* h, int n, int steps, const idocp_
 }
 
 int idocp_rbd_lqr_backward(idocp_rbd_t* h, int n, int steps, const idocp_rbd_lqr_io_t* io) {
-  int rc = checkLqr("idocp_rbd_lqr_backward", h, n, steps, io, true); if (rc) return rc;
+  return lqrHost("idocp_rbd_lqr_backward", h, n, steps, io, 0, nullptr);
+}
+
+int idocp_rbd_lqr_backward_gn_device(idocp_rbd_t* h, int n, int steps, const idocp_rbd_lqr_io_t* io, int g_rows, const double* G_traj) {
+  int rc = checkLqr("idocp_rbd_lqr_backward_gn_device", h, n, steps, io, false); if (rc) return rc;
+  rc = checkLqrGn("idocp_rbd_lqr_backward_gn_device", h, g_rows, G_traj); if (rc) return rc;
   HIP_TRY(hipSetDevice(h->device));
-  const size_t nx = 2 * (size_t)h->model.nv, nu = h->model.nu, N = (size_t)n, S = (size_t)steps;
+  return launchLqrGn(h, n, steps, *io, g_rows, G_traj);
+}
+
+int idocp_rbd_lqr_backward_gn(idocp_rbd_t* h, int n, int steps, const idocp_rbd_lqr_io_t* io, int g_rows, const double* G_traj) {
+  return lqrHost("idocp_rbd_lqr_backward_gn", h, n, steps, io, g_rows, G_traj);
+}
+
+int idocp_rbd_objective_residual_rows(const idocp_rbd_objective_t* o) { return o ? idocp_host::residualRows(o->plan) : 0; }
+
+int idocp_rbd_linearize_rollout_cost_device(idocp_rbd_t* h, const idocp_rbd_objective_t* o, int n, int steps, const int* active, double time_step,
+                                            double dt, const double* u_traj, const double* contact_points, const double* q_traj,
+                                            const double* v_traj, const idocp_rbd_cost_linearization_io_t* io, int touchdown_impulse) {
+  const char* who = "idocp_rbd_linearize_rollout_cost_device";
+  int rc = checkLinearize(who, h, n, steps, active, time_step, dt, contact_points, q_traj, v_traj); if (rc) return rc;
+  rc = checkLinearizeCost(who, h, o, n, steps, u_traj, io); if (rc) return rc;
+  HIP_TRY(hipSetDevice(h->device));
+  return linearizeCostDevice(h, o, n, steps, active, time_step, dt, u_traj, contact_points, q_traj, v_traj, *io, touchdown_impulse);
+}
+
+int idocp_rbd_linearize_rollout_cost(idocp_rbd_t* h, const idocp_rbd_objective_t* o, int n, int steps, const int* active, double time_step, double dt,
+                                     const double* u_traj, const double* contact_points, const double* q_traj, const double* v_traj,
+                                     const idocp_rbd_cost_linearization_io_t* io, int touchdown_impulse) {
+  const char* who = "idocp_rbd_linearize_rollout_cost";
+  int rc = checkLinearize(who, h, n, steps, active, time_step, dt, contact_points, q_traj, v_traj); if (rc) return rc;
+  rc = checkLinearizeCost(who, h, o, n, steps, u_traj, io); if (rc) return rc;
+  HIP_TRY(hipSetDevice(h->device));
+  const size_t nq = h->model.nq, nv = h->model.nv, nu = h->model.nu, nf = 3 * (size_t)h->model.ncontacts, N = (size_t)n, S = (size_t)steps, nx = 2 * nv;
+  const size_t R = (size_t)idocp_host::residualRows(o->plan);
   StagePlan p;
-  idocp_rbd_lqr_io_t d = *io;
-  double* d_status = nullptr;
-  p.in(io->A_traj, S * N * nx * nx, &d.A_traj);
-  p.in(io->B_traj, S * N * nx * nu, &d.B_traj);
-  p.in(io->x_weight, nx, &d.x_weight);
-  p.in(io->u_weight, nu, &d.u_weight);
-  p.in(io->xf_weight, nx, &d.xf_weight);
-  p.in(io->lx_traj, (S + 1) * N * nx, &d.lx_traj);
-  p.in(io->lu_traj, S * N * nu, &d.lu_traj);
-  p.out(io->K_traj, S * N * nx * nu, &d.K_traj);
-  p.out(io->k_traj, S * N * nu, &d.k_traj);
-  p.out(io->P0, N * nx * nx, &d.P0);
-  p.out(io->p0, N * nx, &d.p0);
-  p.out(io->expected, N * 2, &d.expected);
-  if (io->status) p.deviceOnly((N + 1) / 2, &d_status);      // (n ints in a slot of doubles; they come down by a copy of their own, in front of stageOut's wait)
+  const double *d_u, *d_points, *d_q, *d_v;
+  idocp_rbd_cost_linearization_io_t d;
+  p.in(u_traj, S * N * nu, &d_u);
+  p.in(contact_points, S * N * nf, &d_points);
+  p.in(q_traj, (S + 1) * N * nq, &d_q);
+  p.in(v_traj, (S + 1) * N * nv, &d_v);
+  p.out(io->A_traj, S * N * nx * nx, &d.A_traj);
+  p.out(io->B_traj, S * N * nx * nu, &d.B_traj);
+  p.out(io->G_traj, S * N * R * (nx + nu), &d.G_traj);
+  p.out(io->rho_traj, S * N * R, &d.rho_traj);
+  p.out(io->lx_traj, (S + 1) * N * nx, &d.lx_traj);
+  p.out(io->lu_traj, S * N * nu, &d.lu_traj);
   rc = stageIn(h, p); if (rc) return rc;
-  d.status = reinterpret_cast<int*>(d_status);
-  rc = launchLqr(h, n, steps, d); if (rc) return rc;
-  if (io->status) HIP_TRY(hipMemcpyAsync(io->status, d_status, sizeof(int) * N, hipMemcpyDeviceToHost, h->stream));
+  rc = linearizeCostDevice(h, o, n, steps, active, time_step, dt, d_u, d_points, d_q, d_v, d, touchdown_impulse); if (rc) return rc;
   return stageOut(h, p);
 }
 
@@ -1422,39 +1672,25 @@ int idocp_rbd_ilqr_iterate_device(idocp_rbd_t* h, const idocp_rbd_objective_t* o
 
 int idocp_rbd_ilqr_iterate(idocp_rbd_t* h, const idocp_rbd_objective_t* o, int n, int steps, const int* active, double time_step, double dt,
                            const double* contact_points, const idocp_rbd_ilqr_io_t* io, int touchdown_impulse) {
-  const char* who = "idocp_rbd_ilqr_iterate";
-  int rc = checkIterate(who, h, o, n, steps, io, true); if (rc) return rc;
-  {      // (the bounds are host memory here and can be looked at)
-    idocp_rbd_policy_t bounds = idocp_rbd_policy_t();
-    bounds.u_min = io->u_min; bounds.u_max = io->u_max;
-    rc = checkPolicy(who, h, &bounds, true); if (rc) return rc;
-  }
-  if (h->quadruped && !contact_points) { set_last_error(std::string(who) + ": contact_points are needed"); return IDOCP_E_ARG; }
+  return iterateHost("idocp_rbd_ilqr_iterate", h, o, n, steps, active, time_step, dt, contact_points, io, touchdown_impulse, false);
+}
+
+unsigned long long idocp_rbd_ilqr_gn_workspace_bytes(const idocp_rbd_t* h, int n, int steps) {
+  if (!h || n <= 0 || steps < 1) return 0;
+  const int R = (h->model.nv + (h->quadruped ? 3 * h->model.ncontacts : 0) + 3) / 4 * 4;      // (idocp_host::residualRows of any objective of the handle)
+  return sizeof(double) * (unsigned long long)ilqrWorkspace(h, n, steps, R).total;
+}
+
+int idocp_rbd_ilqr_iterate_gn_device(idocp_rbd_t* h, const idocp_rbd_objective_t* o, int n, int steps, const int* active, double time_step, double dt,
+                                     const double* contact_points, const idocp_rbd_ilqr_io_t* io, int touchdown_impulse) {
+  int rc = checkIterate("idocp_rbd_ilqr_iterate_gn_device", h, o, n, steps, io, false, true); if (rc) return rc;
   HIP_TRY(hipSetDevice(h->device));
-  const size_t nq = h->model.nq, nv = h->model.nv, nu = h->model.nu, nf = 3 * (size_t)h->model.ncontacts, N = (size_t)n, S = (size_t)steps;
-  StagePlan p;
-  idocp_rbd_ilqr_io_t d = *io;
-  const double* d_points;
-  double *d_status = nullptr, *d_ws = nullptr;
-  p.update(io->q_traj, (S + 1) * N * nq, &d.q_traj);
-  p.update(io->v_traj, (S + 1) * N * nv, &d.v_traj);
-  p.update(io->u_traj, S * N * nu, &d.u_traj);
-  p.update(io->a_traj, S * N * nv, &d.a_traj);
-  p.update(io->f_traj, S * N * nf, &d.f_traj);
-  p.update(io->cost, N, &d.cost);
-  p.update(io->violation, N, &d.violation);
-  p.in(io->u_min, nu, &d.u_min);
-  p.in(io->u_max, nu, &d.u_max);
-  p.in(contact_points, S * N * nf, &d_points);
-  p.out(io->alpha_accepted, N, &d.alpha_accepted);
-  p.out(io->expected, 2 * N, &d.expected);
-  p.deviceOnly((N + 1) / 2, &d_status);
-  p.deviceOnly(ilqrWorkspace(h, n, steps).total, &d_ws);
-  rc = stageIn(h, p); if (rc) return rc;
-  d.lqr_status = reinterpret_cast<int*>(d_status);
-  rc = iterateDevice(h, o, n, steps, active, time_step, dt, d_points, d, d_ws, touchdown_impulse); if (rc) return rc;
-  HIP_TRY(hipMemcpyAsync(io->lqr_status, d_status, sizeof(int) * N, hipMemcpyDeviceToHost, h->stream));
-  return stageOut(h, p);
+  return iterateDevice(h, o, n, steps, active, time_step, dt, contact_points, *io, static_cast<double*>(io->workspace), touchdown_impulse, true);
+}
+
+int idocp_rbd_ilqr_iterate_gn(idocp_rbd_t* h, const idocp_rbd_objective_t* o, int n, int steps, const int* active, double time_step, double dt,
+                              const double* contact_points, const idocp_rbd_ilqr_io_t* io, int touchdown_impulse) {
+  return iterateHost("idocp_rbd_ilqr_iterate_gn", h, o, n, steps, active, time_step, dt, contact_points, io, touchdown_impulse, true);
 }
 
 }  // extern "C"

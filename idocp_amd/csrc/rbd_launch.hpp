@@ -118,6 +118,28 @@ struct RbdLqrArgs {
   int n, steps, nx, nu;
 };
 void rbdLqrBackward(bool quadruped, const RbdLqrArgs& a, hipStream_t st);
+// The same recursion with G_k^T G_k added to the stage Hessian (idocp_rbd_lqr_backward_gn): G [steps][n][g_rows][nx + nu] row-major, g_rows a
+// multiple of 4.  Another template form of the same kernel; the form above keeps its arguments and its code.  One launch.
+struct RbdLqrGnArgs : RbdLqrArgs {
+  const double* G;
+  int g_rows;
+};
+void rbdLqrBackwardGn(bool quadruped, const RbdLqrGnArgs& a, hipStream_t st);
+
+// The residual rows of the acceleration and contact-force terms (rbd_residual_kernel.hip; idocp_rbd_linearize_rollout_cost).  Every pointer: DEVICE
+// memory.  One pass of one step: `count` samples whose forward solution a [count][nv], f [count][nf] and column-major derivative blocks da_dq, da_dv
+// [count][nv * nv], da_du [count][nv * nu], df_dq, df_dv [count][nf * nv], df_du [count][nf * nu] lie in scratch (16-byte aligned pieces); table: the
+// 2 R doubles of idocp_host::residualTable; mask: bit c = contact c is active at the step.  G [count][R][nz] row-major, rho [count][R], lx
+// [count][2 nv] and lu [count][nu] are the slices of the pass; lx and lu HOLD the diagonal part and gain G^T rho.  An output that is NULL is not stored.
+// One workgroup per RBD_RESIDUAL_SAMPLES consecutive samples (quadruped) or RBD_RESIDUAL_SAMPLES_CHAIN (chain), any count.  One launch.
+// Returns false, having launched nothing, for a chain outside 2 .. 8 joints.
+constexpr int RBD_RESIDUAL_THREADS = 256, RBD_RESIDUAL_SAMPLES = 2, RBD_RESIDUAL_SAMPLES_CHAIN = 16;
+struct RbdResidualArgs {
+  const double *a, *f, *da_dq, *da_dv, *da_du, *df_dq, *df_dv, *df_du, *table;
+  double *G, *rho, *lx, *lu;
+  int count, mask;
+};
+bool rbdResidual(int nv, bool quadruped, const RbdResidualArgs& a, hipStream_t st);
 
 // Gradients of an objective along a rollout (rbd_gradient_kernel.hip; the arrays of idocp_rbd_gradient_io_t).  Every pointer: DEVICE memory;
 // q, v [steps (+ 1 if terminal)][n][..], u [steps][n][nu] or NULL, q_ref / v_ref the objective's tables AT the window's first step, block its

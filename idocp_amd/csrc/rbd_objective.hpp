@@ -212,5 +212,25 @@ inline void lqrWeights(const RbdObjectivePlan& o, double* out) {
   for (int r = 0; r < nv; ++r) { out[ixf + r] = b.qf_weight[r]; out[ixf + nv + r] = b.vf_weight[r]; }
 }
 
+// ---- the acceleration and contact-force terms as Gauss-Newton residual rows (idocp_rbd_linearize_rollout_cost; include/idocp_hip.h defines them)
+// R = roundup4(nv + 3 ncontacts) rows: the accelerations, the contact forces, padding
+inline int residualRows(const RbdObjectivePlan& o) { return (o.nv + 3 * o.ncontacts + 3) / 4 * 4; }
+// "" when every a_weight and f_weight entry has a square root, else the text that names the term
+inline std::string residualUnsupported(const RbdObjectivePlan& o) {
+  for (int r = 0; r < o.nv; ++r) if (o.block.a_weight[r] < 0.0) return "a negative a_weight: a residual row needs its square root";
+  for (int c = 0; c < o.ncontacts; ++c)
+    for (int x = 0; x < 3; ++x) if (o.block.f_weight[c][x] < 0.0) return "a negative f_weight: a residual row needs its square root";
+  return "";
+}
+// out [2 R]: the scales s_r = sqrt(dt w_r) of the rows, then the references of the rows (f_ref on the force rows, 0 elsewhere)
+inline void residualTable(const RbdObjectivePlan& o, double* out) {
+  const RbdScoreBlock& b = o.block;
+  const int R = residualRows(o);
+  for (int i = 0; i < 2 * R; ++i) out[i] = 0.0;
+  for (int r = 0; r < o.nv; ++r) out[r] = std::sqrt(b.dt * b.a_weight[r]);
+  for (int c = 0; c < o.ncontacts; ++c)
+    for (int x = 0; x < 3; ++x) { out[o.nv + 3 * c + x] = std::sqrt(b.dt * b.f_weight[c][x]); out[R + o.nv + 3 * c + x] = b.f_ref[c][x]; }
+}
+
 }  // namespace idocp_host
 #endif  // IDOCP_RBD_OBJECTIVE_HPP_

@@ -401,6 +401,16 @@ class Robot {
                      const std::vector<std::vector<Eigen::Vector3d>>& contact_points, std::vector<Eigen::VectorXd>& q, std::vector<Eigen::VectorXd>& v,
                      std::vector<Eigen::VectorXd>& u, double& total_cost, const double regularization = 1e-6, const double armijo = 1e-4,
                      const int trials = 8) {
+    return ilqrIterateForm(false, cost, t0, dt, time_step, contact_status, contact_points, q, v, u, total_cost, regularization, armijo, trials);
+  }
+
+ private:
+  // the body of ilqrIterate and ilqrIterateGaussNewton: idocp_rbd_ilqr_iterate or, with gauss_newton, idocp_rbd_ilqr_iterate_gn
+  template <class CostFunctionT>
+  double ilqrIterateForm(const bool gauss_newton, const CostFunctionT& cost, const double t0, const double dt, const double time_step,
+                         const std::vector<ContactStatus>& contact_status, const std::vector<std::vector<Eigen::Vector3d>>& contact_points,
+                         std::vector<Eigen::VectorXd>& q, std::vector<Eigen::VectorXd>& v, std::vector<Eigen::VectorXd>& u, double& total_cost,
+                         const double regularization, const double armijo, const int trials) {
     const int steps = (int)u.size(), nc = model_.ncontacts;
     if (steps < 1 || (int)q.size() != steps + 1 || (int)v.size() != steps + 1 ||
         (nc > 0 && ((int)contact_status.size() != steps || (int)contact_points.size() != steps))) {
@@ -431,7 +441,8 @@ class Robot {
     io.q_traj = qs.data(); io.v_traj = vs.data(); io.u_traj = us.data(); io.cost = &total_cost; io.violation = &violation;
     io.regularization = regularization; io.armijo = armijo; io.shrink = 0.5; io.alpha_min = 0.0; io.penalty = 0.0; io.trials = trials;
     io.alpha_accepted = &alpha; io.lqr_status = &status; io.expected = expected;
-    const int rc = idocp_rbd_ilqr_iterate(rbd_.h, objective, 1, steps, nc > 0 ? act.data() : nullptr, time_step, dt, nc > 0 ? pts.data() : nullptr, &io, 0);
+    const int rc = (gauss_newton ? idocp_rbd_ilqr_iterate_gn : idocp_rbd_ilqr_iterate)(rbd_.h, objective, 1, steps, nc > 0 ? act.data() : nullptr, time_step,
+                                                                                       dt, nc > 0 ? pts.data() : nullptr, &io, 0);
     idocp_rbd_objective_destroy(objective);
     ok(rc);
     for (int k = 0; k <= steps; ++k) {
@@ -440,6 +451,17 @@ class Robot {
       if (k < steps) for (size_t j = 0; j < nu; ++j) u[k][j] = us[k * nu + j];
     }
     return alpha;
+  }
+
+ public:
+  // The same iteration under the FULL cost, an ADDITION: idocp_rbd_ilqr_iterate_gn with n = 1 -- the cost's a_weight and f_weight enter as
+  // Gauss-Newton residual rows (idocp_hip.h has the definition), so a cost whose u_weight is zero is fine where a_weight is not.
+  template <class CostFunctionT>
+  double ilqrIterateGaussNewton(const CostFunctionT& cost, const double t0, const double dt, const double time_step,
+                                const std::vector<ContactStatus>& contact_status, const std::vector<std::vector<Eigen::Vector3d>>& contact_points,
+                                std::vector<Eigen::VectorXd>& q, std::vector<Eigen::VectorXd>& v, std::vector<Eigen::VectorXd>& u, double& total_cost,
+                                const double regularization = 1e-6, const double armijo = 1e-4, const int trials = 8) {
+    return ilqrIterateForm(true, cost, t0, dt, time_step, contact_status, contact_points, q, v, u, total_cost, regularization, armijo, trials);
   }
   // Robot::framePosition / frameRotation / framePlacement (robot.hxx:206-233): of any frame of the URDF (pinocchio's frame numbering, as the
   // contact frames and the task-space costs use it), at the configuration of the last updateFrameKinematics / updateKinematics

@@ -1202,6 +1202,73 @@ int idocp_rbd_ilqr_iterate_device(idocp_rbd_t* h, const idocp_rbd_objective_t* o
 int idocp_rbd_ilqr_iterate(idocp_rbd_t* h, const idocp_rbd_objective_t* o, int n, int steps, const int* active, double time_step, double dt,
                            const double* contact_points, const idocp_rbd_ilqr_io_t* io, int touchdown_impulse);
 
+/* ---- iLQR on the full cost: the acceleration and contact-force terms as Gauss-Newton residual rows (rbd_residual_kernel.hip, the GN form of
+ * rbd_lqr_kernel.hip).  ADDITIONS.  The calls above refuse an objective with a non-zero a_weight or f_weight and keep doing so; the calls below
+ * take every objective the score takes.  With nx = 2 nv, nz = nx + nu and R = roundup4(nv + 3 ncontacts) (32 on the quadruped, 4 or 8 on a chain),
+ * the extra cost of stage k is 1/2 |rho|^2 and G = d rho / d [dq; dv; du] -- this is the definition:
+ *   rows r < nv:        rho_r = s_r a_r,                       G[r][:] = s_r [da_r/dq | da_r/dv | da_r/du],  s_r = sqrt(dt a_weight[r])
+ *   rows nv + 3 c + x:  rho = s (f[c][x] - f_ref[c][x]),       G       = s [df/dq | df/dv | df/du],          s = sqrt(dt f_weight[c][x])
+ *                       where contact c is active at step k, else rho and the row of G are zero
+ *   the rows behind nv + 3 ncontacts (padding) are zero.
+ * a, f and the derivative blocks are those idocp_rbd_forward_dynamics_derivatives_batch returns in STAGE mode at slice k (also where step k + 1
+ * carries a touchdown impulse: impulses are not scored).  s is the correctly rounded square root of the rounded product, and each entry of G and
+ * of rho is ONE rounded product of s and the block entry (of s and the rounded difference f - f_ref).
+ * idocp_rbd_objective_residual_rows returns R (0 for a NULL objective). */
+int idocp_rbd_objective_residual_rows(const idocp_rbd_objective_t* o);
+/* idocp_rbd_linearize_rollout_cost: what idocp_rbd_linearize_rollout takes plus an objective; step k of the rollout is step k of the objective and
+ * steps <= the objective's steps.  Every output is optional (at least one is needed):
+ *   A_traj, B_traj                 bit for bit what idocp_rbd_linearize_rollout writes
+ *   G_traj   [steps][n][R][nz]     row-major
+ *   rho_traj [steps][n][R]
+ *   lx_traj  [steps + 1][n][nx], lu_traj [steps][n][nu]: the FULL gradient of `cost`: what idocp_rbd_objective_gradients defines for the diagonal
+ *     terms (first_step 0, the terminal slice included) plus Gx^T rho and Gu^T rho; entry c is d_c + t_c with t_c = sum_r G[r][c] rho_r accumulated
+ *     over the rows in index order by fused multiply-adds from 0.
+ * With every a_weight and f_weight zero, G and rho are zero and lx, lu compare equal to the gradient call's.
+ * Per step the derivative composition runs with its a, f, da_*, df_* outputs in scratch the handle owns -- it only grows, is capped at the 256 MiB of
+ * the derivative call and cuts the sample axis into passes the same way --, and one launch per pass of rbd_residual_kernel.hip turns the column-major
+ * blocks into the row-major scaled G, rho and G^T rho.  A sample's bits depend neither on n, nor on the outputs asked for, nor on the form of the call.
+ * A non-finite input of a sample at a slice (q, v, u, contact_points, or a singular M / J M^-1 J^T) makes that sample's outputs of that slice NaN
+ * and touches nothing else.  Refused: what idocp_rbd_linearize_rollout refuses, a NULL objective or io, an objective of another handle, steps beyond
+ * the objective's, no output at all, u_traj NULL under a non-zero u_weight when lu_traj or lx_traj is asked for, (steps + 1) * n beyond an int (all
+ * IDOCP_E_ARG), and a NEGATIVE a_weight or f_weight entry (IDOCP_E_UNSUPPORTED: a residual row needs its square root).  Task-space terms,
+ * contact_distance and the constraint rows are still not differentiated. */
+typedef struct idocp_rbd_cost_linearization_io {
+  double *A_traj, *B_traj;      /* [steps][n][2nv*2nv], [steps][n][2nv*nu], column-major blocks */
+  double *G_traj;               /* [steps][n][R][nz], row-major */
+  double *rho_traj;             /* [steps][n][R] */
+  double *lx_traj, *lu_traj;    /* [steps + 1][n][2nv], [steps][n][nu] */
+} idocp_rbd_cost_linearization_io_t;
+/* Host pointers; stages through the handle's buffer and returns when the outputs are in place. */
+int idocp_rbd_linearize_rollout_cost(idocp_rbd_t* h, const idocp_rbd_objective_t* o, int n, int steps, const int* active, double time_step, double dt,
+                                     const double* u_traj, const double* contact_points, const double* q_traj, const double* v_traj,
+                                     const idocp_rbd_cost_linearization_io_t* io, int touchdown_impulse);
+/* Device pointers; asynchronous on idocp_rbd_stream(h); allocates only when a scratch has to grow. */
+int idocp_rbd_linearize_rollout_cost_device(idocp_rbd_t* h, const idocp_rbd_objective_t* o, int n, int steps, const int* active, double time_step,
+                                            double dt, const double* u_traj, const double* contact_points, const double* q_traj,
+                                            const double* v_traj, const idocp_rbd_cost_linearization_io_t* io, int touchdown_impulse);
+
+/* idocp_rbd_lqr_backward_gn: the recursion of idocp_rbd_lqr_backward on the same io, with the stage Hessian gaining G_k^T G_k, G_k = G_traj[k][i]
+ * ([g_rows][nz] row-major, columns [dq | dv | du]: what the call above writes with g_rows = R):
+ *   Qxx = Wx + A^T P A + Gx^T Gx,   Qux = B^T P A + Gu^T Gx,   Quu = Wu + regularization I + B^T P B + Gu^T Gu.
+ * G^T G is accumulated on top of Z^T P Z, four rows of G per v_mfma_f64_16x16x4_f64 in row order.  The gradients lx, lu are the caller's (the FULL
+ * ones of the call above); G enters the Hessian only.  g_rows must be a multiple of 4 within 4 .. 64, else IDOCP_E_ARG; G_traj = NULL with
+ * g_rows = 0 is idocp_rbd_lqr_backward bit for bit (the same kernel is launched), G_traj = NULL with another g_rows or g_rows = 0 with a G_traj is
+ * IDOCP_E_ARG.  Failure is per sample as there; a non-finite entry of G_traj[k][i] fails sample i at step k. */
+int idocp_rbd_lqr_backward_gn(idocp_rbd_t* h, int n, int steps, const idocp_rbd_lqr_io_t* io, int g_rows, const double* G_traj);
+/* Device pointers; asynchronous on idocp_rbd_stream(h); allocates nothing. */
+int idocp_rbd_lqr_backward_gn_device(idocp_rbd_t* h, int n, int steps, const idocp_rbd_lqr_io_t* io, int g_rows, const double* G_traj);
+
+/* idocp_rbd_ilqr_iterate_gn: idocp_rbd_ilqr_iterate on the same io with idocp_rbd_linearize_rollout_cost_device in place of the linearisation and
+ * the gradients, idocp_rbd_lqr_backward_gn_device (g_rows = R) in place of the backward pass, and the same trial rounds.  It takes any objective the
+ * score takes; the diagonal weights are those of idocp_rbd_objective_lqr_weights_device (which this call reads without its refusal).  With every
+ * a_weight and f_weight zero it reproduces idocp_rbd_ilqr_iterate to rounding (the sums differ: not bit for bit).  The workspace is the one of
+ * idocp_rbd_ilqr_iterate with G_traj [steps][n][R][nz] carved BEHIND everything else (after done); rho is not kept. */
+unsigned long long idocp_rbd_ilqr_gn_workspace_bytes(const idocp_rbd_t* h, int n, int steps);
+int idocp_rbd_ilqr_iterate_gn_device(idocp_rbd_t* h, const idocp_rbd_objective_t* o, int n, int steps, const int* active, double time_step, double dt,
+                                     const double* contact_points, const idocp_rbd_ilqr_io_t* io, int touchdown_impulse);
+int idocp_rbd_ilqr_iterate_gn(idocp_rbd_t* h, const idocp_rbd_objective_t* o, int n, int steps, const int* active, double time_step, double dt,
+                              const double* contact_points, const idocp_rbd_ilqr_io_t* io, int touchdown_impulse);
+
 /* ---- Sampling around a torque sequence: perturb, weigh, average (rbd_sample_kernel.hip).  Every call of this block is an ADDITION (the reference
  * has no counterpart).  With idocp_rbd_rollout_policy_device and idocp_rbd_score_rollout_device between the first and the second, one iteration of
  * a sampling-based refinement (the MPPI update: the softmin-weighted mean of the sampled torque sequences) runs on the handle's stream without a

@@ -17,6 +17,8 @@ ROLLOUT_STEPS open-loop steps with every contact active and no touchdown impulse
 idocp_rbd_rollout_footholds_device (one latch launch more per step); both carry ms_per_step.  The lqr_* rows are idocp_rbd_lqr_backward_device over
 16 steps (lqr_rows has their description); run with fdd_linearize_s16 they also carry their ratio to the linearisation that feeds them.  The grad_*,
 ilqr_accept and ilqr_iterate rows are the cost gradients, the acceptance step and one whole iLQR iteration (ilqr_rows has their description).
+The gn_* rows are the cost linearisation with residual rows, the backward pass with G^T G and one full-cost iteration (gn_rows has their
+description).
 
     python profiles/rbd_throughput.py [--n 122880] [--launches 20] [--warmup 5] [--rows name,name,...]
 """
@@ -492,6 +494,115 @@ def ilqr_rows(wanted, lib, rt, h, stream, m, n, measure, res):
         lib.idocp_device_free(d)
 
 
+GN_ROWS = ("gn_linearize_s16", "gn_residual_pass_copy", "gn_lqr_backward", "gn_iterate")
+GN_STEPS = 16
+GN_RESIDUAL_DOUBLES = 1470 + 48 + 1536 + 32 + 48      # per quadruped sample and launch of rbd_residual_kernel: a, f and the six blocks in; lx, lu in; G, rho, lx, lu out
+GN_PASS = ((256 << 20) // 8) // (1470 + 8) // 2 * 2      # samples per pass of the cost linearisation (ResidualPlan of rbd_capi.hip)
+
+
+def gn_rows(wanted, lib, rt, h, stream, m, n, measure, res):
+    """the gn_* rows on 16 steps of ANYmal standing on four feet under the ANYmal workload's own cost (a_weight and f_weight set, u_weight zero),
+    about a rollout of zero torques: gn_linearize_s16 is idocp_rbd_linearize_rollout_cost_device with every output (read it against
+    fdd_linearize_s16); gn_residual_pass_copy is a device-to-device copy of the bytes ONE launch of rbd_residual_kernel touches (a pass of GN_PASS
+    samples; the kernel's own time comes from a kernel trace of the gn_linearize_s16 row); gn_lqr_backward is idocp_rbd_lqr_backward_gn_device on what
+    the linearisation wrote, every output (read it against lqr_gains_ilqr); gn_iterate is one idocp_rbd_ilqr_iterate_gn_device with two trial rounds
+    (read it against ilqr_iterate)."""
+    from idocp_amd.workloads import anymal_problem
+    rt.hipMemcpyAsync.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p]
+    rt.hipMemsetAsync.argtypes = [C.c_void_p, C.c_int, C.c_size_t, C.c_void_p]
+    nq, nv, nu, nf, S = m.nq, m.nv, m.nu, 3 * m.ncontacts, GN_STEPS
+    nx, nz = 2 * nv, 2 * nv + nu
+    rng = np.random.default_rng(13)
+    cost = anymal_problem(m, trotting_ref=False)[0]
+    ts, dt = 0.05, 0.01
+    o = C.c_void_p()
+    capi.check(lib.idocp_rbd_objective_create(h, C.byref(cost), None, 0.0, dt, S, C.byref(o)), "objective")
+    R = lib.idocp_rbd_objective_residual_rows(o)
+    want_iterate = not wanted or "gn_iterate" in wanted
+    sizes = {"q": (S + 1) * n * nq, "v": (S + 1) * n * nv, "u": S * n * nu, "a": S * n * nv, "f": S * n * nf, "pts": S * n * nf,
+             "A": S * n * nx * nx, "B": S * n * nx * nu, "G": S * n * R * nz, "rho": S * n * R, "lx": (S + 1) * n * nx, "lu": S * n * nu,
+             "K": S * n * nx * nu, "k": S * n * nu, "P0": n * nx * nx, "p0": n * nx, "wx": nx, "wu": nu, "wxf": nx,
+             "cost": n, "viol": n, "expected": 2 * n, "alpha_accepted": n, "status": (n + 1) // 2}
+    if want_iterate:
+        sizes["work"] = lib.idocp_rbd_ilqr_gn_workspace_bytes(h, n, S) // 8
+    dev = {}
+    for key, size in sizes.items():
+        dev[key] = C.c_void_p()
+        capi.check(lib.idocp_device_alloc(C.byref(dev[key]), 8 * size), "alloc")
+        assert rt.hipMemsetAsync(dev[key], 0, 8 * size, stream) == 0
+    q0 = np.tile(ANYMAL_Q_STANDING, (n, 1))
+    q0[:, 7:] += rng.uniform(-0.02, 0.02, (n, nv - 6))
+    feet = np.zeros(nf)
+    capi.check(lib.idocp_model_contact_positions(C.byref(m), np.ascontiguousarray(ANYMAL_Q_STANDING).ctypes.data, feet.ctypes.data), "feet")
+    pts = np.ascontiguousarray(np.broadcast_to(feet, (S, n, nf)))
+    W = lambda name, k: np.array(getattr(cost, name)[:k])      # noqa: E731
+    for key, x in (("q", q0), ("pts", pts), ("wx", dt * np.concatenate([W("q_weight", nv), W("v_weight", nv)])), ("wu", dt * W("u_weight", nu)),
+                   ("wxf", np.concatenate([W("qf_weight", nv), W("vf_weight", nv)]))):
+        x = np.ascontiguousarray(x)
+        capi.check(lib.idocp_device_upload(dev[key], x.ctypes.data, x.nbytes), "upload")
+    act = (C.c_int * (4 * S))(*([1] * (4 * S)))
+    capi.check(lib.idocp_rbd_rollout_device(h, n, S, act, ts, dt, dev["u"], dev["pts"], dev["q"], dev["v"], dev["a"], dev["f"], 0), "rollout")
+    sc = capi.RbdScoreIO()
+    sc.q_traj, sc.v_traj, sc.u_traj, sc.a_traj, sc.f_traj, sc.cost, sc.violation = dev["q"], dev["v"], dev["u"], dev["a"], dev["f"], dev["cost"], dev["viol"]
+    capi.check(lib.idocp_rbd_score_rollout_device(h, o, n, 0, S, act, 1, 0, C.byref(sc)), "score")
+
+    lin = capi.RbdCostLinearizationIO()
+    lin.A_traj, lin.B_traj, lin.G_traj, lin.rho_traj, lin.lx_traj, lin.lu_traj = dev["A"], dev["B"], dev["G"], dev["rho"], dev["lx"], dev["lu"]
+    linearize = lambda: capi.check(lib.idocp_rbd_linearize_rollout_cost_device(h, o, n, S, act, ts, dt, dev["u"], dev["pts"], dev["q"], dev["v"], C.byref(lin), 0), "linearize_cost")  # noqa: E731
+    linearize()      # (gn_lqr_backward reads what it wrote, whether or not its own row is asked for)
+    lqr = capi.RbdLqrIO()
+    for field, key in (("A_traj", "A"), ("B_traj", "B"), ("x_weight", "wx"), ("u_weight", "wu"), ("xf_weight", "wxf"), ("lx_traj", "lx"), ("lu_traj", "lu"),
+                       ("K_traj", "K"), ("k_traj", "k"), ("P0", "P0"), ("p0", "p0"), ("expected", "expected"), ("status", "status")):
+        setattr(lqr, field, dev[key])
+    lqr.regularization = 1e-6
+    pass_samples = min(n, GN_PASS)
+    pass_bytes = 8 * GN_RESIDUAL_DOUBLES * pass_samples
+
+    def pass_copy():
+        assert rt.hipMemcpyAsync(dev["A"], dev["G"], pass_bytes, 3, stream) == 0
+
+    plan = (("gn_lqr_backward", lambda: capi.check(lib.idocp_rbd_lqr_backward_gn_device(h, n, S, C.byref(lqr), R, dev["G"]), "lqr_gn")),
+            ("gn_residual_pass_copy", pass_copy), ("gn_linearize_s16", linearize))      # (the copy overwrites the front of A: the linearisation runs after it)
+    for row, launch in plan:
+        if wanted and row not in wanted:
+            continue
+        measure(row, launch)
+        res[row]["steps"] = S
+        if row == "gn_lqr_backward":
+            status = np.zeros((n + 1) // 2)
+            capi.check(lib.idocp_rbd_synchronize(h), "synchronize")
+            capi.check(lib.idocp_device_download(status.ctypes.data, dev["status"], status.nbytes), "download")
+            res["gn_lqr_all_solved"] = bool((status.view(np.int32)[:n] == -1).all())
+            res[row].update({"g_rows": R, "ms_per_step": round(res[row]["ms_median"] / S, 4)})
+            if "lqr_gains_ilqr" in res:
+                res[row]["ratio_to_lqr_gains_ilqr"] = round(res[row]["ms_median"] / res["lqr_gains_ilqr"]["ms_median"], 3)
+        if row == "gn_residual_pass_copy":
+            res[row].update({"samples": pass_samples, "bytes": pass_bytes, "GB_per_s": round(pass_bytes / res[row]["ms_median"] / 1e6, 1),
+                             "residual_launches_per_linearisation": S * -(-n // pass_samples)})
+        if row == "gn_linearize_s16":
+            res[row].update({"G_traj_bytes": 8 * sizes["G"], "passes_per_step": -(-n // pass_samples)})
+            if "fdd_linearize_s16" in res:
+                res[row]["ratio_to_fdd_linearize_s16"] = round(res[row]["ms_median"] / res["fdd_linearize_s16"]["ms_median"], 3)
+    if want_iterate:
+        io = capi.RbdIlqrIO()
+        for field, key in (("q_traj", "q"), ("v_traj", "v"), ("u_traj", "u"), ("a_traj", "a"), ("f_traj", "f"), ("cost", "cost"), ("violation", "viol"),
+                           ("alpha_accepted", "alpha_accepted"), ("lqr_status", "status"), ("expected", "expected"), ("workspace", "work")):
+            setattr(io, field, dev[key])
+        io.regularization, io.armijo, io.shrink, io.alpha_min, io.penalty, io.trials = 1e-6, 1e-4, 0.5, 1e-3, 0.0, 2
+        measure("gn_iterate", lambda: capi.check(lib.idocp_rbd_ilqr_iterate_gn_device(h, o, n, S, act, ts, dt, dev["pts"], C.byref(io), 0), "iterate_gn"))
+        res["gn_iterate"].update({"steps": S, "trials": 2, "workspace_bytes": 8 * sizes["work"]})
+        status = np.zeros((n + 1) // 2)
+        capi.check(lib.idocp_rbd_synchronize(h), "synchronize")
+        capi.check(lib.idocp_device_download(status.ctypes.data, dev["status"], status.nbytes), "download")
+        res["gn_iterate_all_solved"] = bool((status.view(np.int32)[:n] == -1).all())
+        if "ilqr_iterate" in res:
+            res["gn_iterate"]["ratio_to_ilqr_iterate"] = round(res["gn_iterate"]["ms_median"] / res["ilqr_iterate"]["ms_median"], 3)
+    capi.check(lib.idocp_rbd_synchronize(h), "synchronize")
+    lib.idocp_rbd_objective_destroy(o)
+    for d in dev.values():
+        lib.idocp_device_free(d)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--n", type=int, default=122880)
@@ -602,6 +713,8 @@ def main():
         lqr_rows(wanted, lib, rt, h, stream, m, n, measure, res)
     if not wanted or set(wanted) & set(ILQR_ROWS):
         ilqr_rows(wanted, lib, rt, h, stream, m, n, measure, res)
+    if not wanted or set(wanted) & set(GN_ROWS):
+        gn_rows(wanted, lib, rt, h, stream, m, n, measure, res)
     ran = [k for k in res if isinstance(res[k], dict)]
     for key, src, width, rows in (("tau_finite", "tau", nv, ("stage_", "impulse_")), ("fd_a_finite", "fd_a", nv, ("fd_",)),
                                   ("policy_u_finite", "u_out", m.nu, ("policy_", "fd_step_closed_loop"))):
