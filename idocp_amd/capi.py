@@ -184,6 +184,12 @@ class RbdCostLinearizationIO(C.Structure):
     _fields_ = [(name, C.c_void_p) for name in OUTPUTS]
 
 
+class RbdPenaltyLinearizationIO(C.Structure):
+    """idocp_rbd_penalty_linearization_io_t: the requested outputs of idocp_rbd_linearize_rollout_penalty(_device); a pointer left at None is NULL"""
+    OUTPUTS = ("A_traj", "B_traj", "G_traj", "rho_traj", "D_traj", "lx_traj", "lu_traj")
+    _fields_ = [(name, C.c_void_p) for name in OUTPUTS]
+
+
 RBD_STAGE, RBD_IMPULSE = 0, 1
 RBD_SCORE_MAX_WINDOW = 1024
 RBD_REDUCE_CHUNK = 1024      # IDOCP_RBD_REDUCE_CHUNK: samples per chunk of the fixed-order sums
@@ -442,6 +448,18 @@ def _proto(lib):
             f = getattr(lib, name + form)
             f.argtypes = args
             f.restype = ci
+    for form in ("", "_device"):
+        for name, args in (("idocp_rbd_score_penalty", [vp, vp, ci, ci, ci, c_int_p, ci, vp, vp, vp, vp, vp, vp]),
+                           ("idocp_rbd_linearize_rollout_penalty", [vp, vp, ci, ci, c_int_p, cd, cd, vp, vp, vp, vp, P(RbdPenaltyLinearizationIO), cd, ci]),
+                           ("idocp_rbd_lqr_backward_gn_diag", [vp, ci, ci, P(RbdLqrIO), ci, vp, vp]),
+                           ("idocp_rbd_ilqr_iterate_penalty", [vp, vp, ci, ci, c_int_p, cd, cd, vp, P(RbdIlqrIO), ci])):
+            f = getattr(lib, name + form)
+            f.argtypes = args
+            f.restype = ci
+    lib.idocp_rbd_objective_constraint_rows.argtypes = [vp]
+    lib.idocp_rbd_objective_constraint_rows.restype = ci
+    lib.idocp_rbd_ilqr_penalty_workspace_bytes.argtypes = [vp, vp, ci, ci]
+    lib.idocp_rbd_ilqr_penalty_workspace_bytes.restype = C.c_ulonglong
     lib.idocp_rbd_objective_residual_rows.argtypes = [vp]
     lib.idocp_rbd_objective_residual_rows.restype = ci
     lib.idocp_rbd_ilqr_gn_workspace_bytes.argtypes = [vp, ci, ci]

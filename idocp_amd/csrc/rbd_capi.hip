@@ -568,6 +568,12 @@ struct CostLinearization {
   const double* table;      // idocp_host::residualTable of the objective, device memory
   double *G, *rho, *lx, *lu;
   int R;
+  // the penalty form (idocp_rbd_linearize_rollout_penalty): G and rho have R + rc rows, D [steps][n][nz]
+  bool penalty = false;
+  const idocp_host::RbdScoreBlock* block = nullptr;
+  double* D = nullptr;
+  double mu = 0.0;
+  int rc = 0;
 };
 
 // every pointer: device memory.  cost == nullptr: idocp_rbd_linearize_rollout.  With cost, step k takes the sample axis in the passes of
@@ -581,7 +587,7 @@ int linearizeDevice(idocp_rbd* h, int n, int steps, const int* active, double ti
     const ResidualPlan p = residualPlan(h, n);
     int rc = h->gn.grow(p.total, h->stream); if (rc) return rc;
     double* const S = h->gn.ptr;
-    const size_t R = (size_t)cost->R, nz = nx + nu;
+    const size_t R = (size_t)cost->R + (size_t)cost->rc, nz = nx + nu;      // (rc = 0 but for the penalty form)
     auto at = [](double* x, size_t off) { return x ? x + off : nullptr; };
     for (int k = 0; k < steps; ++k) {
       const int mask = h->quadruped ? maskOf(h, active + (size_t)k * h->model.ncontacts) : 0;
@@ -600,7 +606,18 @@ int linearizeDevice(idocp_rbd* h, int n, int steps, const int* active, double ti
         r.table = cost->table;
         r.G = at(cost->G, F * R * nz); r.rho = at(cost->rho, F * R); r.lx = at(cost->lx, F * nx); r.lu = at(cost->lu, F * nu);
         r.count = cnt; r.mask = mask;
-        if (!rbdResidual(h->model.nv, h->quadruped, r, h->stream)) { set_last_error("idocp_rbd_linearize_rollout_cost: no residual kernel for this model"); return IDOCP_E_UNSUPPORTED; }
+        bool launched;
+        if (cost->penalty) {
+          RbdResidualPenaltyArgs pr;
+          static_cast<RbdResidualArgs&>(pr) = r;
+          pr.q = io.q; pr.v = io.v; pr.u = io.u; pr.block = cost->block; pr.D = at(cost->D, F * nz);
+          pr.dtmu = dt * cost->mu; pr.scale = std::sqrt(pr.dtmu); pr.rc = cost->rc;
+          launched = rbdResidualPenalty(h->model.nv, h->quadruped, pr, h->stream);
+        } else launched = rbdResidual(h->model.nv, h->quadruped, r, h->stream);
+        if (!launched) {
+          set_last_error(std::string(cost->penalty ? "idocp_rbd_linearize_rollout_penalty" : "idocp_rbd_linearize_rollout_cost") + ": no residual kernel for this model");
+          return IDOCP_E_UNSUPPORTED;
+        }
         HIP_TRY(hipGetLastError());
       }
     }
@@ -740,6 +757,34 @@ int linearizeCostDevice(idocp_rbd* h, const idocp_rbd_objective* o, int n, int s
   return linearizeDevice(h, n, steps, active, time_step, dt, u, contact_points, q_traj, v_traj, io.A_traj, io.B_traj, touchdown_impulse, &c);
 }
 
+// what idocp_rbd_linearize_rollout_penalty refuses beyond the cost call (whose check runs first with `some` = an output of this call's was asked for)
+int checkPenalty(const char* who, const idocp_rbd_objective* o, double mu) {
+  const std::string w(who);
+  if (!std::isfinite(mu) || mu < 0.0) { set_last_error(w + ": mu must be finite and non-negative"); return IDOCP_E_ARG; }
+  const std::string pair = idocp_host::penaltyPairRefused(o->plan);
+  if (!pair.empty()) { set_last_error(w + ": " + pair); return IDOCP_E_ARG; }
+  return IDOCP_OK;
+}
+
+// every pointer: device memory.  As linearizeCostDevice, with the penalty form of the residual kernel: one launch per pass for both kinds of rows.
+int linearizePenaltyDevice(idocp_rbd* h, const idocp_rbd_objective* o, int n, int steps, const int* active, double time_step, double dt, const double* u,
+                           const double* contact_points, const double* q_traj, const double* v_traj, const idocp_rbd_penalty_linearization_io_t& io,
+                           double mu, int touchdown_impulse) {
+  if (!io.G_traj && !io.rho_traj && !io.D_traj && !io.lx_traj && !io.lu_traj)
+    return linearizeDevice(h, n, steps, active, time_step, dt, u, contact_points, q_traj, v_traj, io.A_traj, io.B_traj, touchdown_impulse);
+  if (io.lx_traj || io.lu_traj) {
+    RbdGradientArgs g;
+    g.q = q_traj; g.v = v_traj; g.u = u; g.q_ref = o->d_q_ref; g.v_ref = o->d_v_ref; g.block = o->d_block;
+    g.lx = io.lx_traj; g.lu = io.lu_traj; g.n = n; g.steps = steps; g.terminal = 1;
+    rbdGradient(h->model.nv, h->quadruped, g, h->stream);
+    HIP_TRY(hipGetLastError());
+  }
+  CostLinearization c;
+  c.table = o->d_residual; c.G = io.G_traj; c.rho = io.rho_traj; c.lx = io.lx_traj; c.lu = io.lu_traj; c.R = idocp_host::residualRows(o->plan);
+  c.penalty = true; c.block = o->d_block; c.D = io.D_traj; c.mu = mu; c.rc = idocp_host::constraintRows(o->plan);
+  return linearizeDevice(h, n, steps, active, time_step, dt, u, contact_points, q_traj, v_traj, io.A_traj, io.B_traj, touchdown_impulse, &c);
+}
+
 int checkLqrGn(const char* who, const idocp_rbd* h, int g_rows, const double* G_traj) {
   const std::string w(who);
   if (!G_traj && g_rows == 0) return IDOCP_OK;
@@ -749,30 +794,33 @@ int checkLqrGn(const char* who, const idocp_rbd* h, int g_rows, const double* G_
   return IDOCP_OK;
 }
 
-// io, G: device pointers
-int launchLqrGn(idocp_rbd* h, int n, int steps, const idocp_rbd_lqr_io_t& io, int g_rows, const double* G) {
+// io, G, D: device pointers.  D = nullptr: the GN form; G = nullptr too: the plain form
+int launchLqrGn(idocp_rbd* h, int n, int steps, const idocp_rbd_lqr_io_t& io, int g_rows, const double* G, const double* D = nullptr) {
   if (!G) return launchLqr(h, n, steps, io);
-  RbdLqrGnArgs a;
+  RbdLqrGnDiagArgs a;
   a.A = io.A_traj; a.B = io.B_traj; a.x_weight = io.x_weight; a.u_weight = io.u_weight; a.xf_weight = io.xf_weight;
   a.lx = io.lx_traj; a.lu = io.lu_traj; a.regularization = io.regularization;
   a.K = io.K_traj; a.k = io.k_traj; a.P0 = io.P0; a.p0 = io.p0; a.expected = io.expected; a.status = io.status;
   a.n = n; a.steps = steps; a.nx = 2 * h->model.nv; a.nu = h->model.nu;
-  a.G = G; a.g_rows = g_rows;
-  rbdLqrBackwardGn(h->quadruped, a, h->stream);
+  a.G = G; a.g_rows = g_rows; a.D = D;
+  if (D) rbdLqrBackwardGnDiag(h->quadruped, a, h->stream);
+  else rbdLqrBackwardGn(h->quadruped, a, h->stream);
   HIP_TRY(hipGetLastError());
   return IDOCP_OK;
 }
 
-// the host form of both backward passes
-int lqrHost(const char* who, idocp_rbd* h, int n, int steps, const idocp_rbd_lqr_io_t* io, int g_rows, const double* G_traj) {
+// the host form of the three backward passes
+int lqrHost(const char* who, idocp_rbd* h, int n, int steps, const idocp_rbd_lqr_io_t* io, int g_rows, const double* G_traj,
+            const double* D_traj = nullptr) {
   int rc = checkLqr(who, h, n, steps, io, true); if (rc) return rc;
   rc = checkLqrGn(who, h, g_rows, G_traj); if (rc) return rc;
+  if (D_traj && !G_traj) { set_last_error(std::string(who) + ": D_traj needs a G_traj"); return IDOCP_E_ARG; }
   HIP_TRY(hipSetDevice(h->device));
   const size_t nx = 2 * (size_t)h->model.nv, nu = h->model.nu, N = (size_t)n, S = (size_t)steps;
   StagePlan p;
   idocp_rbd_lqr_io_t d = *io;
   double* d_status = nullptr;
-  const double* d_G = nullptr;
+  const double *d_G = nullptr, *d_D = nullptr;
   p.in(io->A_traj, S * N * nx * nx, &d.A_traj);
   p.in(io->B_traj, S * N * nx * nu, &d.B_traj);
   p.in(io->x_weight, nx, &d.x_weight);
@@ -787,9 +835,10 @@ int lqrHost(const char* who, idocp_rbd* h, int n, int steps, const idocp_rbd_lqr
   p.out(io->expected, N * 2, &d.expected);
   if (io->status) p.deviceOnly((N + 1) / 2, &d_status);      // (n ints in a slot of doubles; they come down by a copy of their own, in front of stageOut's wait)
   p.in(G_traj, S * N * (size_t)g_rows * (nx + nu), &d_G);
+  p.in(D_traj, S * N * (nx + nu), &d_D);
   rc = stageIn(h, p); if (rc) return rc;
   d.status = reinterpret_cast<int*>(d_status);
-  rc = launchLqrGn(h, n, steps, d, g_rows, d_G); if (rc) return rc;
+  rc = launchLqrGn(h, n, steps, d, g_rows, d_G, d_D); if (rc) return rc;
   if (io->status) HIP_TRY(hipMemcpyAsync(io->status, d_status, sizeof(int) * N, hipMemcpyDeviceToHost, h->stream));
   return stageOut(h, p);
 }
@@ -840,10 +889,11 @@ int launchAccept(idocp_rbd* h, int n, int steps, const idocp_rbd_ilqr_accept_io_
 
 // The workspace of one iteration (include/idocp_hip.h names the order): offsets in doubles, each piece at an even number of doubles.
 struct IlqrWorkspace {
-  size_t A, B, lx, lu, K, k, u_ff, q, v, u, a, f, cost, violation, alpha, done, G, total;
+  size_t A, B, lx, lu, K, k, u_ff, q, v, u, a, f, cost, violation, alpha, done, G, D, total;
 };
 // g_rows: the rows of G_traj behind everything else (idocp_rbd_ilqr_iterate_gn), 0: none
-IlqrWorkspace ilqrWorkspace(const idocp_rbd* h, int n, int steps, int g_rows = 0) {
+// diag: D_traj behind G_traj (idocp_rbd_ilqr_iterate_penalty)
+IlqrWorkspace ilqrWorkspace(const idocp_rbd* h, int n, int steps, int g_rows = 0, bool diag = false) {
   const size_t nq = h->model.nq, nv = h->model.nv, nu = h->model.nu, nf = 3 * (size_t)h->model.ncontacts, N = (size_t)n, S = (size_t)steps, nx = 2 * nv;
   IlqrWorkspace w;
   size_t at = 0;
@@ -853,19 +903,27 @@ IlqrWorkspace ilqrWorkspace(const idocp_rbd* h, int n, int steps, int g_rows = 0
   w.q = piece((S + 1) * N * nq); w.v = piece((S + 1) * N * nv); w.u = piece(S * N * nu); w.a = piece(S * N * nv); w.f = piece(S * N * nf);
   w.cost = piece(N); w.violation = piece(N); w.alpha = piece(N); w.done = piece((N + 1) / 2);
   w.G = piece(S * N * (size_t)g_rows * (nx + nu));
+  w.D = piece(diag ? S * N * (nx + nu) : 0);
   w.total = at;
   return w;
 }
 
 // gn: the Gauss-Newton form takes every objective whose a_weight and f_weight have square roots
+enum IlqrForm { ILQR_DIAGONAL = 0, ILQR_GN = 1, ILQR_PENALTY = 2 };
+
 int checkIterate(const char* who, const idocp_rbd* h, const idocp_rbd_objective* o, int n, int steps, const idocp_rbd_ilqr_io_t* io, bool host,
-                 bool gn = false) {
+                 int gn = ILQR_DIAGONAL) {
   const std::string w(who);
   if (!h || !o || !io) { set_last_error(w + ": null handle, objective or io"); return IDOCP_E_ARG; }
   if (o->owner != h) { set_last_error(w + ": the objective was created on another handle"); return IDOCP_E_ARG; }
   if (gn) {
     const std::string unsupported = idocp_host::residualUnsupported(o->plan);
     if (!unsupported.empty()) { set_last_error(w + ": " + unsupported); return IDOCP_E_UNSUPPORTED; }
+    if (gn == ILQR_PENALTY) {
+      const std::string pair = idocp_host::penaltyPairRefused(o->plan);
+      if (!pair.empty()) { set_last_error(w + ": " + pair); return IDOCP_E_ARG; }
+      if (idocp_host::residualRows(o->plan) + idocp_host::constraintRows(o->plan) > 64) { set_last_error(w + ": more than 64 rows"); return IDOCP_E_UNSUPPORTED; }
+    }
   } else { int rc = checkLqrWeights(who, o); if (rc) return rc; }
   if (n <= 0) { set_last_error(w + ": n must be positive"); return IDOCP_E_ARG; }
   if (steps < 1) { set_last_error(w + ": steps must be at least 1"); return IDOCP_E_ARG; }
@@ -878,7 +936,7 @@ int checkIterate(const char* who, const idocp_rbd* h, const idocp_rbd_objective*
   const char* const names[5] = {"regularization", "armijo", "shrink", "alpha_min", "penalty"};
   for (int i = 0; i < 5; ++i)
     if (!std::isfinite(values[i]) || values[i] < 0.0) { set_last_error(w + ": " + names[i] + " must be finite and non-negative"); return IDOCP_E_ARG; }
-  if (!host && !io->workspace) { set_last_error(w + ": the workspace is needed (idocp_rbd_ilqr_workspace_bytes, idocp_rbd_ilqr_gn_workspace_bytes)"); return IDOCP_E_ARG; }
+  if (!host && !io->workspace) { set_last_error(w + ": the workspace is needed (idocp_rbd_ilqr_workspace_bytes, idocp_rbd_ilqr_gn_workspace_bytes, idocp_rbd_ilqr_penalty_workspace_bytes)"); return IDOCP_E_ARG; }
   if (!host && (reinterpret_cast<uintptr_t>(io->workspace) & 15u)) { set_last_error(w + ": the workspace must be 16-byte aligned"); return IDOCP_E_ARG; }
   return IDOCP_OK;
 }
@@ -886,10 +944,12 @@ int checkIterate(const char* who, const idocp_rbd* h, const idocp_rbd_objective*
 // io: device pointers; ws: the workspace.  The chain of include/idocp_hip.h; every call on the handle's stream, no synchronisation, no host read.
 // gn: the chain of idocp_rbd_ilqr_iterate_gn -- the cost linearisation and the backward pass with residual rows in place of the first three calls.
 int iterateDevice(idocp_rbd* h, const idocp_rbd_objective* o, int n, int steps, const int* active, double time_step, double dt,
-                  const double* contact_points, const idocp_rbd_ilqr_io_t& io, double* ws, int touchdown_impulse, bool gn = false) {
+                  const double* contact_points, const idocp_rbd_ilqr_io_t& io, double* ws, int touchdown_impulse, int gn = ILQR_DIAGONAL) {
   const size_t nq = h->model.nq, nv = h->model.nv, nu = h->model.nu, nf = 3 * (size_t)h->model.ncontacts, N = (size_t)n;
-  const int g_rows = gn ? idocp_host::residualRows(o->plan) : 0;
-  const IlqrWorkspace w = ilqrWorkspace(h, n, steps, g_rows);
+  const bool penalty = gn == ILQR_PENALTY;
+  const int rows_c = penalty ? idocp_host::constraintRows(o->plan) : 0;
+  const int g_rows = gn ? idocp_host::residualRows(o->plan) + rows_c : 0;
+  const IlqrWorkspace w = ilqrWorkspace(h, n, steps, g_rows, penalty);
   double *A = ws + w.A, *B = ws + w.B, *lx = ws + w.lx, *lu = ws + w.lu, *K = ws + w.K, *kff = ws + w.k, *u_ff = ws + w.u_ff;
   double *qt = ws + w.q, *vt = ws + w.v, *ut = ws + w.u, *at = ws + w.a, *ft = nf ? ws + w.f : nullptr;
   double *cost_t = ws + w.cost, *violation_t = ws + w.violation, *alpha = ws + w.alpha;
@@ -898,7 +958,18 @@ int iterateDevice(idocp_rbd* h, const idocp_rbd_objective* o, int n, int steps, 
   idocp_rbd_lqr_io_t lqr = idocp_rbd_lqr_io_t();
   lqr.A_traj = A; lqr.B_traj = B; lqr.lx_traj = lx; lqr.lu_traj = lu; lqr.regularization = io.regularization;
   lqr.K_traj = K; lqr.k_traj = kff; lqr.expected = io.expected; lqr.status = io.lqr_status;
-  if (gn) {
+  if (penalty) {
+    // the penalty chain: io.penalty is mu; without constraint rows D stays out and the GN form of the backward pass runs
+    idocp_rbd_penalty_linearization_io_t c = idocp_rbd_penalty_linearization_io_t();
+    c.A_traj = A; c.B_traj = B; c.G_traj = ws + w.G; c.D_traj = rows_c ? ws + w.D : nullptr; c.lx_traj = lx; c.lu_traj = lu;
+    rc = idocp_rbd_linearize_rollout_penalty_device(h, o, n, steps, active, time_step, dt, io.u_traj, contact_points, io.q_traj, io.v_traj, &c, io.penalty,
+                                                    touchdown_impulse);
+    if (rc) return rc;
+    lqr.x_weight = o->d_lqr_weights;
+    lqr.u_weight = o->d_lqr_weights + idocp_host::lqrWeightOffsetU(o->plan);
+    lqr.xf_weight = o->d_lqr_weights + idocp_host::lqrWeightOffsetXf(o->plan);
+    rc = idocp_rbd_lqr_backward_gn_diag_device(h, n, steps, &lqr, g_rows, c.G_traj, c.D_traj); if (rc) return rc;
+  } else if (gn) {
     idocp_rbd_cost_linearization_io_t c = idocp_rbd_cost_linearization_io_t();
     c.A_traj = A; c.B_traj = B; c.G_traj = ws + w.G; c.lx_traj = lx; c.lu_traj = lu;
     rc = idocp_rbd_linearize_rollout_cost_device(h, o, n, steps, active, time_step, dt, io.u_traj, contact_points, io.q_traj, io.v_traj, &c, touchdown_impulse);
@@ -940,10 +1011,15 @@ int iterateDevice(idocp_rbd* h, const idocp_rbd_objective* o, int n, int steps, 
       idocp_rbd_score_io_t sc = idocp_rbd_score_io_t();
       sc.q_traj = qt + first * N * nq; sc.v_traj = vt + first * N * nv; sc.u_traj = ut + first * N * nu; sc.a_traj = at + first * N * nv;
       sc.f_traj = ft ? ft + first * N * nf : nullptr;
-      sc.cost = cost_t; sc.violation = violation_t;
+      sc.cost = cost_t; sc.violation = penalty ? nullptr : violation_t;      // (penalty form: `violation` is sq_violation alone, window by window)
       rc = idocp_rbd_score_rollout_device(h, o, n, first, window, active ? active + (size_t)first * h->model.ncontacts : nullptr,
                                           first + window == steps, first > 0, &sc);
       if (rc) return rc;
+      if (penalty) {      // the trial sq_violation over the score's L1 violation, window by window the same way
+        rc = idocp_rbd_score_penalty_device(h, o, n, first, window, active ? active + (size_t)first * h->model.ncontacts : nullptr, first > 0, sc.q_traj,
+                                            sc.v_traj, sc.u_traj, sc.a_traj, sc.f_traj, violation_t);
+        if (rc) return rc;
+      }
     }
     rc = launchAccept(h, n, steps, acc); if (rc) return rc;
   }
@@ -952,7 +1028,7 @@ int iterateDevice(idocp_rbd* h, const idocp_rbd_objective* o, int n, int steps, 
 
 // the host form of both iterations: stages once, owns the workspace in the staging buffer, reads back once
 int iterateHost(const char* who, idocp_rbd* h, const idocp_rbd_objective* o, int n, int steps, const int* active, double time_step, double dt,
-                const double* contact_points, const idocp_rbd_ilqr_io_t* io, int touchdown_impulse, bool gn) {
+                const double* contact_points, const idocp_rbd_ilqr_io_t* io, int touchdown_impulse, int gn) {
   int rc = checkIterate(who, h, o, n, steps, io, true, gn); if (rc) return rc;
   {      // (the bounds are host memory here and can be looked at)
     idocp_rbd_policy_t bounds = idocp_rbd_policy_t();
@@ -979,7 +1055,8 @@ int iterateHost(const char* who, idocp_rbd* h, const idocp_rbd_objective* o, int
   p.out(io->alpha_accepted, N, &d.alpha_accepted);
   p.out(io->expected, 2 * N, &d.expected);
   p.deviceOnly((N + 1) / 2, &d_status);
-  p.deviceOnly(ilqrWorkspace(h, n, steps, gn ? idocp_host::residualRows(o->plan) : 0).total, &d_ws);
+  const bool penalty = gn == ILQR_PENALTY;
+  p.deviceOnly(ilqrWorkspace(h, n, steps, gn ? idocp_host::residualRows(o->plan) + (penalty ? idocp_host::constraintRows(o->plan) : 0) : 0, penalty).total, &d_ws);
   rc = stageIn(h, p); if (rc) return rc;
   d.lqr_status = reinterpret_cast<int*>(d_status);
   rc = iterateDevice(h, o, n, steps, active, time_step, dt, d_points, d, d_ws, touchdown_impulse, gn); if (rc) return rc;
@@ -1672,7 +1749,7 @@ int idocp_rbd_ilqr_iterate_device(idocp_rbd_t* h, const idocp_rbd_objective_t* o
 
 int idocp_rbd_ilqr_iterate(idocp_rbd_t* h, const idocp_rbd_objective_t* o, int n, int steps, const int* active, double time_step, double dt,
                            const double* contact_points, const idocp_rbd_ilqr_io_t* io, int touchdown_impulse) {
-  return iterateHost("idocp_rbd_ilqr_iterate", h, o, n, steps, active, time_step, dt, contact_points, io, touchdown_impulse, false);
+  return iterateHost("idocp_rbd_ilqr_iterate", h, o, n, steps, active, time_step, dt, contact_points, io, touchdown_impulse, ILQR_DIAGONAL);
 }
 
 unsigned long long idocp_rbd_ilqr_gn_workspace_bytes(const idocp_rbd_t* h, int n, int steps) {
@@ -1683,14 +1760,154 @@ unsigned long long idocp_rbd_ilqr_gn_workspace_bytes(const idocp_rbd_t* h, int n
 
 int idocp_rbd_ilqr_iterate_gn_device(idocp_rbd_t* h, const idocp_rbd_objective_t* o, int n, int steps, const int* active, double time_step, double dt,
                                      const double* contact_points, const idocp_rbd_ilqr_io_t* io, int touchdown_impulse) {
-  int rc = checkIterate("idocp_rbd_ilqr_iterate_gn_device", h, o, n, steps, io, false, true); if (rc) return rc;
+  int rc = checkIterate("idocp_rbd_ilqr_iterate_gn_device", h, o, n, steps, io, false, ILQR_GN); if (rc) return rc;
   HIP_TRY(hipSetDevice(h->device));
-  return iterateDevice(h, o, n, steps, active, time_step, dt, contact_points, *io, static_cast<double*>(io->workspace), touchdown_impulse, true);
+  return iterateDevice(h, o, n, steps, active, time_step, dt, contact_points, *io, static_cast<double*>(io->workspace), touchdown_impulse, ILQR_GN);
 }
 
 int idocp_rbd_ilqr_iterate_gn(idocp_rbd_t* h, const idocp_rbd_objective_t* o, int n, int steps, const int* active, double time_step, double dt,
                               const double* contact_points, const idocp_rbd_ilqr_io_t* io, int touchdown_impulse) {
-  return iterateHost("idocp_rbd_ilqr_iterate_gn", h, o, n, steps, active, time_step, dt, contact_points, io, touchdown_impulse, true);
+  return iterateHost("idocp_rbd_ilqr_iterate_gn", h, o, n, steps, active, time_step, dt, contact_points, io, touchdown_impulse, ILQR_GN);
+}
+
+// ---- the constraint rows as a squared-hinge penalty
+
+int idocp_rbd_objective_constraint_rows(const idocp_rbd_objective_t* o) { return o ? idocp_host::constraintRows(o->plan) : 0; }
+
+namespace {
+// everything idocp_rbd_score_penalty refuses, and the kernel's arguments but for the array pointers
+int checkScorePenalty(const char* who, const idocp_rbd* h, const idocp_rbd_objective* o, int n, int first_step, int steps, const int* active,
+                      int accumulate, const double* q, const double* v, const double* u, const double* a_traj, const double* f, const double* sq,
+                      RbdPenaltyArgs* a) {
+  const std::string w(who);
+  if (!h || !o) { set_last_error(w + ": null handle or objective"); return IDOCP_E_ARG; }
+  if (o->owner != h) { set_last_error(w + ": the objective was created on another handle"); return IDOCP_E_ARG; }
+  if (!sq) { set_last_error(w + ": sq_violation is needed"); return IDOCP_E_ARG; }
+  const idocp_host::RbdScoreCall c = idocp_host::planPenaltyCall(who, o->plan, n, first_step, steps, active, q, v, u, a_traj, f);
+  if (c.rc) { set_last_error(c.error); return c.rc; }
+  std::memcpy(a->masks, c.masks, sizeof(c.masks));
+  a->block = o->d_block; a->steps = steps; a->accumulate = accumulate != 0;
+  return IDOCP_OK;
+}
+}  // namespace
+
+int idocp_rbd_score_penalty_device(idocp_rbd_t* h, const idocp_rbd_objective_t* o, int n, int first_step, int steps, const int* active, int accumulate,
+                                   const double* q_traj, const double* v_traj, const double* u_traj, const double* a_traj, const double* f_traj,
+                                   double* sq_violation) {
+  const char* who = "idocp_rbd_score_penalty_device";
+  RbdPenaltyArgs a;
+  int rc = checkScorePenalty(who, h, o, n, first_step, steps, active, accumulate, q_traj, v_traj, u_traj, a_traj, f_traj, sq_violation, &a); if (rc) return rc;
+  HIP_TRY(hipSetDevice(h->device));
+  a.q = q_traj; a.v = v_traj; a.u = u_traj; a.a = a_traj; a.f = f_traj; a.sq = sq_violation;
+  if (!rbdPenalty(h->model.nv, h->quadruped, a, n, h->stream)) { set_last_error(std::string(who) + ": no penalty kernel for this model"); return IDOCP_E_UNSUPPORTED; }
+  HIP_TRY(hipGetLastError());
+  return IDOCP_OK;
+}
+
+int idocp_rbd_score_penalty(idocp_rbd_t* h, const idocp_rbd_objective_t* o, int n, int first_step, int steps, const int* active, int accumulate,
+                            const double* q_traj, const double* v_traj, const double* u_traj, const double* a_traj, const double* f_traj,
+                            double* sq_violation) {
+  const char* who = "idocp_rbd_score_penalty";
+  RbdPenaltyArgs a;
+  int rc = checkScorePenalty(who, h, o, n, first_step, steps, active, accumulate, q_traj, v_traj, u_traj, a_traj, f_traj, sq_violation, &a); if (rc) return rc;
+  HIP_TRY(hipSetDevice(h->device));
+  const size_t nq = h->model.nq, nv = h->model.nv, nu = h->model.nu, nf = 3 * (size_t)o->plan.ncontacts, N = (size_t)n, S = (size_t)steps;
+  StagePlan p;
+  p.in(q_traj, S * N * nq, &a.q);
+  p.in(v_traj, S * N * nv, &a.v);
+  p.in(u_traj, S * N * nu, &a.u);
+  p.in(a_traj, S * N * nv, &a.a);
+  p.in(f_traj, S * N * nf, &a.f);
+  if (accumulate) p.update(sq_violation, N, &a.sq); else p.out(sq_violation, N, &a.sq);
+  rc = stageIn(h, p); if (rc) return rc;
+  if (!rbdPenalty(h->model.nv, h->quadruped, a, n, h->stream)) { set_last_error(std::string(who) + ": no penalty kernel for this model"); return IDOCP_E_UNSUPPORTED; }
+  HIP_TRY(hipGetLastError());
+  return stageOut(h, p);
+}
+
+namespace {
+// the cost call's io with the outputs of the penalty call that it knows: its refusals are the penalty call's, D_traj alone counts as an output
+idocp_rbd_cost_linearization_io_t costViewOf(const idocp_rbd_penalty_linearization_io_t& io) {
+  idocp_rbd_cost_linearization_io_t c = idocp_rbd_cost_linearization_io_t();
+  c.A_traj = io.A_traj; c.B_traj = io.B_traj; c.G_traj = io.G_traj ? io.G_traj : io.D_traj; c.rho_traj = io.rho_traj; c.lx_traj = io.lx_traj; c.lu_traj = io.lu_traj;
+  return c;
+}
+}  // namespace
+
+int idocp_rbd_linearize_rollout_penalty_device(idocp_rbd_t* h, const idocp_rbd_objective_t* o, int n, int steps, const int* active, double time_step,
+                                               double dt, const double* u_traj, const double* contact_points, const double* q_traj,
+                                               const double* v_traj, const idocp_rbd_penalty_linearization_io_t* io, double mu, int touchdown_impulse) {
+  const char* who = "idocp_rbd_linearize_rollout_penalty_device";
+  int rc = checkLinearize(who, h, n, steps, active, time_step, dt, contact_points, q_traj, v_traj); if (rc) return rc;
+  if (!io) { set_last_error(std::string(who) + ": null objective or io"); return IDOCP_E_ARG; }
+  const idocp_rbd_cost_linearization_io_t view = costViewOf(*io);
+  rc = checkLinearizeCost(who, h, o, n, steps, u_traj, &view); if (rc) return rc;
+  rc = checkPenalty(who, o, mu); if (rc) return rc;
+  HIP_TRY(hipSetDevice(h->device));
+  return linearizePenaltyDevice(h, o, n, steps, active, time_step, dt, u_traj, contact_points, q_traj, v_traj, *io, mu, touchdown_impulse);
+}
+
+int idocp_rbd_linearize_rollout_penalty(idocp_rbd_t* h, const idocp_rbd_objective_t* o, int n, int steps, const int* active, double time_step, double dt,
+                                        const double* u_traj, const double* contact_points, const double* q_traj, const double* v_traj,
+                                        const idocp_rbd_penalty_linearization_io_t* io, double mu, int touchdown_impulse) {
+  const char* who = "idocp_rbd_linearize_rollout_penalty";
+  int rc = checkLinearize(who, h, n, steps, active, time_step, dt, contact_points, q_traj, v_traj); if (rc) return rc;
+  if (!io) { set_last_error(std::string(who) + ": null objective or io"); return IDOCP_E_ARG; }
+  const idocp_rbd_cost_linearization_io_t view = costViewOf(*io);
+  rc = checkLinearizeCost(who, h, o, n, steps, u_traj, &view); if (rc) return rc;
+  rc = checkPenalty(who, o, mu); if (rc) return rc;
+  HIP_TRY(hipSetDevice(h->device));
+  const size_t nq = h->model.nq, nv = h->model.nv, nu = h->model.nu, nf = 3 * (size_t)h->model.ncontacts, N = (size_t)n, S = (size_t)steps, nx = 2 * nv;
+  const size_t R = (size_t)idocp_host::residualRows(o->plan) + (size_t)idocp_host::constraintRows(o->plan);
+  StagePlan p;
+  const double *d_u, *d_points, *d_q, *d_v;
+  idocp_rbd_penalty_linearization_io_t d;
+  p.in(u_traj, S * N * nu, &d_u);
+  p.in(contact_points, S * N * nf, &d_points);
+  p.in(q_traj, (S + 1) * N * nq, &d_q);
+  p.in(v_traj, (S + 1) * N * nv, &d_v);
+  p.out(io->A_traj, S * N * nx * nx, &d.A_traj);
+  p.out(io->B_traj, S * N * nx * nu, &d.B_traj);
+  p.out(io->G_traj, S * N * R * (nx + nu), &d.G_traj);
+  p.out(io->rho_traj, S * N * R, &d.rho_traj);
+  p.out(io->D_traj, S * N * (nx + nu), &d.D_traj);
+  p.out(io->lx_traj, (S + 1) * N * nx, &d.lx_traj);
+  p.out(io->lu_traj, S * N * nu, &d.lu_traj);
+  rc = stageIn(h, p); if (rc) return rc;
+  rc = linearizePenaltyDevice(h, o, n, steps, active, time_step, dt, d_u, d_points, d_q, d_v, d, mu, touchdown_impulse); if (rc) return rc;
+  return stageOut(h, p);
+}
+
+int idocp_rbd_lqr_backward_gn_diag_device(idocp_rbd_t* h, int n, int steps, const idocp_rbd_lqr_io_t* io, int g_rows, const double* G_traj,
+                                          const double* D_traj) {
+  const char* who = "idocp_rbd_lqr_backward_gn_diag_device";
+  int rc = checkLqr(who, h, n, steps, io, false); if (rc) return rc;
+  rc = checkLqrGn(who, h, g_rows, G_traj); if (rc) return rc;
+  if (D_traj && !G_traj) { set_last_error(std::string(who) + ": D_traj needs a G_traj"); return IDOCP_E_ARG; }
+  HIP_TRY(hipSetDevice(h->device));
+  return launchLqrGn(h, n, steps, *io, g_rows, G_traj, D_traj);
+}
+
+int idocp_rbd_lqr_backward_gn_diag(idocp_rbd_t* h, int n, int steps, const idocp_rbd_lqr_io_t* io, int g_rows, const double* G_traj,
+                                   const double* D_traj) {
+  return lqrHost("idocp_rbd_lqr_backward_gn_diag", h, n, steps, io, g_rows, G_traj, D_traj);
+}
+
+unsigned long long idocp_rbd_ilqr_penalty_workspace_bytes(const idocp_rbd_t* h, const idocp_rbd_objective_t* o, int n, int steps) {
+  if (!h || !o || o->owner != h || n <= 0 || steps < 1) return 0;
+  return sizeof(double) * (unsigned long long)ilqrWorkspace(h, n, steps, idocp_host::residualRows(o->plan) + idocp_host::constraintRows(o->plan), true).total;
+}
+
+int idocp_rbd_ilqr_iterate_penalty_device(idocp_rbd_t* h, const idocp_rbd_objective_t* o, int n, int steps, const int* active, double time_step,
+                                          double dt, const double* contact_points, const idocp_rbd_ilqr_io_t* io, int touchdown_impulse) {
+  int rc = checkIterate("idocp_rbd_ilqr_iterate_penalty_device", h, o, n, steps, io, false, ILQR_PENALTY); if (rc) return rc;
+  HIP_TRY(hipSetDevice(h->device));
+  return iterateDevice(h, o, n, steps, active, time_step, dt, contact_points, *io, static_cast<double*>(io->workspace), touchdown_impulse, ILQR_PENALTY);
+}
+
+int idocp_rbd_ilqr_iterate_penalty(idocp_rbd_t* h, const idocp_rbd_objective_t* o, int n, int steps, const int* active, double time_step, double dt,
+                                   const double* contact_points, const idocp_rbd_ilqr_io_t* io, int touchdown_impulse) {
+  return iterateHost("idocp_rbd_ilqr_iterate_penalty", h, o, n, steps, active, time_step, dt, contact_points, io, touchdown_impulse, ILQR_PENALTY);
 }
 
 }  // extern "C"

@@ -125,6 +125,12 @@ struct RbdLqrGnArgs : RbdLqrArgs {
   int g_rows;
 };
 void rbdLqrBackwardGn(bool quadruped, const RbdLqrGnArgs& a, hipStream_t st);
+// The GN form with a per-sample per-stage diagonal (idocp_rbd_lqr_backward_gn_diag): D [steps][n][nx + nu] is added to the diagonal of the stage
+// Hessian where wx / wu are.  A third template form (rbd_lqr_gn_diag_kernel.hip); the two forms above keep their code.  One launch.
+struct RbdLqrGnDiagArgs : RbdLqrGnArgs {
+  const double* D;
+};
+void rbdLqrBackwardGnDiag(bool quadruped, const RbdLqrGnDiagArgs& a, hipStream_t st);
 
 // The residual rows of the acceleration and contact-force terms (rbd_residual_kernel.hip; idocp_rbd_linearize_rollout_cost).  Every pointer: DEVICE
 // memory.  One pass of one step: `count` samples whose forward solution a [count][nv], f [count][nf] and column-major derivative blocks da_dq, da_dv
@@ -140,6 +146,30 @@ struct RbdResidualArgs {
   int count, mask;
 };
 bool rbdResidual(int nv, bool quadruped, const RbdResidualArgs& a, hipStream_t st);
+// The penalty form (rbd_residual_penalty_kernel.hip; idocp_rbd_linearize_rollout_penalty): the same pass also writes the rc constraint rows behind
+// the R cost rows -- G [count][R + rc][nz], rho [count][R + rc] --, D [count][nz] and the diagonal gradient terms.  q [count][nq], v [count][nv],
+// u [count][nu] or NULL: the slices of the rollout (read where their limits are switched on); block: the objective's; scale = sqrt(dt mu),
+// dtmu = dt mu; rc = idocp_host::constraintRows (0: no constraint rows).  lx, lu as above (either may be NULL).  One launch.
+struct RbdResidualPenaltyArgs : RbdResidualArgs {
+  const double *q, *v, *u;
+  const idocp_host::RbdScoreBlock* block;
+  double* D;
+  double scale, dtmu;
+  int rc;
+};
+bool rbdResidualPenalty(int nv, bool quadruped, const RbdResidualPenaltyArgs& a, hipStream_t st);
+
+// The squared-hinge penalty of a rollout (rbd_penalty_kernel.hip; idocp_rbd_score_penalty).  Every pointer: DEVICE memory, the slices of the window:
+// q, v, u, a, f [steps][n][..], any may be NULL where no enabled row reads it; masks as for the score; sq [n], in / out with accumulate.
+// One wavefront per sample.  One launch.  Returns false, having launched nothing, for a chain outside 2 .. 8 joints.
+struct RbdPenaltyArgs {
+  const double *q, *v, *u, *a, *f;
+  const idocp_host::RbdScoreBlock* block;
+  double* sq;
+  int steps, accumulate;
+  unsigned masks[idocp_host::RBD_SCORE_MASK_WORDS];
+};
+bool rbdPenalty(int nv, bool quadruped, const RbdPenaltyArgs& a, int n, hipStream_t st);
 
 // Gradients of an objective along a rollout (rbd_gradient_kernel.hip; the arrays of idocp_rbd_gradient_io_t).  Every pointer: DEVICE memory;
 // q, v [steps (+ 1 if terminal)][n][..], u [steps][n][nu] or NULL, q_ref / v_ref the objective's tables AT the window's first step, block its

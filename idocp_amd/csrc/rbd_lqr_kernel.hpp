@@ -33,13 +33,19 @@ struct RbdLqrLds {
   static_assert(Q_AT + Q_SIZE <= LDZ * NZM + PAD, "Qux, [K | k] and Quu fit in Z");
 };
 
+// the LDS of the DIAG form alone: D_k of the step (the other forms declare nothing more)
+static_assert(RBD_LQR_WAVES == 1, "the LDS of the kernel, lqrDiagShared included, is one sample's: one wavefront per workgroup");
+template <int NZM>
+__device__ __forceinline__ double* lqrDiagShared() { __shared__ double d[NZM]; return d; }
+
 __device__ __forceinline__ bool finite2(double x, double y) { return std::isfinite(x) && std::isfinite(y); }
 
 // Args = RbdLqrArgs: the recursion at the head of rbd_lqr_kernel.hip.  Args = RbdLqrGnArgs (the GN form, idocp_rbd_lqr_backward_gn): H gains G_k^T G_k before it is stored.
+// Args = RbdLqrGnDiagArgs (idocp_rbd_lqr_backward_gn_diag): the GN form, and the diagonal of H also gains D_k where wx / wu are added.
 template <int NXM, int NUM, class Args = RbdLqrArgs>
 __global__ __launch_bounds__(64 * RBD_LQR_WAVES) void rbd_lqr_kernel(Args a) {
   using W = RbdLqrLds<NXM, NUM>;
-  constexpr bool GN = std::is_same<Args, RbdLqrGnArgs>::value;
+  constexpr bool GN = std::is_base_of<RbdLqrGnArgs, Args>::value, DIAG = std::is_same<Args, RbdLqrGnDiagArgs>::value;
   typedef double d2 __attribute__((ext_vector_type(2), aligned(8)));      // (a caller's device pointer need not be 16-byte aligned)
   constexpr int LDP = W::LDP, LDZ = W::LDZ, LDU = W::LDU;
   constexpr int RT = (NXM + 15) / 16, ZT = (NXM + NUM + 15) / 16, KT = (NXM + 1 + 15) / 16;
@@ -105,6 +111,14 @@ __global__ __launch_bounds__(64 * RBD_LQR_WAVES) void rbd_lqr_kernel(Args a) {
       bad = bad || !std::isfinite(g);
     }
     if (__ballot(bad) != 0) { failed = k; break; }
+    if constexpr (DIAG) {
+      // D_k, entry c on lane c: it must be finite and not negative, else the sample fails here.  (The reads of the previous step's are behind a
+      // waveLdsSync; the one below orders this write before the reads.)
+      double* const Dk = lqrDiagShared<NXM + NUM>();
+      bool dbad = false;
+      if (lane < nz) { const double d = a.D[((size_t)k * N + sample) * nz + lane]; dbad = !(d >= 0.0) || !std::isfinite(d); Dk[lane] = d; }
+      if (__ballot(dbad) != 0) { failed = k; break; }
+    }
     if (k > 0) fetch(k - 1);
     if (lane == 0) L.ok = 1;
     waveLdsSync();
@@ -163,6 +177,11 @@ __global__ __launch_bounds__(64 * RBD_LQR_WAVES) void rbd_lqr_kernel(Args a) {
       }
       if (__ballot(gbad) != 0) { failed = k; break; }
     }
+    // the DIAG form: entry (r, r) of the Hessian gains D_k[r] on top of its weight; the other forms: nothing
+    auto diag = [&](int r, int c, double q) {
+      if constexpr (DIAG) return r == c ? q + lqrDiagShared<NXM + NUM>()[r] : q;
+      else { (void)r; (void)c; return q; }
+    };
     // Z and P are dead: Qxx over P, Qux and Quu (the lower triangle, mirrored) into Z's room
 #pragma unroll
     for (int ct = 0; ct < ZT; ++ct)
@@ -170,9 +189,9 @@ __global__ __launch_bounds__(64 * RBD_LQR_WAVES) void rbd_lqr_kernel(Args a) {
       for (int t = 0; t < ZT; ++t)
         if (16 * ct < nz && 16 * t < nz)
           mfmaTileStore(H[t][ct], 16 * t, 16 * ct, nz, nz, lane, [&](int r, int c, double v) {
-            if (r < nx) { if (c < nx) L.Pm[r + LDP * c] = v + (r == c ? L.wx[r] : 0.0); }
+            if (r < nx) { if (c < nx) L.Pm[r + LDP * c] = diag(r, c, v + (r == c ? L.wx[r] : 0.0)); }
             else if (c < nx) U[(r - nx) + LDU * c] = v;
-            else if (r >= c) { const int i = r - nx, j = c - nx; const double q = v + (i == j ? L.wu[i] : 0.0); Q[i + NUM * j] = q; Q[j + NUM * i] = q; }
+            else if (r >= c) { const int i = r - nx, j = c - nx; const double q = diag(r, c, v + (i == j ? L.wu[i] : 0.0)); Q[i + NUM * j] = q; Q[j + NUM * i] = q; }
           });
     waveLdsSync();
 

@@ -41,6 +41,7 @@ struct RbdObjectivePlan {
   std::vector<double> q_ref, v_ref;      // [steps + 1][nq], [steps + 1][nv]: v_ref is vRefOnAt(t_k) times the cost's reference velocity
   RbdScoreBlock block;
   int reads = 0;                         // RbdScoreReads: the optional arrays an enabled weight or row reads
+  bool has_constraints = false;          // created with an idocp_constraints_t (constraintRows below)
 };
 
 namespace rbd_objective_detail {
@@ -90,6 +91,7 @@ inline RbdObjectivePlan planObjective(const idocp_model_t& model, bool floating,
   b = RbdScoreBlock();
   if (constraints) {
     const idocp_constraints_t& c = *constraints;
+    p.has_constraints = true;
     b.position_limits = c.joint_position_limits != 0; b.velocity_limits = c.joint_velocity_limits != 0; b.torque_limits = c.joint_torque_limits != 0;
     b.acceleration_lower = c.joint_acceleration_lower_limit != 0; b.acceleration_upper = c.joint_acceleration_upper_limit != 0;
     b.cone = nc == 0 ? 0 : (c.linearized_friction_cone ? 1 : (c.friction_cone ? 2 : 0));
@@ -230,6 +232,52 @@ inline void residualTable(const RbdObjectivePlan& o, double* out) {
   for (int r = 0; r < o.nv; ++r) out[r] = std::sqrt(b.dt * b.a_weight[r]);
   for (int c = 0; c < o.ncontacts; ++c)
     for (int x = 0; x < 3; ++x) { out[o.nv + 3 * c + x] = std::sqrt(b.dt * b.f_weight[c][x]); out[R + o.nv + 3 * c + x] = b.f_ref[c][x]; }
+}
+
+// ---- the constraint rows as a squared-hinge penalty (idocp_rbd_score_penalty, idocp_rbd_linearize_rollout_penalty; include/idocp_hip.h defines them)
+inline int coneRows(const RbdObjectivePlan& o) { return o.block.cone == 1 ? 5 : (o.block.cone == 2 ? 2 : 0); }
+// Rc = roundup4(nu + ncone ncontacts) dense rows: the acceleration boxes, the cone rows, padding; 0 for an objective without constraints
+inline int constraintRows(const RbdObjectivePlan& o) { return o.has_constraints ? (o.nu + coneRows(o) * o.ncontacts + 3) / 4 * 4 : 0; }
+// "" when every enabled lower / upper pair has lo <= hi (the pair is then ONE signed row), else the text that names the pair
+inline std::string penaltyPairRefused(const RbdObjectivePlan& o) {
+  const RbdScoreBlock& b = o.block;
+  for (int j = 0; j < o.nu; ++j) {
+    const std::string at = " of actuated joint " + std::to_string(j) + " has lo > hi";
+    if (b.position_limits && b.q_min[j] > b.q_max[j]) return "the pair (q_min, q_max)" + at;
+    if (b.velocity_limits && b.v_max[j] < 0.0) return "the pair (-v_max, v_max)" + at;
+    if (b.torque_limits && b.u_max[j] < 0.0) return "the pair (-u_max, u_max)" + at;
+    if (b.acceleration_lower && b.acceleration_upper && b.a_min[j] > b.a_max[j]) return "the pair (a_min, a_max)" + at;
+  }
+  return "";
+}
+// One call of the penalty score: what is refused without looking at device memory, and the masks (those of planScoreCall).  An array is needed
+// only where an enabled row reads it.
+inline RbdScoreCall planPenaltyCall(const char* who_, const RbdObjectivePlan& o, int n, int first_step, int steps, const int* active, bool have_q,
+                                    bool have_v, bool have_u, bool have_a, bool have_f) {
+  RbdScoreCall c;
+  for (int i = 0; i < RBD_SCORE_MASK_WORDS; ++i) c.masks[i] = 0u;
+  const std::string who = std::string(who_) + ": ";
+  auto refuse = [&](const std::string& what) { c.rc = IDOCP_E_ARG; c.error = who + what; return c; };
+  const RbdScoreBlock& b = o.block;
+  if (n <= 0) return refuse("n must be positive");
+  if (steps < 1) return refuse("steps must be at least 1");
+  if (steps > IDOCP_RBD_SCORE_MAX_WINDOW) return refuse("at most IDOCP_RBD_SCORE_MAX_WINDOW = " + std::to_string(IDOCP_RBD_SCORE_MAX_WINDOW) + " steps per call (score window by window with accumulate)");
+  if (first_step < 0 || first_step > o.steps - steps) return refuse("first_step + steps must lie within the objective's " + std::to_string(o.steps) + " steps");
+  const std::string pair = penaltyPairRefused(o);
+  if (!pair.empty()) return refuse(pair);
+  if (o.ncontacts == 0 && (active || have_f)) return refuse("a fixed-base chain has no contacts (active and f_traj must be NULL)");
+  if (o.ncontacts && !active) return refuse("the contact status `active` is needed");
+  if (b.position_limits && !have_q) return refuse("q_traj is NULL but the position limits read it");
+  if (b.velocity_limits && !have_v) return refuse("v_traj is NULL but the velocity limits read it");
+  if (b.torque_limits && !have_u) return refuse("u_traj is NULL but the torque limits read it");
+  if ((b.acceleration_lower || b.acceleration_upper) && !have_a) return refuse("a_traj is NULL but the acceleration limits read it");
+  if (b.cone && !have_f) return refuse("f_traj is NULL but the friction cone reads it");
+  for (int k = 0; k < steps && o.ncontacts; ++k) {
+    unsigned m = 0;
+    for (int j = 0; j < o.ncontacts; ++j) if (active[(size_t)k * o.ncontacts + j]) m |= 1u << j;
+    c.masks[k / 8] |= m << (4 * (k % 8));
+  }
+  return c;
 }
 
 }  // namespace idocp_host

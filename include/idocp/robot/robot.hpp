@@ -405,12 +405,15 @@ class Robot {
   }
 
  private:
-  // the body of ilqrIterate and ilqrIterateGaussNewton: idocp_rbd_ilqr_iterate or, with gauss_newton, idocp_rbd_ilqr_iterate_gn
+  // the body of ilqrIterate, ilqrIterateGaussNewton and ilqrIterateConstrained: idocp_rbd_ilqr_iterate or, with gauss_newton,
+  // idocp_rbd_ilqr_iterate_gn or, with constraints, idocp_rbd_ilqr_iterate_penalty (mu its penalty; *sq_violation receives the sq_violation of the
+  // trajectory the call leaves, the trajectory that comes in being scored first: rolled out again for its a and f, then idocp_rbd_score_penalty)
   template <class CostFunctionT>
   double ilqrIterateForm(const bool gauss_newton, const CostFunctionT& cost, const double t0, const double dt, const double time_step,
                          const std::vector<ContactStatus>& contact_status, const std::vector<std::vector<Eigen::Vector3d>>& contact_points,
                          std::vector<Eigen::VectorXd>& q, std::vector<Eigen::VectorXd>& v, std::vector<Eigen::VectorXd>& u, double& total_cost,
-                         const double regularization, const double armijo, const int trials) {
+                         const double regularization, const double armijo, const int trials, const idocp_constraints_t* constraints = nullptr,
+                         const double mu = 0.0, double* sq_violation = nullptr) {
     const int steps = (int)u.size(), nc = model_.ncontacts;
     if (steps < 1 || (int)q.size() != steps + 1 || (int)v.size() != steps + 1 ||
         (nc > 0 && ((int)contact_status.size() != steps || (int)contact_points.size() != steps))) {
@@ -434,15 +437,27 @@ class Robot {
     const idocp_cost_t c = cost.native();
     if (!rbd_.h) ok(idocp_rbd_create(&model_, 0, &rbd_.h));
     idocp_rbd_objective_t* objective = nullptr;
-    ok(idocp_rbd_objective_create(rbd_.h, &c, nullptr, t0, dt, steps, &objective));
+    ok(idocp_rbd_objective_create(rbd_.h, &c, constraints, t0, dt, steps, &objective));
     double violation = 0.0, alpha = 0.0, expected[2] = {0.0, 0.0};
     int status = -1;
     idocp_rbd_ilqr_io_t io = idocp_rbd_ilqr_io_t();
     io.q_traj = qs.data(); io.v_traj = vs.data(); io.u_traj = us.data(); io.cost = &total_cost; io.violation = &violation;
-    io.regularization = regularization; io.armijo = armijo; io.shrink = 0.5; io.alpha_min = 0.0; io.penalty = 0.0; io.trials = trials;
+    io.regularization = regularization; io.armijo = armijo; io.shrink = 0.5; io.alpha_min = 0.0; io.penalty = constraints ? mu : 0.0; io.trials = trials;
     io.alpha_accepted = &alpha; io.lqr_status = &status; io.expected = expected;
-    const int rc = (gauss_newton ? idocp_rbd_ilqr_iterate_gn : idocp_rbd_ilqr_iterate)(rbd_.h, objective, 1, steps, nc > 0 ? act.data() : nullptr, time_step,
-                                                                                       dt, nc > 0 ? pts.data() : nullptr, &io, 0);
+    const int* const actp = nc > 0 ? act.data() : nullptr;
+    const double* const ptsp = nc > 0 ? pts.data() : nullptr;
+    int rc = IDOCP_OK;
+    if (constraints) {
+      // sq_violation of the trajectory that comes in: its a and f from a rollout of its own torques, its q, v, u as given
+      std::vector<double> tq(qs), tv(vs), ta((size_t)steps * nv), tf((size_t)steps * 3 * nc);
+      rc = idocp_rbd_rollout(rbd_.h, 1, steps, actp, time_step, dt, us.data(), ptsp, tq.data(), tv.data(), ta.data(), nc > 0 ? tf.data() : nullptr, 0);
+      if (rc == IDOCP_OK)
+        rc = idocp_rbd_score_penalty(rbd_.h, objective, 1, 0, steps, actp, 0, qs.data(), vs.data(), us.data(), ta.data(), nc > 0 ? tf.data() : nullptr, &violation);
+      if (rc == IDOCP_OK) rc = idocp_rbd_ilqr_iterate_penalty(rbd_.h, objective, 1, steps, actp, time_step, dt, ptsp, &io, 0);
+      if (sq_violation) *sq_violation = violation;
+    } else {
+      rc = (gauss_newton ? idocp_rbd_ilqr_iterate_gn : idocp_rbd_ilqr_iterate)(rbd_.h, objective, 1, steps, actp, time_step, dt, ptsp, &io, 0);
+    }
     idocp_rbd_objective_destroy(objective);
     ok(rc);
     for (int k = 0; k <= steps; ++k) {
@@ -462,6 +477,19 @@ class Robot {
                                 std::vector<Eigen::VectorXd>& q, std::vector<Eigen::VectorXd>& v, std::vector<Eigen::VectorXd>& u, double& total_cost,
                                 const double regularization = 1e-6, const double armijo = 1e-4, const int trials = 8) {
     return ilqrIterateForm(true, cost, t0, dt, time_step, contact_status, contact_points, q, v, u, total_cost, regularization, armijo, trials);
+  }
+  // The same iteration under the cost AND the constraints, an ADDITION: idocp_rbd_ilqr_iterate_penalty with n = 1 -- the rows the score sums into its
+  // violation enter as a squared-hinge penalty with the weight mu (idocp_hip.h has the definition).  total_cost is the cost of the trajectory that
+  // comes in and of the one that is left; sq_violation receives that of the one that is left (the incoming trajectory is scored by the call).
+  template <class CostFunctionT, class ConstraintsT>
+  double ilqrIterateConstrained(const CostFunctionT& cost, const ConstraintsT& constraints, const double t0, const double dt, const double time_step,
+                                const std::vector<ContactStatus>& contact_status, const std::vector<std::vector<Eigen::Vector3d>>& contact_points,
+                                std::vector<Eigen::VectorXd>& q, std::vector<Eigen::VectorXd>& v, std::vector<Eigen::VectorXd>& u, double& total_cost,
+                                double& sq_violation, const double mu, const double regularization = 1e-6, const double armijo = 1e-4,
+                                const int trials = 8) {
+    const idocp_constraints_t g = constraints.native();
+    return ilqrIterateForm(true, cost, t0, dt, time_step, contact_status, contact_points, q, v, u, total_cost, regularization, armijo, trials, &g, mu,
+                           &sq_violation);
   }
   // Robot::framePosition / frameRotation / framePlacement (robot.hxx:206-233): of any frame of the URDF (pinocchio's frame numbering, as the
   // contact frames and the task-space costs use it), at the configuration of the last updateFrameKinematics / updateKinematics

@@ -1231,7 +1231,7 @@ int idocp_rbd_objective_residual_rows(const idocp_rbd_objective_t* o);
  * and touches nothing else.  Refused: what idocp_rbd_linearize_rollout refuses, a NULL objective or io, an objective of another handle, steps beyond
  * the objective's, no output at all, u_traj NULL under a non-zero u_weight when lu_traj or lx_traj is asked for, (steps + 1) * n beyond an int (all
  * IDOCP_E_ARG), and a NEGATIVE a_weight or f_weight entry (IDOCP_E_UNSUPPORTED: a residual row needs its square root).  Task-space terms,
- * contact_distance and the constraint rows are still not differentiated. */
+ * contact_distance and the constraint rows are still not differentiated (the constraint rows: idocp_rbd_linearize_rollout_penalty below). */
 typedef struct idocp_rbd_cost_linearization_io {
   double *A_traj, *B_traj;      /* [steps][n][2nv*2nv], [steps][n][2nv*nu], column-major blocks */
   double *G_traj;               /* [steps][n][R][nz], row-major */
@@ -1268,6 +1268,93 @@ int idocp_rbd_ilqr_iterate_gn_device(idocp_rbd_t* h, const idocp_rbd_objective_t
                                      const double* contact_points, const idocp_rbd_ilqr_io_t* io, int touchdown_impulse);
 int idocp_rbd_ilqr_iterate_gn(idocp_rbd_t* h, const idocp_rbd_objective_t* o, int n, int steps, const int* active, double time_step, double dt,
                               const double* contact_points, const idocp_rbd_ilqr_io_t* io, int touchdown_impulse);
+
+/* ---- Constrained iLQR: the constraint rows of the objective as a squared-hinge penalty (rbd_penalty_kernel.hip, the penalty form of
+ * rbd_residual_kernel.hip, the third form of rbd_lqr_kernel.hip).  ADDITIONS.  The calls above do not differentiate the constraint rows and keep
+ * their refusals and their bits; the calls below do.  This is the definition.  The rows of stage k are the g_row of idocp_rbd_score_rollout,
+ * h_row = max(0, g_row); the terminal slice has no rows:
+ *   sq_violation[i] = sum_k dt 1/2 sum_rows h_row^2
+ *   merit[i]        = cost[i] + mu sq_violation[i],   mu >= 0.
+ * A lower / upper pair on one quantity x cannot both be positive when lo <= hi, so the pair is ONE signed row b = max(0, x - hi) - max(0, lo - x)
+ * (a side that is switched off is left out).  The calls below refuse an enabled pair with lo > hi (IDOCP_E_ARG, idocp_last_error names the pair).
+ * A row is active iff g > 0 strictly.  To the optimiser the penalty is more Gauss-Newton rows plus a diagonal; with s = sqrt(dt mu), the correctly
+ * rounded root of the rounded product:
+ *   dense rows, Rc = roundup4(nu + ncone ncontacts) of them, ncone = 0, 5 (LinearizedFrictionCone) or 2 (FrictionCone); 32 or 20 on the
+ *   quadruped, roundup4(nu) on a chain:
+ *     row j < nu, the acceleration box of actuated joint j:   sigma = s b_a[j],   Gc row = s [b != 0] [da_j/dq | da_j/dv | da_j/du]
+ *     row nu + ncone c + r, contact c active at step k:       sigma = s h,        Gc row = s [g > 0] (dg/df_c) [df_c/dq | df_c/dv | df_c/du]
+ *       LinearizedFrictionCone: g = (Jc f_c)_r, dg/df_c = (Jc)_r with the Jc of the score;
+ *       FrictionCone: g_0 = -fz, g_1 = fx^2 + fy^2 - mu_f^2 fz^2 with dg_1/df_c = (2 fx, 2 fy, -2 mu_f^2 fz), mu_f the friction coefficient
+ *     rows of kinds switched off, of inactive contacts, and the padding rows are zero;
+ *   diagonal part: the q, v and u boxes of the actuated joints are diagonal in [dq; dv; du] and get no dense row --
+ *     D[k][i][c] = dt mu [b != 0] at the joint's own dq, dv or du column, 0 elsewhere (the base columns are 0); the gradient gains dt mu b there.
+ * The gradient of the merit is that of idocp_rbd_linearize_rollout_cost plus Gc^T sigma plus the diagonal terms.  The blocks are those of STAGE
+ * mode at slice k, as for the cost rows.  Out of scope: multipliers, task-space terms, contact_distance, impulse cones.
+ * idocp_rbd_objective_constraint_rows returns Rc (0 for a NULL objective and for one created with constraints == NULL). */
+int idocp_rbd_objective_constraint_rows(const idocp_rbd_objective_t* o);
+/* idocp_rbd_score_penalty: sq_violation [n] of the window of `steps` steps at first_step, with first_step, steps, active and accumulate as
+ * idocp_rbd_score_rollout takes them; q_traj, v_traj, u_traj, a_traj, f_traj are the window's [steps][n][..] slices.  An array is read only where
+ * an enabled row needs it and may be NULL otherwise; a missing array under an enabled row is IDOCP_E_ARG naming the array.  One launch.  The rows
+ * of a step are folded by a fixed tree, the steps added in index order, so a sample's result is bit for bit the same whatever n is and whether it
+ * was scored at once or window by window.  A non-finite entry in what is read of a sample makes its result NaN and touches no other sample.
+ * Host pointers; returns when the result is in place. */
+int idocp_rbd_score_penalty(idocp_rbd_t* h, const idocp_rbd_objective_t* o, int n, int first_step, int steps, const int* active, int accumulate,
+                            const double* q_traj, const double* v_traj, const double* u_traj, const double* a_traj, const double* f_traj,
+                            double* sq_violation);
+/* Device pointers, asynchronous on idocp_rbd_stream(h); allocates nothing. */
+int idocp_rbd_score_penalty_device(idocp_rbd_t* h, const idocp_rbd_objective_t* o, int n, int first_step, int steps, const int* active, int accumulate,
+                                   const double* q_traj, const double* v_traj, const double* u_traj, const double* a_traj, const double* f_traj,
+                                   double* sq_violation);
+/* idocp_rbd_linearize_rollout_penalty: idocp_rbd_linearize_rollout_cost plus mu.  Every output is optional (at least one is needed):
+ *   A_traj, B_traj                      bit for bit the cost call's
+ *   G_traj   [steps][n][R + Rc][nz]     rows 0 .. R - 1 bit for bit the cost call's G, the constraint rows behind them
+ *   rho_traj [steps][n][R + Rc]         the cost call's rho, sigma behind it
+ *   D_traj   [steps][n][nz]
+ *   lx_traj, lu_traj                    as the cost call's, the gradient of merit: entry c is (d_c + t_c) + dt mu b_c, t_c the cost call's sum continued
+ *                                       over the constraint rows in index order
+ * With mu = 0, or no row switched on, the constraint rows and D are zero and lx, lu compare equal to the cost call's.  One launch per pass of the
+ * penalty form of rbd_residual_kernel.hip loads the scratch blocks once and writes both kinds of rows.  An entry of a constraint row is the
+ * coefficient s [active] dg/df times the block entry; a cone row sums its three products by fused multiply-adds in the order x, y, z.  NaN containment,
+ * independence of n and of the outputs asked for, and the refusals are the cost call's; besides, a negative or non-finite mu and an enabled pair
+ * with lo > hi are IDOCP_E_ARG. */
+typedef struct idocp_rbd_penalty_linearization_io {
+  double *A_traj, *B_traj;      /* [steps][n][2nv*2nv], [steps][n][2nv*nu], column-major blocks */
+  double *G_traj;               /* [steps][n][R + Rc][nz], row-major */
+  double *rho_traj;             /* [steps][n][R + Rc] */
+  double *D_traj;               /* [steps][n][nz] */
+  double *lx_traj, *lu_traj;    /* [steps + 1][n][2nv], [steps][n][nu] */
+} idocp_rbd_penalty_linearization_io_t;
+/* Host pointers; stages through the handle's buffer and returns when the outputs are in place. */
+int idocp_rbd_linearize_rollout_penalty(idocp_rbd_t* h, const idocp_rbd_objective_t* o, int n, int steps, const int* active, double time_step, double dt,
+                                        const double* u_traj, const double* contact_points, const double* q_traj, const double* v_traj,
+                                        const idocp_rbd_penalty_linearization_io_t* io, double mu, int touchdown_impulse);
+/* Device pointers; asynchronous on idocp_rbd_stream(h); allocates only when a scratch has to grow. */
+int idocp_rbd_linearize_rollout_penalty_device(idocp_rbd_t* h, const idocp_rbd_objective_t* o, int n, int steps, const int* active, double time_step,
+                                               double dt, const double* u_traj, const double* contact_points, const double* q_traj,
+                                               const double* v_traj, const idocp_rbd_penalty_linearization_io_t* io, double mu, int touchdown_impulse);
+
+/* idocp_rbd_lqr_backward_gn_diag: idocp_rbd_lqr_backward_gn with D_traj [steps][n][nz]: Qxx and Quu gain diag(D_k) at the point where wx / wu are
+ * added when H is stored -- entry (c, c) is (H + w) + D_k[c].  D_traj = NULL reproduces idocp_rbd_lqr_backward_gn bit for bit (the same kernel is
+ * launched); a D_traj without a G_traj is IDOCP_E_ARG.  A negative or non-finite entry of D_traj[k][i] fails sample i at step k.  g_rows is capped
+ * at 64 as there: the 32 + 32 rows of the quadruped fit exactly. */
+int idocp_rbd_lqr_backward_gn_diag(idocp_rbd_t* h, int n, int steps, const idocp_rbd_lqr_io_t* io, int g_rows, const double* G_traj,
+                                   const double* D_traj);
+/* Device pointers; asynchronous on idocp_rbd_stream(h); allocates nothing. */
+int idocp_rbd_lqr_backward_gn_diag_device(idocp_rbd_t* h, int n, int steps, const idocp_rbd_lqr_io_t* io, int g_rows, const double* G_traj,
+                                          const double* D_traj);
+
+/* idocp_rbd_ilqr_iterate_penalty: idocp_rbd_ilqr_iterate_gn on the same io, read like this: `penalty` is mu, and `violation` holds sq_violation in
+ * and out (the caller scores the first rollout with idocp_rbd_score_penalty).  The chain: idocp_rbd_linearize_rollout_penalty_device;
+ * idocp_rbd_lqr_backward_gn_diag_device with g_rows = R + Rc; the same trial rounds, with idocp_rbd_score_penalty_device filling the trial
+ * `violation` after idocp_rbd_score_rollout_device has filled the trial cost; the unchanged idocp_rbd_ilqr_accept_device.  A sample's merit
+ * therefore never rises.  An objective created with constraints == NULL has Rc = 0: D stays out, and the iteration compares equal to
+ * idocp_rbd_ilqr_iterate_gn.  No host decisions on the stream.  The workspace is the one of idocp_rbd_ilqr_iterate_gn with G_traj
+ * [steps][n][R + Rc][nz] and D_traj [steps][n][nz] behind it; its size depends on the objective's cone (0 for a NULL or foreign objective). */
+unsigned long long idocp_rbd_ilqr_penalty_workspace_bytes(const idocp_rbd_t* h, const idocp_rbd_objective_t* o, int n, int steps);
+int idocp_rbd_ilqr_iterate_penalty_device(idocp_rbd_t* h, const idocp_rbd_objective_t* o, int n, int steps, const int* active, double time_step,
+                                          double dt, const double* contact_points, const idocp_rbd_ilqr_io_t* io, int touchdown_impulse);
+int idocp_rbd_ilqr_iterate_penalty(idocp_rbd_t* h, const idocp_rbd_objective_t* o, int n, int steps, const int* active, double time_step, double dt,
+                                   const double* contact_points, const idocp_rbd_ilqr_io_t* io, int touchdown_impulse);
 
 /* ---- Sampling around a torque sequence: perturb, weigh, average (rbd_sample_kernel.hip).  Every call of this block is an ADDITION (the reference
  * has no counterpart).  With idocp_rbd_rollout_policy_device and idocp_rbd_score_rollout_device between the first and the second, one iteration of

@@ -17,6 +17,7 @@ ROLLOUT_STEPS open-loop steps with every contact active and no touchdown impulse
 idocp_rbd_rollout_footholds_device (one latch launch more per step); both carry ms_per_step.  The lqr_* rows are idocp_rbd_lqr_backward_device over
 16 steps (lqr_rows has their description); run with fdd_linearize_s16 they also carry their ratio to the linearisation that feeds them.  The grad_*,
 ilqr_accept and ilqr_iterate rows are the cost gradients, the acceptance step and one whole iLQR iteration (ilqr_rows has their description).
+The penalty_* rows are the gn_* rows under constraints with the penalty calls (gn_rows with penalty=True has their setting).
 The gn_* rows are the cost linearisation with residual rows, the backward pass with G^T G and one full-cost iteration (gn_rows has their
 description).
 
@@ -495,18 +496,24 @@ def ilqr_rows(wanted, lib, rt, h, stream, m, n, measure, res):
 
 
 GN_ROWS = ("gn_linearize_s16", "gn_residual_pass_copy", "gn_lqr_backward", "gn_iterate")
+PENALTY_ROWS = ("penalty_linearize_s16", "penalty_residual_pass_copy", "penalty_lqr_backward", "penalty_iterate")
 GN_STEPS = 16
 GN_RESIDUAL_DOUBLES = 1470 + 48 + 1536 + 32 + 48      # per quadruped sample and launch of rbd_residual_kernel: a, f and the six blocks in; lx, lu in; G, rho, lx, lu out
 GN_PASS = ((256 << 20) // 8) // (1470 + 8) // 2 * 2      # samples per pass of the cost linearisation (ResidualPlan of rbd_capi.hip)
 
 
-def gn_rows(wanted, lib, rt, h, stream, m, n, measure, res):
+def gn_rows(wanted, lib, rt, h, stream, m, n, measure, res, penalty=False):
     """the gn_* rows on 16 steps of ANYmal standing on four feet under the ANYmal workload's own cost (a_weight and f_weight set, u_weight zero),
     about a rollout of zero torques: gn_linearize_s16 is idocp_rbd_linearize_rollout_cost_device with every output (read it against
     fdd_linearize_s16); gn_residual_pass_copy is a device-to-device copy of the bytes ONE launch of rbd_residual_kernel touches (a pass of GN_PASS
     samples; the kernel's own time comes from a kernel trace of the gn_linearize_s16 row); gn_lqr_backward is idocp_rbd_lqr_backward_gn_device on what
     the linearisation wrote, every output (read it against lqr_gains_ilqr); gn_iterate is one idocp_rbd_ilqr_iterate_gn_device with two trial rounds
-    (read it against ilqr_iterate)."""
+    (read it against ilqr_iterate).
+    penalty: the penalty_* rows instead -- the same setting under constraints (every joint limit of the model, an acceleration box of +- 5, the
+    LinearizedFrictionCone with mu = 0.7) and mu = 10: idocp_rbd_linearize_rollout_penalty_device with all seven outputs (read it against
+    gn_linearize_s16), the copy of the bytes one launch of the penalty form touches (G and rho twice as wide, D more), idocp_rbd_lqr_backward_gn_diag_device
+    at R + Rc = 64 rows (against gn_lqr_backward at 32) and idocp_rbd_ilqr_iterate_penalty_device (against gn_iterate)."""
+    P = "penalty_" if penalty else "gn_"
     from idocp_amd.workloads import anymal_problem
     rt.hipMemcpyAsync.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p]
     rt.hipMemsetAsync.argtypes = [C.c_void_p, C.c_int, C.c_size_t, C.c_void_p]
@@ -516,15 +523,27 @@ def gn_rows(wanted, lib, rt, h, stream, m, n, measure, res):
     cost = anymal_problem(m, trotting_ref=False)[0]
     ts, dt = 0.05, 0.01
     o = C.c_void_p()
-    capi.check(lib.idocp_rbd_objective_create(h, C.byref(cost), None, 0.0, dt, S, C.byref(o)), "objective")
-    R = lib.idocp_rbd_objective_residual_rows(o)
-    want_iterate = not wanted or "gn_iterate" in wanted
+    cons = None
+    if penalty:
+        cons = capi.Constraints()
+        cons.joint_position_limits = cons.joint_velocity_limits = cons.joint_torque_limits = cons.linearized_friction_cone = 1
+        cons.joint_acceleration_lower_limit = cons.joint_acceleration_upper_limit = 1
+        cons.mu = 0.7
+        for j in range(nu):
+            cons.a_min[j], cons.a_max[j] = -5.0, 5.0
+    capi.check(lib.idocp_rbd_objective_create(h, C.byref(cost), C.byref(cons) if penalty else None, 0.0, dt, S, C.byref(o)), "objective")
+    Rc = lib.idocp_rbd_objective_constraint_rows(o) if penalty else 0
+    R = lib.idocp_rbd_objective_residual_rows(o) + Rc
+    MU = 10.0
+    want_iterate = not wanted or P + "iterate" in wanted
     sizes = {"q": (S + 1) * n * nq, "v": (S + 1) * n * nv, "u": S * n * nu, "a": S * n * nv, "f": S * n * nf, "pts": S * n * nf,
              "A": S * n * nx * nx, "B": S * n * nx * nu, "G": S * n * R * nz, "rho": S * n * R, "lx": (S + 1) * n * nx, "lu": S * n * nu,
              "K": S * n * nx * nu, "k": S * n * nu, "P0": n * nx * nx, "p0": n * nx, "wx": nx, "wu": nu, "wxf": nx,
              "cost": n, "viol": n, "expected": 2 * n, "alpha_accepted": n, "status": (n + 1) // 2}
+    if penalty:
+        sizes["D"] = S * n * nz
     if want_iterate:
-        sizes["work"] = lib.idocp_rbd_ilqr_gn_workspace_bytes(h, n, S) // 8
+        sizes["work"] = (lib.idocp_rbd_ilqr_penalty_workspace_bytes(h, o, n, S) if penalty else lib.idocp_rbd_ilqr_gn_workspace_bytes(h, n, S)) // 8
     dev = {}
     for key, size in sizes.items():
         dev[key] = C.c_void_p()
@@ -545,10 +564,16 @@ def gn_rows(wanted, lib, rt, h, stream, m, n, measure, res):
     sc = capi.RbdScoreIO()
     sc.q_traj, sc.v_traj, sc.u_traj, sc.a_traj, sc.f_traj, sc.cost, sc.violation = dev["q"], dev["v"], dev["u"], dev["a"], dev["f"], dev["cost"], dev["viol"]
     capi.check(lib.idocp_rbd_score_rollout_device(h, o, n, 0, S, act, 1, 0, C.byref(sc)), "score")
+    if penalty:      # (`violation` of the iteration holds sq_violation)
+        capi.check(lib.idocp_rbd_score_penalty_device(h, o, n, 0, S, act, 0, dev["q"], dev["v"], dev["u"], dev["a"], dev["f"], dev["viol"]), "score_penalty")
 
-    lin = capi.RbdCostLinearizationIO()
+    lin = capi.RbdPenaltyLinearizationIO() if penalty else capi.RbdCostLinearizationIO()
     lin.A_traj, lin.B_traj, lin.G_traj, lin.rho_traj, lin.lx_traj, lin.lu_traj = dev["A"], dev["B"], dev["G"], dev["rho"], dev["lx"], dev["lu"]
-    linearize = lambda: capi.check(lib.idocp_rbd_linearize_rollout_cost_device(h, o, n, S, act, ts, dt, dev["u"], dev["pts"], dev["q"], dev["v"], C.byref(lin), 0), "linearize_cost")  # noqa: E731
+    if penalty:
+        lin.D_traj = dev["D"]
+        linearize = lambda: capi.check(lib.idocp_rbd_linearize_rollout_penalty_device(h, o, n, S, act, ts, dt, dev["u"], dev["pts"], dev["q"], dev["v"], C.byref(lin), MU, 0), "linearize_penalty")  # noqa: E731
+    else:
+        linearize = lambda: capi.check(lib.idocp_rbd_linearize_rollout_cost_device(h, o, n, S, act, ts, dt, dev["u"], dev["pts"], dev["q"], dev["v"], C.byref(lin), 0), "linearize_cost")  # noqa: E731
     linearize()      # (gn_lqr_backward reads what it wrote, whether or not its own row is asked for)
     lqr = capi.RbdLqrIO()
     for field, key in (("A_traj", "A"), ("B_traj", "B"), ("x_weight", "wx"), ("u_weight", "wu"), ("xf_weight", "wxf"), ("lx_traj", "lx"), ("lu_traj", "lu"),
@@ -556,47 +581,55 @@ def gn_rows(wanted, lib, rt, h, stream, m, n, measure, res):
         setattr(lqr, field, dev[key])
     lqr.regularization = 1e-6
     pass_samples = min(n, GN_PASS)
-    pass_bytes = 8 * GN_RESIDUAL_DOUBLES * pass_samples
+    pass_bytes = 8 * (GN_RESIDUAL_DOUBLES + Rc * (nz + 1) + nz + nq + nv + nu) * pass_samples      # (penalty: the wider G and rho, D out, q, v, u in)
 
     def pass_copy():
         assert rt.hipMemcpyAsync(dev["A"], dev["G"], pass_bytes, 3, stream) == 0
 
-    plan = (("gn_lqr_backward", lambda: capi.check(lib.idocp_rbd_lqr_backward_gn_device(h, n, S, C.byref(lqr), R, dev["G"]), "lqr_gn")),
-            ("gn_residual_pass_copy", pass_copy), ("gn_linearize_s16", linearize))      # (the copy overwrites the front of A: the linearisation runs after it)
+    if penalty:
+        backward = lambda: capi.check(lib.idocp_rbd_lqr_backward_gn_diag_device(h, n, S, C.byref(lqr), R, dev["G"], dev["D"]), "lqr_gn_diag")  # noqa: E731
+    else:
+        backward = lambda: capi.check(lib.idocp_rbd_lqr_backward_gn_device(h, n, S, C.byref(lqr), R, dev["G"]), "lqr_gn")  # noqa: E731
+    plan = ((P + "lqr_backward", backward),
+            (P + "residual_pass_copy", pass_copy), (P + "linearize_s16", linearize))      # (the copy overwrites the front of A: the linearisation runs after it)
     for row, launch in plan:
         if wanted and row not in wanted:
             continue
         measure(row, launch)
         res[row]["steps"] = S
-        if row == "gn_lqr_backward":
+        if row == P + "lqr_backward":
             status = np.zeros((n + 1) // 2)
             capi.check(lib.idocp_rbd_synchronize(h), "synchronize")
             capi.check(lib.idocp_device_download(status.ctypes.data, dev["status"], status.nbytes), "download")
-            res["gn_lqr_all_solved"] = bool((status.view(np.int32)[:n] == -1).all())
+            res[P + "lqr_all_solved"] = bool((status.view(np.int32)[:n] == -1).all())
             res[row].update({"g_rows": R, "ms_per_step": round(res[row]["ms_median"] / S, 4)})
-            if "lqr_gains_ilqr" in res:
-                res[row]["ratio_to_lqr_gains_ilqr"] = round(res[row]["ms_median"] / res["lqr_gains_ilqr"]["ms_median"], 3)
-        if row == "gn_residual_pass_copy":
+            for other in ("lqr_gains_ilqr", "gn_lqr_backward"):
+                if other in res and other != row:
+                    res[row]["ratio_to_" + other] = round(res[row]["ms_median"] / res[other]["ms_median"], 3)
+        if row == P + "residual_pass_copy":
             res[row].update({"samples": pass_samples, "bytes": pass_bytes, "GB_per_s": round(pass_bytes / res[row]["ms_median"] / 1e6, 1),
                              "residual_launches_per_linearisation": S * -(-n // pass_samples)})
-        if row == "gn_linearize_s16":
+        if row == P + "linearize_s16":
             res[row].update({"G_traj_bytes": 8 * sizes["G"], "passes_per_step": -(-n // pass_samples)})
-            if "fdd_linearize_s16" in res:
-                res[row]["ratio_to_fdd_linearize_s16"] = round(res[row]["ms_median"] / res["fdd_linearize_s16"]["ms_median"], 3)
+            for other in ("fdd_linearize_s16", "gn_linearize_s16"):
+                if other in res and other != row:
+                    res[row]["ratio_to_" + other] = round(res[row]["ms_median"] / res[other]["ms_median"], 3)
     if want_iterate:
         io = capi.RbdIlqrIO()
         for field, key in (("q_traj", "q"), ("v_traj", "v"), ("u_traj", "u"), ("a_traj", "a"), ("f_traj", "f"), ("cost", "cost"), ("violation", "viol"),
                            ("alpha_accepted", "alpha_accepted"), ("lqr_status", "status"), ("expected", "expected"), ("workspace", "work")):
             setattr(io, field, dev[key])
-        io.regularization, io.armijo, io.shrink, io.alpha_min, io.penalty, io.trials = 1e-6, 1e-4, 0.5, 1e-3, 0.0, 2
-        measure("gn_iterate", lambda: capi.check(lib.idocp_rbd_ilqr_iterate_gn_device(h, o, n, S, act, ts, dt, dev["pts"], C.byref(io), 0), "iterate_gn"))
-        res["gn_iterate"].update({"steps": S, "trials": 2, "workspace_bytes": 8 * sizes["work"]})
+        io.regularization, io.armijo, io.shrink, io.alpha_min, io.penalty, io.trials = 1e-6, 1e-4, 0.5, 1e-3, MU if penalty else 0.0, 2
+        iterate = lib.idocp_rbd_ilqr_iterate_penalty_device if penalty else lib.idocp_rbd_ilqr_iterate_gn_device
+        measure(P + "iterate", lambda: capi.check(iterate(h, o, n, S, act, ts, dt, dev["pts"], C.byref(io), 0), "iterate"))
+        res[P + "iterate"].update({"steps": S, "trials": 2, "workspace_bytes": 8 * sizes["work"]})
         status = np.zeros((n + 1) // 2)
         capi.check(lib.idocp_rbd_synchronize(h), "synchronize")
         capi.check(lib.idocp_device_download(status.ctypes.data, dev["status"], status.nbytes), "download")
-        res["gn_iterate_all_solved"] = bool((status.view(np.int32)[:n] == -1).all())
-        if "ilqr_iterate" in res:
-            res["gn_iterate"]["ratio_to_ilqr_iterate"] = round(res["gn_iterate"]["ms_median"] / res["ilqr_iterate"]["ms_median"], 3)
+        res[P + "iterate_all_solved"] = bool((status.view(np.int32)[:n] == -1).all())
+        for other in ("ilqr_iterate", "gn_iterate"):
+            if other in res and other != P + "iterate":
+                res[P + "iterate"]["ratio_to_" + other] = round(res[P + "iterate"]["ms_median"] / res[other]["ms_median"], 3)
     capi.check(lib.idocp_rbd_synchronize(h), "synchronize")
     lib.idocp_rbd_objective_destroy(o)
     for d in dev.values():
@@ -715,6 +748,8 @@ def main():
         ilqr_rows(wanted, lib, rt, h, stream, m, n, measure, res)
     if not wanted or set(wanted) & set(GN_ROWS):
         gn_rows(wanted, lib, rt, h, stream, m, n, measure, res)
+    if not wanted or set(wanted) & set(PENALTY_ROWS):
+        gn_rows(wanted, lib, rt, h, stream, m, n, measure, res, penalty=True)
     ran = [k for k in res if isinstance(res[k], dict)]
     for key, src, width, rows in (("tau_finite", "tau", nv, ("stage_", "impulse_")), ("fd_a_finite", "fd_a", nv, ("fd_",)),
                                   ("policy_u_finite", "u_out", m.nu, ("policy_", "fd_step_closed_loop"))):
