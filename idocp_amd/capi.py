@@ -456,6 +456,19 @@ def _proto(lib):
             f = getattr(lib, name + form)
             f.argtypes = args
             f.restype = ci
+    # the augmented Lagrangian: multipliers on the constraint rows
+    window = [vp, vp, ci, ci, ci, c_int_p, ci, vp, vp, vp, vp, vp, cd]
+    for form in ("", "_device"):
+        for name, args in (("idocp_rbd_score_al", window + [vp, vp]),
+                           ("idocp_rbd_multiplier_update", window + [vp, vp, vp, vp]),
+                           ("idocp_rbd_linearize_rollout_al", [vp, vp, ci, ci, c_int_p, cd, cd, vp, vp, vp, vp, P(RbdPenaltyLinearizationIO), cd, vp, ci]),
+                           ("idocp_rbd_ilqr_iterate_al", [vp, vp, ci, ci, c_int_p, cd, cd, vp, P(RbdIlqrIO), vp, ci]),
+                           ("idocp_rbd_ilqr_al_update", [vp, vp, ci, ci, c_int_p, vp, vp, vp, vp, vp, cd, cd, vp, vp, vp, vp])):
+            f = getattr(lib, name + form)
+            f.argtypes = args
+            f.restype = ci
+    lib.idocp_rbd_objective_multiplier_rows.argtypes = [vp]
+    lib.idocp_rbd_objective_multiplier_rows.restype = ci
     lib.idocp_rbd_objective_constraint_rows.argtypes = [vp]
     lib.idocp_rbd_objective_constraint_rows.restype = ci
     lib.idocp_rbd_ilqr_penalty_workspace_bytes.argtypes = [vp, vp, ci, ci]

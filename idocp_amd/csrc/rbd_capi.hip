@@ -574,6 +574,10 @@ struct CostLinearization {
   double* D = nullptr;
   double mu = 0.0;
   int rc = 0;
+  // the augmented-Lagrangian form (idocp_rbd_linearize_rollout_al): the rows at their shifted values; lambda [steps][n][L] or nullptr
+  bool al = false;
+  const double* lambda = nullptr;
+  int L = 0;
 };
 
 // every pointer: device memory.  cost == nullptr: idocp_rbd_linearize_rollout.  With cost, step k takes the sample axis in the passes of
@@ -612,10 +616,16 @@ int linearizeDevice(idocp_rbd* h, int n, int steps, const int* active, double ti
           static_cast<RbdResidualArgs&>(pr) = r;
           pr.q = io.q; pr.v = io.v; pr.u = io.u; pr.block = cost->block; pr.D = at(cost->D, F * nz);
           pr.dtmu = dt * cost->mu; pr.scale = std::sqrt(pr.dtmu); pr.rc = cost->rc;
-          launched = rbdResidualPenalty(h->model.nv, h->quadruped, pr, h->stream);
+          if (cost->al) {
+            RbdResidualAlArgs ar;
+            static_cast<RbdResidualPenaltyArgs&>(ar) = pr;
+            ar.lambda = cost->lambda ? cost->lambda + F * (size_t)cost->L : nullptr; ar.penalty = cost->mu;
+            launched = rbdResidualAl(h->model.nv, h->quadruped, ar, h->stream);
+          } else launched = rbdResidualPenalty(h->model.nv, h->quadruped, pr, h->stream);
         } else launched = rbdResidual(h->model.nv, h->quadruped, r, h->stream);
         if (!launched) {
-          set_last_error(std::string(cost->penalty ? "idocp_rbd_linearize_rollout_penalty" : "idocp_rbd_linearize_rollout_cost") + ": no residual kernel for this model");
+          set_last_error(std::string(cost->al ? "idocp_rbd_linearize_rollout_al" : (cost->penalty ? "idocp_rbd_linearize_rollout_penalty" : "idocp_rbd_linearize_rollout_cost")) +
+                         ": no residual kernel for this model");
           return IDOCP_E_UNSUPPORTED;
         }
         HIP_TRY(hipGetLastError());
@@ -769,7 +779,7 @@ int checkPenalty(const char* who, const idocp_rbd_objective* o, double mu) {
 // every pointer: device memory.  As linearizeCostDevice, with the penalty form of the residual kernel: one launch per pass for both kinds of rows.
 int linearizePenaltyDevice(idocp_rbd* h, const idocp_rbd_objective* o, int n, int steps, const int* active, double time_step, double dt, const double* u,
                            const double* contact_points, const double* q_traj, const double* v_traj, const idocp_rbd_penalty_linearization_io_t& io,
-                           double mu, int touchdown_impulse) {
+                           double mu, int touchdown_impulse, bool al = false, const double* lambda = nullptr) {
   if (!io.G_traj && !io.rho_traj && !io.D_traj && !io.lx_traj && !io.lu_traj)
     return linearizeDevice(h, n, steps, active, time_step, dt, u, contact_points, q_traj, v_traj, io.A_traj, io.B_traj, touchdown_impulse);
   if (io.lx_traj || io.lu_traj) {
@@ -782,6 +792,7 @@ int linearizePenaltyDevice(idocp_rbd* h, const idocp_rbd_objective* o, int n, in
   CostLinearization c;
   c.table = o->d_residual; c.G = io.G_traj; c.rho = io.rho_traj; c.lx = io.lx_traj; c.lu = io.lu_traj; c.R = idocp_host::residualRows(o->plan);
   c.penalty = true; c.block = o->d_block; c.D = io.D_traj; c.mu = mu; c.rc = idocp_host::constraintRows(o->plan);
+  c.al = al; c.L = idocp_host::multiplierRows(o->plan); c.lambda = c.L ? lambda : nullptr;
   return linearizeDevice(h, n, steps, active, time_step, dt, u, contact_points, q_traj, v_traj, io.A_traj, io.B_traj, touchdown_impulse, &c);
 }
 
@@ -909,7 +920,8 @@ IlqrWorkspace ilqrWorkspace(const idocp_rbd* h, int n, int steps, int g_rows = 0
 }
 
 // gn: the Gauss-Newton form takes every objective whose a_weight and f_weight have square roots
-enum IlqrForm { ILQR_DIAGONAL = 0, ILQR_GN = 1, ILQR_PENALTY = 2 };
+// al: the penalty chain on the shifted rows (idocp_rbd_ilqr_iterate_al)
+enum IlqrForm { ILQR_DIAGONAL = 0, ILQR_GN = 1, ILQR_PENALTY = 2, ILQR_AL = 3 };
 
 int checkIterate(const char* who, const idocp_rbd* h, const idocp_rbd_objective* o, int n, int steps, const idocp_rbd_ilqr_io_t* io, bool host,
                  int gn = ILQR_DIAGONAL) {
@@ -919,7 +931,7 @@ int checkIterate(const char* who, const idocp_rbd* h, const idocp_rbd_objective*
   if (gn) {
     const std::string unsupported = idocp_host::residualUnsupported(o->plan);
     if (!unsupported.empty()) { set_last_error(w + ": " + unsupported); return IDOCP_E_UNSUPPORTED; }
-    if (gn == ILQR_PENALTY) {
+    if (gn >= ILQR_PENALTY) {
       const std::string pair = idocp_host::penaltyPairRefused(o->plan);
       if (!pair.empty()) { set_last_error(w + ": " + pair); return IDOCP_E_ARG; }
       if (idocp_host::residualRows(o->plan) + idocp_host::constraintRows(o->plan) > 64) { set_last_error(w + ": more than 64 rows"); return IDOCP_E_UNSUPPORTED; }
@@ -936,6 +948,7 @@ int checkIterate(const char* who, const idocp_rbd* h, const idocp_rbd_objective*
   const char* const names[5] = {"regularization", "armijo", "shrink", "alpha_min", "penalty"};
   for (int i = 0; i < 5; ++i)
     if (!std::isfinite(values[i]) || values[i] < 0.0) { set_last_error(w + ": " + names[i] + " must be finite and non-negative"); return IDOCP_E_ARG; }
+  if (gn == ILQR_AL && !(io->penalty > 0.0)) { set_last_error(w + ": penalty (mu) must be positive"); return IDOCP_E_ARG; }
   if (!host && !io->workspace) { set_last_error(w + ": the workspace is needed (idocp_rbd_ilqr_workspace_bytes, idocp_rbd_ilqr_gn_workspace_bytes, idocp_rbd_ilqr_penalty_workspace_bytes)"); return IDOCP_E_ARG; }
   if (!host && (reinterpret_cast<uintptr_t>(io->workspace) & 15u)) { set_last_error(w + ": the workspace must be 16-byte aligned"); return IDOCP_E_ARG; }
   return IDOCP_OK;
@@ -944,9 +957,11 @@ int checkIterate(const char* who, const idocp_rbd* h, const idocp_rbd_objective*
 // io: device pointers; ws: the workspace.  The chain of include/idocp_hip.h; every call on the handle's stream, no synchronisation, no host read.
 // gn: the chain of idocp_rbd_ilqr_iterate_gn -- the cost linearisation and the backward pass with residual rows in place of the first three calls.
 int iterateDevice(idocp_rbd* h, const idocp_rbd_objective* o, int n, int steps, const int* active, double time_step, double dt,
-                  const double* contact_points, const idocp_rbd_ilqr_io_t& io, double* ws, int touchdown_impulse, int gn = ILQR_DIAGONAL) {
+                  const double* contact_points, const idocp_rbd_ilqr_io_t& io, double* ws, int touchdown_impulse, int gn = ILQR_DIAGONAL,
+                  const double* lambda = nullptr) {
   const size_t nq = h->model.nq, nv = h->model.nv, nu = h->model.nu, nf = 3 * (size_t)h->model.ncontacts, N = (size_t)n;
-  const bool penalty = gn == ILQR_PENALTY;
+  const bool penalty = gn >= ILQR_PENALTY, al = gn == ILQR_AL;
+  const size_t rows_l = al ? (size_t)idocp_host::multiplierRows(o->plan) : 0;
   const int rows_c = penalty ? idocp_host::constraintRows(o->plan) : 0;
   const int g_rows = gn ? idocp_host::residualRows(o->plan) + rows_c : 0;
   const IlqrWorkspace w = ilqrWorkspace(h, n, steps, g_rows, penalty);
@@ -962,8 +977,10 @@ int iterateDevice(idocp_rbd* h, const idocp_rbd_objective* o, int n, int steps, 
     // the penalty chain: io.penalty is mu; without constraint rows D stays out and the GN form of the backward pass runs
     idocp_rbd_penalty_linearization_io_t c = idocp_rbd_penalty_linearization_io_t();
     c.A_traj = A; c.B_traj = B; c.G_traj = ws + w.G; c.D_traj = rows_c ? ws + w.D : nullptr; c.lx_traj = lx; c.lu_traj = lu;
-    rc = idocp_rbd_linearize_rollout_penalty_device(h, o, n, steps, active, time_step, dt, io.u_traj, contact_points, io.q_traj, io.v_traj, &c, io.penalty,
-                                                    touchdown_impulse);
+    if (al) rc = idocp_rbd_linearize_rollout_al_device(h, o, n, steps, active, time_step, dt, io.u_traj, contact_points, io.q_traj, io.v_traj, &c, io.penalty,
+                                                       lambda, touchdown_impulse);
+    else rc = idocp_rbd_linearize_rollout_penalty_device(h, o, n, steps, active, time_step, dt, io.u_traj, contact_points, io.q_traj, io.v_traj, &c, io.penalty,
+                                                         touchdown_impulse);
     if (rc) return rc;
     lqr.x_weight = o->d_lqr_weights;
     lqr.u_weight = o->d_lqr_weights + idocp_host::lqrWeightOffsetU(o->plan);
@@ -1015,7 +1032,11 @@ int iterateDevice(idocp_rbd* h, const idocp_rbd_objective* o, int n, int steps, 
       rc = idocp_rbd_score_rollout_device(h, o, n, first, window, active ? active + (size_t)first * h->model.ncontacts : nullptr,
                                           first + window == steps, first > 0, &sc);
       if (rc) return rc;
-      if (penalty) {      // the trial sq_violation over the score's L1 violation, window by window the same way
+      if (al) {           // the trial sq_shifted under the window's multipliers
+        rc = idocp_rbd_score_al_device(h, o, n, first, window, active ? active + (size_t)first * h->model.ncontacts : nullptr, first > 0, sc.q_traj,
+                                       sc.v_traj, sc.u_traj, sc.a_traj, sc.f_traj, io.penalty, lambda ? lambda + (size_t)first * N * rows_l : nullptr, violation_t);
+        if (rc) return rc;
+      } else if (penalty) {      // the trial sq_violation over the score's L1 violation, window by window the same way
         rc = idocp_rbd_score_penalty_device(h, o, n, first, window, active ? active + (size_t)first * h->model.ncontacts : nullptr, first > 0, sc.q_traj,
                                             sc.v_traj, sc.u_traj, sc.a_traj, sc.f_traj, violation_t);
         if (rc) return rc;
@@ -1028,7 +1049,7 @@ int iterateDevice(idocp_rbd* h, const idocp_rbd_objective* o, int n, int steps, 
 
 // the host form of both iterations: stages once, owns the workspace in the staging buffer, reads back once
 int iterateHost(const char* who, idocp_rbd* h, const idocp_rbd_objective* o, int n, int steps, const int* active, double time_step, double dt,
-                const double* contact_points, const idocp_rbd_ilqr_io_t* io, int touchdown_impulse, int gn) {
+                const double* contact_points, const idocp_rbd_ilqr_io_t* io, int touchdown_impulse, int gn, const double* lambda = nullptr) {
   int rc = checkIterate(who, h, o, n, steps, io, true, gn); if (rc) return rc;
   {      // (the bounds are host memory here and can be looked at)
     idocp_rbd_policy_t bounds = idocp_rbd_policy_t();
@@ -1055,11 +1076,13 @@ int iterateHost(const char* who, idocp_rbd* h, const idocp_rbd_objective* o, int
   p.out(io->alpha_accepted, N, &d.alpha_accepted);
   p.out(io->expected, 2 * N, &d.expected);
   p.deviceOnly((N + 1) / 2, &d_status);
-  const bool penalty = gn == ILQR_PENALTY;
+  const bool penalty = gn >= ILQR_PENALTY;
+  const double* d_lambda = nullptr;
+  if (gn == ILQR_AL) p.in(lambda, S * N * (size_t)idocp_host::multiplierRows(o->plan), &d_lambda);
   p.deviceOnly(ilqrWorkspace(h, n, steps, gn ? idocp_host::residualRows(o->plan) + (penalty ? idocp_host::constraintRows(o->plan) : 0) : 0, penalty).total, &d_ws);
   rc = stageIn(h, p); if (rc) return rc;
   d.lqr_status = reinterpret_cast<int*>(d_status);
-  rc = iterateDevice(h, o, n, steps, active, time_step, dt, d_points, d, d_ws, touchdown_impulse, gn); if (rc) return rc;
+  rc = iterateDevice(h, o, n, steps, active, time_step, dt, d_points, d, d_ws, touchdown_impulse, gn, d_lambda); if (rc) return rc;
   HIP_TRY(hipMemcpyAsync(io->lqr_status, d_status, sizeof(int) * N, hipMemcpyDeviceToHost, h->stream));
   return stageOut(h, p);
 }
@@ -1908,6 +1931,257 @@ int idocp_rbd_ilqr_iterate_penalty_device(idocp_rbd_t* h, const idocp_rbd_object
 int idocp_rbd_ilqr_iterate_penalty(idocp_rbd_t* h, const idocp_rbd_objective_t* o, int n, int steps, const int* active, double time_step, double dt,
                                    const double* contact_points, const idocp_rbd_ilqr_io_t* io, int touchdown_impulse) {
   return iterateHost("idocp_rbd_ilqr_iterate_penalty", h, o, n, steps, active, time_step, dt, contact_points, io, touchdown_impulse, ILQR_PENALTY);
+}
+
+// ---- the augmented Lagrangian: multipliers on the constraint rows
+
+int idocp_rbd_objective_multiplier_rows(const idocp_rbd_objective_t* o) { return o ? idocp_host::multiplierRows(o->plan) : 0; }
+
+namespace {
+int checkMu(const char* who, double mu, const char* name = "mu") {
+  if (!std::isfinite(mu) || !(mu > 0.0)) { set_last_error(std::string(who) + ": " + name + " must be positive and finite"); return IDOCP_E_ARG; }
+  return IDOCP_OK;
+}
+
+// what idocp_rbd_score_al and idocp_rbd_multiplier_update refuse, and the kernel's arguments but for the array pointers.  update: lambda_out is
+// needed where the objective has multiplier rows; score: sq is
+int checkAl(const char* who, const idocp_rbd* h, const idocp_rbd_objective* o, int n, int first_step, int steps, const int* active, int accumulate,
+            const double* q, const double* v, const double* u, const double* a_traj, const double* f, double mu, bool update, const double* out,
+            RbdAlArgs* a) {
+  const std::string w(who);
+  if (!h || !o) { set_last_error(w + ": null handle or objective"); return IDOCP_E_ARG; }
+  if (o->owner != h) { set_last_error(w + ": the objective was created on another handle"); return IDOCP_E_ARG; }
+  int rc = checkMu(who, mu); if (rc) return rc;
+  if (!update && !out) { set_last_error(w + ": sq_shifted is needed"); return IDOCP_E_ARG; }
+  if (update && !out && idocp_host::multiplierRows(o->plan)) { set_last_error(w + ": lambda_out is needed"); return IDOCP_E_ARG; }
+  const idocp_host::RbdScoreCall c = idocp_host::planPenaltyCall(who, o->plan, n, first_step, steps, active, q, v, u, a_traj, f);
+  if (c.rc) { set_last_error(c.error); return c.rc; }
+  std::memcpy(a->masks, c.masks, sizeof(c.masks));
+  a->block = o->d_block; a->steps = steps; a->accumulate = accumulate != 0; a->penalty = mu;
+  a->sq = nullptr; a->lambda = nullptr; a->lambda_out = nullptr; a->infeasibility = nullptr; a->change = nullptr;
+  return IDOCP_OK;
+}
+
+// a: device pointers.  An objective without multiplier rows has nothing to update: the statistics are zero (kept as they are with accumulate)
+int launchAlUpdate(const char* who, idocp_rbd* h, const idocp_rbd_objective* o, const RbdAlArgs& a, int n) {
+  if (idocp_host::multiplierRows(o->plan) == 0) {
+    if (!a.accumulate) {
+      if (a.infeasibility) HIP_TRY(hipMemsetAsync(a.infeasibility, 0, sizeof(double) * (size_t)n, h->stream));
+      if (a.change) HIP_TRY(hipMemsetAsync(a.change, 0, sizeof(double) * (size_t)n, h->stream));
+    }
+    return IDOCP_OK;
+  }
+  if (!rbdAlUpdate(h->model.nv, h->quadruped, a, n, h->stream)) { set_last_error(std::string(who) + ": no multiplier kernel for this model"); return IDOCP_E_UNSUPPORTED; }
+  HIP_TRY(hipGetLastError());
+  return IDOCP_OK;
+}
+}  // namespace
+
+int idocp_rbd_score_al_device(idocp_rbd_t* h, const idocp_rbd_objective_t* o, int n, int first_step, int steps, const int* active, int accumulate,
+                              const double* q_traj, const double* v_traj, const double* u_traj, const double* a_traj, const double* f_traj, double mu,
+                              const double* lambda_traj, double* sq_shifted) {
+  const char* who = "idocp_rbd_score_al_device";
+  RbdAlArgs a;
+  int rc = checkAl(who, h, o, n, first_step, steps, active, accumulate, q_traj, v_traj, u_traj, a_traj, f_traj, mu, false, sq_shifted, &a); if (rc) return rc;
+  HIP_TRY(hipSetDevice(h->device));
+  a.q = q_traj; a.v = v_traj; a.u = u_traj; a.a = a_traj; a.f = f_traj; a.sq = sq_shifted;
+  a.lambda = idocp_host::multiplierRows(o->plan) ? lambda_traj : nullptr;
+  if (!rbdAlScore(h->model.nv, h->quadruped, a, n, h->stream)) { set_last_error(std::string(who) + ": no multiplier kernel for this model"); return IDOCP_E_UNSUPPORTED; }
+  HIP_TRY(hipGetLastError());
+  return IDOCP_OK;
+}
+
+int idocp_rbd_score_al(idocp_rbd_t* h, const idocp_rbd_objective_t* o, int n, int first_step, int steps, const int* active, int accumulate,
+                       const double* q_traj, const double* v_traj, const double* u_traj, const double* a_traj, const double* f_traj, double mu,
+                       const double* lambda_traj, double* sq_shifted) {
+  const char* who = "idocp_rbd_score_al";
+  RbdAlArgs a;
+  int rc = checkAl(who, h, o, n, first_step, steps, active, accumulate, q_traj, v_traj, u_traj, a_traj, f_traj, mu, false, sq_shifted, &a); if (rc) return rc;
+  HIP_TRY(hipSetDevice(h->device));
+  const size_t nq = h->model.nq, nv = h->model.nv, nu = h->model.nu, nf = 3 * (size_t)o->plan.ncontacts, N = (size_t)n, S = (size_t)steps;
+  StagePlan p;
+  p.in(q_traj, S * N * nq, &a.q);
+  p.in(v_traj, S * N * nv, &a.v);
+  p.in(u_traj, S * N * nu, &a.u);
+  p.in(a_traj, S * N * nv, &a.a);
+  p.in(f_traj, S * N * nf, &a.f);
+  p.in(lambda_traj, S * N * (size_t)idocp_host::multiplierRows(o->plan), &a.lambda);
+  if (accumulate) p.update(sq_shifted, N, &a.sq); else p.out(sq_shifted, N, &a.sq);
+  rc = stageIn(h, p); if (rc) return rc;
+  if (!rbdAlScore(h->model.nv, h->quadruped, a, n, h->stream)) { set_last_error(std::string(who) + ": no multiplier kernel for this model"); return IDOCP_E_UNSUPPORTED; }
+  HIP_TRY(hipGetLastError());
+  return stageOut(h, p);
+}
+
+int idocp_rbd_multiplier_update_device(idocp_rbd_t* h, const idocp_rbd_objective_t* o, int n, int first_step, int steps, const int* active, int accumulate,
+                                       const double* q_traj, const double* v_traj, const double* u_traj, const double* a_traj, const double* f_traj,
+                                       double mu, const double* lambda_traj, double* lambda_out, double* infeasibility, double* multiplier_change) {
+  const char* who = "idocp_rbd_multiplier_update_device";
+  RbdAlArgs a;
+  int rc = checkAl(who, h, o, n, first_step, steps, active, accumulate, q_traj, v_traj, u_traj, a_traj, f_traj, mu, true, lambda_out, &a); if (rc) return rc;
+  HIP_TRY(hipSetDevice(h->device));
+  a.q = q_traj; a.v = v_traj; a.u = u_traj; a.a = a_traj; a.f = f_traj;
+  a.lambda = lambda_traj; a.lambda_out = lambda_out; a.infeasibility = infeasibility; a.change = multiplier_change;
+  return launchAlUpdate(who, h, o, a, n);
+}
+
+int idocp_rbd_multiplier_update(idocp_rbd_t* h, const idocp_rbd_objective_t* o, int n, int first_step, int steps, const int* active, int accumulate,
+                                const double* q_traj, const double* v_traj, const double* u_traj, const double* a_traj, const double* f_traj, double mu,
+                                const double* lambda_traj, double* lambda_out, double* infeasibility, double* multiplier_change) {
+  const char* who = "idocp_rbd_multiplier_update";
+  RbdAlArgs a;
+  int rc = checkAl(who, h, o, n, first_step, steps, active, accumulate, q_traj, v_traj, u_traj, a_traj, f_traj, mu, true, lambda_out, &a); if (rc) return rc;
+  HIP_TRY(hipSetDevice(h->device));
+  const size_t nq = h->model.nq, nv = h->model.nv, nu = h->model.nu, nf = 3 * (size_t)o->plan.ncontacts, N = (size_t)n, S = (size_t)steps;
+  const size_t rows = (size_t)idocp_host::multiplierRows(o->plan);
+  StagePlan p;
+  p.in(q_traj, S * N * nq, &a.q);
+  p.in(v_traj, S * N * nv, &a.v);
+  p.in(u_traj, S * N * nu, &a.u);
+  p.in(a_traj, S * N * nv, &a.a);
+  p.in(f_traj, S * N * nf, &a.f);
+  // (the staged copies are two slots even where the caller's arrays are one: in place is the caller's business, not the stage's)
+  p.in(lambda_traj, S * N * rows, &a.lambda);
+  p.out(lambda_out, S * N * rows, &a.lambda_out);
+  if (accumulate) { p.update(infeasibility, N, &a.infeasibility); p.update(multiplier_change, N, &a.change); }
+  else { p.out(infeasibility, N, &a.infeasibility, true); p.out(multiplier_change, N, &a.change, true); }
+  rc = stageIn(h, p); if (rc) return rc;
+  rc = launchAlUpdate(who, h, o, a, n); if (rc) return rc;
+  return stageOut(h, p);
+}
+
+namespace {
+int checkLinearizeAl(const char* who, idocp_rbd* h, const idocp_rbd_objective* o, int n, int steps, const int* active, double time_step, double dt,
+                     const double* u_traj, const double* contact_points, const double* q_traj, const double* v_traj,
+                     const idocp_rbd_penalty_linearization_io_t* io, double mu) {
+  int rc = checkLinearize(who, h, n, steps, active, time_step, dt, contact_points, q_traj, v_traj); if (rc) return rc;
+  if (!io) { set_last_error(std::string(who) + ": null objective or io"); return IDOCP_E_ARG; }
+  const idocp_rbd_cost_linearization_io_t view = costViewOf(*io);
+  rc = checkLinearizeCost(who, h, o, n, steps, u_traj, &view); if (rc) return rc;
+  rc = checkMu(who, mu); if (rc) return rc;
+  return checkPenalty(who, o, mu);
+}
+}  // namespace
+
+int idocp_rbd_linearize_rollout_al_device(idocp_rbd_t* h, const idocp_rbd_objective_t* o, int n, int steps, const int* active, double time_step, double dt,
+                                          const double* u_traj, const double* contact_points, const double* q_traj, const double* v_traj,
+                                          const idocp_rbd_penalty_linearization_io_t* io, double mu, const double* lambda_traj, int touchdown_impulse) {
+  const char* who = "idocp_rbd_linearize_rollout_al_device";
+  int rc = checkLinearizeAl(who, h, o, n, steps, active, time_step, dt, u_traj, contact_points, q_traj, v_traj, io, mu); if (rc) return rc;
+  HIP_TRY(hipSetDevice(h->device));
+  return linearizePenaltyDevice(h, o, n, steps, active, time_step, dt, u_traj, contact_points, q_traj, v_traj, *io, mu, touchdown_impulse, true, lambda_traj);
+}
+
+int idocp_rbd_linearize_rollout_al(idocp_rbd_t* h, const idocp_rbd_objective_t* o, int n, int steps, const int* active, double time_step, double dt,
+                                   const double* u_traj, const double* contact_points, const double* q_traj, const double* v_traj,
+                                   const idocp_rbd_penalty_linearization_io_t* io, double mu, const double* lambda_traj, int touchdown_impulse) {
+  const char* who = "idocp_rbd_linearize_rollout_al";
+  int rc = checkLinearizeAl(who, h, o, n, steps, active, time_step, dt, u_traj, contact_points, q_traj, v_traj, io, mu); if (rc) return rc;
+  HIP_TRY(hipSetDevice(h->device));
+  const size_t nq = h->model.nq, nv = h->model.nv, nu = h->model.nu, nf = 3 * (size_t)h->model.ncontacts, N = (size_t)n, S = (size_t)steps, nx = 2 * nv;
+  const size_t R = (size_t)idocp_host::residualRows(o->plan) + (size_t)idocp_host::constraintRows(o->plan);
+  StagePlan p;
+  const double *d_u, *d_points, *d_q, *d_v, *d_lambda;
+  idocp_rbd_penalty_linearization_io_t d;
+  p.in(u_traj, S * N * nu, &d_u);
+  p.in(contact_points, S * N * nf, &d_points);
+  p.in(q_traj, (S + 1) * N * nq, &d_q);
+  p.in(v_traj, (S + 1) * N * nv, &d_v);
+  p.in(lambda_traj, S * N * (size_t)idocp_host::multiplierRows(o->plan), &d_lambda);
+  p.out(io->A_traj, S * N * nx * nx, &d.A_traj);
+  p.out(io->B_traj, S * N * nx * nu, &d.B_traj);
+  p.out(io->G_traj, S * N * R * (nx + nu), &d.G_traj);
+  p.out(io->rho_traj, S * N * R, &d.rho_traj);
+  p.out(io->D_traj, S * N * (nx + nu), &d.D_traj);
+  p.out(io->lx_traj, (S + 1) * N * nx, &d.lx_traj);
+  p.out(io->lu_traj, S * N * nu, &d.lu_traj);
+  rc = stageIn(h, p); if (rc) return rc;
+  rc = linearizePenaltyDevice(h, o, n, steps, active, time_step, dt, d_u, d_points, d_q, d_v, d, mu, touchdown_impulse, true, d_lambda); if (rc) return rc;
+  return stageOut(h, p);
+}
+
+int idocp_rbd_ilqr_iterate_al_device(idocp_rbd_t* h, const idocp_rbd_objective_t* o, int n, int steps, const int* active, double time_step, double dt,
+                                     const double* contact_points, const idocp_rbd_ilqr_io_t* io, const double* lambda_traj, int touchdown_impulse) {
+  int rc = checkIterate("idocp_rbd_ilqr_iterate_al_device", h, o, n, steps, io, false, ILQR_AL); if (rc) return rc;
+  HIP_TRY(hipSetDevice(h->device));
+  return iterateDevice(h, o, n, steps, active, time_step, dt, contact_points, *io, static_cast<double*>(io->workspace), touchdown_impulse, ILQR_AL, lambda_traj);
+}
+
+int idocp_rbd_ilqr_iterate_al(idocp_rbd_t* h, const idocp_rbd_objective_t* o, int n, int steps, const int* active, double time_step, double dt,
+                              const double* contact_points, const idocp_rbd_ilqr_io_t* io, const double* lambda_traj, int touchdown_impulse) {
+  return iterateHost("idocp_rbd_ilqr_iterate_al", h, o, n, steps, active, time_step, dt, contact_points, io, touchdown_impulse, ILQR_AL, lambda_traj);
+}
+
+namespace {
+// every pointer: device memory.  The outer step: the multipliers in place under mu, window by window with the running maxima, then `violation`
+// = sq_shifted under the new multipliers and mu_next, window by window with accumulate
+int alUpdateDevice(const char* who, idocp_rbd* h, const idocp_rbd_objective* o, int n, int steps, const int* active, const double* q, const double* v,
+                   const double* u, const double* a, const double* f, double mu, double mu_next, double* lambda, double* violation, double* infeasibility,
+                   double* change) {
+  const size_t nq = h->model.nq, nv = h->model.nv, nu = h->model.nu, nf = 3 * (size_t)h->model.ncontacts, N = (size_t)n;
+  const size_t rows = (size_t)idocp_host::multiplierRows(o->plan);
+  for (int pass = 0; pass < 2; ++pass)
+    for (int first = 0; first < steps; first += IDOCP_RBD_SCORE_MAX_WINDOW) {
+      const int window = steps - first < IDOCP_RBD_SCORE_MAX_WINDOW ? steps - first : IDOCP_RBD_SCORE_MAX_WINDOW;
+      const int* act = active ? active + (size_t)first * h->model.ncontacts : nullptr;
+      const double *qk = q + first * N * nq, *vk = v + first * N * nv, *uk = u ? u + first * N * nu : nullptr, *ak = a ? a + first * N * nv : nullptr;
+      const double* fk = f ? f + first * N * nf : nullptr;
+      double* lk = lambda ? lambda + first * N * rows : nullptr;
+      int rc;
+      if (pass == 0) rc = idocp_rbd_multiplier_update_device(h, o, n, first, window, act, first > 0, qk, vk, uk, ak, fk, mu, lk, lk, infeasibility, change);
+      else rc = idocp_rbd_score_al_device(h, o, n, first, window, act, first > 0, qk, vk, uk, ak, fk, mu_next, lk, violation);
+      if (rc) return rc;      // (idocp_last_error names the inner call)
+    }
+  (void)who;
+  return IDOCP_OK;
+}
+
+int checkAlUpdate(const char* who, const idocp_rbd* h, const idocp_rbd_objective* o, int n, int steps, const double* q, const double* v, double mu,
+                  double mu_next, const double* lambda, const double* violation) {
+  const std::string w(who);
+  if (!h || !o) { set_last_error(w + ": null handle or objective"); return IDOCP_E_ARG; }
+  if (o->owner != h) { set_last_error(w + ": the objective was created on another handle"); return IDOCP_E_ARG; }
+  if (n <= 0) { set_last_error(w + ": n must be positive"); return IDOCP_E_ARG; }
+  if (steps < 1 || steps > o->plan.steps) { set_last_error(w + ": steps must lie within 1 .. the objective's " + std::to_string(o->plan.steps) + " steps"); return IDOCP_E_ARG; }
+  if (!q || !v) { set_last_error(w + ": q_traj and v_traj are needed"); return IDOCP_E_ARG; }
+  if (!violation) { set_last_error(w + ": violation is needed"); return IDOCP_E_ARG; }
+  if (!lambda && idocp_host::multiplierRows(o->plan)) { set_last_error(w + ": lambda_traj is needed (the update is in place)"); return IDOCP_E_ARG; }
+  int rc = checkMu(who, mu); if (rc) return rc;
+  return checkMu(who, mu_next, "mu_next");
+}
+}  // namespace
+
+int idocp_rbd_ilqr_al_update_device(idocp_rbd_t* h, const idocp_rbd_objective_t* o, int n, int steps, const int* active, const double* q_traj,
+                                    const double* v_traj, const double* u_traj, const double* a_traj, const double* f_traj, double mu, double mu_next,
+                                    double* lambda_traj, double* violation, double* infeasibility, double* multiplier_change) {
+  const char* who = "idocp_rbd_ilqr_al_update_device";
+  int rc = checkAlUpdate(who, h, o, n, steps, q_traj, v_traj, mu, mu_next, lambda_traj, violation); if (rc) return rc;
+  HIP_TRY(hipSetDevice(h->device));
+  return alUpdateDevice(who, h, o, n, steps, active, q_traj, v_traj, u_traj, a_traj, f_traj, mu, mu_next, lambda_traj, violation, infeasibility, multiplier_change);
+}
+
+int idocp_rbd_ilqr_al_update(idocp_rbd_t* h, const idocp_rbd_objective_t* o, int n, int steps, const int* active, const double* q_traj,
+                             const double* v_traj, const double* u_traj, const double* a_traj, const double* f_traj, double mu, double mu_next,
+                             double* lambda_traj, double* violation, double* infeasibility, double* multiplier_change) {
+  const char* who = "idocp_rbd_ilqr_al_update";
+  int rc = checkAlUpdate(who, h, o, n, steps, q_traj, v_traj, mu, mu_next, lambda_traj, violation); if (rc) return rc;
+  HIP_TRY(hipSetDevice(h->device));
+  const size_t nq = h->model.nq, nv = h->model.nv, nu = h->model.nu, nf = 3 * (size_t)o->plan.ncontacts, N = (size_t)n, S = (size_t)steps;
+  StagePlan p;
+  const double *d_q, *d_v, *d_u, *d_a, *d_f;
+  double *d_lambda, *d_violation, *d_inf, *d_change;
+  p.in(q_traj, S * N * nq, &d_q);      // (the stage slices alone: the terminal slice has no rows)
+  p.in(v_traj, S * N * nv, &d_v);
+  p.in(u_traj, S * N * nu, &d_u);
+  p.in(a_traj, S * N * nv, &d_a);
+  p.in(f_traj, S * N * nf, &d_f);
+  p.update(lambda_traj, S * N * (size_t)idocp_host::multiplierRows(o->plan), &d_lambda);
+  p.out(violation, N, &d_violation);
+  p.out(infeasibility, N, &d_inf, true);
+  p.out(multiplier_change, N, &d_change, true);
+  rc = stageIn(h, p); if (rc) return rc;
+  rc = alUpdateDevice(who, h, o, n, steps, active, d_q, d_v, d_u, d_a, d_f, mu, mu_next, d_lambda, d_violation, d_inf, d_change); if (rc) return rc;
+  return stageOut(h, p);
 }
 
 }  // extern "C"

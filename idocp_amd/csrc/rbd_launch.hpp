@@ -171,6 +171,25 @@ struct RbdPenaltyArgs {
 };
 bool rbdPenalty(int nv, bool quadruped, const RbdPenaltyArgs& a, int n, hipStream_t st);
 
+// The augmented-Lagrangian forms (rbd_al_kernel.hip, rbd_residual_al_kernel.hip; idocp_rbd_score_al, idocp_rbd_multiplier_update,
+// idocp_rbd_linearize_rollout_al).  lambda: the window's [steps][n][L] multipliers, L = idocp_host::multiplierRows, or NULL (all zeros); mu > 0.
+// Score: sq [n] as above, of the shifted rows.  Update: lambda_out [steps][n][L] (may be lambda), infeasibility and change [n] or NULL, running maxima
+// with accumulate.  One wavefront per sample.  One launch each.  Both return false, having launched nothing, for a chain outside 2 .. 8 joints.
+struct RbdAlArgs : RbdPenaltyArgs {
+  const double* lambda;
+  double penalty;      // mu (RbdScoreBlock::mu is the friction coefficient)
+  double *lambda_out, *infeasibility, *change;
+};
+bool rbdAlScore(int nv, bool quadruped, const RbdAlArgs& a, int n, hipStream_t st);
+bool rbdAlUpdate(int nv, bool quadruped, const RbdAlArgs& a, int n, hipStream_t st);
+// The AL form of the residual pass: the penalty form with every constraint row evaluated at its shifted value.  lambda: the pass's slice
+// [count][L] or NULL; penalty: mu.
+struct RbdResidualAlArgs : RbdResidualPenaltyArgs {
+  const double* lambda;
+  double penalty;
+};
+bool rbdResidualAl(int nv, bool quadruped, const RbdResidualAlArgs& a, hipStream_t st);
+
 // Gradients of an objective along a rollout (rbd_gradient_kernel.hip; the arrays of idocp_rbd_gradient_io_t).  Every pointer: DEVICE memory;
 // q, v [steps (+ 1 if terminal)][n][..], u [steps][n][nu] or NULL, q_ref / v_ref the objective's tables AT the window's first step, block its
 // weights; lx [steps (+ 1)][n][2 nv] and lu [steps][n][nu], either may be NULL.  (steps + 1) * n fits an int.  One wavefront per

@@ -238,6 +238,8 @@ inline void residualTable(const RbdObjectivePlan& o, double* out) {
 inline int coneRows(const RbdObjectivePlan& o) { return o.block.cone == 1 ? 5 : (o.block.cone == 2 ? 2 : 0); }
 // Rc = roundup4(nu + ncone ncontacts) dense rows: the acceleration boxes, the cone rows, padding; 0 for an objective without constraints
 inline int constraintRows(const RbdObjectivePlan& o) { return o.has_constraints ? (o.nu + coneRows(o) * o.ncontacts + 3) / 4 * 4 : 0; }
+// L = 4 nu + ncone ncontacts multiplier rows per (step, sample) (idocp_rbd_objective_multiplier_rows): the q, v, u, a boxes, then the cone rows
+inline int multiplierRows(const RbdObjectivePlan& o) { return o.has_constraints ? 4 * o.nu + coneRows(o) * o.ncontacts : 0; }
 // "" when every enabled lower / upper pair has lo <= hi (the pair is then ONE signed row), else the text that names the pair
 inline std::string penaltyPairRefused(const RbdObjectivePlan& o) {
   const RbdScoreBlock& b = o.block;

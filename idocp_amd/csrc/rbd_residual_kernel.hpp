@@ -1,5 +1,6 @@
-// The kernel template of rbd_residual_kernel.hip and rbd_residual_penalty_kernel.hip (their heads have the method).  It lives in a header so that
-// each form is instantiated in a translation unit of its own: the code of the cost form does not depend on whether the penalty form is built beside it.
+// The kernel template of rbd_residual_kernel.hip, rbd_residual_penalty_kernel.hip and rbd_residual_al_kernel.hip (their heads have the method).  It
+// lives in a header so that each form is instantiated in a translation unit of its own: the code of the cost form does not depend on whether the
+// penalty form is built beside it, nor that of the penalty form on the augmented-Lagrangian form.
 #ifndef IDOCP_RBD_RESIDUAL_KERNEL_HPP_
 #define IDOCP_RBD_RESIDUAL_KERNEL_HPP_
 
@@ -55,12 +56,15 @@ __device__ __forceinline__ void residualLoadRun(const double* __restrict__ src, 
 }
 
 // Args = RbdResidualArgs: the cost rows at the head of rbd_residual_kernel.hip.  Args = RbdResidualPenaltyArgs (idocp_rbd_linearize_rollout_penalty):
-// the same blocks in LDS also give the constraint rows behind the cost rows, the diagonal D and the gradient of the merit.
+// the same blocks in LDS also give the constraint rows behind the cost rows, the diagonal D and the gradient of the merit.  Args = RbdResidualAlArgs
+// (idocp_rbd_linearize_rollout_al): the penalty form with every constraint row taken at its shifted value x + lambda / mu, g + lambda / mu; a
+// multiplier is read once, by the lane that forms its row, straight from global memory -- no LDS beyond the penalty form's.
 template <int NV, int NF, int NU, int S, class Args = RbdResidualArgs>
 __global__ __launch_bounds__(THREADS) void rbd_residual_kernel(Args a) {
   using Lds = RbdResidualLds<NV, NF, NU, S>;
   typedef double d2 __attribute__((ext_vector_type(2)));
-  constexpr bool PEN = std::is_same<Args, RbdResidualPenaltyArgs>::value;
+  constexpr bool AL = std::is_same<Args, RbdResidualAlArgs>::value;
+  constexpr bool PEN = std::is_same<Args, RbdResidualPenaltyArgs>::value || AL;
   constexpr int NX = Lds::NX, NZ = Lds::NZ, R = Lds::R, LDA = Lds::LDA, LDF = Lds::LDF;
   static_assert(S % 2 == 0 && (R * NZ) % 2 == 0, "the runs of a workgroup start at an even number of doubles");
   __shared__ Lds L;
@@ -110,7 +114,21 @@ __global__ __launch_bounds__(THREADS) void rbd_residual_kernel(Args a) {
           const double lo = kind == 0 ? W.q_min[j] : (kind == 1 ? -W.v_max[j] : -W.u_max[j]);
           const double hi = kind == 0 ? W.q_max[j] : (kind == 1 ? W.v_max[j] : W.u_max[j]);
           flag(s, x);
-          b = (x - hi > 0.0 ? x - hi : 0.0) - (lo - x > 0.0 ? lo - x : 0.0);
+          if constexpr (AL) {
+            // the multiplier row kind * NU + j of the sample shifts the value: the quotient rounded, then the sum
+            if (a.lambda) {
+#pragma clang fp contract(off)
+              const int rows = 4 * NU + (NF ? (W.cone == 1 ? 5 : (W.cone == 2 ? 2 : 0)) * (NF / 3) : 0);
+              const double l = a.lambda[(s0 + s) * (size_t)rows + kind * NU + j];
+              flag(s, l);
+              const double y = x + l / a.penalty;
+              b = (y - hi > 0.0 ? y - hi : 0.0) - (lo - y > 0.0 ? lo - y : 0.0);
+            } else {
+              b = (x - hi > 0.0 ? x - hi : 0.0) - (lo - x > 0.0 ? lo - x : 0.0);
+            }
+          } else {
+            b = (x - hi > 0.0 ? x - hi : 0.0) - (lo - x > 0.0 ? lo - x : 0.0);
+          }
         }
       }
       P.b[s][c] = b;
@@ -136,11 +154,24 @@ __global__ __launch_bounds__(THREADS) void rbd_residual_kernel(Args a) {
     const double sc = a.scale;
     const int cone = NF ? W.cone : 0, ncone = cone == 1 ? 5 : (cone == 2 ? 2 : 0);
     const double mu = W.mu, m = mu * 0.70710678118654752440;
+    // (AL) lambda / mu of multiplier row `row` of sample s; a non-finite multiplier flags the sample -- the barrier below stands before the stores
+    auto shift = [&](int s, int row) {
+#pragma clang fp contract(off)
+      double q = 0.0;
+      if constexpr (AL) {
+        if (a.lambda) { const double l = a.lambda[(s0 + s) * (size_t)(4 * NU + ncone * (NF / 3)) + row]; flag(s, l); q = l / a.penalty; }
+      }
+      return q;
+    };
     for (int t = tid; t < cnt * a.rc; t += THREADS) {
       const int s = t / a.rc, r = t - s * a.rc;
       double g = 0.0, w0 = 0.0, w1 = 0.0, w2 = 0.0;
       if (r < NU) {
-        const double x = L.a[s][NV - NU + r];
+        double x = L.a[s][NV - NU + r];
+        if constexpr (AL) {
+#pragma clang fp contract(off)
+          if (W.acceleration_upper || W.acceleration_lower) x = x + shift(s, 3 * NU + r);
+        }
         g = (W.acceleration_upper && x - W.a_max[r] > 0.0 ? x - W.a_max[r] : 0.0) - (W.acceleration_lower && W.a_min[r] - x > 0.0 ? W.a_min[r] - x : 0.0);
         w0 = g != 0.0 ? sc : 0.0;      // (the signed row: its gradient is that of x on either side)
       } else if (NF && r < NU + ncone * (NF / 3)) {
@@ -153,6 +184,10 @@ __global__ __launch_bounds__(THREADS) void rbd_residual_kernel(Args a) {
             j0 = i == 1 ? 1.0 : (i == 2 ? -1.0 : 0.0); j1 = i == 3 ? 1.0 : (i == 4 ? -1.0 : 0.0); j2 = -m;
             g = (i < 3 ? j0 * fx : j1 * fy) - m * fz;
           } else { g = fx * fx + fy * fy - mu * mu * fz * fz; j0 = 2.0 * fx; j1 = 2.0 * fy; j2 = -2.0 * (mu * mu) * fz; }
+          if constexpr (AL) {
+#pragma clang fp contract(off)
+            g = g + shift(s, 4 * NU + ncone * c + i);
+          }
           if (g > 0.0) { w0 = sc * j0; w1 = sc * j1; w2 = sc * j2; } else g = 0.0;
         }
       }

@@ -405,7 +405,8 @@ class Robot {
   }
 
  private:
-  // the body of ilqrIterate, ilqrIterateGaussNewton and ilqrIterateConstrained: idocp_rbd_ilqr_iterate or, with gauss_newton,
+  // the body of ilqrIterate, ilqrIterateGaussNewton, ilqrIterateConstrained, ilqrIterateAugmentedLagrangian and updateMultipliers (with
+  // multipliers: idocp_rbd_score_al and idocp_rbd_ilqr_iterate_al, or, with mu_next, idocp_rbd_ilqr_al_update alone): idocp_rbd_ilqr_iterate or, with gauss_newton,
   // idocp_rbd_ilqr_iterate_gn or, with constraints, idocp_rbd_ilqr_iterate_penalty (mu its penalty; *sq_violation receives the sq_violation of the
   // trajectory the call leaves, the trajectory that comes in being scored first: rolled out again for its a and f, then idocp_rbd_score_penalty)
   template <class CostFunctionT>
@@ -413,7 +414,8 @@ class Robot {
                          const std::vector<ContactStatus>& contact_status, const std::vector<std::vector<Eigen::Vector3d>>& contact_points,
                          std::vector<Eigen::VectorXd>& q, std::vector<Eigen::VectorXd>& v, std::vector<Eigen::VectorXd>& u, double& total_cost,
                          const double regularization, const double armijo, const int trials, const idocp_constraints_t* constraints = nullptr,
-                         const double mu = 0.0, double* sq_violation = nullptr) {
+                         const double mu = 0.0, double* sq_violation = nullptr, std::vector<double>* multipliers = nullptr,
+                         const double* mu_next = nullptr, double* multiplier_change = nullptr) {
     const int steps = (int)u.size(), nc = model_.ncontacts;
     if (steps < 1 || (int)q.size() != steps + 1 || (int)v.size() != steps + 1 ||
         (nc > 0 && ((int)contact_status.size() != steps || (int)contact_points.size() != steps))) {
@@ -451,9 +453,24 @@ class Robot {
       // sq_violation of the trajectory that comes in: its a and f from a rollout of its own torques, its q, v, u as given
       std::vector<double> tq(qs), tv(vs), ta((size_t)steps * nv), tf((size_t)steps * 3 * nc);
       rc = idocp_rbd_rollout(rbd_.h, 1, steps, actp, time_step, dt, us.data(), ptsp, tq.data(), tv.data(), ta.data(), nc > 0 ? tf.data() : nullptr, 0);
-      if (rc == IDOCP_OK)
-        rc = idocp_rbd_score_penalty(rbd_.h, objective, 1, 0, steps, actp, 0, qs.data(), vs.data(), us.data(), ta.data(), nc > 0 ? tf.data() : nullptr, &violation);
-      if (rc == IDOCP_OK) rc = idocp_rbd_ilqr_iterate_penalty(rbd_.h, objective, 1, steps, actp, time_step, dt, ptsp, &io, 0);
+      const double* const tfp = nc > 0 ? tf.data() : nullptr;
+      if (multipliers) {
+        // the augmented-Lagrangian forms: multipliers [steps][L], all zeros where the caller's vector has another size
+        const size_t rows = (size_t)steps * idocp_rbd_objective_multiplier_rows(objective);
+        if (multipliers->size() != rows) multipliers->assign(rows, 0.0);
+        if (mu_next) {      // updateMultipliers: alpha carries the infeasibility back
+          if (rc == IDOCP_OK)
+            rc = idocp_rbd_ilqr_al_update(rbd_.h, objective, 1, steps, actp, qs.data(), vs.data(), us.data(), ta.data(), tfp, mu, *mu_next, multipliers->data(),
+                                          &violation, &alpha, multiplier_change);
+        } else {
+          if (rc == IDOCP_OK)
+            rc = idocp_rbd_score_al(rbd_.h, objective, 1, 0, steps, actp, 0, qs.data(), vs.data(), us.data(), ta.data(), tfp, mu, multipliers->data(), &violation);
+          if (rc == IDOCP_OK) rc = idocp_rbd_ilqr_iterate_al(rbd_.h, objective, 1, steps, actp, time_step, dt, ptsp, &io, multipliers->data(), 0);
+        }
+      } else {
+        if (rc == IDOCP_OK) rc = idocp_rbd_score_penalty(rbd_.h, objective, 1, 0, steps, actp, 0, qs.data(), vs.data(), us.data(), ta.data(), tfp, &violation);
+        if (rc == IDOCP_OK) rc = idocp_rbd_ilqr_iterate_penalty(rbd_.h, objective, 1, steps, actp, time_step, dt, ptsp, &io, 0);
+      }
       if (sq_violation) *sq_violation = violation;
     } else {
       rc = (gauss_newton ? idocp_rbd_ilqr_iterate_gn : idocp_rbd_ilqr_iterate)(rbd_.h, objective, 1, steps, actp, time_step, dt, ptsp, &io, 0);
@@ -490,6 +507,32 @@ class Robot {
     const idocp_constraints_t g = constraints.native();
     return ilqrIterateForm(true, cost, t0, dt, time_step, contact_status, contact_points, q, v, u, total_cost, regularization, armijo, trials, &g, mu,
                            &sq_violation);
+  }
+  // The augmented-Lagrangian iteration, an ADDITION: idocp_rbd_ilqr_iterate_al with n = 1 at the penalty weight mu > 0 under the multipliers
+  // [N][L], L = 4 dimu + (cone rows) * contacts (idocp_hip.h has the layout; a vector of another size is replaced by zeros).  sq_shifted receives
+  // the shifted squared violation of the trajectory that is left; the multipliers are read, not written.
+  template <class CostFunctionT, class ConstraintsT>
+  double ilqrIterateAugmentedLagrangian(const CostFunctionT& cost, const ConstraintsT& constraints, const double t0, const double dt, const double time_step,
+                                        const std::vector<ContactStatus>& contact_status, const std::vector<std::vector<Eigen::Vector3d>>& contact_points,
+                                        std::vector<Eigen::VectorXd>& q, std::vector<Eigen::VectorXd>& v, std::vector<Eigen::VectorXd>& u, double& total_cost,
+                                        double& sq_shifted, std::vector<double>& multipliers, const double mu, const double regularization = 1e-6,
+                                        const double armijo = 1e-4, const int trials = 8) {
+    const idocp_constraints_t g = constraints.native();
+    return ilqrIterateForm(true, cost, t0, dt, time_step, contact_status, contact_points, q, v, u, total_cost, regularization, armijo, trials, &g, mu,
+                           &sq_shifted, &multipliers);
+  }
+  // The outer step, an ADDITION: idocp_rbd_ilqr_al_update with n = 1 -- the multipliers become mu times the shifted rows of the trajectory, in place;
+  // sq_shifted receives the shifted squared violation under the new multipliers and mu_next.  Returns the infeasibility (the largest unshifted row);
+  // multiplier_change receives the largest change of a multiplier.  The trajectory is left as it is.
+  template <class CostFunctionT, class ConstraintsT>
+  double updateMultipliers(const CostFunctionT& cost, const ConstraintsT& constraints, const double t0, const double dt, const double time_step,
+                           const std::vector<ContactStatus>& contact_status, const std::vector<std::vector<Eigen::Vector3d>>& contact_points,
+                           std::vector<Eigen::VectorXd>& q, std::vector<Eigen::VectorXd>& v, std::vector<Eigen::VectorXd>& u,
+                           std::vector<double>& multipliers, const double mu, const double mu_next, double& sq_shifted, double& multiplier_change) {
+    const idocp_constraints_t g = constraints.native();
+    double unused_cost = 0.0;
+    return ilqrIterateForm(true, cost, t0, dt, time_step, contact_status, contact_points, q, v, u, unused_cost, 1e-6, 1e-4, 1, &g, mu, &sq_shifted,
+                           &multipliers, &mu_next, &multiplier_change);
   }
   // Robot::framePosition / frameRotation / framePlacement (robot.hxx:206-233): of any frame of the URDF (pinocchio's frame numbering, as the
   // contact frames and the task-space costs use it), at the configuration of the last updateFrameKinematics / updateKinematics

@@ -1289,7 +1289,7 @@ int idocp_rbd_ilqr_iterate_gn(idocp_rbd_t* h, const idocp_rbd_objective_t* o, in
  *   diagonal part: the q, v and u boxes of the actuated joints are diagonal in [dq; dv; du] and get no dense row --
  *     D[k][i][c] = dt mu [b != 0] at the joint's own dq, dv or du column, 0 elsewhere (the base columns are 0); the gradient gains dt mu b there.
  * The gradient of the merit is that of idocp_rbd_linearize_rollout_cost plus Gc^T sigma plus the diagonal terms.  The blocks are those of STAGE
- * mode at slice k, as for the cost rows.  Out of scope: multipliers, task-space terms, contact_distance, impulse cones.
+ * mode at slice k, as for the cost rows.  Out of scope: task-space terms, contact_distance, impulse cones (multipliers: the block below).
  * idocp_rbd_objective_constraint_rows returns Rc (0 for a NULL objective and for one created with constraints == NULL). */
 int idocp_rbd_objective_constraint_rows(const idocp_rbd_objective_t* o);
 /* idocp_rbd_score_penalty: sq_violation [n] of the window of `steps` steps at first_step, with first_step, steps, active and accumulate as
@@ -1355,6 +1355,86 @@ int idocp_rbd_ilqr_iterate_penalty_device(idocp_rbd_t* h, const idocp_rbd_object
                                           double dt, const double* contact_points, const idocp_rbd_ilqr_io_t* io, int touchdown_impulse);
 int idocp_rbd_ilqr_iterate_penalty(idocp_rbd_t* h, const idocp_rbd_objective_t* o, int n, int steps, const int* active, double time_step, double dt,
                                    const double* contact_points, const idocp_rbd_ilqr_io_t* io, int touchdown_impulse);
+
+/* ---- Augmented-Lagrangian iLQR: a first-order multiplier on every constraint row (rbd_al_kernel.hip, the AL form of rbd_residual_kernel.hip).
+ * ADDITIONS.  The penalty calls above keep their refusals and their bits.  A pure penalty reaches feasibility only as mu grows without bound,
+ * which ruins the conditioning of the stage Hessian; with a multiplier estimate per row mu stays moderate.  This is the definition.
+ * Multiplier layout.  L = idocp_rbd_objective_multiplier_rows(o) = 4 nu + ncone ncontacts rows per (step, sample): 68 or 56 on the quadruped,
+ * 4 nv on a chain, always even; 0 for a NULL objective and for one created with constraints == NULL.  Row kind nu + j, kind = 0 .. 3, is the q, v,
+ * u, a box of actuated joint j; row 4 nu + ncone c + r is cone row r of contact c.  lambda_traj is [steps][n][L]; lambda_traj == NULL means all
+ * zeros.  Rows of kinds switched off, and of contacts inactive at a step, are ignored on read and written as 0 by the update.
+ * The shift.  Every call of this block needs mu > 0, finite (IDOCP_E_ARG otherwise).  The augmented Lagrangian of a row is the squared hinge of
+ * the shifted row minus a term that does not depend on the trajectory: for g <= 0 with lambda >= 0,
+ *   psi = (1 / 2 mu) (max(0, lambda + mu g)^2 - lambda^2) = (mu / 2) max(0, g + lambda / mu)^2 - lambda^2 / 2 mu,
+ * and for a lower / upper pair on x with ONE signed lambda (Rockafellar's form for x in [lo, hi]) psi = (mu / 2) dist(x + lambda / mu, [lo, hi])^2
+ * - lambda^2 / 2 mu.  In this order of operations, without contraction into fused multiply-adds:
+ *   box:       y = x + lambda / mu (the quotient rounded, then the sum),   b~ = [upper] max(0, y - hi) - [lower] max(0, lo - y)
+ *   cone row:  g~ = g + lambda / mu,  h~ = max(0, g~),  g as idocp_rbd_score_penalty computes it; the row is active iff g~ > 0, dg/df is unchanged
+ *   sq_shifted[i] = sum_k dt 1/2 sum_rows b~^2 | h~^2, folded by the same tree and step order as sq_violation
+ *   merit[i]      = cost[i] + mu sq_shifted[i]: the constant sum lambda^2 / 2 mu is DROPPED -- it moves no minimiser and no Armijo test, but
+ *                   merits under different multipliers are not comparable
+ *   update:    lambda+ = mu b~ (box, signed) or mu h~ (cone), ONE rounded product.
+ * A non-finite lambda makes that sample's result NaN and touches no other sample.  A wrong-signed lambda on a one-sided row (a negative one on a
+ * cone row or on an upper-only acceleration box, a positive one on a lower-only box) is NOT refused: it merely shifts the row away from its
+ * bound; the update never produces one.  Still out of scope: task-space terms, contact_distance, impulse cones, latching footholds in the trial
+ * rollouts. */
+int idocp_rbd_objective_multiplier_rows(const idocp_rbd_objective_t* o);
+/* idocp_rbd_score_al: idocp_rbd_score_penalty plus mu and the window's lambda_traj [steps][n][L]; returns sq_shifted [n].  One launch; a sample's
+ * result is bit for bit independent of n and of the windowing.  With lambda_traj == NULL or all zeros it is idocp_rbd_score_penalty bit for bit. */
+int idocp_rbd_score_al(idocp_rbd_t* h, const idocp_rbd_objective_t* o, int n, int first_step, int steps, const int* active, int accumulate,
+                       const double* q_traj, const double* v_traj, const double* u_traj, const double* a_traj, const double* f_traj, double mu,
+                       const double* lambda_traj, double* sq_shifted);
+/* Device pointers, asynchronous on idocp_rbd_stream(h); allocates nothing. */
+int idocp_rbd_score_al_device(idocp_rbd_t* h, const idocp_rbd_objective_t* o, int n, int first_step, int steps, const int* active, int accumulate,
+                              const double* q_traj, const double* v_traj, const double* u_traj, const double* a_traj, const double* f_traj, double mu,
+                              const double* lambda_traj, double* sq_shifted);
+/* idocp_rbd_multiplier_update: on the same window, lambda_out [steps][n][L] = lambda+ (lambda_out may alias lambda_traj; needed where L > 0), and
+ * two optional statistics [n]:
+ *   infeasibility     = max over steps and rows of the UNSHIFTED |b| / max(0, g)
+ *   multiplier_change = max over steps and rows of |lambda+ - lambda| (rows that are ignored count 0)
+ * With accumulate both take the maximum with what the arrays hold (window after window); a maximum has no order, so the bits are fixed.  A
+ * non-finite entry in what is read of a sample makes both statistics of the sample NaN (and keeps them NaN under accumulate) and every row of
+ * lambda_out of the (step, sample) where it was read NaN.  One launch, one wavefront per sample; no atomics. */
+int idocp_rbd_multiplier_update(idocp_rbd_t* h, const idocp_rbd_objective_t* o, int n, int first_step, int steps, const int* active, int accumulate,
+                                const double* q_traj, const double* v_traj, const double* u_traj, const double* a_traj, const double* f_traj, double mu,
+                                const double* lambda_traj, double* lambda_out, double* infeasibility, double* multiplier_change);
+/* Device pointers, asynchronous on idocp_rbd_stream(h); allocates nothing. */
+int idocp_rbd_multiplier_update_device(idocp_rbd_t* h, const idocp_rbd_objective_t* o, int n, int first_step, int steps, const int* active, int accumulate,
+                                       const double* q_traj, const double* v_traj, const double* u_traj, const double* a_traj, const double* f_traj,
+                                       double mu, const double* lambda_traj, double* lambda_out, double* infeasibility, double* multiplier_change);
+/* idocp_rbd_linearize_rollout_al: idocp_rbd_linearize_rollout_penalty plus lambda_traj [steps][n][L], into the same io.  The constraint rows of
+ * G_traj and rho_traj hold sigma = s b~ | s h~ with the coefficients s [b~ != 0] and s [g~ > 0] dg/df, D = dt mu [b~ != 0], and the gradient gains
+ * dt mu b~: the gradient of merit = cost + mu sq_shifted.  Everything else is the penalty call's: A, B and the cost rows bit for bit, one launch per
+ * pass, NaN containment (a non-finite multiplier counts as an input of its sample for G, rho, D, lx and lu; A and B do not read it), independence of n and of the outputs asked for, the refusals
+ * -- but mu = 0 is refused here.  lambda_traj == NULL or all zeros gives every output of the penalty call bit for bit. */
+int idocp_rbd_linearize_rollout_al(idocp_rbd_t* h, const idocp_rbd_objective_t* o, int n, int steps, const int* active, double time_step, double dt,
+                                   const double* u_traj, const double* contact_points, const double* q_traj, const double* v_traj,
+                                   const idocp_rbd_penalty_linearization_io_t* io, double mu, const double* lambda_traj, int touchdown_impulse);
+/* Device pointers; asynchronous on idocp_rbd_stream(h); allocates only when a scratch has to grow. */
+int idocp_rbd_linearize_rollout_al_device(idocp_rbd_t* h, const idocp_rbd_objective_t* o, int n, int steps, const int* active, double time_step, double dt,
+                                          const double* u_traj, const double* contact_points, const double* q_traj, const double* v_traj,
+                                          const idocp_rbd_penalty_linearization_io_t* io, double mu, const double* lambda_traj, int touchdown_impulse);
+/* idocp_rbd_ilqr_iterate_al: idocp_rbd_ilqr_iterate_penalty plus lambda_traj [steps][n][L] (NULL: zeros; then it is that call bit for bit).
+ * `penalty` of io is mu (> 0), `violation` holds sq_shifted in and out.  The chain: idocp_rbd_linearize_rollout_al_device; the unchanged
+ * idocp_rbd_lqr_backward_gn_diag_device; the trial rounds with idocp_rbd_score_al_device filling the trial `violation`; the unchanged
+ * idocp_rbd_ilqr_accept_device.  A sample's cost + mu sq_shifted never rises while lambda and mu stay.  The workspace is the one of
+ * idocp_rbd_ilqr_penalty_workspace_bytes.  No host decisions on the stream.  The multipliers are read, never written. */
+int idocp_rbd_ilqr_iterate_al_device(idocp_rbd_t* h, const idocp_rbd_objective_t* o, int n, int steps, const int* active, double time_step, double dt,
+                                     const double* contact_points, const idocp_rbd_ilqr_io_t* io, const double* lambda_traj, int touchdown_impulse);
+int idocp_rbd_ilqr_iterate_al(idocp_rbd_t* h, const idocp_rbd_objective_t* o, int n, int steps, const int* active, double time_step, double dt,
+                              const double* contact_points, const idocp_rbd_ilqr_io_t* io, const double* lambda_traj, int touchdown_impulse);
+/* idocp_rbd_ilqr_al_update: the outer step on the current rollout (q_traj, v_traj, u_traj, a_traj, f_traj as idocp_rbd_ilqr_io_t holds them; the
+ * `steps` stage slices are read).  lambda_traj [steps][n][L] becomes lambda+ under mu, IN PLACE; then violation [n] = sq_shifted under lambda+ and
+ * mu_next, so that the next iteration's acceptance test has a consistent baseline; infeasibility and multiplier_change [n] (either may be NULL)
+ * are the statistics of idocp_rbd_multiplier_update over all steps.  Beyond IDOCP_RBD_SCORE_MAX_WINDOW steps both passes go window by window.
+ * The schedule of mu (mu_next = mu keeps it) stays with the caller.  Host pointers; returns when the results are in place. */
+int idocp_rbd_ilqr_al_update(idocp_rbd_t* h, const idocp_rbd_objective_t* o, int n, int steps, const int* active, const double* q_traj,
+                             const double* v_traj, const double* u_traj, const double* a_traj, const double* f_traj, double mu, double mu_next,
+                             double* lambda_traj, double* violation, double* infeasibility, double* multiplier_change);
+/* Device pointers, asynchronous on idocp_rbd_stream(h); allocates nothing. */
+int idocp_rbd_ilqr_al_update_device(idocp_rbd_t* h, const idocp_rbd_objective_t* o, int n, int steps, const int* active, const double* q_traj,
+                                    const double* v_traj, const double* u_traj, const double* a_traj, const double* f_traj, double mu, double mu_next,
+                                    double* lambda_traj, double* violation, double* infeasibility, double* multiplier_change);
 
 /* ---- Sampling around a torque sequence: perturb, weigh, average (rbd_sample_kernel.hip).  Every call of this block is an ADDITION (the reference
  * has no counterpart).  With idocp_rbd_rollout_policy_device and idocp_rbd_score_rollout_device between the first and the second, one iteration of

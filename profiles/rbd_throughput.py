@@ -18,6 +18,7 @@ idocp_rbd_rollout_footholds_device (one latch launch more per step); both carry 
 16 steps (lqr_rows has their description); run with fdd_linearize_s16 they also carry their ratio to the linearisation that feeds them.  The grad_*,
 ilqr_accept and ilqr_iterate rows are the cost gradients, the acceptance step and one whole iLQR iteration (ilqr_rows has their description).
 The penalty_* rows are the gn_* rows under constraints with the penalty calls (gn_rows with penalty=True has their setting).
+The al_* rows are the augmented-Lagrangian calls in the same setting, next to them (al_rows has their description).
 The gn_* rows are the cost linearisation with residual rows, the backward pass with G^T G and one full-cost iteration (gn_rows has their
 description).
 
@@ -497,6 +498,7 @@ def ilqr_rows(wanted, lib, rt, h, stream, m, n, measure, res):
 
 GN_ROWS = ("gn_linearize_s16", "gn_residual_pass_copy", "gn_lqr_backward", "gn_iterate")
 PENALTY_ROWS = ("penalty_linearize_s16", "penalty_residual_pass_copy", "penalty_lqr_backward", "penalty_iterate")
+AL_ROWS = ("al_score", "al_score_copy", "al_update", "al_update_copy", "al_linearize_s16", "al_iterate")
 GN_STEPS = 16
 GN_RESIDUAL_DOUBLES = 1470 + 48 + 1536 + 32 + 48      # per quadruped sample and launch of rbd_residual_kernel: a, f and the six blocks in; lx, lu in; G, rho, lx, lu out
 GN_PASS = ((256 << 20) // 8) // (1470 + 8) // 2 * 2      # samples per pass of the cost linearisation (ResidualPlan of rbd_capi.hip)
@@ -535,7 +537,7 @@ def gn_rows(wanted, lib, rt, h, stream, m, n, measure, res, penalty=False):
     Rc = lib.idocp_rbd_objective_constraint_rows(o) if penalty else 0
     R = lib.idocp_rbd_objective_residual_rows(o) + Rc
     MU = 10.0
-    want_iterate = not wanted or P + "iterate" in wanted
+    want_iterate = not wanted or P + "iterate" in wanted or (penalty and "al_iterate" in wanted)
     sizes = {"q": (S + 1) * n * nq, "v": (S + 1) * n * nv, "u": S * n * nu, "a": S * n * nv, "f": S * n * nf, "pts": S * n * nf,
              "A": S * n * nx * nx, "B": S * n * nx * nu, "G": S * n * R * nz, "rho": S * n * R, "lx": (S + 1) * n * nx, "lu": S * n * nu,
              "K": S * n * nx * nu, "k": S * n * nu, "P0": n * nx * nx, "p0": n * nx, "wx": nx, "wu": nu, "wxf": nx,
@@ -614,7 +616,7 @@ def gn_rows(wanted, lib, rt, h, stream, m, n, measure, res, penalty=False):
             for other in ("fdd_linearize_s16", "gn_linearize_s16"):
                 if other in res and other != row:
                     res[row]["ratio_to_" + other] = round(res[row]["ms_median"] / res[other]["ms_median"], 3)
-    if want_iterate:
+    if want_iterate and (not wanted or P + "iterate" in wanted):
         io = capi.RbdIlqrIO()
         for field, key in (("q_traj", "q"), ("v_traj", "v"), ("u_traj", "u"), ("a_traj", "a"), ("f_traj", "f"), ("cost", "cost"), ("violation", "viol"),
                            ("alpha_accepted", "alpha_accepted"), ("lqr_status", "status"), ("expected", "expected"), ("workspace", "work")):
@@ -630,10 +632,61 @@ def gn_rows(wanted, lib, rt, h, stream, m, n, measure, res, penalty=False):
         for other in ("ilqr_iterate", "gn_iterate"):
             if other in res and other != P + "iterate":
                 res[P + "iterate"]["ratio_to_" + other] = round(res[P + "iterate"]["ms_median"] / res[other]["ms_median"], 3)
+    if penalty and (not wanted or set(wanted) & set(AL_ROWS)):
+        al_rows(wanted, lib, rt, h, stream, o, n, S, act, ts, dt, MU, dev, lin, sizes, measure, res)
     capi.check(lib.idocp_rbd_synchronize(h), "synchronize")
     lib.idocp_rbd_objective_destroy(o)
     for d in dev.values():
         lib.idocp_device_free(d)
+
+
+def al_rows(wanted, lib, rt, h, stream, o, n, S, act, ts, dt, MU, dev, lin, sizes, measure, res):
+    """the al_* rows, in the setting and on the buffers of the penalty_* rows (read each against the penalty_* row of the same run), multipliers
+    [S][n][L] as one idocp_rbd_ilqr_al_update_device from zero leaves them: al_score is idocp_rbd_score_al_device and al_update
+    idocp_rbd_multiplier_update_device in place with both statistics, over all S steps; al_score_copy / al_update_copy a device-to-device copy of the
+    bytes each touches (the q, v, u, a, f slices and the multipliers in; the multipliers out for the update), capped at the size of A_traj;
+    al_linearize_s16 is idocp_rbd_linearize_rollout_al_device with all seven outputs; al_iterate one idocp_rbd_ilqr_iterate_al_device with two
+    trial rounds."""
+    L = lib.idocp_rbd_objective_multiplier_rows(o)
+    for key, size in (("lam", S * n * L), ("inf", n), ("change", n), ("sq", n)):
+        dev[key] = C.c_void_p()
+        capi.check(lib.idocp_device_alloc(C.byref(dev[key]), 8 * size), "alloc")
+        assert rt.hipMemsetAsync(dev[key], 0, 8 * size, stream) == 0
+    traj = (dev["q"], dev["v"], dev["u"], dev["a"], dev["f"])
+    capi.check(lib.idocp_rbd_ilqr_al_update_device(h, o, n, S, act, *traj, MU, MU, dev["lam"], dev["viol"], dev["inf"], dev["change"]), "al_update")
+    per_slice = (sizes["q"] + sizes["v"]) // (S + 1)
+    read = 8 * (sizes["u"] + sizes["a"] + sizes["f"] + S * per_slice + S * n * L)
+    cap = 8 * min(sizes["A"], sizes["G"])
+
+    def copy(nbytes):
+        assert rt.hipMemcpyAsync(dev["A"], dev["G"], min(nbytes, cap), 3, stream) == 0
+
+    plan = (("al_score", lambda: capi.check(lib.idocp_rbd_score_al_device(h, o, n, 0, S, act, 0, *traj, MU, dev["lam"], dev["sq"]), "score_al"), 0),
+            ("al_score_copy", lambda: copy(read), read),
+            ("al_update", lambda: capi.check(lib.idocp_rbd_multiplier_update_device(h, o, n, 0, S, act, 0, *traj, MU, dev["lam"], dev["lam"], dev["inf"], dev["change"]),
+                                             "multiplier_update"), 0),
+            ("al_update_copy", lambda: copy(read + 8 * S * n * L), read + 8 * S * n * L),
+            ("al_linearize_s16", lambda: capi.check(lib.idocp_rbd_linearize_rollout_al_device(h, o, n, S, act, ts, dt, dev["u"], dev["pts"], dev["q"], dev["v"], C.byref(lin),
+                                                                                            MU, dev["lam"], 0), "linearize_al"), 0))
+    for row, launch, nbytes in plan:
+        if wanted and row not in wanted:
+            continue
+        measure(row, launch)
+        res[row].update({"steps": S, "multiplier_rows": L})
+        if nbytes:
+            res[row].update({"bytes": min(nbytes, cap), "GB_per_s": round(min(nbytes, cap) / res[row]["ms_median"] / 1e6, 1)})
+        if row == "al_linearize_s16" and "penalty_linearize_s16" in res:
+            res[row]["ratio_to_penalty_linearize_s16"] = round(res[row]["ms_median"] / res["penalty_linearize_s16"]["ms_median"], 3)
+    if (not wanted or "al_iterate" in wanted) and "work" in dev:
+        io = capi.RbdIlqrIO()
+        for field, key in (("q_traj", "q"), ("v_traj", "v"), ("u_traj", "u"), ("a_traj", "a"), ("f_traj", "f"), ("cost", "cost"), ("violation", "viol"),
+                           ("alpha_accepted", "alpha_accepted"), ("lqr_status", "status"), ("expected", "expected"), ("workspace", "work")):
+            setattr(io, field, dev[key])
+        io.regularization, io.armijo, io.shrink, io.alpha_min, io.penalty, io.trials = 1e-6, 1e-4, 0.5, 1e-3, MU, 2
+        measure("al_iterate", lambda: capi.check(lib.idocp_rbd_ilqr_iterate_al_device(h, o, n, S, act, ts, dt, dev["pts"], C.byref(io), dev["lam"], 0), "iterate_al"))
+        res["al_iterate"].update({"steps": S, "trials": 2})
+        if "penalty_iterate" in res:
+            res["al_iterate"]["ratio_to_penalty_iterate"] = round(res["al_iterate"]["ms_median"] / res["penalty_iterate"]["ms_median"], 3)
 
 
 def main():
@@ -748,7 +801,7 @@ def main():
         ilqr_rows(wanted, lib, rt, h, stream, m, n, measure, res)
     if not wanted or set(wanted) & set(GN_ROWS):
         gn_rows(wanted, lib, rt, h, stream, m, n, measure, res)
-    if not wanted or set(wanted) & set(PENALTY_ROWS):
+    if not wanted or set(wanted) & set(PENALTY_ROWS + AL_ROWS):
         gn_rows(wanted, lib, rt, h, stream, m, n, measure, res, penalty=True)
     ran = [k for k in res if isinstance(res[k], dict)]
     for key, src, width, rows in (("tau_finite", "tau", nv, ("stage_", "impulse_")), ("fd_a_finite", "fd_a", nv, ("fd_",)),
