@@ -563,101 +563,124 @@ ResidualPlan residualPlan(const idocp_rbd* h, int n) {
   return p;
 }
 
-// what the cost form of the linearisation adds (idocp_rbd_linearize_rollout_cost): G, rho and the gradients lx, lu, which hold the diagonal part
-struct CostLinearization {
-  const double* table;      // idocp_host::residualTable of the objective, device memory
-  double *G, *rho, *lx, *lu;
-  int R;
-  // the penalty form (idocp_rbd_linearize_rollout_penalty): G and rho have R + rc rows, D [steps][n][nz]
-  bool penalty = false;
-  const idocp_host::RbdScoreBlock* block = nullptr;
-  double* D = nullptr;
-  double mu = 0.0;
-  int rc = 0;
-  // the augmented-Lagrangian form (idocp_rbd_linearize_rollout_al): the rows at their shifted values; lambda [steps][n][L] or nullptr
-  bool al = false;
-  const double* lambda = nullptr;
-  int L = 0;
+// The form of an iLQR chain and of its pieces (the linearisation with rows, the backward pass, the workspace): built ONCE per call from the entry's
+// chain, the handle and the objective; every layer below asks it instead of deriving the rows again.
+//   DIAGONAL  idocp_rbd_ilqr_iterate          the plain linearisation, the gradients, the diagonal backward pass
+//   GN        idocp_rbd_ilqr_iterate_gn       the cost rows of a_weight and f_weight (every objective whose weights have square roots)
+//   PENALTY   idocp_rbd_ilqr_iterate_penalty  the constraint rows behind the cost rows, and the diagonal D
+//   AL        idocp_rbd_ilqr_iterate_al       the penalty chain on the rows shifted by the multipliers
+struct IlqrForm {
+  enum Chain { DIAGONAL, GN, PENALTY, AL };
+  Chain chain;
+  int cost_rows = 0, constraint_rows = 0, multiplier_rows = 0;      // R, Rc and L of include/idocp_hip.h; 0 where the chain has none
+  // o == nullptr (a refusal to come, or idocp_rbd_ilqr_gn_workspace_bytes, which has none): the cost rows of any objective of the handle
+  IlqrForm(Chain c, const idocp_rbd* h, const idocp_rbd_objective* o) : chain(c) {
+    if (chain == DIAGONAL || (!h && !o)) return;
+    cost_rows = o ? idocp_host::residualRows(o->plan) : idocp_host::residualRows(h->model.nv, h->quadruped ? h->model.ncontacts : 0);
+    if (o && penalty()) constraint_rows = idocp_host::constraintRows(o->plan);
+    if (o && al()) multiplier_rows = idocp_host::multiplierRows(o->plan);
+  }
+  bool penalty() const { return chain == PENALTY || chain == AL; }      // the workspace and the io have a D_traj
+  bool al() const { return chain == AL; }
+  int rows() const { return cost_rows + constraint_rows; }              // of G_traj and rho_traj
+  bool diagonal() const { return constraint_rows > 0; }                 // D_traj is written and read (without constraint rows it stays out)
+  const double* lambdaOf(const double* lambda) const { return multiplier_rows ? lambda : nullptr; }      // NULL (all zeros) where no row reads it
+  const char* linearization() const {
+    return al() ? "idocp_rbd_linearize_rollout_al" : (penalty() ? "idocp_rbd_linearize_rollout_penalty" : "idocp_rbd_linearize_rollout_cost");
+  }
 };
 
-// every pointer: device memory.  cost == nullptr: idocp_rbd_linearize_rollout.  With cost, step k takes the sample axis in the passes of
-// residualPlan: the derivative composition of the pass with a, f and the blocks into h->gn, then one launch of rbd_residual_kernel.hip.
-int linearizeDevice(idocp_rbd* h, int n, int steps, const int* active, double time_step, double dt, const double* u, const double* contact_points,
-                    const double* q_traj, const double* v_traj, double* A_traj, double* B_traj, int touchdown_impulse,
-                    const CostLinearization* cost = nullptr) {
+// every pointer: device memory.  The touchdown impulse in front of step k + 1, if there is one, folded into A_k and B_k in place.
+int touchdownProduct(idocp_rbd* h, int n, int steps, int k, const int* active, double time_step, double dt, const double* u, const double* contact_points,
+                     const double* q_traj, const double* v_traj, double* A_traj, double* B_traj) {
+  if (!h->quadruped || k + 1 >= steps) return IDOCP_OK;
   const size_t nq = h->model.nq, nv = h->model.nv, nu = h->model.nu, nf = 3 * (size_t)h->model.ncontacts, N = (size_t)n, nx = 2 * nv;
-  if (!cost && !A_traj && !B_traj) return IDOCP_OK;
-  if (cost) {
-    const ResidualPlan p = residualPlan(h, n);
-    int rc = h->gn.grow(p.total, h->stream); if (rc) return rc;
-    double* const S = h->gn.ptr;
-    const size_t R = (size_t)cost->R + (size_t)cost->rc, nz = nx + nu;      // (rc = 0 but for the penalty form)
-    auto at = [](double* x, size_t off) { return x ? x + off : nullptr; };
-    for (int k = 0; k < steps; ++k) {
-      const int mask = h->quadruped ? maskOf(h, active + (size_t)k * h->model.ncontacts) : 0;
-      for (int first = 0; first < n; first += p.chunk) {
-        const int cnt = n - first < p.chunk ? n - first : p.chunk;
-        const size_t F = (size_t)k * N + first;      // (slice k, sample `first`)
-        idocp_rbd_fdd_io_t io = idocp_rbd_fdd_io_t();
-        io.q = q_traj + F * nq; io.v = v_traj + F * nv; io.u = u ? u + F * nu : nullptr;
-        io.contact_points = contact_points ? contact_points + F * nf : nullptr;
-        io.A = at(A_traj, F * nx * nx); io.B = at(B_traj, F * nx * nu);
-        io.a = S + p.a; io.da_dq = S + p.da_dq; io.da_dv = S + p.da_dv; io.da_du = S + p.da_du;
-        if (h->quadruped) { io.f = S + p.f; io.df_dq = S + p.df_dq; io.df_dv = S + p.df_dv; io.df_du = S + p.df_du; }
-        rc = launchDerivatives(h, IDOCP_RBD_STAGE, cnt, mask, time_step, dt, io); if (rc) return rc;
-        RbdResidualArgs r;
-        r.a = io.a; r.f = io.f; r.da_dq = io.da_dq; r.da_dv = io.da_dv; r.da_du = io.da_du; r.df_dq = io.df_dq; r.df_dv = io.df_dv; r.df_du = io.df_du;
-        r.table = cost->table;
-        r.G = at(cost->G, F * R * nz); r.rho = at(cost->rho, F * R); r.lx = at(cost->lx, F * nx); r.lu = at(cost->lu, F * nu);
-        r.count = cnt; r.mask = mask;
-        bool launched;
-        if (cost->penalty) {
-          RbdResidualPenaltyArgs pr;
-          static_cast<RbdResidualArgs&>(pr) = r;
-          pr.q = io.q; pr.v = io.v; pr.u = io.u; pr.block = cost->block; pr.D = at(cost->D, F * nz);
-          pr.dtmu = dt * cost->mu; pr.scale = std::sqrt(pr.dtmu); pr.rc = cost->rc;
-          if (cost->al) {
-            RbdResidualAlArgs ar;
-            static_cast<RbdResidualPenaltyArgs&>(ar) = pr;
-            ar.lambda = cost->lambda ? cost->lambda + F * (size_t)cost->L : nullptr; ar.penalty = cost->mu;
-            launched = rbdResidualAl(h->model.nv, h->quadruped, ar, h->stream);
-          } else launched = rbdResidualPenalty(h->model.nv, h->quadruped, pr, h->stream);
-        } else launched = rbdResidual(h->model.nv, h->quadruped, r, h->stream);
-        if (!launched) {
-          set_last_error(std::string(cost->al ? "idocp_rbd_linearize_rollout_al" : (cost->penalty ? "idocp_rbd_linearize_rollout_penalty" : "idocp_rbd_linearize_rollout_cost")) +
-                         ": no residual kernel for this model");
-          return IDOCP_E_UNSUPPORTED;
-        }
-        HIP_TRY(hipGetLastError());
-      }
-    }
-    if (!A_traj && !B_traj) return IDOCP_OK;
-  }
+  const int mask = maskOf(h, active + (size_t)k * h->model.ncontacts), touchdown = maskOf(h, active + (size_t)(k + 1) * h->model.ncontacts) & ~mask;
+  if (!touchdown) return IDOCP_OK;
+  const double *qk = q_traj + k * N * nq, *vk = v_traj + k * N * nv;
+  int rc = h->lin.grow(N * nv + N * nx * nx, h->stream); if (rc) return rc;
+  double *v_pre = h->lin.ptr, *E = v_pre + N * nv;
+  idocp_rbd_fd_io_t fd = idocp_rbd_fd_io_t();
+  fd.q = qk; fd.v = vk; fd.u = u ? u + k * N * nu : nullptr; fd.contact_points = contact_points ? contact_points + k * N * nf : nullptr;
+  fd.v_next = v_pre;      // the pre-impulse velocity v_k + dt a, recomputed
+  rc = launchForward(h, IDOCP_RBD_STAGE, n, mask, time_step, dt, fd); if (rc) return rc;
+  idocp_rbd_fdd_io_t imp = idocp_rbd_fdd_io_t();
+  imp.q = qk + N * nq; imp.v = v_pre; imp.A = E;
+  rc = launchDerivatives(h, IDOCP_RBD_IMPULSE, n, touchdown, time_step, dt, imp); if (rc) return rc;
+  rbdFddImpulseProduct((int)nx, (int)nu, E, A_traj ? A_traj + k * N * nx * nx : nullptr, B_traj ? B_traj + k * N * nx * nu : nullptr, n, h->stream);
+  HIP_TRY(hipGetLastError());
+  return IDOCP_OK;
+}
+
+// every pointer: device memory.  idocp_rbd_linearize_rollout: per step the derivative composition, then the touchdown in front of the next step.
+int linearizeDevice(idocp_rbd* h, int n, int steps, const int* active, double time_step, double dt, const double* u, const double* contact_points,
+                    const double* q_traj, const double* v_traj, double* A_traj, double* B_traj, int touchdown_impulse) {
+  const size_t nq = h->model.nq, nv = h->model.nv, nu = h->model.nu, nf = 3 * (size_t)h->model.ncontacts, N = (size_t)n, nx = 2 * nv;
+  if (!A_traj && !B_traj) return IDOCP_OK;
   for (int k = 0; k < steps; ++k) {
-    const int mask = h->quadruped ? maskOf(h, active + (size_t)k * h->model.ncontacts) : 0;
-    const int next = (h->quadruped && k + 1 < steps) ? maskOf(h, active + (size_t)(k + 1) * h->model.ncontacts) : 0;
-    const int touchdown = touchdown_impulse ? (next & ~mask) : 0;      // the impulse in front of step k + 1
-    const double *qk = q_traj + k * N * nq, *vk = v_traj + k * N * nv;
-    const double* uk = u ? u + k * N * nu : nullptr;
-    const double* pk = contact_points ? contact_points + k * N * nf : nullptr;
     idocp_rbd_fdd_io_t io = idocp_rbd_fdd_io_t();
-    io.q = qk; io.v = vk; io.u = uk; io.contact_points = pk;
+    io.q = q_traj + k * N * nq; io.v = v_traj + k * N * nv; io.u = u ? u + k * N * nu : nullptr;
+    io.contact_points = contact_points ? contact_points + k * N * nf : nullptr;
     io.A = A_traj ? A_traj + k * N * nx * nx : nullptr;
     io.B = B_traj ? B_traj + k * N * nx * nu : nullptr;
-    int rc = IDOCP_OK;
-    if (!cost) { rc = launchDerivatives(h, IDOCP_RBD_STAGE, n, mask, time_step, dt, io); if (rc) return rc; }      // (with cost: A_k, B_k are in place)
-    if (!touchdown) continue;
-    rc = h->lin.grow(N * nv + N * nx * nx, h->stream); if (rc) return rc;
-    double *v_pre = h->lin.ptr, *E = v_pre + N * nv;
-    idocp_rbd_fd_io_t fd = idocp_rbd_fd_io_t();
-    fd.q = qk; fd.v = vk; fd.u = uk; fd.contact_points = pk; fd.v_next = v_pre;      // the pre-impulse velocity v_k + dt a, recomputed
-    rc = launchForward(h, IDOCP_RBD_STAGE, n, mask, time_step, dt, fd); if (rc) return rc;
-    idocp_rbd_fdd_io_t imp = idocp_rbd_fdd_io_t();
-    imp.q = qk + N * nq; imp.v = v_pre; imp.A = E;
-    rc = launchDerivatives(h, IDOCP_RBD_IMPULSE, n, touchdown, time_step, dt, imp); if (rc) return rc;
-    rbdFddImpulseProduct((int)nx, (int)nu, E, io.A, io.B, n, h->stream);
+    int rc = launchDerivatives(h, IDOCP_RBD_STAGE, n, h->quadruped ? maskOf(h, active + (size_t)k * h->model.ncontacts) : 0, time_step, dt, io); if (rc) return rc;
+    if (touchdown_impulse) { rc = touchdownProduct(h, n, steps, k, active, time_step, dt, u, contact_points, q_traj, v_traj, A_traj, B_traj); if (rc) return rc; }
+  }
+  return IDOCP_OK;
+}
+
+// every pointer: device memory.  The linearisation with the rows of `form` (idocp_rbd_linearize_rollout_cost, _penalty, _al; mu and lambda where the
+// form has them).  The diagonal part of the gradients first (rbd_gradient_kernel.hip, first_step 0, the terminal slice included); then step k takes
+// the sample axis in the passes of residualPlan: the derivative composition of the pass with a, f and the blocks into h->gn, then ONE launch of the
+// form's residual kernel for both kinds of rows, on top of the gradients; A_k, B_k are then in place and the touchdowns follow.
+int linearizeRowsDevice(idocp_rbd* h, const idocp_rbd_objective* o, const IlqrForm& form, int n, int steps, const int* active, double time_step, double dt,
+                        const double* u, const double* contact_points, const double* q_traj, const double* v_traj,
+                        const idocp_rbd_penalty_linearization_io_t& out, double mu, const double* lambda, int touchdown_impulse) {
+  // A_traj, B_traj alone: the plain linearisation (the same bits: a sample's do not depend on how the sample axis is cut), no rows formed
+  if (!out.G_traj && !out.rho_traj && !out.D_traj && !out.lx_traj && !out.lu_traj)
+    return linearizeDevice(h, n, steps, active, time_step, dt, u, contact_points, q_traj, v_traj, out.A_traj, out.B_traj, touchdown_impulse);
+  if (out.lx_traj || out.lu_traj) {
+    RbdGradientArgs g;
+    g.q = q_traj; g.v = v_traj; g.u = u; g.q_ref = o->d_q_ref; g.v_ref = o->d_v_ref; g.block = o->d_block;
+    g.lx = out.lx_traj; g.lu = out.lu_traj; g.n = n; g.steps = steps; g.terminal = 1;
+    rbdGradient(h->model.nv, h->quadruped, g, h->stream);
     HIP_TRY(hipGetLastError());
   }
+  const size_t nq = h->model.nq, nv = h->model.nv, nu = h->model.nu, nf = 3 * (size_t)h->model.ncontacts, N = (size_t)n, nx = 2 * nv, nz = nx + nu;
+  const size_t R = (size_t)form.rows(), L = (size_t)form.multiplier_rows;
+  const ResidualPlan p = residualPlan(h, n);
+  int rc = h->gn.grow(p.total, h->stream); if (rc) return rc;
+  double* const S = h->gn.ptr;
+  lambda = form.lambdaOf(lambda);
+  auto at = [](double* x, size_t off) { return x ? x + off : nullptr; };
+  for (int k = 0; k < steps; ++k) {
+    const int mask = h->quadruped ? maskOf(h, active + (size_t)k * h->model.ncontacts) : 0;
+    for (int first = 0; first < n; first += p.chunk) {
+      const int cnt = n - first < p.chunk ? n - first : p.chunk;
+      const size_t F = (size_t)k * N + first;      // (slice k, sample `first`)
+      idocp_rbd_fdd_io_t io = idocp_rbd_fdd_io_t();
+      io.q = q_traj + F * nq; io.v = v_traj + F * nv; io.u = u ? u + F * nu : nullptr;
+      io.contact_points = contact_points ? contact_points + F * nf : nullptr;
+      io.A = at(out.A_traj, F * nx * nx); io.B = at(out.B_traj, F * nx * nu);
+      io.a = S + p.a; io.da_dq = S + p.da_dq; io.da_dv = S + p.da_dv; io.da_du = S + p.da_du;
+      if (h->quadruped) { io.f = S + p.f; io.df_dq = S + p.df_dq; io.df_dv = S + p.df_dv; io.df_du = S + p.df_du; }
+      rc = launchDerivatives(h, IDOCP_RBD_STAGE, cnt, mask, time_step, dt, io); if (rc) return rc;
+      RbdResidualAlArgs r;      // (the widest of the three argument structs: each launcher takes the part it knows)
+      r.a = io.a; r.f = io.f; r.da_dq = io.da_dq; r.da_dv = io.da_dv; r.da_du = io.da_du; r.df_dq = io.df_dq; r.df_dv = io.df_dv; r.df_du = io.df_du;
+      r.table = o->d_residual;
+      r.G = at(out.G_traj, F * R * nz); r.rho = at(out.rho_traj, F * R); r.lx = at(out.lx_traj, F * nx); r.lu = at(out.lu_traj, F * nu);
+      r.count = cnt; r.mask = mask;
+      r.q = io.q; r.v = io.v; r.u = io.u; r.block = o->d_block; r.D = at(out.D_traj, F * nz);
+      r.dtmu = dt * mu; r.scale = std::sqrt(r.dtmu); r.rc = form.constraint_rows;
+      r.lambda = lambda ? lambda + F * L : nullptr; r.penalty = mu;
+      const bool launched = form.al() ? rbdResidualAl(h->model.nv, h->quadruped, r, h->stream)
+                                      : (form.penalty() ? rbdResidualPenalty(h->model.nv, h->quadruped, r, h->stream) : rbdResidual(h->model.nv, h->quadruped, r, h->stream));
+      if (!launched) { set_last_error(std::string(form.linearization()) + ": no residual kernel for this model"); return IDOCP_E_UNSUPPORTED; }
+      HIP_TRY(hipGetLastError());
+    }
+  }
+  if (!touchdown_impulse || (!out.A_traj && !out.B_traj)) return IDOCP_OK;
+  for (int k = 0; k < steps; ++k) { rc = touchdownProduct(h, n, steps, k, active, time_step, dt, u, contact_points, q_traj, v_traj, out.A_traj, out.B_traj); if (rc) return rc; }
   return IDOCP_OK;
 }
 
@@ -688,16 +711,37 @@ int checkLqr(const char* who, const idocp_rbd* h, int n, int steps, const idocp_
   return IDOCP_OK;
 }
 
-// io: device pointers
-int launchLqr(idocp_rbd* h, int n, int steps, const idocp_rbd_lqr_io_t& io) {
-  RbdLqrArgs a;
+int checkLqrGn(const char* who, int g_rows, const double* G_traj, const double* D_traj) {
+  const std::string w(who);
+  if (G_traj || g_rows != 0) {
+    if (!G_traj || g_rows == 0) { set_last_error(w + ": G_traj and g_rows come together (NULL with 0, or both given)"); return IDOCP_E_ARG; }
+    if (g_rows < 4 || g_rows > 64 || g_rows % 4 != 0) { set_last_error(w + ": g_rows must be a multiple of 4 within 4 .. 64"); return IDOCP_E_ARG; }
+  }
+  if (D_traj && !G_traj) { set_last_error(w + ": D_traj needs a G_traj"); return IDOCP_E_ARG; }
+  return IDOCP_OK;
+}
+
+// io, G, D: device pointers.  The three backward passes: G = nullptr: the plain form; D = nullptr: the GN form; both: the GN form with the diagonal.
+// (The widest of the three argument structs is filled; each launcher takes the part it knows.)
+int launchLqr(idocp_rbd* h, int n, int steps, const idocp_rbd_lqr_io_t& io, int g_rows, const double* G, const double* D) {
+  RbdLqrGnDiagArgs a;
   a.A = io.A_traj; a.B = io.B_traj; a.x_weight = io.x_weight; a.u_weight = io.u_weight; a.xf_weight = io.xf_weight;
   a.lx = io.lx_traj; a.lu = io.lu_traj; a.regularization = io.regularization;
   a.K = io.K_traj; a.k = io.k_traj; a.P0 = io.P0; a.p0 = io.p0; a.expected = io.expected; a.status = io.status;
   a.n = n; a.steps = steps; a.nx = 2 * h->model.nv; a.nu = h->model.nu;
-  rbdLqrBackward(h->quadruped, a, h->stream);
+  a.G = G; a.g_rows = g_rows; a.D = D;
+  if (!G) rbdLqrBackward(h->quadruped, a, h->stream);
+  else if (D) rbdLqrBackwardGnDiag(h->quadruped, a, h->stream);
+  else rbdLqrBackwardGn(h->quadruped, a, h->stream);
   HIP_TRY(hipGetLastError());
   return IDOCP_OK;
+}
+
+// what the three backward passes refuse, in their order.  host: the weight arrays are host memory
+int checkLqrCall(const char* who, const idocp_rbd* h, int n, int steps, const idocp_rbd_lqr_io_t* io, bool host, int g_rows, const double* G_traj,
+                 const double* D_traj) {
+  int rc = checkLqr(who, h, n, steps, io, host); if (rc) return rc;
+  return checkLqrGn(who, g_rows, G_traj, D_traj);
 }
 
 // ---- gradients of an objective, the line-search step of iLQR, one iteration ----
@@ -726,106 +770,89 @@ int checkLqrWeights(const char* who, const idocp_rbd_objective* o) {
   return IDOCP_OK;
 }
 
-// ---- the cost linearisation and the backward pass with residual rows
+// ---- the linearisation with rows and the backward pass with residual rows
 
-// what idocp_rbd_linearize_rollout_cost refuses beyond checkLinearize
-int checkLinearizeCost(const char* who, const idocp_rbd* h, const idocp_rbd_objective* o, int n, int steps, const double* u_traj,
-                       const idocp_rbd_cost_linearization_io_t* io) {
+int checkMu(const char* who, double mu, const char* name) {
+  if (!std::isfinite(mu) || !(mu > 0.0)) { set_last_error(std::string(who) + ": " + name + " must be positive and finite"); return IDOCP_E_ARG; }
+  return IDOCP_OK;
+}
+
+// what idocp_rbd_linearize_rollout_cost, _penalty and _al refuse, in this order (the cost call's io comes widened: D_traj = NULL, and mu = 0)
+int checkLinearizeRows(const char* who, const IlqrForm& form, idocp_rbd* h, const idocp_rbd_objective* o, int n, int steps, const int* active,
+                       double time_step, double dt, const double* u_traj, const double* contact_points, const double* q_traj, const double* v_traj,
+                       const idocp_rbd_penalty_linearization_io_t* io, double mu) {
   const std::string w(who);
+  int rc = checkLinearize(who, h, n, steps, active, time_step, dt, contact_points, q_traj, v_traj); if (rc) return rc;
   if (!o || !io) { set_last_error(w + ": null objective or io"); return IDOCP_E_ARG; }
   if (o->owner != h) { set_last_error(w + ": the objective was created on another handle"); return IDOCP_E_ARG; }
   if (steps > o->plan.steps) { set_last_error(w + ": steps must lie within the objective's " + std::to_string(o->plan.steps) + " steps"); return IDOCP_E_ARG; }
   const std::string unsupported = idocp_host::residualUnsupported(o->plan);
   if (!unsupported.empty()) { set_last_error(w + ": " + unsupported); return IDOCP_E_UNSUPPORTED; }
-  if (!io->A_traj && !io->B_traj && !io->G_traj && !io->rho_traj && !io->lx_traj && !io->lu_traj) {
+  if (!io->A_traj && !io->B_traj && !io->G_traj && !io->rho_traj && !io->D_traj && !io->lx_traj && !io->lu_traj) {
     set_last_error(w + ": no output was asked for"); return IDOCP_E_ARG;
   }
   if (((long long)steps + 1) * n > 2147483647LL) { set_last_error(w + ": (steps + 1) * n must fit an int"); return IDOCP_E_ARG; }
   if (!u_traj && (io->lx_traj || io->lu_traj) && idocp_host::rbd_objective_detail::anyNonZero(o->plan.block.u_weight, o->plan.nu)) {
     set_last_error(w + ": u_traj is NULL but a non-zero u_weight reads it"); return IDOCP_E_ARG;
   }
-  return IDOCP_OK;
-}
-
-// every pointer: device memory.  The diagonal part of the gradients first (rbd_gradient_kernel.hip, first_step 0, the terminal slice included),
-// then the linearisation with the residual rows on top.
-int linearizeCostDevice(idocp_rbd* h, const idocp_rbd_objective* o, int n, int steps, const int* active, double time_step, double dt, const double* u,
-                        const double* contact_points, const double* q_traj, const double* v_traj, const idocp_rbd_cost_linearization_io_t& io,
-                        int touchdown_impulse) {
-  // A_traj, B_traj alone: the plain linearisation (the same bits: a sample's do not depend on how the sample axis is cut), no rows formed
-  if (!io.G_traj && !io.rho_traj && !io.lx_traj && !io.lu_traj)
-    return linearizeDevice(h, n, steps, active, time_step, dt, u, contact_points, q_traj, v_traj, io.A_traj, io.B_traj, touchdown_impulse);
-  if (io.lx_traj || io.lu_traj) {
-    RbdGradientArgs g;
-    g.q = q_traj; g.v = v_traj; g.u = u; g.q_ref = o->d_q_ref; g.v_ref = o->d_v_ref; g.block = o->d_block;
-    g.lx = io.lx_traj; g.lu = io.lu_traj; g.n = n; g.steps = steps; g.terminal = 1;
-    rbdGradient(h->model.nv, h->quadruped, g, h->stream);
-    HIP_TRY(hipGetLastError());
-  }
-  CostLinearization c;
-  c.table = o->d_residual; c.G = io.G_traj; c.rho = io.rho_traj; c.lx = io.lx_traj; c.lu = io.lu_traj; c.R = idocp_host::residualRows(o->plan);
-  return linearizeDevice(h, n, steps, active, time_step, dt, u, contact_points, q_traj, v_traj, io.A_traj, io.B_traj, touchdown_impulse, &c);
-}
-
-// what idocp_rbd_linearize_rollout_penalty refuses beyond the cost call (whose check runs first with `some` = an output of this call's was asked for)
-int checkPenalty(const char* who, const idocp_rbd_objective* o, double mu) {
-  const std::string w(who);
+  if (form.al()) { rc = checkMu(who, mu, "mu"); if (rc) return rc; }
+  if (!form.penalty()) return IDOCP_OK;
   if (!std::isfinite(mu) || mu < 0.0) { set_last_error(w + ": mu must be finite and non-negative"); return IDOCP_E_ARG; }
   const std::string pair = idocp_host::penaltyPairRefused(o->plan);
   if (!pair.empty()) { set_last_error(w + ": " + pair); return IDOCP_E_ARG; }
   return IDOCP_OK;
 }
 
-// every pointer: device memory.  As linearizeCostDevice, with the penalty form of the residual kernel: one launch per pass for both kinds of rows.
-int linearizePenaltyDevice(idocp_rbd* h, const idocp_rbd_objective* o, int n, int steps, const int* active, double time_step, double dt, const double* u,
-                           const double* contact_points, const double* q_traj, const double* v_traj, const idocp_rbd_penalty_linearization_io_t& io,
-                           double mu, int touchdown_impulse, bool al = false, const double* lambda = nullptr) {
-  if (!io.G_traj && !io.rho_traj && !io.D_traj && !io.lx_traj && !io.lu_traj)
-    return linearizeDevice(h, n, steps, active, time_step, dt, u, contact_points, q_traj, v_traj, io.A_traj, io.B_traj, touchdown_impulse);
-  if (io.lx_traj || io.lu_traj) {
-    RbdGradientArgs g;
-    g.q = q_traj; g.v = v_traj; g.u = u; g.q_ref = o->d_q_ref; g.v_ref = o->d_v_ref; g.block = o->d_block;
-    g.lx = io.lx_traj; g.lu = io.lu_traj; g.n = n; g.steps = steps; g.terminal = 1;
-    rbdGradient(h->model.nv, h->quadruped, g, h->stream);
-    HIP_TRY(hipGetLastError());
-  }
-  CostLinearization c;
-  c.table = o->d_residual; c.G = io.G_traj; c.rho = io.rho_traj; c.lx = io.lx_traj; c.lu = io.lu_traj; c.R = idocp_host::residualRows(o->plan);
-  c.penalty = true; c.block = o->d_block; c.D = io.D_traj; c.mu = mu; c.rc = idocp_host::constraintRows(o->plan);
-  c.al = al; c.L = idocp_host::multiplierRows(o->plan); c.lambda = c.L ? lambda : nullptr;
-  return linearizeDevice(h, n, steps, active, time_step, dt, u, contact_points, q_traj, v_traj, io.A_traj, io.B_traj, touchdown_impulse, &c);
+// the device form of the three linearisations with rows
+int linearizeRowsEntry(const char* who, IlqrForm::Chain chain, idocp_rbd* h, const idocp_rbd_objective* o, int n, int steps, const int* active,
+                       double time_step, double dt, const double* u_traj, const double* contact_points, const double* q_traj, const double* v_traj,
+                       const idocp_rbd_penalty_linearization_io_t* io, double mu, const double* lambda_traj, int touchdown_impulse) {
+  const IlqrForm form(chain, h, o);
+  int rc = checkLinearizeRows(who, form, h, o, n, steps, active, time_step, dt, u_traj, contact_points, q_traj, v_traj, io, mu); if (rc) return rc;
+  HIP_TRY(hipSetDevice(h->device));
+  return linearizeRowsDevice(h, o, form, n, steps, active, time_step, dt, u_traj, contact_points, q_traj, v_traj, *io, mu, lambda_traj, touchdown_impulse);
 }
 
-int checkLqrGn(const char* who, const idocp_rbd* h, int g_rows, const double* G_traj) {
-  const std::string w(who);
-  if (!G_traj && g_rows == 0) return IDOCP_OK;
-  if (!G_traj || g_rows == 0) { set_last_error(w + ": G_traj and g_rows come together (NULL with 0, or both given)"); return IDOCP_E_ARG; }
-  if (g_rows < 4 || g_rows > 64 || g_rows % 4 != 0) { set_last_error(w + ": g_rows must be a multiple of 4 within 4 .. 64"); return IDOCP_E_ARG; }
-  (void)h;
-  return IDOCP_OK;
+// the host form of the three: one staging list, D_traj and lambda_traj taking no room where the form has none
+int linearizeRowsHost(const char* who, IlqrForm::Chain chain, idocp_rbd* h, const idocp_rbd_objective* o, int n, int steps, const int* active,
+                      double time_step, double dt, const double* u_traj, const double* contact_points, const double* q_traj, const double* v_traj,
+                      const idocp_rbd_penalty_linearization_io_t* io, double mu, const double* lambda_traj, int touchdown_impulse) {
+  const IlqrForm form(chain, h, o);
+  int rc = checkLinearizeRows(who, form, h, o, n, steps, active, time_step, dt, u_traj, contact_points, q_traj, v_traj, io, mu); if (rc) return rc;
+  HIP_TRY(hipSetDevice(h->device));
+  const size_t nq = h->model.nq, nv = h->model.nv, nu = h->model.nu, nf = 3 * (size_t)h->model.ncontacts, N = (size_t)n, S = (size_t)steps, nx = 2 * nv;
+  const size_t R = (size_t)form.rows();
+  StagePlan p;
+  const double *d_u, *d_points, *d_q, *d_v, *d_lambda;
+  idocp_rbd_penalty_linearization_io_t d;
+  p.in(u_traj, S * N * nu, &d_u);
+  p.in(contact_points, S * N * nf, &d_points);
+  p.in(q_traj, (S + 1) * N * nq, &d_q);
+  p.in(v_traj, (S + 1) * N * nv, &d_v);
+  p.in(lambda_traj, S * N * (size_t)form.multiplier_rows, &d_lambda);
+  p.out(io->A_traj, S * N * nx * nx, &d.A_traj);
+  p.out(io->B_traj, S * N * nx * nu, &d.B_traj);
+  p.out(io->G_traj, S * N * R * (nx + nu), &d.G_traj);
+  p.out(io->rho_traj, S * N * R, &d.rho_traj);
+  p.out(io->D_traj, S * N * (nx + nu), &d.D_traj);
+  p.out(io->lx_traj, (S + 1) * N * nx, &d.lx_traj);
+  p.out(io->lu_traj, S * N * nu, &d.lu_traj);
+  rc = stageIn(h, p); if (rc) return rc;
+  rc = linearizeRowsDevice(h, o, form, n, steps, active, time_step, dt, d_u, d_points, d_q, d_v, d, mu, d_lambda, touchdown_impulse); if (rc) return rc;
+  return stageOut(h, p);
 }
 
-// io, G, D: device pointers.  D = nullptr: the GN form; G = nullptr too: the plain form
-int launchLqrGn(idocp_rbd* h, int n, int steps, const idocp_rbd_lqr_io_t& io, int g_rows, const double* G, const double* D = nullptr) {
-  if (!G) return launchLqr(h, n, steps, io);
-  RbdLqrGnDiagArgs a;
-  a.A = io.A_traj; a.B = io.B_traj; a.x_weight = io.x_weight; a.u_weight = io.u_weight; a.xf_weight = io.xf_weight;
-  a.lx = io.lx_traj; a.lu = io.lu_traj; a.regularization = io.regularization;
-  a.K = io.K_traj; a.k = io.k_traj; a.P0 = io.P0; a.p0 = io.p0; a.expected = io.expected; a.status = io.status;
-  a.n = n; a.steps = steps; a.nx = 2 * h->model.nv; a.nu = h->model.nu;
-  a.G = G; a.g_rows = g_rows; a.D = D;
-  if (D) rbdLqrBackwardGnDiag(h->quadruped, a, h->stream);
-  else rbdLqrBackwardGn(h->quadruped, a, h->stream);
-  HIP_TRY(hipGetLastError());
-  return IDOCP_OK;
+// the cost call's io as the penalty call's: D_traj = NULL
+const idocp_rbd_penalty_linearization_io_t* widened(const idocp_rbd_cost_linearization_io_t* io, idocp_rbd_penalty_linearization_io_t* wide) {
+  if (!io) return nullptr;
+  *wide = idocp_rbd_penalty_linearization_io_t();
+  wide->A_traj = io->A_traj; wide->B_traj = io->B_traj; wide->G_traj = io->G_traj; wide->rho_traj = io->rho_traj; wide->lx_traj = io->lx_traj; wide->lu_traj = io->lu_traj;
+  return wide;
 }
 
 // the host form of the three backward passes
-int lqrHost(const char* who, idocp_rbd* h, int n, int steps, const idocp_rbd_lqr_io_t* io, int g_rows, const double* G_traj,
-            const double* D_traj = nullptr) {
-  int rc = checkLqr(who, h, n, steps, io, true); if (rc) return rc;
-  rc = checkLqrGn(who, h, g_rows, G_traj); if (rc) return rc;
-  if (D_traj && !G_traj) { set_last_error(std::string(who) + ": D_traj needs a G_traj"); return IDOCP_E_ARG; }
+int lqrHost(const char* who, idocp_rbd* h, int n, int steps, const idocp_rbd_lqr_io_t* io, int g_rows, const double* G_traj, const double* D_traj) {
+  int rc = checkLqrCall(who, h, n, steps, io, true, g_rows, G_traj, D_traj); if (rc) return rc;
   HIP_TRY(hipSetDevice(h->device));
   const size_t nx = 2 * (size_t)h->model.nv, nu = h->model.nu, N = (size_t)n, S = (size_t)steps;
   StagePlan p;
@@ -849,7 +876,7 @@ int lqrHost(const char* who, idocp_rbd* h, int n, int steps, const idocp_rbd_lqr
   p.in(D_traj, S * N * (nx + nu), &d_D);
   rc = stageIn(h, p); if (rc) return rc;
   d.status = reinterpret_cast<int*>(d_status);
-  rc = launchLqrGn(h, n, steps, d, g_rows, d_G, d_D); if (rc) return rc;
+  rc = launchLqr(h, n, steps, d, g_rows, d_G, d_D); if (rc) return rc;
   if (io->status) HIP_TRY(hipMemcpyAsync(io->status, d_status, sizeof(int) * N, hipMemcpyDeviceToHost, h->stream));
   return stageOut(h, p);
 }
@@ -902,9 +929,8 @@ int launchAccept(idocp_rbd* h, int n, int steps, const idocp_rbd_ilqr_accept_io_
 struct IlqrWorkspace {
   size_t A, B, lx, lu, K, k, u_ff, q, v, u, a, f, cost, violation, alpha, done, G, D, total;
 };
-// g_rows: the rows of G_traj behind everything else (idocp_rbd_ilqr_iterate_gn), 0: none
-// diag: D_traj behind G_traj (idocp_rbd_ilqr_iterate_penalty)
-IlqrWorkspace ilqrWorkspace(const idocp_rbd* h, int n, int steps, int g_rows = 0, bool diag = false) {
+// Behind everything else: G_traj with the form's rows (none on the diagonal chain), then D_traj on the penalty and AL chains.
+IlqrWorkspace ilqrWorkspace(const idocp_rbd* h, const IlqrForm& form, int n, int steps) {
   const size_t nq = h->model.nq, nv = h->model.nv, nu = h->model.nu, nf = 3 * (size_t)h->model.ncontacts, N = (size_t)n, S = (size_t)steps, nx = 2 * nv;
   IlqrWorkspace w;
   size_t at = 0;
@@ -913,30 +939,28 @@ IlqrWorkspace ilqrWorkspace(const idocp_rbd* h, int n, int steps, int g_rows = 0
   w.K = piece(S * N * nx * nu); w.k = piece(S * N * nu); w.u_ff = piece(S * N * nu);
   w.q = piece((S + 1) * N * nq); w.v = piece((S + 1) * N * nv); w.u = piece(S * N * nu); w.a = piece(S * N * nv); w.f = piece(S * N * nf);
   w.cost = piece(N); w.violation = piece(N); w.alpha = piece(N); w.done = piece((N + 1) / 2);
-  w.G = piece(S * N * (size_t)g_rows * (nx + nu));
-  w.D = piece(diag ? S * N * (nx + nu) : 0);
+  w.G = piece(S * N * (size_t)form.rows() * (nx + nu));
+  w.D = piece(form.penalty() ? S * N * (nx + nu) : 0);
   w.total = at;
   return w;
 }
 
-// gn: the Gauss-Newton form takes every objective whose a_weight and f_weight have square roots
-// al: the penalty chain on the shifted rows (idocp_rbd_ilqr_iterate_al)
-enum IlqrForm { ILQR_DIAGONAL = 0, ILQR_GN = 1, ILQR_PENALTY = 2, ILQR_AL = 3 };
-
-int checkIterate(const char* who, const idocp_rbd* h, const idocp_rbd_objective* o, int n, int steps, const idocp_rbd_ilqr_io_t* io, bool host,
-                 int gn = ILQR_DIAGONAL) {
+// host: the workspace is the staging buffer's, and io->workspace is not looked at
+int checkIterate(const char* who, const IlqrForm& form, const idocp_rbd* h, const idocp_rbd_objective* o, int n, int steps, const idocp_rbd_ilqr_io_t* io,
+                 bool host) {
   const std::string w(who);
   if (!h || !o || !io) { set_last_error(w + ": null handle, objective or io"); return IDOCP_E_ARG; }
   if (o->owner != h) { set_last_error(w + ": the objective was created on another handle"); return IDOCP_E_ARG; }
-  if (gn) {
+  if (form.chain == IlqrForm::DIAGONAL) { int rc = checkLqrWeights(who, o); if (rc) return rc; }
+  else {
     const std::string unsupported = idocp_host::residualUnsupported(o->plan);
     if (!unsupported.empty()) { set_last_error(w + ": " + unsupported); return IDOCP_E_UNSUPPORTED; }
-    if (gn >= ILQR_PENALTY) {
+    if (form.penalty()) {
       const std::string pair = idocp_host::penaltyPairRefused(o->plan);
       if (!pair.empty()) { set_last_error(w + ": " + pair); return IDOCP_E_ARG; }
-      if (idocp_host::residualRows(o->plan) + idocp_host::constraintRows(o->plan) > 64) { set_last_error(w + ": more than 64 rows"); return IDOCP_E_UNSUPPORTED; }
+      if (form.rows() > 64) { set_last_error(w + ": more than 64 rows"); return IDOCP_E_UNSUPPORTED; }
     }
-  } else { int rc = checkLqrWeights(who, o); if (rc) return rc; }
+  }
   if (n <= 0) { set_last_error(w + ": n must be positive"); return IDOCP_E_ARG; }
   if (steps < 1) { set_last_error(w + ": steps must be at least 1"); return IDOCP_E_ARG; }
   if (steps > o->plan.steps) { set_last_error(w + ": steps must lie within the objective's " + std::to_string(o->plan.steps) + " steps"); return IDOCP_E_ARG; }
@@ -948,23 +972,121 @@ int checkIterate(const char* who, const idocp_rbd* h, const idocp_rbd_objective*
   const char* const names[5] = {"regularization", "armijo", "shrink", "alpha_min", "penalty"};
   for (int i = 0; i < 5; ++i)
     if (!std::isfinite(values[i]) || values[i] < 0.0) { set_last_error(w + ": " + names[i] + " must be finite and non-negative"); return IDOCP_E_ARG; }
-  if (gn == ILQR_AL && !(io->penalty > 0.0)) { set_last_error(w + ": penalty (mu) must be positive"); return IDOCP_E_ARG; }
+  if (form.al() && !(io->penalty > 0.0)) { set_last_error(w + ": penalty (mu) must be positive"); return IDOCP_E_ARG; }
   if (!host && !io->workspace) { set_last_error(w + ": the workspace is needed (idocp_rbd_ilqr_workspace_bytes, idocp_rbd_ilqr_gn_workspace_bytes, idocp_rbd_ilqr_penalty_workspace_bytes)"); return IDOCP_E_ARG; }
   if (!host && (reinterpret_cast<uintptr_t>(io->workspace) & 15u)) { set_last_error(w + ": the workspace must be 16-byte aligned"); return IDOCP_E_ARG; }
   return IDOCP_OK;
 }
 
-// io: device pointers; ws: the workspace.  The chain of include/idocp_hip.h; every call on the handle's stream, no synchronisation, no host read.
-// gn: the chain of idocp_rbd_ilqr_iterate_gn -- the cost linearisation and the backward pass with residual rows in place of the first three calls.
-int iterateDevice(idocp_rbd* h, const idocp_rbd_objective* o, int n, int steps, const int* active, double time_step, double dt,
-                  const double* contact_points, const idocp_rbd_ilqr_io_t& io, double* ws, int touchdown_impulse, int gn = ILQR_DIAGONAL,
-                  const double* lambda = nullptr) {
+// the five arrays of a rollout that the score and the row calls read: [steps][n][..] each, those a call can do without may be NULL
+struct RolloutArrays { const double *q, *v, *u, *a, *f; };
+
+// A rollout of more than IDOCP_RBD_SCORE_MAX_WINDOW steps is scored window by window (the windows of the header, with accumulate):
+// body(first, window, accumulate, the window's contact status, the window's slices) for each, until one refuses.
+template <class Body>
+int forEachWindow(const idocp_rbd* h, int n, int steps, const int* active, const RolloutArrays& t, Body body) {
   const size_t nq = h->model.nq, nv = h->model.nv, nu = h->model.nu, nf = 3 * (size_t)h->model.ncontacts, N = (size_t)n;
-  const bool penalty = gn >= ILQR_PENALTY, al = gn == ILQR_AL;
-  const size_t rows_l = al ? (size_t)idocp_host::multiplierRows(o->plan) : 0;
-  const int rows_c = penalty ? idocp_host::constraintRows(o->plan) : 0;
-  const int g_rows = gn ? idocp_host::residualRows(o->plan) + rows_c : 0;
-  const IlqrWorkspace w = ilqrWorkspace(h, n, steps, g_rows, penalty);
+  auto at = [](const double* x, size_t off) { return x ? x + off : nullptr; };
+  for (int first = 0; first < steps; first += IDOCP_RBD_SCORE_MAX_WINDOW) {
+    const int window = steps - first < IDOCP_RBD_SCORE_MAX_WINDOW ? steps - first : IDOCP_RBD_SCORE_MAX_WINDOW;
+    const RolloutArrays w = {at(t.q, first * N * nq), at(t.v, first * N * nv), at(t.u, first * N * nu), at(t.a, first * N * nv), at(t.f, first * N * nf)};
+    const int rc = body(first, window, first > 0, active ? active + (size_t)first * h->model.ncontacts : nullptr, w); if (rc) return rc;
+  }
+  return IDOCP_OK;
+}
+
+// the host form of the calls that take such arrays: their five slots
+void stageRollout(StagePlan& p, const idocp_rbd* h, const idocp_rbd_objective* o, int n, int steps, const RolloutArrays& host, RolloutArrays* dev) {
+  const size_t nq = h->model.nq, nv = h->model.nv, nu = h->model.nu, nf = 3 * (size_t)o->plan.ncontacts, N = (size_t)n, S = (size_t)steps;
+  p.in(host.q, S * N * nq, &dev->q);      // (the stage slices alone: the terminal slice has no rows)
+  p.in(host.v, S * N * nv, &dev->v);
+  p.in(host.u, S * N * nu, &dev->u);
+  p.in(host.a, S * N * nv, &dev->a);
+  p.in(host.f, S * N * nf, &dev->f);
+}
+
+// ---- the constraint rows of a window: their square sum plain (idocp_rbd_score_penalty) or shifted (idocp_rbd_score_al), and the multiplier update
+
+enum RowCall { SCORE_PENALTY, SCORE_AL, MULTIPLIER_UPDATE };
+
+// everything the three refuse, and the kernel's arguments but for the array pointers.  mu: not looked at by SCORE_PENALTY; out: sq_violation,
+// sq_shifted, or lambda_out, which is needed where the objective has multiplier rows
+int checkRowCall(const char* who, RowCall call, const idocp_rbd* h, const idocp_rbd_objective* o, int n, int first_step, int steps, const int* active,
+                 int accumulate, const RolloutArrays& t, double mu, const double* out, RbdAlArgs* a) {
+  const std::string w(who);
+  if (!h || !o) { set_last_error(w + ": null handle or objective"); return IDOCP_E_ARG; }
+  if (o->owner != h) { set_last_error(w + ": the objective was created on another handle"); return IDOCP_E_ARG; }
+  if (call != SCORE_PENALTY) { int rc = checkMu(who, mu, "mu"); if (rc) return rc; }
+  if (call != MULTIPLIER_UPDATE && !out) { set_last_error(w + (call == SCORE_AL ? ": sq_shifted is needed" : ": sq_violation is needed")); return IDOCP_E_ARG; }
+  if (call == MULTIPLIER_UPDATE && !out && idocp_host::multiplierRows(o->plan)) { set_last_error(w + ": lambda_out is needed"); return IDOCP_E_ARG; }
+  const idocp_host::RbdScoreCall c = idocp_host::planPenaltyCall(who, o->plan, n, first_step, steps, active, t.q, t.v, t.u, t.a, t.f);
+  if (c.rc) { set_last_error(c.error); return c.rc; }
+  std::memcpy(a->masks, c.masks, sizeof(c.masks));
+  a->block = o->d_block; a->steps = steps; a->accumulate = accumulate != 0; a->penalty = mu;
+  a->sq = nullptr; a->lambda = nullptr; a->lambda_out = nullptr; a->infeasibility = nullptr; a->change = nullptr;
+  return IDOCP_OK;
+}
+
+// a: device pointers.  An objective without multiplier rows has nothing to update: the statistics are zero (kept as they are with accumulate)
+int launchRowCall(const char* who, RowCall call, idocp_rbd* h, const idocp_rbd_objective* o, const RbdAlArgs& a, int n) {
+  bool launched = true;
+  if (call == SCORE_PENALTY) launched = rbdPenalty(h->model.nv, h->quadruped, a, n, h->stream);
+  else if (call == SCORE_AL) launched = rbdAlScore(h->model.nv, h->quadruped, a, n, h->stream);
+  else if (idocp_host::multiplierRows(o->plan)) launched = rbdAlUpdate(h->model.nv, h->quadruped, a, n, h->stream);
+  else if (!a.accumulate) {
+    if (a.infeasibility) HIP_TRY(hipMemsetAsync(a.infeasibility, 0, sizeof(double) * (size_t)n, h->stream));
+    if (a.change) HIP_TRY(hipMemsetAsync(a.change, 0, sizeof(double) * (size_t)n, h->stream));
+  }
+  if (!launched) { set_last_error(std::string(who) + (call == SCORE_PENALTY ? ": no penalty kernel for this model" : ": no multiplier kernel for this model")); return IDOCP_E_UNSUPPORTED; }
+  HIP_TRY(hipGetLastError());
+  return IDOCP_OK;
+}
+
+// the device form of the three.  out as for checkRowCall; infeasibility and change: of MULTIPLIER_UPDATE
+int rowCallDevice(const char* who, RowCall call, idocp_rbd* h, const idocp_rbd_objective* o, int n, int first_step, int steps, const int* active, int accumulate,
+                  const RolloutArrays& t, double mu, const double* lambda, double* out, double* infeasibility, double* change) {
+  RbdAlArgs a;
+  int rc = checkRowCall(who, call, h, o, n, first_step, steps, active, accumulate, t, mu, out, &a); if (rc) return rc;
+  HIP_TRY(hipSetDevice(h->device));
+  a.q = t.q; a.v = t.v; a.u = t.u; a.a = t.a; a.f = t.f;
+  a.lambda = idocp_host::multiplierRows(o->plan) ? lambda : nullptr;
+  if (call == MULTIPLIER_UPDATE) { a.lambda_out = out; a.infeasibility = infeasibility; a.change = change; }
+  else a.sq = out;
+  return launchRowCall(who, call, h, o, a, n);
+}
+
+// the host form of the three
+int rowCallHost(const char* who, RowCall call, idocp_rbd* h, const idocp_rbd_objective* o, int n, int first_step, int steps, const int* active, int accumulate,
+                const RolloutArrays& t, double mu, const double* lambda, double* out, double* infeasibility, double* change) {
+  RbdAlArgs a;
+  int rc = checkRowCall(who, call, h, o, n, first_step, steps, active, accumulate, t, mu, out, &a); if (rc) return rc;
+  HIP_TRY(hipSetDevice(h->device));
+  const size_t N = (size_t)n, rows = (size_t)steps * N * (size_t)idocp_host::multiplierRows(o->plan);
+  StagePlan p;
+  RolloutArrays d;
+  stageRollout(p, h, o, n, steps, t, &d);
+  p.in(lambda, rows, &a.lambda);
+  if (call == MULTIPLIER_UPDATE) {
+    // (the staged copies are two slots even where the caller's arrays are one: in place is the caller's business, not the stage's)
+    p.out(out, rows, &a.lambda_out);
+    if (accumulate) { p.update(infeasibility, N, &a.infeasibility); p.update(change, N, &a.change); }
+    else { p.out(infeasibility, N, &a.infeasibility, true); p.out(change, N, &a.change, true); }
+  } else if (accumulate) p.update(out, N, &a.sq);
+  else p.out(out, N, &a.sq);
+  rc = stageIn(h, p); if (rc) return rc;
+  a.q = d.q; a.v = d.v; a.u = d.u; a.a = d.a; a.f = d.f;
+  rc = launchRowCall(who, call, h, o, a, n); if (rc) return rc;
+  return stageOut(h, p);
+}
+
+// io: device pointers; ws: the workspace; lambda: the multipliers of the AL chain.  The chain of include/idocp_hip.h for the form: the linearisation
+// and the backward pass that belong to it (with rows: the objective's own weight tables, without the refusal of
+// idocp_rbd_objective_lqr_weights_device), then the rounds of trials.  Every call on the handle's stream, no synchronisation, no host read; an
+// inner call that refuses leaves its own name in idocp_last_error.
+int iterateDevice(idocp_rbd* h, const idocp_rbd_objective* o, const IlqrForm& form, int n, int steps, const int* active, double time_step, double dt,
+                  const double* contact_points, const idocp_rbd_ilqr_io_t& io, double* ws, const double* lambda, int touchdown_impulse) {
+  const size_t nq = h->model.nq, nv = h->model.nv, nf = 3 * (size_t)h->model.ncontacts, N = (size_t)n;
+  const IlqrWorkspace w = ilqrWorkspace(h, form, n, steps);
   double *A = ws + w.A, *B = ws + w.B, *lx = ws + w.lx, *lu = ws + w.lu, *K = ws + w.K, *kff = ws + w.k, *u_ff = ws + w.u_ff;
   double *qt = ws + w.q, *vt = ws + w.v, *ut = ws + w.u, *at = ws + w.a, *ft = nf ? ws + w.f : nullptr;
   double *cost_t = ws + w.cost, *violation_t = ws + w.violation, *alpha = ws + w.alpha;
@@ -973,29 +1095,7 @@ int iterateDevice(idocp_rbd* h, const idocp_rbd_objective* o, int n, int steps, 
   idocp_rbd_lqr_io_t lqr = idocp_rbd_lqr_io_t();
   lqr.A_traj = A; lqr.B_traj = B; lqr.lx_traj = lx; lqr.lu_traj = lu; lqr.regularization = io.regularization;
   lqr.K_traj = K; lqr.k_traj = kff; lqr.expected = io.expected; lqr.status = io.lqr_status;
-  if (penalty) {
-    // the penalty chain: io.penalty is mu; without constraint rows D stays out and the GN form of the backward pass runs
-    idocp_rbd_penalty_linearization_io_t c = idocp_rbd_penalty_linearization_io_t();
-    c.A_traj = A; c.B_traj = B; c.G_traj = ws + w.G; c.D_traj = rows_c ? ws + w.D : nullptr; c.lx_traj = lx; c.lu_traj = lu;
-    if (al) rc = idocp_rbd_linearize_rollout_al_device(h, o, n, steps, active, time_step, dt, io.u_traj, contact_points, io.q_traj, io.v_traj, &c, io.penalty,
-                                                       lambda, touchdown_impulse);
-    else rc = idocp_rbd_linearize_rollout_penalty_device(h, o, n, steps, active, time_step, dt, io.u_traj, contact_points, io.q_traj, io.v_traj, &c, io.penalty,
-                                                         touchdown_impulse);
-    if (rc) return rc;
-    lqr.x_weight = o->d_lqr_weights;
-    lqr.u_weight = o->d_lqr_weights + idocp_host::lqrWeightOffsetU(o->plan);
-    lqr.xf_weight = o->d_lqr_weights + idocp_host::lqrWeightOffsetXf(o->plan);
-    rc = idocp_rbd_lqr_backward_gn_diag_device(h, n, steps, &lqr, g_rows, c.G_traj, c.D_traj); if (rc) return rc;
-  } else if (gn) {
-    idocp_rbd_cost_linearization_io_t c = idocp_rbd_cost_linearization_io_t();
-    c.A_traj = A; c.B_traj = B; c.G_traj = ws + w.G; c.lx_traj = lx; c.lu_traj = lu;
-    rc = idocp_rbd_linearize_rollout_cost_device(h, o, n, steps, active, time_step, dt, io.u_traj, contact_points, io.q_traj, io.v_traj, &c, touchdown_impulse);
-    if (rc) return rc;
-    lqr.x_weight = o->d_lqr_weights;      // (the tables of idocp_rbd_objective_lqr_weights_device, without its refusal)
-    lqr.u_weight = o->d_lqr_weights + idocp_host::lqrWeightOffsetU(o->plan);
-    lqr.xf_weight = o->d_lqr_weights + idocp_host::lqrWeightOffsetXf(o->plan);
-    rc = idocp_rbd_lqr_backward_gn_device(h, n, steps, &lqr, g_rows, c.G_traj); if (rc) return rc;
-  } else {
+  if (form.chain == IlqrForm::DIAGONAL) {
     rc = idocp_rbd_linearize_rollout_device(h, n, steps, active, time_step, dt, io.u_traj, contact_points, io.q_traj, io.v_traj, A, B, touchdown_impulse);
     if (rc) return rc;
     idocp_rbd_gradient_io_t g = idocp_rbd_gradient_io_t();
@@ -1003,6 +1103,28 @@ int iterateDevice(idocp_rbd* h, const idocp_rbd_objective* o, int n, int steps, 
     rc = idocp_rbd_objective_gradients_device(h, o, n, 0, steps, 1, &g); if (rc) return rc;
     rc = idocp_rbd_objective_lqr_weights_device(o, &lqr.x_weight, &lqr.u_weight, &lqr.xf_weight); if (rc) return rc;
     rc = idocp_rbd_lqr_backward_device(h, n, steps, &lqr); if (rc) return rc;
+  } else {
+    // with rows: io.penalty is mu; without constraint rows D stays out and the GN form of the backward pass runs
+    idocp_rbd_penalty_linearization_io_t c = idocp_rbd_penalty_linearization_io_t();
+    c.A_traj = A; c.B_traj = B; c.G_traj = ws + w.G; c.D_traj = form.diagonal() ? ws + w.D : nullptr; c.lx_traj = lx; c.lu_traj = lu;
+    lqr.x_weight = o->d_lqr_weights;
+    lqr.u_weight = o->d_lqr_weights + idocp_host::lqrWeightOffsetU(o->plan);
+    lqr.xf_weight = o->d_lqr_weights + idocp_host::lqrWeightOffsetXf(o->plan);
+    if (form.al())
+      rc = idocp_rbd_linearize_rollout_al_device(h, o, n, steps, active, time_step, dt, io.u_traj, contact_points, io.q_traj, io.v_traj, &c, io.penalty, lambda,
+                                                 touchdown_impulse);
+    else if (form.penalty())
+      rc = idocp_rbd_linearize_rollout_penalty_device(h, o, n, steps, active, time_step, dt, io.u_traj, contact_points, io.q_traj, io.v_traj, &c, io.penalty,
+                                                      touchdown_impulse);
+    else {
+      idocp_rbd_cost_linearization_io_t narrow = idocp_rbd_cost_linearization_io_t();
+      narrow.A_traj = A; narrow.B_traj = B; narrow.G_traj = c.G_traj; narrow.lx_traj = lx; narrow.lu_traj = lu;
+      rc = idocp_rbd_linearize_rollout_cost_device(h, o, n, steps, active, time_step, dt, io.u_traj, contact_points, io.q_traj, io.v_traj, &narrow, touchdown_impulse);
+    }
+    if (rc) return rc;
+    if (form.penalty()) rc = idocp_rbd_lqr_backward_gn_diag_device(h, n, steps, &lqr, form.rows(), c.G_traj, c.D_traj);
+    else rc = idocp_rbd_lqr_backward_gn_device(h, n, steps, &lqr, form.rows(), c.G_traj);
+    if (rc) return rc;
   }
   rbdIlqrInit(alpha, done, io.alpha_accepted, n, h->stream);
   HIP_TRY(hipGetLastError());
@@ -1018,39 +1140,44 @@ int iterateDevice(idocp_rbd* h, const idocp_rbd_objective* o, int n, int steps, 
   acc.trial_cost = cost_t; acc.trial_violation = violation_t; acc.expected = io.expected; acc.alpha = alpha; acc.done = done;
   acc.alpha_accepted = io.alpha_accepted;
   acc.penalty = io.penalty; acc.armijo = io.armijo; acc.shrink = io.shrink; acc.alpha_min = io.alpha_min;
+  const RolloutArrays trial = {qt, vt, ut, at, ft};
   // A sample accepted in an early round is rolled out again in the later rounds, about the trajectory it now holds, and that trial is ignored
   // (done[i] != 0): simpler than compacting the batch, and the stream stays free of host decisions.
   for (int round = 0; round < io.trials; ++round) {
     rc = idocp_rbd_ilqr_step_torques_device(h, n, steps, io.u_traj, kff, alpha, u_ff); if (rc) return rc;
     rc = idocp_rbd_rollout_policy_device(h, n, steps, active, time_step, dt, &pol, contact_points, qt, vt, ut, at, ft, touchdown_impulse); if (rc) return rc;
-    for (int first = 0; first < steps; first += IDOCP_RBD_SCORE_MAX_WINDOW) {      // (the windows of the header, with accumulate)
-      const int window = steps - first < IDOCP_RBD_SCORE_MAX_WINDOW ? steps - first : IDOCP_RBD_SCORE_MAX_WINDOW;
+    rc = forEachWindow(h, n, steps, active, trial, [&](int first, int window, int accumulate, const int* act, const RolloutArrays& t) {
       idocp_rbd_score_io_t sc = idocp_rbd_score_io_t();
-      sc.q_traj = qt + first * N * nq; sc.v_traj = vt + first * N * nv; sc.u_traj = ut + first * N * nu; sc.a_traj = at + first * N * nv;
-      sc.f_traj = ft ? ft + first * N * nf : nullptr;
-      sc.cost = cost_t; sc.violation = penalty ? nullptr : violation_t;      // (penalty form: `violation` is sq_violation alone, window by window)
-      rc = idocp_rbd_score_rollout_device(h, o, n, first, window, active ? active + (size_t)first * h->model.ncontacts : nullptr,
-                                          first + window == steps, first > 0, &sc);
-      if (rc) return rc;
-      if (al) {           // the trial sq_shifted under the window's multipliers
-        rc = idocp_rbd_score_al_device(h, o, n, first, window, active ? active + (size_t)first * h->model.ncontacts : nullptr, first > 0, sc.q_traj,
-                                       sc.v_traj, sc.u_traj, sc.a_traj, sc.f_traj, io.penalty, lambda ? lambda + (size_t)first * N * rows_l : nullptr, violation_t);
-        if (rc) return rc;
-      } else if (penalty) {      // the trial sq_violation over the score's L1 violation, window by window the same way
-        rc = idocp_rbd_score_penalty_device(h, o, n, first, window, active ? active + (size_t)first * h->model.ncontacts : nullptr, first > 0, sc.q_traj,
-                                            sc.v_traj, sc.u_traj, sc.a_traj, sc.f_traj, violation_t);
-        if (rc) return rc;
-      }
-    }
+      sc.q_traj = t.q; sc.v_traj = t.v; sc.u_traj = t.u; sc.a_traj = t.a; sc.f_traj = t.f;
+      sc.cost = cost_t; sc.violation = form.penalty() ? nullptr : violation_t;      // (with constraint rows `violation` is their square sum alone, below)
+      const int refused = idocp_rbd_score_rollout_device(h, o, n, first, window, act, first + window == steps, accumulate, &sc);
+      if (refused || !form.penalty()) return refused;
+      if (form.al())      // the trial sq_shifted under the window's multipliers
+        return idocp_rbd_score_al_device(h, o, n, first, window, act, accumulate, t.q, t.v, t.u, t.a, t.f, io.penalty,
+                                         lambda ? lambda + (size_t)first * N * (size_t)form.multiplier_rows : nullptr, violation_t);
+      // the trial sq_violation over the score's L1 violation, window by window the same way
+      return idocp_rbd_score_penalty_device(h, o, n, first, window, act, accumulate, t.q, t.v, t.u, t.a, t.f, violation_t);
+    });
+    if (rc) return rc;
     rc = launchAccept(h, n, steps, acc); if (rc) return rc;
   }
   return IDOCP_OK;
 }
 
-// the host form of both iterations: stages once, owns the workspace in the staging buffer, reads back once
-int iterateHost(const char* who, idocp_rbd* h, const idocp_rbd_objective* o, int n, int steps, const int* active, double time_step, double dt,
-                const double* contact_points, const idocp_rbd_ilqr_io_t* io, int touchdown_impulse, int gn, const double* lambda = nullptr) {
-  int rc = checkIterate(who, h, o, n, steps, io, true, gn); if (rc) return rc;
+// the two forms of the four iterations.  Device: io holds device pointers and the caller's workspace
+int iterateEntry(const char* who, IlqrForm::Chain chain, idocp_rbd* h, const idocp_rbd_objective* o, int n, int steps, const int* active, double time_step,
+                 double dt, const double* contact_points, const idocp_rbd_ilqr_io_t* io, const double* lambda, int touchdown_impulse) {
+  const IlqrForm form(chain, h, o);
+  int rc = checkIterate(who, form, h, o, n, steps, io, false); if (rc) return rc;
+  HIP_TRY(hipSetDevice(h->device));
+  return iterateDevice(h, o, form, n, steps, active, time_step, dt, contact_points, *io, static_cast<double*>(io->workspace), lambda, touchdown_impulse);
+}
+
+// Host: stages once, owns the workspace in the staging buffer, reads back once
+int iterateHost(const char* who, IlqrForm::Chain chain, idocp_rbd* h, const idocp_rbd_objective* o, int n, int steps, const int* active, double time_step,
+                double dt, const double* contact_points, const idocp_rbd_ilqr_io_t* io, const double* lambda, int touchdown_impulse) {
+  const IlqrForm form(chain, h, o);
+  int rc = checkIterate(who, form, h, o, n, steps, io, true); if (rc) return rc;
   {      // (the bounds are host memory here and can be looked at)
     idocp_rbd_policy_t bounds = idocp_rbd_policy_t();
     bounds.u_min = io->u_min; bounds.u_max = io->u_max;
@@ -1061,7 +1188,7 @@ int iterateHost(const char* who, idocp_rbd* h, const idocp_rbd_objective* o, int
   const size_t nq = h->model.nq, nv = h->model.nv, nu = h->model.nu, nf = 3 * (size_t)h->model.ncontacts, N = (size_t)n, S = (size_t)steps;
   StagePlan p;
   idocp_rbd_ilqr_io_t d = *io;
-  const double* d_points;
+  const double *d_points, *d_lambda;
   double *d_status = nullptr, *d_ws = nullptr;
   p.update(io->q_traj, (S + 1) * N * nq, &d.q_traj);
   p.update(io->v_traj, (S + 1) * N * nv, &d.v_traj);
@@ -1076,13 +1203,11 @@ int iterateHost(const char* who, idocp_rbd* h, const idocp_rbd_objective* o, int
   p.out(io->alpha_accepted, N, &d.alpha_accepted);
   p.out(io->expected, 2 * N, &d.expected);
   p.deviceOnly((N + 1) / 2, &d_status);
-  const bool penalty = gn >= ILQR_PENALTY;
-  const double* d_lambda = nullptr;
-  if (gn == ILQR_AL) p.in(lambda, S * N * (size_t)idocp_host::multiplierRows(o->plan), &d_lambda);
-  p.deviceOnly(ilqrWorkspace(h, n, steps, gn ? idocp_host::residualRows(o->plan) + (penalty ? idocp_host::constraintRows(o->plan) : 0) : 0, penalty).total, &d_ws);
+  p.in(lambda, S * N * (size_t)form.multiplier_rows, &d_lambda);      // (no room but on the AL chain)
+  p.deviceOnly(ilqrWorkspace(h, form, n, steps).total, &d_ws);
   rc = stageIn(h, p); if (rc) return rc;
   d.lqr_status = reinterpret_cast<int*>(d_status);
-  rc = iterateDevice(h, o, n, steps, active, time_step, dt, d_points, d, d_ws, touchdown_impulse, gn, d_lambda); if (rc) return rc;
+  rc = iterateDevice(h, o, form, n, steps, active, time_step, dt, d_points, d, d_ws, d_lambda, touchdown_impulse); if (rc) return rc;
   HIP_TRY(hipMemcpyAsync(io->lqr_status, d_status, sizeof(int) * N, hipMemcpyDeviceToHost, h->stream));
   return stageOut(h, p);
 }
@@ -1586,24 +1711,23 @@ int idocp_rbd_weighted_mean(idocp_rbd_t* h, int n, int rows, int m, const double
 }
 
 int idocp_rbd_lqr_backward_device(idocp_rbd_t* h, int n, int steps, const idocp_rbd_lqr_io_t* io) {
-  int rc = checkLqr("idocp_rbd_lqr_backward_device", h, n, steps, io, false); if (rc) return rc;
+  int rc = checkLqrCall("idocp_rbd_lqr_backward_device", h, n, steps, io, false, 0, nullptr, nullptr); if (rc) return rc;
   HIP_TRY(hipSetDevice(h->device));
-  return launchLqr(h, n, steps, *io);
+  return launchLqr(h, n, steps, *io, 0, nullptr, nullptr);
 }
 
 int idocp_rbd_lqr_backward(idocp_rbd_t* h, int n, int steps, const idocp_rbd_lqr_io_t* io) {
-  return lqrHost("idocp_rbd_lqr_backward", h, n, steps, io, 0, nullptr);
+  return lqrHost("idocp_rbd_lqr_backward", h, n, steps, io, 0, nullptr, nullptr);
 }
 
 int idocp_rbd_lqr_backward_gn_device(idocp_rbd_t* h, int n, int steps, const idocp_rbd_lqr_io_t* io, int g_rows, const double* G_traj) {
-  int rc = checkLqr("idocp_rbd_lqr_backward_gn_device", h, n, steps, io, false); if (rc) return rc;
-  rc = checkLqrGn("idocp_rbd_lqr_backward_gn_device", h, g_rows, G_traj); if (rc) return rc;
+  int rc = checkLqrCall("idocp_rbd_lqr_backward_gn_device", h, n, steps, io, false, g_rows, G_traj, nullptr); if (rc) return rc;
   HIP_TRY(hipSetDevice(h->device));
-  return launchLqrGn(h, n, steps, *io, g_rows, G_traj);
+  return launchLqr(h, n, steps, *io, g_rows, G_traj, nullptr);
 }
 
 int idocp_rbd_lqr_backward_gn(idocp_rbd_t* h, int n, int steps, const idocp_rbd_lqr_io_t* io, int g_rows, const double* G_traj) {
-  return lqrHost("idocp_rbd_lqr_backward_gn", h, n, steps, io, g_rows, G_traj);
+  return lqrHost("idocp_rbd_lqr_backward_gn", h, n, steps, io, g_rows, G_traj, nullptr);
 }
 
 int idocp_rbd_objective_residual_rows(const idocp_rbd_objective_t* o) { return o ? idocp_host::residualRows(o->plan) : 0; }
@@ -1611,38 +1735,17 @@ int idocp_rbd_objective_residual_rows(const idocp_rbd_objective_t* o) { return o
 int idocp_rbd_linearize_rollout_cost_device(idocp_rbd_t* h, const idocp_rbd_objective_t* o, int n, int steps, const int* active, double time_step,
                                             double dt, const double* u_traj, const double* contact_points, const double* q_traj,
                                             const double* v_traj, const idocp_rbd_cost_linearization_io_t* io, int touchdown_impulse) {
-  const char* who = "idocp_rbd_linearize_rollout_cost_device";
-  int rc = checkLinearize(who, h, n, steps, active, time_step, dt, contact_points, q_traj, v_traj); if (rc) return rc;
-  rc = checkLinearizeCost(who, h, o, n, steps, u_traj, io); if (rc) return rc;
-  HIP_TRY(hipSetDevice(h->device));
-  return linearizeCostDevice(h, o, n, steps, active, time_step, dt, u_traj, contact_points, q_traj, v_traj, *io, touchdown_impulse);
+  idocp_rbd_penalty_linearization_io_t wide;
+  return linearizeRowsEntry("idocp_rbd_linearize_rollout_cost_device", IlqrForm::GN, h, o, n, steps, active, time_step, dt, u_traj, contact_points, q_traj, v_traj,
+                            widened(io, &wide), 0.0, nullptr, touchdown_impulse);
 }
 
 int idocp_rbd_linearize_rollout_cost(idocp_rbd_t* h, const idocp_rbd_objective_t* o, int n, int steps, const int* active, double time_step, double dt,
                                      const double* u_traj, const double* contact_points, const double* q_traj, const double* v_traj,
                                      const idocp_rbd_cost_linearization_io_t* io, int touchdown_impulse) {
-  const char* who = "idocp_rbd_linearize_rollout_cost";
-  int rc = checkLinearize(who, h, n, steps, active, time_step, dt, contact_points, q_traj, v_traj); if (rc) return rc;
-  rc = checkLinearizeCost(who, h, o, n, steps, u_traj, io); if (rc) return rc;
-  HIP_TRY(hipSetDevice(h->device));
-  const size_t nq = h->model.nq, nv = h->model.nv, nu = h->model.nu, nf = 3 * (size_t)h->model.ncontacts, N = (size_t)n, S = (size_t)steps, nx = 2 * nv;
-  const size_t R = (size_t)idocp_host::residualRows(o->plan);
-  StagePlan p;
-  const double *d_u, *d_points, *d_q, *d_v;
-  idocp_rbd_cost_linearization_io_t d;
-  p.in(u_traj, S * N * nu, &d_u);
-  p.in(contact_points, S * N * nf, &d_points);
-  p.in(q_traj, (S + 1) * N * nq, &d_q);
-  p.in(v_traj, (S + 1) * N * nv, &d_v);
-  p.out(io->A_traj, S * N * nx * nx, &d.A_traj);
-  p.out(io->B_traj, S * N * nx * nu, &d.B_traj);
-  p.out(io->G_traj, S * N * R * (nx + nu), &d.G_traj);
-  p.out(io->rho_traj, S * N * R, &d.rho_traj);
-  p.out(io->lx_traj, (S + 1) * N * nx, &d.lx_traj);
-  p.out(io->lu_traj, S * N * nu, &d.lu_traj);
-  rc = stageIn(h, p); if (rc) return rc;
-  rc = linearizeCostDevice(h, o, n, steps, active, time_step, dt, d_u, d_points, d_q, d_v, d, touchdown_impulse); if (rc) return rc;
-  return stageOut(h, p);
+  idocp_rbd_penalty_linearization_io_t wide;
+  return linearizeRowsHost("idocp_rbd_linearize_rollout_cost", IlqrForm::GN, h, o, n, steps, active, time_step, dt, u_traj, contact_points, q_traj, v_traj,
+                           widened(io, &wide), 0.0, nullptr, touchdown_impulse);
 }
 
 int idocp_rbd_objective_gradients_device(idocp_rbd_t* h, const idocp_rbd_objective_t* o, int n, int first_step, int steps, int terminal,
@@ -1760,155 +1863,69 @@ int idocp_rbd_ilqr_accept(idocp_rbd_t* h, int n, int steps, const idocp_rbd_ilqr
 
 unsigned long long idocp_rbd_ilqr_workspace_bytes(const idocp_rbd_t* h, int n, int steps) {
   if (!h || n <= 0 || steps < 1) return 0;
-  return sizeof(double) * (unsigned long long)ilqrWorkspace(h, n, steps).total;
+  return sizeof(double) * (unsigned long long)ilqrWorkspace(h, IlqrForm(IlqrForm::DIAGONAL, h, nullptr), n, steps).total;
 }
 
 int idocp_rbd_ilqr_iterate_device(idocp_rbd_t* h, const idocp_rbd_objective_t* o, int n, int steps, const int* active, double time_step, double dt,
                                   const double* contact_points, const idocp_rbd_ilqr_io_t* io, int touchdown_impulse) {
-  int rc = checkIterate("idocp_rbd_ilqr_iterate_device", h, o, n, steps, io, false); if (rc) return rc;
-  HIP_TRY(hipSetDevice(h->device));
-  return iterateDevice(h, o, n, steps, active, time_step, dt, contact_points, *io, static_cast<double*>(io->workspace), touchdown_impulse);
+  return iterateEntry("idocp_rbd_ilqr_iterate_device", IlqrForm::DIAGONAL, h, o, n, steps, active, time_step, dt, contact_points, io, nullptr, touchdown_impulse);
 }
 
 int idocp_rbd_ilqr_iterate(idocp_rbd_t* h, const idocp_rbd_objective_t* o, int n, int steps, const int* active, double time_step, double dt,
                            const double* contact_points, const idocp_rbd_ilqr_io_t* io, int touchdown_impulse) {
-  return iterateHost("idocp_rbd_ilqr_iterate", h, o, n, steps, active, time_step, dt, contact_points, io, touchdown_impulse, ILQR_DIAGONAL);
+  return iterateHost("idocp_rbd_ilqr_iterate", IlqrForm::DIAGONAL, h, o, n, steps, active, time_step, dt, contact_points, io, nullptr, touchdown_impulse);
 }
 
 unsigned long long idocp_rbd_ilqr_gn_workspace_bytes(const idocp_rbd_t* h, int n, int steps) {
   if (!h || n <= 0 || steps < 1) return 0;
-  const int R = (h->model.nv + (h->quadruped ? 3 * h->model.ncontacts : 0) + 3) / 4 * 4;      // (idocp_host::residualRows of any objective of the handle)
-  return sizeof(double) * (unsigned long long)ilqrWorkspace(h, n, steps, R).total;
+  return sizeof(double) * (unsigned long long)ilqrWorkspace(h, IlqrForm(IlqrForm::GN, h, nullptr), n, steps).total;      // (the cost rows of any objective of the handle)
 }
 
 int idocp_rbd_ilqr_iterate_gn_device(idocp_rbd_t* h, const idocp_rbd_objective_t* o, int n, int steps, const int* active, double time_step, double dt,
                                      const double* contact_points, const idocp_rbd_ilqr_io_t* io, int touchdown_impulse) {
-  int rc = checkIterate("idocp_rbd_ilqr_iterate_gn_device", h, o, n, steps, io, false, ILQR_GN); if (rc) return rc;
-  HIP_TRY(hipSetDevice(h->device));
-  return iterateDevice(h, o, n, steps, active, time_step, dt, contact_points, *io, static_cast<double*>(io->workspace), touchdown_impulse, ILQR_GN);
+  return iterateEntry("idocp_rbd_ilqr_iterate_gn_device", IlqrForm::GN, h, o, n, steps, active, time_step, dt, contact_points, io, nullptr, touchdown_impulse);
 }
 
 int idocp_rbd_ilqr_iterate_gn(idocp_rbd_t* h, const idocp_rbd_objective_t* o, int n, int steps, const int* active, double time_step, double dt,
                               const double* contact_points, const idocp_rbd_ilqr_io_t* io, int touchdown_impulse) {
-  return iterateHost("idocp_rbd_ilqr_iterate_gn", h, o, n, steps, active, time_step, dt, contact_points, io, touchdown_impulse, ILQR_GN);
+  return iterateHost("idocp_rbd_ilqr_iterate_gn", IlqrForm::GN, h, o, n, steps, active, time_step, dt, contact_points, io, nullptr, touchdown_impulse);
 }
 
 // ---- the constraint rows as a squared-hinge penalty
 
 int idocp_rbd_objective_constraint_rows(const idocp_rbd_objective_t* o) { return o ? idocp_host::constraintRows(o->plan) : 0; }
 
-namespace {
-// everything idocp_rbd_score_penalty refuses, and the kernel's arguments but for the array pointers
-int checkScorePenalty(const char* who, const idocp_rbd* h, const idocp_rbd_objective* o, int n, int first_step, int steps, const int* active,
-                      int accumulate, const double* q, const double* v, const double* u, const double* a_traj, const double* f, const double* sq,
-                      RbdPenaltyArgs* a) {
-  const std::string w(who);
-  if (!h || !o) { set_last_error(w + ": null handle or objective"); return IDOCP_E_ARG; }
-  if (o->owner != h) { set_last_error(w + ": the objective was created on another handle"); return IDOCP_E_ARG; }
-  if (!sq) { set_last_error(w + ": sq_violation is needed"); return IDOCP_E_ARG; }
-  const idocp_host::RbdScoreCall c = idocp_host::planPenaltyCall(who, o->plan, n, first_step, steps, active, q, v, u, a_traj, f);
-  if (c.rc) { set_last_error(c.error); return c.rc; }
-  std::memcpy(a->masks, c.masks, sizeof(c.masks));
-  a->block = o->d_block; a->steps = steps; a->accumulate = accumulate != 0;
-  return IDOCP_OK;
-}
-}  // namespace
-
 int idocp_rbd_score_penalty_device(idocp_rbd_t* h, const idocp_rbd_objective_t* o, int n, int first_step, int steps, const int* active, int accumulate,
                                    const double* q_traj, const double* v_traj, const double* u_traj, const double* a_traj, const double* f_traj,
                                    double* sq_violation) {
-  const char* who = "idocp_rbd_score_penalty_device";
-  RbdPenaltyArgs a;
-  int rc = checkScorePenalty(who, h, o, n, first_step, steps, active, accumulate, q_traj, v_traj, u_traj, a_traj, f_traj, sq_violation, &a); if (rc) return rc;
-  HIP_TRY(hipSetDevice(h->device));
-  a.q = q_traj; a.v = v_traj; a.u = u_traj; a.a = a_traj; a.f = f_traj; a.sq = sq_violation;
-  if (!rbdPenalty(h->model.nv, h->quadruped, a, n, h->stream)) { set_last_error(std::string(who) + ": no penalty kernel for this model"); return IDOCP_E_UNSUPPORTED; }
-  HIP_TRY(hipGetLastError());
-  return IDOCP_OK;
+  return rowCallDevice("idocp_rbd_score_penalty_device", SCORE_PENALTY, h, o, n, first_step, steps, active, accumulate, {q_traj, v_traj, u_traj, a_traj, f_traj}, 0.0, nullptr, sq_violation, nullptr, nullptr);
 }
 
 int idocp_rbd_score_penalty(idocp_rbd_t* h, const idocp_rbd_objective_t* o, int n, int first_step, int steps, const int* active, int accumulate,
                             const double* q_traj, const double* v_traj, const double* u_traj, const double* a_traj, const double* f_traj,
                             double* sq_violation) {
-  const char* who = "idocp_rbd_score_penalty";
-  RbdPenaltyArgs a;
-  int rc = checkScorePenalty(who, h, o, n, first_step, steps, active, accumulate, q_traj, v_traj, u_traj, a_traj, f_traj, sq_violation, &a); if (rc) return rc;
-  HIP_TRY(hipSetDevice(h->device));
-  const size_t nq = h->model.nq, nv = h->model.nv, nu = h->model.nu, nf = 3 * (size_t)o->plan.ncontacts, N = (size_t)n, S = (size_t)steps;
-  StagePlan p;
-  p.in(q_traj, S * N * nq, &a.q);
-  p.in(v_traj, S * N * nv, &a.v);
-  p.in(u_traj, S * N * nu, &a.u);
-  p.in(a_traj, S * N * nv, &a.a);
-  p.in(f_traj, S * N * nf, &a.f);
-  if (accumulate) p.update(sq_violation, N, &a.sq); else p.out(sq_violation, N, &a.sq);
-  rc = stageIn(h, p); if (rc) return rc;
-  if (!rbdPenalty(h->model.nv, h->quadruped, a, n, h->stream)) { set_last_error(std::string(who) + ": no penalty kernel for this model"); return IDOCP_E_UNSUPPORTED; }
-  HIP_TRY(hipGetLastError());
-  return stageOut(h, p);
+  return rowCallHost("idocp_rbd_score_penalty", SCORE_PENALTY, h, o, n, first_step, steps, active, accumulate, {q_traj, v_traj, u_traj, a_traj, f_traj}, 0.0, nullptr, sq_violation, nullptr, nullptr);
 }
-
-namespace {
-// the cost call's io with the outputs of the penalty call that it knows: its refusals are the penalty call's, D_traj alone counts as an output
-idocp_rbd_cost_linearization_io_t costViewOf(const idocp_rbd_penalty_linearization_io_t& io) {
-  idocp_rbd_cost_linearization_io_t c = idocp_rbd_cost_linearization_io_t();
-  c.A_traj = io.A_traj; c.B_traj = io.B_traj; c.G_traj = io.G_traj ? io.G_traj : io.D_traj; c.rho_traj = io.rho_traj; c.lx_traj = io.lx_traj; c.lu_traj = io.lu_traj;
-  return c;
-}
-}  // namespace
 
 int idocp_rbd_linearize_rollout_penalty_device(idocp_rbd_t* h, const idocp_rbd_objective_t* o, int n, int steps, const int* active, double time_step,
                                                double dt, const double* u_traj, const double* contact_points, const double* q_traj,
                                                const double* v_traj, const idocp_rbd_penalty_linearization_io_t* io, double mu, int touchdown_impulse) {
-  const char* who = "idocp_rbd_linearize_rollout_penalty_device";
-  int rc = checkLinearize(who, h, n, steps, active, time_step, dt, contact_points, q_traj, v_traj); if (rc) return rc;
-  if (!io) { set_last_error(std::string(who) + ": null objective or io"); return IDOCP_E_ARG; }
-  const idocp_rbd_cost_linearization_io_t view = costViewOf(*io);
-  rc = checkLinearizeCost(who, h, o, n, steps, u_traj, &view); if (rc) return rc;
-  rc = checkPenalty(who, o, mu); if (rc) return rc;
-  HIP_TRY(hipSetDevice(h->device));
-  return linearizePenaltyDevice(h, o, n, steps, active, time_step, dt, u_traj, contact_points, q_traj, v_traj, *io, mu, touchdown_impulse);
+  return linearizeRowsEntry("idocp_rbd_linearize_rollout_penalty_device", IlqrForm::PENALTY, h, o, n, steps, active, time_step, dt, u_traj, contact_points, q_traj,
+                            v_traj, io, mu, nullptr, touchdown_impulse);
 }
 
 int idocp_rbd_linearize_rollout_penalty(idocp_rbd_t* h, const idocp_rbd_objective_t* o, int n, int steps, const int* active, double time_step, double dt,
                                         const double* u_traj, const double* contact_points, const double* q_traj, const double* v_traj,
                                         const idocp_rbd_penalty_linearization_io_t* io, double mu, int touchdown_impulse) {
-  const char* who = "idocp_rbd_linearize_rollout_penalty";
-  int rc = checkLinearize(who, h, n, steps, active, time_step, dt, contact_points, q_traj, v_traj); if (rc) return rc;
-  if (!io) { set_last_error(std::string(who) + ": null objective or io"); return IDOCP_E_ARG; }
-  const idocp_rbd_cost_linearization_io_t view = costViewOf(*io);
-  rc = checkLinearizeCost(who, h, o, n, steps, u_traj, &view); if (rc) return rc;
-  rc = checkPenalty(who, o, mu); if (rc) return rc;
-  HIP_TRY(hipSetDevice(h->device));
-  const size_t nq = h->model.nq, nv = h->model.nv, nu = h->model.nu, nf = 3 * (size_t)h->model.ncontacts, N = (size_t)n, S = (size_t)steps, nx = 2 * nv;
-  const size_t R = (size_t)idocp_host::residualRows(o->plan) + (size_t)idocp_host::constraintRows(o->plan);
-  StagePlan p;
-  const double *d_u, *d_points, *d_q, *d_v;
-  idocp_rbd_penalty_linearization_io_t d;
-  p.in(u_traj, S * N * nu, &d_u);
-  p.in(contact_points, S * N * nf, &d_points);
-  p.in(q_traj, (S + 1) * N * nq, &d_q);
-  p.in(v_traj, (S + 1) * N * nv, &d_v);
-  p.out(io->A_traj, S * N * nx * nx, &d.A_traj);
-  p.out(io->B_traj, S * N * nx * nu, &d.B_traj);
-  p.out(io->G_traj, S * N * R * (nx + nu), &d.G_traj);
-  p.out(io->rho_traj, S * N * R, &d.rho_traj);
-  p.out(io->D_traj, S * N * (nx + nu), &d.D_traj);
-  p.out(io->lx_traj, (S + 1) * N * nx, &d.lx_traj);
-  p.out(io->lu_traj, S * N * nu, &d.lu_traj);
-  rc = stageIn(h, p); if (rc) return rc;
-  rc = linearizePenaltyDevice(h, o, n, steps, active, time_step, dt, d_u, d_points, d_q, d_v, d, mu, touchdown_impulse); if (rc) return rc;
-  return stageOut(h, p);
+  return linearizeRowsHost("idocp_rbd_linearize_rollout_penalty", IlqrForm::PENALTY, h, o, n, steps, active, time_step, dt, u_traj, contact_points, q_traj, v_traj,
+                           io, mu, nullptr, touchdown_impulse);
 }
 
 int idocp_rbd_lqr_backward_gn_diag_device(idocp_rbd_t* h, int n, int steps, const idocp_rbd_lqr_io_t* io, int g_rows, const double* G_traj,
                                           const double* D_traj) {
-  const char* who = "idocp_rbd_lqr_backward_gn_diag_device";
-  int rc = checkLqr(who, h, n, steps, io, false); if (rc) return rc;
-  rc = checkLqrGn(who, h, g_rows, G_traj); if (rc) return rc;
-  if (D_traj && !G_traj) { set_last_error(std::string(who) + ": D_traj needs a G_traj"); return IDOCP_E_ARG; }
+  int rc = checkLqrCall("idocp_rbd_lqr_backward_gn_diag_device", h, n, steps, io, false, g_rows, G_traj, D_traj); if (rc) return rc;
   HIP_TRY(hipSetDevice(h->device));
-  return launchLqrGn(h, n, steps, *io, g_rows, G_traj, D_traj);
+  return launchLqr(h, n, steps, *io, g_rows, G_traj, D_traj);
 }
 
 int idocp_rbd_lqr_backward_gn_diag(idocp_rbd_t* h, int n, int steps, const idocp_rbd_lqr_io_t* io, int g_rows, const double* G_traj,
@@ -1918,221 +1935,88 @@ int idocp_rbd_lqr_backward_gn_diag(idocp_rbd_t* h, int n, int steps, const idocp
 
 unsigned long long idocp_rbd_ilqr_penalty_workspace_bytes(const idocp_rbd_t* h, const idocp_rbd_objective_t* o, int n, int steps) {
   if (!h || !o || o->owner != h || n <= 0 || steps < 1) return 0;
-  return sizeof(double) * (unsigned long long)ilqrWorkspace(h, n, steps, idocp_host::residualRows(o->plan) + idocp_host::constraintRows(o->plan), true).total;
+  return sizeof(double) * (unsigned long long)ilqrWorkspace(h, IlqrForm(IlqrForm::PENALTY, h, o), n, steps).total;
 }
 
 int idocp_rbd_ilqr_iterate_penalty_device(idocp_rbd_t* h, const idocp_rbd_objective_t* o, int n, int steps, const int* active, double time_step,
                                           double dt, const double* contact_points, const idocp_rbd_ilqr_io_t* io, int touchdown_impulse) {
-  int rc = checkIterate("idocp_rbd_ilqr_iterate_penalty_device", h, o, n, steps, io, false, ILQR_PENALTY); if (rc) return rc;
-  HIP_TRY(hipSetDevice(h->device));
-  return iterateDevice(h, o, n, steps, active, time_step, dt, contact_points, *io, static_cast<double*>(io->workspace), touchdown_impulse, ILQR_PENALTY);
+  return iterateEntry("idocp_rbd_ilqr_iterate_penalty_device", IlqrForm::PENALTY, h, o, n, steps, active, time_step, dt, contact_points, io, nullptr, touchdown_impulse);
 }
 
 int idocp_rbd_ilqr_iterate_penalty(idocp_rbd_t* h, const idocp_rbd_objective_t* o, int n, int steps, const int* active, double time_step, double dt,
                                    const double* contact_points, const idocp_rbd_ilqr_io_t* io, int touchdown_impulse) {
-  return iterateHost("idocp_rbd_ilqr_iterate_penalty", h, o, n, steps, active, time_step, dt, contact_points, io, touchdown_impulse, ILQR_PENALTY);
+  return iterateHost("idocp_rbd_ilqr_iterate_penalty", IlqrForm::PENALTY, h, o, n, steps, active, time_step, dt, contact_points, io, nullptr, touchdown_impulse);
 }
 
 // ---- the augmented Lagrangian: multipliers on the constraint rows
 
 int idocp_rbd_objective_multiplier_rows(const idocp_rbd_objective_t* o) { return o ? idocp_host::multiplierRows(o->plan) : 0; }
 
-namespace {
-int checkMu(const char* who, double mu, const char* name = "mu") {
-  if (!std::isfinite(mu) || !(mu > 0.0)) { set_last_error(std::string(who) + ": " + name + " must be positive and finite"); return IDOCP_E_ARG; }
-  return IDOCP_OK;
-}
-
-// what idocp_rbd_score_al and idocp_rbd_multiplier_update refuse, and the kernel's arguments but for the array pointers.  update: lambda_out is
-// needed where the objective has multiplier rows; score: sq is
-int checkAl(const char* who, const idocp_rbd* h, const idocp_rbd_objective* o, int n, int first_step, int steps, const int* active, int accumulate,
-            const double* q, const double* v, const double* u, const double* a_traj, const double* f, double mu, bool update, const double* out,
-            RbdAlArgs* a) {
-  const std::string w(who);
-  if (!h || !o) { set_last_error(w + ": null handle or objective"); return IDOCP_E_ARG; }
-  if (o->owner != h) { set_last_error(w + ": the objective was created on another handle"); return IDOCP_E_ARG; }
-  int rc = checkMu(who, mu); if (rc) return rc;
-  if (!update && !out) { set_last_error(w + ": sq_shifted is needed"); return IDOCP_E_ARG; }
-  if (update && !out && idocp_host::multiplierRows(o->plan)) { set_last_error(w + ": lambda_out is needed"); return IDOCP_E_ARG; }
-  const idocp_host::RbdScoreCall c = idocp_host::planPenaltyCall(who, o->plan, n, first_step, steps, active, q, v, u, a_traj, f);
-  if (c.rc) { set_last_error(c.error); return c.rc; }
-  std::memcpy(a->masks, c.masks, sizeof(c.masks));
-  a->block = o->d_block; a->steps = steps; a->accumulate = accumulate != 0; a->penalty = mu;
-  a->sq = nullptr; a->lambda = nullptr; a->lambda_out = nullptr; a->infeasibility = nullptr; a->change = nullptr;
-  return IDOCP_OK;
-}
-
-// a: device pointers.  An objective without multiplier rows has nothing to update: the statistics are zero (kept as they are with accumulate)
-int launchAlUpdate(const char* who, idocp_rbd* h, const idocp_rbd_objective* o, const RbdAlArgs& a, int n) {
-  if (idocp_host::multiplierRows(o->plan) == 0) {
-    if (!a.accumulate) {
-      if (a.infeasibility) HIP_TRY(hipMemsetAsync(a.infeasibility, 0, sizeof(double) * (size_t)n, h->stream));
-      if (a.change) HIP_TRY(hipMemsetAsync(a.change, 0, sizeof(double) * (size_t)n, h->stream));
-    }
-    return IDOCP_OK;
-  }
-  if (!rbdAlUpdate(h->model.nv, h->quadruped, a, n, h->stream)) { set_last_error(std::string(who) + ": no multiplier kernel for this model"); return IDOCP_E_UNSUPPORTED; }
-  HIP_TRY(hipGetLastError());
-  return IDOCP_OK;
-}
-}  // namespace
-
 int idocp_rbd_score_al_device(idocp_rbd_t* h, const idocp_rbd_objective_t* o, int n, int first_step, int steps, const int* active, int accumulate,
                               const double* q_traj, const double* v_traj, const double* u_traj, const double* a_traj, const double* f_traj, double mu,
                               const double* lambda_traj, double* sq_shifted) {
-  const char* who = "idocp_rbd_score_al_device";
-  RbdAlArgs a;
-  int rc = checkAl(who, h, o, n, first_step, steps, active, accumulate, q_traj, v_traj, u_traj, a_traj, f_traj, mu, false, sq_shifted, &a); if (rc) return rc;
-  HIP_TRY(hipSetDevice(h->device));
-  a.q = q_traj; a.v = v_traj; a.u = u_traj; a.a = a_traj; a.f = f_traj; a.sq = sq_shifted;
-  a.lambda = idocp_host::multiplierRows(o->plan) ? lambda_traj : nullptr;
-  if (!rbdAlScore(h->model.nv, h->quadruped, a, n, h->stream)) { set_last_error(std::string(who) + ": no multiplier kernel for this model"); return IDOCP_E_UNSUPPORTED; }
-  HIP_TRY(hipGetLastError());
-  return IDOCP_OK;
+  return rowCallDevice("idocp_rbd_score_al_device", SCORE_AL, h, o, n, first_step, steps, active, accumulate, {q_traj, v_traj, u_traj, a_traj, f_traj}, mu, lambda_traj, sq_shifted, nullptr, nullptr);
 }
 
 int idocp_rbd_score_al(idocp_rbd_t* h, const idocp_rbd_objective_t* o, int n, int first_step, int steps, const int* active, int accumulate,
                        const double* q_traj, const double* v_traj, const double* u_traj, const double* a_traj, const double* f_traj, double mu,
                        const double* lambda_traj, double* sq_shifted) {
-  const char* who = "idocp_rbd_score_al";
-  RbdAlArgs a;
-  int rc = checkAl(who, h, o, n, first_step, steps, active, accumulate, q_traj, v_traj, u_traj, a_traj, f_traj, mu, false, sq_shifted, &a); if (rc) return rc;
-  HIP_TRY(hipSetDevice(h->device));
-  const size_t nq = h->model.nq, nv = h->model.nv, nu = h->model.nu, nf = 3 * (size_t)o->plan.ncontacts, N = (size_t)n, S = (size_t)steps;
-  StagePlan p;
-  p.in(q_traj, S * N * nq, &a.q);
-  p.in(v_traj, S * N * nv, &a.v);
-  p.in(u_traj, S * N * nu, &a.u);
-  p.in(a_traj, S * N * nv, &a.a);
-  p.in(f_traj, S * N * nf, &a.f);
-  p.in(lambda_traj, S * N * (size_t)idocp_host::multiplierRows(o->plan), &a.lambda);
-  if (accumulate) p.update(sq_shifted, N, &a.sq); else p.out(sq_shifted, N, &a.sq);
-  rc = stageIn(h, p); if (rc) return rc;
-  if (!rbdAlScore(h->model.nv, h->quadruped, a, n, h->stream)) { set_last_error(std::string(who) + ": no multiplier kernel for this model"); return IDOCP_E_UNSUPPORTED; }
-  HIP_TRY(hipGetLastError());
-  return stageOut(h, p);
+  return rowCallHost("idocp_rbd_score_al", SCORE_AL, h, o, n, first_step, steps, active, accumulate, {q_traj, v_traj, u_traj, a_traj, f_traj}, mu, lambda_traj, sq_shifted, nullptr, nullptr);
 }
 
 int idocp_rbd_multiplier_update_device(idocp_rbd_t* h, const idocp_rbd_objective_t* o, int n, int first_step, int steps, const int* active, int accumulate,
                                        const double* q_traj, const double* v_traj, const double* u_traj, const double* a_traj, const double* f_traj,
                                        double mu, const double* lambda_traj, double* lambda_out, double* infeasibility, double* multiplier_change) {
-  const char* who = "idocp_rbd_multiplier_update_device";
-  RbdAlArgs a;
-  int rc = checkAl(who, h, o, n, first_step, steps, active, accumulate, q_traj, v_traj, u_traj, a_traj, f_traj, mu, true, lambda_out, &a); if (rc) return rc;
-  HIP_TRY(hipSetDevice(h->device));
-  a.q = q_traj; a.v = v_traj; a.u = u_traj; a.a = a_traj; a.f = f_traj;
-  a.lambda = lambda_traj; a.lambda_out = lambda_out; a.infeasibility = infeasibility; a.change = multiplier_change;
-  return launchAlUpdate(who, h, o, a, n);
+  return rowCallDevice("idocp_rbd_multiplier_update_device", MULTIPLIER_UPDATE, h, o, n, first_step, steps, active, accumulate, {q_traj, v_traj, u_traj, a_traj, f_traj}, mu, lambda_traj, lambda_out,
+                       infeasibility, multiplier_change);
 }
 
 int idocp_rbd_multiplier_update(idocp_rbd_t* h, const idocp_rbd_objective_t* o, int n, int first_step, int steps, const int* active, int accumulate,
                                 const double* q_traj, const double* v_traj, const double* u_traj, const double* a_traj, const double* f_traj, double mu,
                                 const double* lambda_traj, double* lambda_out, double* infeasibility, double* multiplier_change) {
-  const char* who = "idocp_rbd_multiplier_update";
-  RbdAlArgs a;
-  int rc = checkAl(who, h, o, n, first_step, steps, active, accumulate, q_traj, v_traj, u_traj, a_traj, f_traj, mu, true, lambda_out, &a); if (rc) return rc;
-  HIP_TRY(hipSetDevice(h->device));
-  const size_t nq = h->model.nq, nv = h->model.nv, nu = h->model.nu, nf = 3 * (size_t)o->plan.ncontacts, N = (size_t)n, S = (size_t)steps;
-  const size_t rows = (size_t)idocp_host::multiplierRows(o->plan);
-  StagePlan p;
-  p.in(q_traj, S * N * nq, &a.q);
-  p.in(v_traj, S * N * nv, &a.v);
-  p.in(u_traj, S * N * nu, &a.u);
-  p.in(a_traj, S * N * nv, &a.a);
-  p.in(f_traj, S * N * nf, &a.f);
-  // (the staged copies are two slots even where the caller's arrays are one: in place is the caller's business, not the stage's)
-  p.in(lambda_traj, S * N * rows, &a.lambda);
-  p.out(lambda_out, S * N * rows, &a.lambda_out);
-  if (accumulate) { p.update(infeasibility, N, &a.infeasibility); p.update(multiplier_change, N, &a.change); }
-  else { p.out(infeasibility, N, &a.infeasibility, true); p.out(multiplier_change, N, &a.change, true); }
-  rc = stageIn(h, p); if (rc) return rc;
-  rc = launchAlUpdate(who, h, o, a, n); if (rc) return rc;
-  return stageOut(h, p);
+  return rowCallHost("idocp_rbd_multiplier_update", MULTIPLIER_UPDATE, h, o, n, first_step, steps, active, accumulate, {q_traj, v_traj, u_traj, a_traj, f_traj}, mu, lambda_traj, lambda_out,
+                       infeasibility, multiplier_change);
 }
-
-namespace {
-int checkLinearizeAl(const char* who, idocp_rbd* h, const idocp_rbd_objective* o, int n, int steps, const int* active, double time_step, double dt,
-                     const double* u_traj, const double* contact_points, const double* q_traj, const double* v_traj,
-                     const idocp_rbd_penalty_linearization_io_t* io, double mu) {
-  int rc = checkLinearize(who, h, n, steps, active, time_step, dt, contact_points, q_traj, v_traj); if (rc) return rc;
-  if (!io) { set_last_error(std::string(who) + ": null objective or io"); return IDOCP_E_ARG; }
-  const idocp_rbd_cost_linearization_io_t view = costViewOf(*io);
-  rc = checkLinearizeCost(who, h, o, n, steps, u_traj, &view); if (rc) return rc;
-  rc = checkMu(who, mu); if (rc) return rc;
-  return checkPenalty(who, o, mu);
-}
-}  // namespace
 
 int idocp_rbd_linearize_rollout_al_device(idocp_rbd_t* h, const idocp_rbd_objective_t* o, int n, int steps, const int* active, double time_step, double dt,
                                           const double* u_traj, const double* contact_points, const double* q_traj, const double* v_traj,
                                           const idocp_rbd_penalty_linearization_io_t* io, double mu, const double* lambda_traj, int touchdown_impulse) {
-  const char* who = "idocp_rbd_linearize_rollout_al_device";
-  int rc = checkLinearizeAl(who, h, o, n, steps, active, time_step, dt, u_traj, contact_points, q_traj, v_traj, io, mu); if (rc) return rc;
-  HIP_TRY(hipSetDevice(h->device));
-  return linearizePenaltyDevice(h, o, n, steps, active, time_step, dt, u_traj, contact_points, q_traj, v_traj, *io, mu, touchdown_impulse, true, lambda_traj);
+  return linearizeRowsEntry("idocp_rbd_linearize_rollout_al_device", IlqrForm::AL, h, o, n, steps, active, time_step, dt, u_traj, contact_points, q_traj, v_traj,
+                            io, mu, lambda_traj, touchdown_impulse);
 }
 
 int idocp_rbd_linearize_rollout_al(idocp_rbd_t* h, const idocp_rbd_objective_t* o, int n, int steps, const int* active, double time_step, double dt,
                                    const double* u_traj, const double* contact_points, const double* q_traj, const double* v_traj,
                                    const idocp_rbd_penalty_linearization_io_t* io, double mu, const double* lambda_traj, int touchdown_impulse) {
-  const char* who = "idocp_rbd_linearize_rollout_al";
-  int rc = checkLinearizeAl(who, h, o, n, steps, active, time_step, dt, u_traj, contact_points, q_traj, v_traj, io, mu); if (rc) return rc;
-  HIP_TRY(hipSetDevice(h->device));
-  const size_t nq = h->model.nq, nv = h->model.nv, nu = h->model.nu, nf = 3 * (size_t)h->model.ncontacts, N = (size_t)n, S = (size_t)steps, nx = 2 * nv;
-  const size_t R = (size_t)idocp_host::residualRows(o->plan) + (size_t)idocp_host::constraintRows(o->plan);
-  StagePlan p;
-  const double *d_u, *d_points, *d_q, *d_v, *d_lambda;
-  idocp_rbd_penalty_linearization_io_t d;
-  p.in(u_traj, S * N * nu, &d_u);
-  p.in(contact_points, S * N * nf, &d_points);
-  p.in(q_traj, (S + 1) * N * nq, &d_q);
-  p.in(v_traj, (S + 1) * N * nv, &d_v);
-  p.in(lambda_traj, S * N * (size_t)idocp_host::multiplierRows(o->plan), &d_lambda);
-  p.out(io->A_traj, S * N * nx * nx, &d.A_traj);
-  p.out(io->B_traj, S * N * nx * nu, &d.B_traj);
-  p.out(io->G_traj, S * N * R * (nx + nu), &d.G_traj);
-  p.out(io->rho_traj, S * N * R, &d.rho_traj);
-  p.out(io->D_traj, S * N * (nx + nu), &d.D_traj);
-  p.out(io->lx_traj, (S + 1) * N * nx, &d.lx_traj);
-  p.out(io->lu_traj, S * N * nu, &d.lu_traj);
-  rc = stageIn(h, p); if (rc) return rc;
-  rc = linearizePenaltyDevice(h, o, n, steps, active, time_step, dt, d_u, d_points, d_q, d_v, d, mu, touchdown_impulse, true, d_lambda); if (rc) return rc;
-  return stageOut(h, p);
+  return linearizeRowsHost("idocp_rbd_linearize_rollout_al", IlqrForm::AL, h, o, n, steps, active, time_step, dt, u_traj, contact_points, q_traj, v_traj, io, mu,
+                           lambda_traj, touchdown_impulse);
 }
 
 int idocp_rbd_ilqr_iterate_al_device(idocp_rbd_t* h, const idocp_rbd_objective_t* o, int n, int steps, const int* active, double time_step, double dt,
                                      const double* contact_points, const idocp_rbd_ilqr_io_t* io, const double* lambda_traj, int touchdown_impulse) {
-  int rc = checkIterate("idocp_rbd_ilqr_iterate_al_device", h, o, n, steps, io, false, ILQR_AL); if (rc) return rc;
-  HIP_TRY(hipSetDevice(h->device));
-  return iterateDevice(h, o, n, steps, active, time_step, dt, contact_points, *io, static_cast<double*>(io->workspace), touchdown_impulse, ILQR_AL, lambda_traj);
+  return iterateEntry("idocp_rbd_ilqr_iterate_al_device", IlqrForm::AL, h, o, n, steps, active, time_step, dt, contact_points, io, lambda_traj, touchdown_impulse);
 }
 
 int idocp_rbd_ilqr_iterate_al(idocp_rbd_t* h, const idocp_rbd_objective_t* o, int n, int steps, const int* active, double time_step, double dt,
                               const double* contact_points, const idocp_rbd_ilqr_io_t* io, const double* lambda_traj, int touchdown_impulse) {
-  return iterateHost("idocp_rbd_ilqr_iterate_al", h, o, n, steps, active, time_step, dt, contact_points, io, touchdown_impulse, ILQR_AL, lambda_traj);
+  return iterateHost("idocp_rbd_ilqr_iterate_al", IlqrForm::AL, h, o, n, steps, active, time_step, dt, contact_points, io, lambda_traj, touchdown_impulse);
 }
 
 namespace {
 // every pointer: device memory.  The outer step: the multipliers in place under mu, window by window with the running maxima, then `violation`
-// = sq_shifted under the new multipliers and mu_next, window by window with accumulate
-int alUpdateDevice(const char* who, idocp_rbd* h, const idocp_rbd_objective* o, int n, int steps, const int* active, const double* q, const double* v,
-                   const double* u, const double* a, const double* f, double mu, double mu_next, double* lambda, double* violation, double* infeasibility,
-                   double* change) {
-  const size_t nq = h->model.nq, nv = h->model.nv, nu = h->model.nu, nf = 3 * (size_t)h->model.ncontacts, N = (size_t)n;
-  const size_t rows = (size_t)idocp_host::multiplierRows(o->plan);
-  for (int pass = 0; pass < 2; ++pass)
-    for (int first = 0; first < steps; first += IDOCP_RBD_SCORE_MAX_WINDOW) {
-      const int window = steps - first < IDOCP_RBD_SCORE_MAX_WINDOW ? steps - first : IDOCP_RBD_SCORE_MAX_WINDOW;
-      const int* act = active ? active + (size_t)first * h->model.ncontacts : nullptr;
-      const double *qk = q + first * N * nq, *vk = v + first * N * nv, *uk = u ? u + first * N * nu : nullptr, *ak = a ? a + first * N * nv : nullptr;
-      const double* fk = f ? f + first * N * nf : nullptr;
-      double* lk = lambda ? lambda + first * N * rows : nullptr;
-      int rc;
-      if (pass == 0) rc = idocp_rbd_multiplier_update_device(h, o, n, first, window, act, first > 0, qk, vk, uk, ak, fk, mu, lk, lk, infeasibility, change);
-      else rc = idocp_rbd_score_al_device(h, o, n, first, window, act, first > 0, qk, vk, uk, ak, fk, mu_next, lk, violation);
-      if (rc) return rc;      // (idocp_last_error names the inner call)
-    }
-  (void)who;
+// = sq_shifted under the new multipliers and mu_next, window by window with accumulate.  A window that refuses leaves the inner call's name in
+// idocp_last_error.
+int alUpdateDevice(idocp_rbd* h, const idocp_rbd_objective* o, int n, int steps, const int* active, const RolloutArrays& t, double mu, double mu_next,
+                   double* lambda, double* violation, double* infeasibility, double* change) {
+  const size_t per_step = (size_t)n * (size_t)idocp_host::multiplierRows(o->plan);
+  for (int pass = 0; pass < 2; ++pass) {
+    const int rc = forEachWindow(h, n, steps, active, t, [&](int first, int window, int accumulate, const int* act, const RolloutArrays& w) {
+      double* const lk = lambda ? lambda + first * per_step : nullptr;
+      if (pass == 0) return idocp_rbd_multiplier_update_device(h, o, n, first, window, act, accumulate, w.q, w.v, w.u, w.a, w.f, mu, lk, lk, infeasibility, change);
+      return idocp_rbd_score_al_device(h, o, n, first, window, act, accumulate, w.q, w.v, w.u, w.a, w.f, mu_next, lk, violation);
+    });
+    if (rc) return rc;
+  }
   return IDOCP_OK;
 }
 
@@ -2146,7 +2030,7 @@ int checkAlUpdate(const char* who, const idocp_rbd* h, const idocp_rbd_objective
   if (!q || !v) { set_last_error(w + ": q_traj and v_traj are needed"); return IDOCP_E_ARG; }
   if (!violation) { set_last_error(w + ": violation is needed"); return IDOCP_E_ARG; }
   if (!lambda && idocp_host::multiplierRows(o->plan)) { set_last_error(w + ": lambda_traj is needed (the update is in place)"); return IDOCP_E_ARG; }
-  int rc = checkMu(who, mu); if (rc) return rc;
+  int rc = checkMu(who, mu, "mu"); if (rc) return rc;
   return checkMu(who, mu_next, "mu_next");
 }
 }  // namespace
@@ -2154,33 +2038,27 @@ int checkAlUpdate(const char* who, const idocp_rbd* h, const idocp_rbd_objective
 int idocp_rbd_ilqr_al_update_device(idocp_rbd_t* h, const idocp_rbd_objective_t* o, int n, int steps, const int* active, const double* q_traj,
                                     const double* v_traj, const double* u_traj, const double* a_traj, const double* f_traj, double mu, double mu_next,
                                     double* lambda_traj, double* violation, double* infeasibility, double* multiplier_change) {
-  const char* who = "idocp_rbd_ilqr_al_update_device";
-  int rc = checkAlUpdate(who, h, o, n, steps, q_traj, v_traj, mu, mu_next, lambda_traj, violation); if (rc) return rc;
+  int rc = checkAlUpdate("idocp_rbd_ilqr_al_update_device", h, o, n, steps, q_traj, v_traj, mu, mu_next, lambda_traj, violation); if (rc) return rc;
   HIP_TRY(hipSetDevice(h->device));
-  return alUpdateDevice(who, h, o, n, steps, active, q_traj, v_traj, u_traj, a_traj, f_traj, mu, mu_next, lambda_traj, violation, infeasibility, multiplier_change);
+  return alUpdateDevice(h, o, n, steps, active, {q_traj, v_traj, u_traj, a_traj, f_traj}, mu, mu_next, lambda_traj, violation, infeasibility, multiplier_change);
 }
 
 int idocp_rbd_ilqr_al_update(idocp_rbd_t* h, const idocp_rbd_objective_t* o, int n, int steps, const int* active, const double* q_traj,
                              const double* v_traj, const double* u_traj, const double* a_traj, const double* f_traj, double mu, double mu_next,
                              double* lambda_traj, double* violation, double* infeasibility, double* multiplier_change) {
-  const char* who = "idocp_rbd_ilqr_al_update";
-  int rc = checkAlUpdate(who, h, o, n, steps, q_traj, v_traj, mu, mu_next, lambda_traj, violation); if (rc) return rc;
+  int rc = checkAlUpdate("idocp_rbd_ilqr_al_update", h, o, n, steps, q_traj, v_traj, mu, mu_next, lambda_traj, violation); if (rc) return rc;
   HIP_TRY(hipSetDevice(h->device));
-  const size_t nq = h->model.nq, nv = h->model.nv, nu = h->model.nu, nf = 3 * (size_t)o->plan.ncontacts, N = (size_t)n, S = (size_t)steps;
+  const size_t N = (size_t)n;
   StagePlan p;
-  const double *d_q, *d_v, *d_u, *d_a, *d_f;
+  RolloutArrays d;
   double *d_lambda, *d_violation, *d_inf, *d_change;
-  p.in(q_traj, S * N * nq, &d_q);      // (the stage slices alone: the terminal slice has no rows)
-  p.in(v_traj, S * N * nv, &d_v);
-  p.in(u_traj, S * N * nu, &d_u);
-  p.in(a_traj, S * N * nv, &d_a);
-  p.in(f_traj, S * N * nf, &d_f);
-  p.update(lambda_traj, S * N * (size_t)idocp_host::multiplierRows(o->plan), &d_lambda);
+  stageRollout(p, h, o, n, steps, {q_traj, v_traj, u_traj, a_traj, f_traj}, &d);
+  p.update(lambda_traj, (size_t)steps * N * (size_t)idocp_host::multiplierRows(o->plan), &d_lambda);
   p.out(violation, N, &d_violation);
   p.out(infeasibility, N, &d_inf, true);
   p.out(multiplier_change, N, &d_change, true);
   rc = stageIn(h, p); if (rc) return rc;
-  rc = alUpdateDevice(who, h, o, n, steps, active, d_q, d_v, d_u, d_a, d_f, mu, mu_next, d_lambda, d_violation, d_inf, d_change); if (rc) return rc;
+  rc = alUpdateDevice(h, o, n, steps, active, d, mu, mu_next, d_lambda, d_violation, d_inf, d_change); if (rc) return rc;
   return stageOut(h, p);
 }
 

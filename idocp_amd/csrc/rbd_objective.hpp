@@ -216,7 +216,8 @@ inline void lqrWeights(const RbdObjectivePlan& o, double* out) {
 
 // ---- the acceleration and contact-force terms as Gauss-Newton residual rows (idocp_rbd_linearize_rollout_cost; include/idocp_hip.h defines them)
 // R = roundup4(nv + 3 ncontacts) rows: the accelerations, the contact forces, padding
-inline int residualRows(const RbdObjectivePlan& o) { return (o.nv + 3 * o.ncontacts + 3) / 4 * 4; }
+inline int residualRows(int nv, int ncontacts) { return (nv + 3 * ncontacts + 3) / 4 * 4; }      // (of every objective of a model with these dimensions)
+inline int residualRows(const RbdObjectivePlan& o) { return residualRows(o.nv, o.ncontacts); }
 // "" when every a_weight and f_weight entry has a square root, else the text that names the term
 inline std::string residualUnsupported(const RbdObjectivePlan& o) {
   for (int r = 0; r < o.nv; ++r) if (o.block.a_weight[r] < 0.0) return "a negative a_weight: a residual row needs its square root";

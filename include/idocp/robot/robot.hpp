@@ -285,31 +285,16 @@ class Robot {
         (nc > 0 && ((int)f.size() != steps || (int)contact_status.size() != steps))) {
       std::cerr << "invalid size: a trajectory of N stages has N + 1 states q, v and N of a, u, f and contact_status!" << '\n'; std::exit(EXIT_FAILURE);
     }
-    const size_t nq = model_.nq, nv = model_.nv, nu = model_.nu;
-    std::vector<double> qs((steps + 1) * nq), vs((steps + 1) * nv), as(steps * nv), us(steps * nu), fs((size_t)steps * 3 * nc, 0.0);
-    std::vector<int> act((size_t)steps * nc, 0);
-    for (int k = 0; k <= steps; ++k) {
-      sized(q[k], model_.nq, "q"); sized(v[k], model_.nv, "v");
-      for (size_t j = 0; j < nq; ++j) qs[k * nq + j] = q[k][j];
-      for (size_t j = 0; j < nv; ++j) vs[k * nv + j] = v[k][j];
-      if (k == steps) break;
-      sized(a[k], model_.nv, "a"); sized(u[k], model_.nu, "u");
-      for (size_t j = 0; j < nv; ++j) as[k * nv + j] = a[k][j];
-      for (size_t j = 0; j < nu; ++j) us[k * nu + j] = u[k][j];
-      for (int c = 0; c < nc; ++c) {
-        act[(size_t)k * nc + c] = contact_status[k].isContactActive(c) ? 1 : 0;
-        if (act[(size_t)k * nc + c]) for (int x = 0; x < 3; ++x) fs[((size_t)k * nc + c) * 3 + x] = f[k][c][x];
-      }
-    }
+    const FlatTrajectory t = flatten(q, v, &a, u, &f, &contact_status, nullptr);
     const idocp_cost_t c = cost.native();
     const idocp_constraints_t g = constraints.native();
     if (!rbd_.h) ok(idocp_rbd_create(&model_, 0, &rbd_.h));
     idocp_rbd_objective_t* objective = nullptr;
     ok(idocp_rbd_objective_create(rbd_.h, &c, &g, t0, dt, steps, &objective));
     idocp_rbd_score_io_t io = idocp_rbd_score_io_t();
-    io.q_traj = qs.data(); io.v_traj = vs.data(); io.a_traj = as.data(); io.u_traj = us.data(); io.f_traj = nc > 0 ? fs.data() : nullptr;
+    io.q_traj = t.q.data(); io.v_traj = t.v.data(); io.a_traj = t.a.data(); io.u_traj = t.u.data(); io.f_traj = orNull(t.f);
     io.cost = &total_cost; io.violation = &violation;
-    const int rc = idocp_rbd_score_rollout(rbd_.h, objective, 1, 0, steps, nc > 0 ? act.data() : nullptr, 1, 0, &io);
+    const int rc = idocp_rbd_score_rollout(rbd_.h, objective, 1, 0, steps, orNull(t.active), 1, 0, &io);
     idocp_rbd_objective_destroy(objective);
     ok(rc);
   }
@@ -368,22 +353,15 @@ class Robot {
     if (steps < 1 || (int)q.size() != steps + 1 || (int)v.size() != steps + 1) {
       std::cerr << "invalid size: a trajectory of N stages has N + 1 states q, v and N of u!" << '\n'; std::exit(EXIT_FAILURE);
     }
-    const size_t nq = model_.nq, nv = model_.nv, nu = model_.nu;
-    std::vector<double> qs((steps + 1) * nq), vs((steps + 1) * nv), us(steps * nu), lxs((size_t)(steps + 1) * nx), lus(steps * nu);
-    for (int k = 0; k <= steps; ++k) {
-      sized(q[k], model_.nq, "q"); sized(v[k], model_.nv, "v");
-      for (size_t j = 0; j < nq; ++j) qs[k * nq + j] = q[k][j];
-      for (size_t j = 0; j < nv; ++j) vs[k * nv + j] = v[k][j];
-      if (k == steps) break;
-      sized(u[k], model_.nu, "u");
-      for (size_t j = 0; j < nu; ++j) us[k * nu + j] = u[k][j];
-    }
+    const size_t nu = model_.nu;
+    const FlatTrajectory t = flatten(q, v, nullptr, u, nullptr, nullptr, nullptr);
+    std::vector<double> lxs((size_t)(steps + 1) * nx), lus(steps * nu);
     const idocp_cost_t c = cost.native();
     if (!rbd_.h) ok(idocp_rbd_create(&model_, 0, &rbd_.h));
     idocp_rbd_objective_t* objective = nullptr;
     ok(idocp_rbd_objective_create(rbd_.h, &c, nullptr, t0, dt, steps, &objective));
     idocp_rbd_gradient_io_t io = idocp_rbd_gradient_io_t();
-    io.q_traj = qs.data(); io.v_traj = vs.data(); io.u_traj = us.data(); io.lx_traj = lxs.data(); io.lu_traj = lus.data();
+    io.q_traj = t.q.data(); io.v_traj = t.v.data(); io.u_traj = t.u.data(); io.lx_traj = lxs.data(); io.lu_traj = lus.data();
     const int rc = idocp_rbd_objective_gradients(rbd_.h, objective, 1, 0, steps, 1, &io);
     idocp_rbd_objective_destroy(objective);
     ok(rc);
@@ -401,41 +379,91 @@ class Robot {
                      const std::vector<std::vector<Eigen::Vector3d>>& contact_points, std::vector<Eigen::VectorXd>& q, std::vector<Eigen::VectorXd>& v,
                      std::vector<Eigen::VectorXd>& u, double& total_cost, const double regularization = 1e-6, const double armijo = 1e-4,
                      const int trials = 8) {
-    return ilqrIterateForm(false, cost, t0, dt, time_step, contact_status, contact_points, q, v, u, total_cost, regularization, armijo, trials);
+    return ilqrIterateForm(IlqrChain::Diagonal, cost, nullptr, t0, dt, time_step, contact_status, contact_points, q, v, u, total_cost, nullptr, nullptr,
+                           0.0, regularization, armijo, trials);
   }
 
  private:
-  // the body of ilqrIterate, ilqrIterateGaussNewton, ilqrIterateConstrained, ilqrIterateAugmentedLagrangian and updateMultipliers (with
-  // multipliers: idocp_rbd_score_al and idocp_rbd_ilqr_iterate_al, or, with mu_next, idocp_rbd_ilqr_al_update alone): idocp_rbd_ilqr_iterate or, with gauss_newton,
-  // idocp_rbd_ilqr_iterate_gn or, with constraints, idocp_rbd_ilqr_iterate_penalty (mu its penalty; *sq_violation receives the sq_violation of the
-  // trajectory the call leaves, the trajectory that comes in being scored first: rolled out again for its a and f, then idocp_rbd_score_penalty)
-  template <class CostFunctionT>
-  double ilqrIterateForm(const bool gauss_newton, const CostFunctionT& cost, const double t0, const double dt, const double time_step,
-                         const std::vector<ContactStatus>& contact_status, const std::vector<std::vector<Eigen::Vector3d>>& contact_points,
-                         std::vector<Eigen::VectorXd>& q, std::vector<Eigen::VectorXd>& v, std::vector<Eigen::VectorXd>& u, double& total_cost,
-                         const double regularization, const double armijo, const int trials, const idocp_constraints_t* constraints = nullptr,
-                         const double mu = 0.0, double* sq_violation = nullptr, std::vector<double>* multipliers = nullptr,
-                         const double* mu_next = nullptr, double* multiplier_change = nullptr) {
+  // ONE trajectory as the step-major arrays the C ABI takes with n = 1: q, v of the N + 1 states, u of the N stages and, where the caller has them,
+  // a, f (the active contacts' alone), the contact status and the contact points of the stages.  What is left out (nullptr) stays empty and goes
+  // to the C ABI as NULL (orNull).  The entries are checked here, the lengths of the trajectory by the caller, which knows what it takes.
+  struct FlatTrajectory {
+    std::vector<double> q, v, a, u, f, points;
+    std::vector<int> active;
+  };
+  template <class T> static const T* orNull(const std::vector<T>& x) { return x.empty() ? nullptr : x.data(); }
+  FlatTrajectory flatten(const std::vector<Eigen::VectorXd>& q, const std::vector<Eigen::VectorXd>& v, const std::vector<Eigen::VectorXd>* a,
+                         const std::vector<Eigen::VectorXd>& u, const std::vector<std::vector<Eigen::Vector3d>>* f,
+                         const std::vector<ContactStatus>* contact_status, const std::vector<std::vector<Eigen::Vector3d>>* contact_points) const {
+    const int steps = (int)u.size(), nc = contact_status ? model_.ncontacts : 0;
+    const size_t nq = model_.nq, nv = model_.nv, nu = model_.nu;
+    FlatTrajectory t;
+    t.q.resize((steps + 1) * nq); t.v.resize((steps + 1) * nv); t.u.resize(steps * nu); t.active.assign((size_t)steps * nc, 0);
+    if (a) t.a.resize(steps * nv);
+    if (f) t.f.assign((size_t)steps * 3 * nc, 0.0);
+    if (contact_points) t.points.assign((size_t)steps * 3 * nc, 0.0);
+    for (int k = 0; k <= steps; ++k) {
+      sized(q[k], model_.nq, "q"); sized(v[k], model_.nv, "v");
+      for (size_t j = 0; j < nq; ++j) t.q[k * nq + j] = q[k][j];
+      for (size_t j = 0; j < nv; ++j) t.v[k * nv + j] = v[k][j];
+      if (k == steps) break;
+      if (a) { sized((*a)[k], model_.nv, "a"); for (size_t j = 0; j < nv; ++j) t.a[k * nv + j] = (*a)[k][j]; }
+      sized(u[k], model_.nu, "u");
+      for (size_t j = 0; j < nu; ++j) t.u[k * nu + j] = u[k][j];
+      for (int c = 0; c < nc; ++c) {
+        const size_t at = (size_t)k * nc + c;
+        t.active[at] = (*contact_status)[k].isContactActive(c) ? 1 : 0;
+        if (f && t.active[at]) for (int x = 0; x < 3; ++x) t.f[at * 3 + x] = (*f)[k][c][x];
+        if (contact_points) for (int x = 0; x < 3; ++x) t.points[at * 3 + x] = (*contact_points)[k][c][x];
+      }
+    }
+    return t;
+  }
+  void unflatten(const FlatTrajectory& t, std::vector<Eigen::VectorXd>& q, std::vector<Eigen::VectorXd>& v, std::vector<Eigen::VectorXd>& u) const {
+    const size_t nq = model_.nq, nv = model_.nv, nu = model_.nu;
+    for (size_t k = 0; k < q.size(); ++k) {
+      for (size_t j = 0; j < nq; ++j) q[k][j] = t.q[k * nq + j];
+      for (size_t j = 0; j < nv; ++j) v[k][j] = t.v[k * nv + j];
+      if (k < u.size()) for (size_t j = 0; j < nu; ++j) u[k][j] = t.u[k * nu + j];
+    }
+  }
+  // what the iLQR methods and updateMultipliers take: the rollout of u under contact_status with the contacts held at contact_points
+  void rolloutSized(const std::vector<Eigen::VectorXd>& q, const std::vector<Eigen::VectorXd>& v, const std::vector<Eigen::VectorXd>& u,
+                    const std::vector<ContactStatus>& contact_status, const std::vector<std::vector<Eigen::Vector3d>>& contact_points) const {
     const int steps = (int)u.size(), nc = model_.ncontacts;
     if (steps < 1 || (int)q.size() != steps + 1 || (int)v.size() != steps + 1 ||
         (nc > 0 && ((int)contact_status.size() != steps || (int)contact_points.size() != steps))) {
       std::cerr << "invalid size: a trajectory of N stages has N + 1 states q, v and N of u, contact_status and contact_points!" << '\n'; std::exit(EXIT_FAILURE);
     }
-    const size_t nq = model_.nq, nv = model_.nv, nu = model_.nu;
-    std::vector<double> qs((steps + 1) * nq), vs((steps + 1) * nv), us(steps * nu), pts((size_t)steps * 3 * nc, 0.0);
-    std::vector<int> act((size_t)steps * nc, 0);
-    for (int k = 0; k <= steps; ++k) {
-      sized(q[k], model_.nq, "q"); sized(v[k], model_.nv, "v");
-      for (size_t j = 0; j < nq; ++j) qs[k * nq + j] = q[k][j];
-      for (size_t j = 0; j < nv; ++j) vs[k * nv + j] = v[k][j];
-      if (k == steps) break;
-      sized(u[k], model_.nu, "u");
-      for (size_t j = 0; j < nu; ++j) us[k * nu + j] = u[k][j];
-      for (int c = 0; c < nc; ++c) {
-        act[(size_t)k * nc + c] = contact_status[k].isContactActive(c) ? 1 : 0;
-        for (int x = 0; x < 3; ++x) pts[((size_t)k * nc + c) * 3 + x] = contact_points[k][c][x];
-      }
-    }
+  }
+  // a and f of the stages of a flattened trajectory, which the constraint rows read: from a rollout of its own torques, its q, v, u as given
+  int stageAccelerations(const FlatTrajectory& t, const double time_step, const double dt, std::vector<double>& a, std::vector<double>& f) const {
+    const int steps = (int)(t.u.size() / model_.nu);
+    std::vector<double> tq(t.q), tv(t.v);
+    a.resize((size_t)steps * model_.nv); f.resize((size_t)steps * 3 * model_.ncontacts);
+    return idocp_rbd_rollout(rbd_.h, 1, steps, orNull(t.active), time_step, dt, t.u.data(), orNull(t.points), tq.data(), tv.data(), a.data(),
+                             f.empty() ? nullptr : f.data(), 0);
+  }
+  // the augmented-Lagrangian forms: multipliers [steps][L], all zeros where the caller's vector has another size
+  static void sizeMultipliers(const idocp_rbd_objective_t* objective, const int steps, std::vector<double>& multipliers) {
+    const size_t rows = (size_t)steps * idocp_rbd_objective_multiplier_rows(objective);
+    if (multipliers.size() != rows) multipliers.assign(rows, 0.0);
+  }
+  // which chain of include/idocp_hip.h an iteration runs: idocp_rbd_ilqr_iterate, _gn, _penalty or _al
+  enum class IlqrChain { Diagonal, GaussNewton, Penalty, AugmentedLagrangian };
+  // The body of ilqrIterate, ilqrIterateGaussNewton, ilqrIterateConstrained and ilqrIterateAugmentedLagrangian.  The last two take the constraints,
+  // the weight mu, the multipliers (AugmentedLagrangian alone) and *violation_left, which receives the sq_violation (sq_shifted) of the trajectory the
+  // call leaves; the trajectory that comes in is scored first: rolled out again for its a and f, then idocp_rbd_score_penalty (idocp_rbd_score_al).
+  template <class CostFunctionT>
+  double ilqrIterateForm(const IlqrChain chain, const CostFunctionT& cost, const idocp_constraints_t* constraints, const double t0, const double dt,
+                         const double time_step, const std::vector<ContactStatus>& contact_status,
+                         const std::vector<std::vector<Eigen::Vector3d>>& contact_points, std::vector<Eigen::VectorXd>& q,
+                         std::vector<Eigen::VectorXd>& v, std::vector<Eigen::VectorXd>& u, double& total_cost, double* violation_left,
+                         std::vector<double>* multipliers, const double mu, const double regularization, const double armijo, const int trials) {
+    rolloutSized(q, v, u, contact_status, contact_points);
+    const int steps = (int)u.size();
+    const bool constrained = chain == IlqrChain::Penalty || chain == IlqrChain::AugmentedLagrangian;
+    FlatTrajectory t = flatten(q, v, nullptr, u, nullptr, &contact_status, &contact_points);
     const idocp_cost_t c = cost.native();
     if (!rbd_.h) ok(idocp_rbd_create(&model_, 0, &rbd_.h));
     idocp_rbd_objective_t* objective = nullptr;
@@ -443,45 +471,31 @@ class Robot {
     double violation = 0.0, alpha = 0.0, expected[2] = {0.0, 0.0};
     int status = -1;
     idocp_rbd_ilqr_io_t io = idocp_rbd_ilqr_io_t();
-    io.q_traj = qs.data(); io.v_traj = vs.data(); io.u_traj = us.data(); io.cost = &total_cost; io.violation = &violation;
-    io.regularization = regularization; io.armijo = armijo; io.shrink = 0.5; io.alpha_min = 0.0; io.penalty = constraints ? mu : 0.0; io.trials = trials;
+    io.q_traj = t.q.data(); io.v_traj = t.v.data(); io.u_traj = t.u.data(); io.cost = &total_cost; io.violation = &violation;
+    io.regularization = regularization; io.armijo = armijo; io.shrink = 0.5; io.alpha_min = 0.0; io.penalty = constrained ? mu : 0.0; io.trials = trials;
     io.alpha_accepted = &alpha; io.lqr_status = &status; io.expected = expected;
-    const int* const actp = nc > 0 ? act.data() : nullptr;
-    const double* const ptsp = nc > 0 ? pts.data() : nullptr;
+    const int* const act = orNull(t.active);
+    const double* const pts = orNull(t.points);
     int rc = IDOCP_OK;
-    if (constraints) {
-      // sq_violation of the trajectory that comes in: its a and f from a rollout of its own torques, its q, v, u as given
-      std::vector<double> tq(qs), tv(vs), ta((size_t)steps * nv), tf((size_t)steps * 3 * nc);
-      rc = idocp_rbd_rollout(rbd_.h, 1, steps, actp, time_step, dt, us.data(), ptsp, tq.data(), tv.data(), ta.data(), nc > 0 ? tf.data() : nullptr, 0);
-      const double* const tfp = nc > 0 ? tf.data() : nullptr;
-      if (multipliers) {
-        // the augmented-Lagrangian forms: multipliers [steps][L], all zeros where the caller's vector has another size
-        const size_t rows = (size_t)steps * idocp_rbd_objective_multiplier_rows(objective);
-        if (multipliers->size() != rows) multipliers->assign(rows, 0.0);
-        if (mu_next) {      // updateMultipliers: alpha carries the infeasibility back
-          if (rc == IDOCP_OK)
-            rc = idocp_rbd_ilqr_al_update(rbd_.h, objective, 1, steps, actp, qs.data(), vs.data(), us.data(), ta.data(), tfp, mu, *mu_next, multipliers->data(),
-                                          &violation, &alpha, multiplier_change);
-        } else {
-          if (rc == IDOCP_OK)
-            rc = idocp_rbd_score_al(rbd_.h, objective, 1, 0, steps, actp, 0, qs.data(), vs.data(), us.data(), ta.data(), tfp, mu, multipliers->data(), &violation);
-          if (rc == IDOCP_OK) rc = idocp_rbd_ilqr_iterate_al(rbd_.h, objective, 1, steps, actp, time_step, dt, ptsp, &io, multipliers->data(), 0);
-        }
+    if (constrained) {
+      std::vector<double> ta, tf;
+      rc = stageAccelerations(t, time_step, dt, ta, tf);
+      if (chain == IlqrChain::AugmentedLagrangian) {
+        sizeMultipliers(objective, steps, *multipliers);
+        if (rc == IDOCP_OK)
+          rc = idocp_rbd_score_al(rbd_.h, objective, 1, 0, steps, act, 0, t.q.data(), t.v.data(), t.u.data(), ta.data(), orNull(tf), mu, multipliers->data(), &violation);
+        if (rc == IDOCP_OK) rc = idocp_rbd_ilqr_iterate_al(rbd_.h, objective, 1, steps, act, time_step, dt, pts, &io, multipliers->data(), 0);
       } else {
-        if (rc == IDOCP_OK) rc = idocp_rbd_score_penalty(rbd_.h, objective, 1, 0, steps, actp, 0, qs.data(), vs.data(), us.data(), ta.data(), tfp, &violation);
-        if (rc == IDOCP_OK) rc = idocp_rbd_ilqr_iterate_penalty(rbd_.h, objective, 1, steps, actp, time_step, dt, ptsp, &io, 0);
+        if (rc == IDOCP_OK) rc = idocp_rbd_score_penalty(rbd_.h, objective, 1, 0, steps, act, 0, t.q.data(), t.v.data(), t.u.data(), ta.data(), orNull(tf), &violation);
+        if (rc == IDOCP_OK) rc = idocp_rbd_ilqr_iterate_penalty(rbd_.h, objective, 1, steps, act, time_step, dt, pts, &io, 0);
       }
-      if (sq_violation) *sq_violation = violation;
+      *violation_left = violation;
     } else {
-      rc = (gauss_newton ? idocp_rbd_ilqr_iterate_gn : idocp_rbd_ilqr_iterate)(rbd_.h, objective, 1, steps, actp, time_step, dt, ptsp, &io, 0);
+      rc = (chain == IlqrChain::GaussNewton ? idocp_rbd_ilqr_iterate_gn : idocp_rbd_ilqr_iterate)(rbd_.h, objective, 1, steps, act, time_step, dt, pts, &io, 0);
     }
     idocp_rbd_objective_destroy(objective);
     ok(rc);
-    for (int k = 0; k <= steps; ++k) {
-      for (size_t j = 0; j < nq; ++j) q[k][j] = qs[k * nq + j];
-      for (size_t j = 0; j < nv; ++j) v[k][j] = vs[k * nv + j];
-      if (k < steps) for (size_t j = 0; j < nu; ++j) u[k][j] = us[k * nu + j];
-    }
+    unflatten(t, q, v, u);
     return alpha;
   }
 
@@ -493,7 +507,8 @@ class Robot {
                                 const std::vector<ContactStatus>& contact_status, const std::vector<std::vector<Eigen::Vector3d>>& contact_points,
                                 std::vector<Eigen::VectorXd>& q, std::vector<Eigen::VectorXd>& v, std::vector<Eigen::VectorXd>& u, double& total_cost,
                                 const double regularization = 1e-6, const double armijo = 1e-4, const int trials = 8) {
-    return ilqrIterateForm(true, cost, t0, dt, time_step, contact_status, contact_points, q, v, u, total_cost, regularization, armijo, trials);
+    return ilqrIterateForm(IlqrChain::GaussNewton, cost, nullptr, t0, dt, time_step, contact_status, contact_points, q, v, u, total_cost, nullptr, nullptr,
+                           0.0, regularization, armijo, trials);
   }
   // The same iteration under the cost AND the constraints, an ADDITION: idocp_rbd_ilqr_iterate_penalty with n = 1 -- the rows the score sums into its
   // violation enter as a squared-hinge penalty with the weight mu (idocp_hip.h has the definition).  total_cost is the cost of the trajectory that
@@ -505,8 +520,8 @@ class Robot {
                                 double& sq_violation, const double mu, const double regularization = 1e-6, const double armijo = 1e-4,
                                 const int trials = 8) {
     const idocp_constraints_t g = constraints.native();
-    return ilqrIterateForm(true, cost, t0, dt, time_step, contact_status, contact_points, q, v, u, total_cost, regularization, armijo, trials, &g, mu,
-                           &sq_violation);
+    return ilqrIterateForm(IlqrChain::Penalty, cost, &g, t0, dt, time_step, contact_status, contact_points, q, v, u, total_cost, &sq_violation, nullptr, mu,
+                           regularization, armijo, trials);
   }
   // The augmented-Lagrangian iteration, an ADDITION: idocp_rbd_ilqr_iterate_al with n = 1 at the penalty weight mu > 0 under the multipliers
   // [N][L], L = 4 dimu + (cone rows) * contacts (idocp_hip.h has the layout; a vector of another size is replaced by zeros).  sq_shifted receives
@@ -518,8 +533,8 @@ class Robot {
                                         double& sq_shifted, std::vector<double>& multipliers, const double mu, const double regularization = 1e-6,
                                         const double armijo = 1e-4, const int trials = 8) {
     const idocp_constraints_t g = constraints.native();
-    return ilqrIterateForm(true, cost, t0, dt, time_step, contact_status, contact_points, q, v, u, total_cost, regularization, armijo, trials, &g, mu,
-                           &sq_shifted, &multipliers);
+    return ilqrIterateForm(IlqrChain::AugmentedLagrangian, cost, &g, t0, dt, time_step, contact_status, contact_points, q, v, u, total_cost, &sq_shifted,
+                           &multipliers, mu, regularization, armijo, trials);
   }
   // The outer step, an ADDITION: idocp_rbd_ilqr_al_update with n = 1 -- the multipliers become mu times the shifted rows of the trajectory, in place;
   // sq_shifted receives the shifted squared violation under the new multipliers and mu_next.  Returns the infeasibility (the largest unshifted row);
@@ -529,10 +544,24 @@ class Robot {
                            const std::vector<ContactStatus>& contact_status, const std::vector<std::vector<Eigen::Vector3d>>& contact_points,
                            std::vector<Eigen::VectorXd>& q, std::vector<Eigen::VectorXd>& v, std::vector<Eigen::VectorXd>& u,
                            std::vector<double>& multipliers, const double mu, const double mu_next, double& sq_shifted, double& multiplier_change) {
+    rolloutSized(q, v, u, contact_status, contact_points);
+    const int steps = (int)u.size();
+    const FlatTrajectory t = flatten(q, v, nullptr, u, nullptr, &contact_status, &contact_points);
+    const idocp_cost_t c = cost.native();
     const idocp_constraints_t g = constraints.native();
-    double unused_cost = 0.0;
-    return ilqrIterateForm(true, cost, t0, dt, time_step, contact_status, contact_points, q, v, u, unused_cost, 1e-6, 1e-4, 1, &g, mu, &sq_shifted,
-                           &multipliers, &mu_next, &multiplier_change);
+    if (!rbd_.h) ok(idocp_rbd_create(&model_, 0, &rbd_.h));
+    idocp_rbd_objective_t* objective = nullptr;
+    ok(idocp_rbd_objective_create(rbd_.h, &c, &g, t0, dt, steps, &objective));
+    std::vector<double> ta, tf;
+    double infeasibility = 0.0;
+    int rc = stageAccelerations(t, time_step, dt, ta, tf);
+    sizeMultipliers(objective, steps, multipliers);
+    if (rc == IDOCP_OK)
+      rc = idocp_rbd_ilqr_al_update(rbd_.h, objective, 1, steps, orNull(t.active), t.q.data(), t.v.data(), t.u.data(), ta.data(), orNull(tf), mu, mu_next,
+                                    multipliers.data(), &sq_shifted, &infeasibility, &multiplier_change);
+    idocp_rbd_objective_destroy(objective);
+    ok(rc);
+    return infeasibility;
   }
   // Robot::framePosition / frameRotation / framePlacement (robot.hxx:206-233): of any frame of the URDF (pinocchio's frame numbering, as the
   // contact frames and the task-space costs use it), at the configuration of the last updateFrameKinematics / updateKinematics
