@@ -35,6 +35,44 @@ static double maxDiff(const ex::Vec& a, const ex::Vec& b) {
   return m;
 }
 
+// q, u and lmd of one stage, end to end
+template <typename S>
+static ex::Vec stageProbe(const S& solver, const int stage) {
+  const idocp::SplitSolution& s = solver.getSolution(stage);
+  ex::Vec p(s.q.size() + s.u.size() + s.lmd.size());
+  int k = 0;
+  for (const ex::Vec* part : {&s.q, &s.u, &s.lmd}) for (int j = 0; j < part->size(); ++j) p[k++] = (*part)[j];
+  return p;
+}
+
+// Copy and move of LIVE solvers beyond the copy constructor: self-assignment, copy and move assignment onto a live solver, a moved-from solver
+// that is assigned again.  `start` and `other` are live solvers in different states; whatever ends up holding the state of `start` must take
+// the step that a plain copy of `start` takes, bit for bit.
+template <typename S, typename Step>
+static int liveSolverSemantics(const S& start, const S& other, Step step) {
+  S twin(start);
+  step(twin);
+  const ex::Vec want = stageProbe(twin, 3);
+  REQUIRE(maxDiff(stageProbe(other, 3), stageProbe(start, 3)) > 0.0 && maxDiff(want, stageProbe(start, 3)) > 0.0);
+  S a(start);
+  S& self = a;
+  a = self;                                           // a = a
+  step(a);
+  REQUIRE(maxDiff(stageProbe(a, 3), want) == 0.0);
+  S b(other);
+  b = start;                                          // copy assignment onto a live solver
+  step(b);
+  REQUIRE(maxDiff(stageProbe(b, 3), want) == 0.0);
+  S c(other), from(start);
+  c = std::move(from);                                // move assignment onto a live solver
+  step(c);
+  REQUIRE(maxDiff(stageProbe(c, 3), want) == 0.0);
+  from = start;                                       // the moved-from solver, assigned a live one
+  step(from);
+  REQUIRE(maxDiff(stageProbe(from, 3), want) == 0.0);
+  return 0;
+}
+
 int main(int argc, char** argv) {
   if (emptySolverSemantics<idocp::OCPSolver>() || emptySolverSemantics<idocp::UnOCPSolver>() ||
       emptySolverSemantics<idocp::ParNMPCSolver>() || emptySolverSemantics<idocp::UnParNMPCSolver>()) return 1;
@@ -126,6 +164,11 @@ int main(int argc, char** argv) {
       idocp::ParNMPCSolver opn2(opn);
       opn.updateSolution(0.0, q, v); opn2.updateSolution(0.0, q, v);
       REQUIRE(maxDiff(opn2.getSolution(3).u, opn.getSolution(3).u) == 0.0);
+      idocp::OCPSolver oc_other(oc);                                            // (the bound solvers: the fixed-base solver is copied and moved with them)
+      oc_other.updateSolution(0.0, q, v);
+      if (liveSolverSemantics(oc, oc_other, [&](idocp::OCPSolver& s) { s.updateSolution(0.0, q, v); })) return 1;
+      opn2.updateSolution(0.0, q, v);
+      if (liveSolverSemantics(opn, opn2, [&](idocp::ParNMPCSolver& s) { s.updateSolution(0.0, q, v); })) return 1;
       std::cout << "contact-path solvers on the fixed-base robot: ok" << std::endl;
     }
     {  // the cost function is SHARED with the driver (unocp_solver.hpp: shared_ptr members): a reference moved after construction takes effect
@@ -162,6 +205,13 @@ int main(int argc, char** argv) {
       for (idocp::UnParNMPCSolver* sp : {&early_pn, &late_pn}) { sp->setSolution("q", q); sp->setSolution("v", v); sp->initBackwardCorrection(0.0); sp->updateSolution(0.0, q, v); }
       REQUIRE(maxDiff(early_pn.getSolution(4).a, late_pn.getSolution(4).a) == 0.0);
       std::cout << "shared cost function: ok" << std::endl;
+    }
+    {  // assignment and move of live solvers
+      idocp::UnOCPSolver other(solver);
+      other.updateSolution(0.0, q, v);
+      if (liveSolverSemantics(solver, other, [&](idocp::UnOCPSolver& s) { s.updateSolution(0.0, q, v); })) return 1;
+      pn2.updateSolution(0.0, q, v);
+      if (liveSolverSemantics(pn, pn2, [&](idocp::UnParNMPCSolver& s) { s.updateSolution(0.0, q, v); })) return 1;
     }
     std::cout << "fixed-base solvers: ok" << std::endl;
     {  // Robot::integrateConfiguration (both overloads) / subtractConfiguration / normalizeConfiguration on the fixed-base arm (robot.hpp:82-147)
@@ -255,6 +305,35 @@ int main(int argc, char** argv) {
     REQUIRE(maxDiff(s0.beta, cs.getSolution("beta")[0]) == 0.0 && maxDiff(s0.nu_passive, cs.getSolution("nu_passive")[0]) == 0.0);
     REQUIRE((int)s0.f.size() == robot.maxPointContacts() && s0.f[1][2] == s0.f_stack()[5]);
     REQUIRE(maxDiff(cs.getSolution(N).v, cs.getSolution("v")[N]) == 0.0);
+    {  // assignment and move of live solvers
+      idocp::OCPSolver other(solver);
+      other.updateSolution(0.0, stand, v);
+      if (liveSolverSemantics(solver, other, [&](idocp::OCPSolver& s) { s.updateSolution(0.0, stand, v); })) return 1;
+    }
+    {  // a live ParNMPCSolver on the floating base (parnmpc_solver.hpp:103): the const getters agree, stage by stage
+      idocp::ParNMPCSolver pn(robot, cost, ex::jointLimits(robot, 0.7, false, true), 0.25, N);
+      standing.install(pn, robot);
+      ex::restingGuess(pn, robot, stand);
+      pn.initConstraints(0.0);
+      pn.initBackwardCorrection(0.0);
+      pn.updateSolution(0.0, stand, v);
+      const idocp::ParNMPCSolver& cpn = pn;
+      const std::vector<ex::Vec> us = cpn.getSolution("u"), qs = cpn.getSolution("q"), fs = cpn.getSolution("f"), nus = cpn.getSolution("nu_passive");
+      REQUIRE((int)us.size() == N && (int)qs.size() == N && (int)fs.size() == N);
+      for (int i = 0; i < N; ++i) {
+        const idocp::SplitSolution& si = cpn.getSolution(i);
+        REQUIRE(maxDiff(si.u, us[i]) == 0.0 && maxDiff(si.q, qs[i]) == 0.0 && maxDiff(si.f_stack(), fs[i]) == 0.0);
+      }
+      // "nu_passive" is dim_passive() wide, as in OCPSolver
+      REQUIRE((int)nus.size() == N);
+      for (int i = 0; i < N; ++i) REQUIRE((int)nus[i].size() == robot.dim_passive() && maxDiff(nus[i], cpn.getSolution(i).nu_passive) == 0.0);
+      idocp::ParNMPCSolver pn2(pn);
+      pn.updateSolution(0.0, stand, v); pn2.updateSolution(0.0, stand, v);
+      REQUIRE(maxDiff(stageProbe(pn2, 3), stageProbe(pn, 3)) == 0.0 && maxDiff(pn2.getSolution(N - 1).lmd, pn.getSolution(N - 1).lmd) == 0.0);
+      pn2.updateSolution(0.0, stand, v);
+      if (liveSolverSemantics(pn, pn2, [&](idocp::ParNMPCSolver& s) { s.updateSolution(0.0, stand, v); })) return 1;
+      std::cout << "floating-base ParNMPCSolver: ok" << std::endl;
+    }
     {  // the shared cost function on the floating base (ocp_solver.hpp:37-39): weights changed through the component after construction
        // reach the solver at its next call -- the step of a solver constructed with those weights
       auto pc1 = std::make_shared<idocp::ConfigurationSpaceCost>(robot), pc2 = std::make_shared<idocp::ConfigurationSpaceCost>(robot);

@@ -266,7 +266,8 @@ def test_anymal_trotting_parnmpc_example_matches_oracle():
 
 def test_facade_surface_const_getters_copies_and_default_constructors(tmp_path):
     # ocp_solver.hpp:44,97 and its siblings: `getSolution(stage) const` (one device-to-host copy, idocp_*_get_split_solution) equals
-    # the field getters; deep copies of live solvers continue identically; default-constructed solvers can be assigned
+    # the field getters; deep copies of live solvers continue identically; default-constructed solvers can be assigned; self-assignment, copy and
+    # move assignment onto live solvers of all four classes (include/idocp/detail/solver_core.hpp)
     exe = str(tmp_path / "facade_surface")
     r = subprocess.run(["g++", "-O1", "-std=c++17", "-I" + os.path.join(ROOT, "include"), os.path.join(ROOT, "tests/cpp/facade_surface.cpp"),
                         "-L" + os.path.join(ROOT, "idocp_amd/lib"), "-lidocp_hip", "-Wl,-rpath," + os.path.join(ROOT, "idocp_amd/lib"), "-o", exe],
@@ -275,3 +276,4 @@ def test_facade_surface_const_getters_copies_and_default_constructors(tmp_path):
     r = subprocess.run([exe, IIWA_URDF, ANYMAL_URDF], capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, (r.stdout + r.stderr)[-3000:]
     assert "fixed-base solvers: ok" in r.stdout and "shared cost function: ok" in r.stdout and "contact-path solvers on the fixed-base robot: ok" in r.stdout and "floating-base solver: ok" in r.stdout and "receding horizon through the facade: ok" in r.stdout
+    assert "floating-base ParNMPCSolver: ok" in r.stdout
