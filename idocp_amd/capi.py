@@ -493,6 +493,9 @@ def _proto(lib):
         ("idocp_ocp_get_contact_dynamics_chain", [vp, ci, ci, c_double_p, c_double_p, c_double_p]),
         ("idocp_ocp_get_ext_terms", [vp, ci, ci] + [c_double_p] * 9),
         ("idocp_ocp_set_lqr_stage", [vp, ci, ci] + [c_double_p] * 11),
+        ("idocp_ocp_set_lqr_stage_chain", [vp, ci, ci] + [c_double_p] * 11),
+        ("idocp_ocp_set_switching_constraint", [vp, ci, ci, ci] + [c_double_p] * 3),
+        ("idocp_ocp_get_switching_policy", [vp, ci, ci, c_double_p, c_double_p]),
         ("idocp_parnmpc_get_new_solution_chain", [vp, C.c_char_p, ci, c_double_p]),
         ("idocp_parnmpc_get_aux_mat_chain", [vp, ci, c_double_p]),
         ("idocp_comm_get_unique_id", [vp]),

@@ -1256,31 +1256,121 @@ int idocp_ocp_get_profile(idocp_ocp_t* h, long long* out, int n) {
 // The inverse of idocp_ocp_get_lqr_stage, for every instance: the condensed LQR stage the backward sweep reads (its kkt record), so that a test can run
 // the sweep alone on a problem whose answer it knows (tests/test_golden_riccati.py: the dense KKT solution of a random LQR problem in the reference's
 // block structure).  Column-major blocks; terminal != 0: Qxx and lx only.
-int idocp_ocp_set_lqr_stage(idocp_ocp_t* h, int stage, int terminal, const double* Qxx, const double* Qxu, const double* Quu, const double* Fqq6,
-                            const double* Fqv6, const double* Fvq, const double* Fvv, const double* Fvu, const double* lx, const double* lu,
-                            const double* Fx) {
-  if (!h || !Qxx || !lx || stage < 0 || stage > h->plan.Ngrid) return IDOCP_E_ARG;
-  if (!terminal && (!Qxu || !Quu || !Fqq6 || !Fqv6 || !Fvq || !Fvv || !Fvu || !lu || !Fx)) return IDOCP_E_ARG;
+// The head of the three test-only entries addressed by chain position: the refusals they share, each under the caller's name.
+static int chainPositionO(idocp_ocp_t* h, const char* who, int instance, int lowest_instance, int position, bool needs_switch, const OcpNode** nd) {
+  const std::string name(who);
+  if (!h) { set_last_error(name + ": null handle"); return IDOCP_E_ARG; }
+  if (h->parnmpc) { set_last_error(name + ": a ParNMPC handle has no Riccati sweep to inject into"); return IDOCP_E_ARG; }
   int rc = enterO(h); if (rc) return rc;
+  if ((rc = ensureDiscretized(h))) return rc;
+  if (instance < lowest_instance || instance >= h->batch) { set_last_error(name + ": instance out of range"); return IDOCP_E_ARG; }
+  if (position < 0 || position >= h->M()) { set_last_error(name + ": position out of range"); return IDOCP_E_ARG; }
+  *nd = &h->plan.nodes[position];
+  if (needs_switch && (*nd)->sw_dimi == 0) { set_last_error(name + ": no switching constraint at position " + std::to_string(position)); return IDOCP_E_ARG; }
+  return IDOCP_OK;
+}
+
+// The inverse of idocp_ocp_get_lqr_stage by chain position: the condensed LQR stage the sweeps read (the kkt record of the node's slot), of one
+// instance or of all (instance == -1), so that a test can run a sweep alone on a problem whose answer it knows (tests/riccati_chain_cases.py: the
+// dense KKT solution of a random LQ problem along a chain with events).  Column-major blocks.  Terminal node: Qxx and lx only.  Impulse node: no
+// control -- the record gets what K5b leaves there (Quu = I, Qxu = 0, Fvu = 0, lu = 0, Fqv6 = 0) and the caller's Qxu, Quu, Fqv6, Fvu, lu are not read.
+int idocp_ocp_set_lqr_stage_chain(idocp_ocp_t* h, int instance, int position, const double* Qxx, const double* Qxu, const double* Quu,
+                                  const double* Fqq6, const double* Fqv6, const double* Fvq, const double* Fvv, const double* Fvu, const double* lx,
+                                  const double* lu, const double* Fx) {
+  const char* who = "idocp_ocp_set_lqr_stage_chain";
+  const OcpNode* nd = nullptr;
+  int rc = chainPositionO(h, who, instance, -1, position, false, &nd); if (rc) return rc;
+  const bool terminal = nd->kind == 4, impulse = nd->kind == 1;
+  if (!Qxx || !lx || (!terminal && (!Fqq6 || !Fvq || !Fvv || !Fx)) || (!terminal && !impulse && (!Qxu || !Quu || !Fqv6 || !Fvu || !lu))) {
+    set_last_error(std::string(who) + ": a block this node kind needs is null");
+    return IDOCP_E_ARG;
+  }
   const int nv = DQ::NV, nx = DQ::NX, nu = DQ::NU;
   std::vector<double> k(LQ::KKT, 0.0);
   for (int c = 0; c < nx; ++c) for (int r = 0; r <= c; ++r) k[LQ::K_QXX + LQ::xsym(r, c)] = Qxx[c * nx + r];
   std::memcpy(&k[LQ::K_LX], lx, sizeof(double) * nx);
   if (!terminal) {
-    std::memcpy(&k[LQ::K_QXU], Qxu, sizeof(double) * nx * nu);
-    std::memcpy(&k[LQ::K_QUU], Quu, sizeof(double) * nu * nu);
     std::memcpy(&k[LQ::K_FQQ], Fqq6, sizeof(double) * 36);
-    std::memcpy(&k[LQ::K_FQV], Fqv6, sizeof(double) * 36);
     std::memcpy(&k[LQ::K_FVQ], Fvq, sizeof(double) * nv * nv);
     std::memcpy(&k[LQ::K_FVV], Fvv, sizeof(double) * nv * nv);
-    std::memcpy(&k[LQ::K_FVU], Fvu, sizeof(double) * nv * nu);
-    std::memcpy(&k[LQ::K_LU], lu, sizeof(double) * nu);
     std::memcpy(&k[LQ::K_FX], Fx, sizeof(double) * nx);
+    if (impulse) {
+      for (int j = 0; j < nu; ++j) k[LQ::K_QUU + j + nu * j] = 1.0;
+    } else {
+      std::memcpy(&k[LQ::K_QXU], Qxu, sizeof(double) * nx * nu);
+      std::memcpy(&k[LQ::K_QUU], Quu, sizeof(double) * nu * nu);
+      std::memcpy(&k[LQ::K_FQV], Fqv6, sizeof(double) * 36);
+      std::memcpy(&k[LQ::K_FVU], Fvu, sizeof(double) * nv * nu);
+      std::memcpy(&k[LQ::K_LU], lu, sizeof(double) * nu);
+    }
   }
   HIP_TRY(hipStreamSynchronize(h->stream));
-  for (long b = 0; b < h->batch; ++b)
-    HIP_TRY(hipMemcpy(h->B.kkt + ((size_t)b * h->NS + stage) * LQ::KKT, k.data(), k.size() * sizeof(double), hipMemcpyHostToDevice));
+  for (long b = instance < 0 ? 0 : instance; b < (instance < 0 ? h->batch : instance + 1); ++b)
+    HIP_TRY(hipMemcpy(h->B.kkt + ((size_t)b * h->NS + nd->slot) * LQ::KKT, k.data(), k.size() * sizeof(double), hipMemcpyHostToDevice));
   return IDOCP_OK;
+}
+
+// The grid-stage form of the above, for every instance (tests/test_golden_riccati.py): stage = grid index, terminal != 0 for stage N.
+int idocp_ocp_set_lqr_stage(idocp_ocp_t* h, int stage, int terminal, const double* Qxx, const double* Qxu, const double* Quu, const double* Fqq6,
+                            const double* Fqv6, const double* Fvq, const double* Fvv, const double* Fvu, const double* lx, const double* lu,
+                            const double* Fx) {
+  if (!h || !Qxx || !lx || stage < 0) return IDOCP_E_ARG;
+  if (!terminal && (!Qxu || !Quu || !Fqq6 || !Fqv6 || !Fvq || !Fvv || !Fvu || !lu || !Fx)) return IDOCP_E_ARG;
+  int rc = enterO(h); if (rc) return rc;
+  if ((rc = ensureDiscretized(h))) return rc;
+  for (int p = 0; p < h->M(); ++p) {
+    const OcpNode& nd = h->plan.nodes[p];
+    if (nd.slot != stage || (nd.kind != 0 && nd.kind != 4)) continue;
+    if ((nd.kind == 4) != (terminal != 0)) return IDOCP_E_ARG;
+    return idocp_ocp_set_lqr_stage_chain(h, -1, p, Qxx, Qxu, Quu, Fqq6, Fqv6, Fvq, Fvv, Fvu, lx, lu, Fx);
+  }
+  return IDOCP_E_ARG;
+}
+
+// The swc record of one chain position as the sweeps read it: P (dimi), Phix (dimi x NX), Phiu (dimi x NU), column-major with leading dimension dimi,
+// into the record's leading dimension NF; of one instance or of all (instance == -1).  Rows dimi .. NF - 1 of the record are left as they are, which
+// is how ocp_switch_kernel.hip and the condensation leave them: both write rows 0 .. dimi - 1 only, so those rows hold the zeros of the allocation or
+// what an earlier, taller constraint wrote there, and the sweep must not read them.  Phia (consumed by the condensation) is not touched.
+int idocp_ocp_set_switching_constraint(idocp_ocp_t* h, int instance, int position, int dimi, const double* P, const double* Phix, const double* Phiu) {
+  const char* who = "idocp_ocp_set_switching_constraint";
+  const OcpNode* nd = nullptr;
+  int rc = chainPositionO(h, who, instance, -1, position, true, &nd); if (rc) return rc;
+  if (dimi != nd->sw_dimi) {
+    set_last_error(std::string(who) + ": dimi " + std::to_string(dimi) + " is not the " + std::to_string(nd->sw_dimi) + " rows of the node");
+    return IDOCP_E_ARG;
+  }
+  if (!P || !Phix || !Phiu) { set_last_error(std::string(who) + ": null block"); return IDOCP_E_ARG; }
+  const int nx = DQ::NX, nu = DQ::NU, nf = DQ::NF;
+  std::vector<double> w(LQ::SWC);
+  HIP_TRY(hipStreamSynchronize(h->stream));
+  for (long b = instance < 0 ? 0 : instance; b < (instance < 0 ? h->batch : instance + 1); ++b) {
+    double* rec = h->B.swc + ((size_t)b * h->NS + nd->slot) * LQ::SWC;
+    HIP_TRY(hipMemcpy(w.data(), rec, w.size() * sizeof(double), hipMemcpyDeviceToHost));
+    for (int j = 0; j < dimi; ++j) {
+      w[LQ::W_P + j] = P[j];
+      for (int c = 0; c < nx; ++c) w[LQ::W_PHIX + j + nf * c] = Phix[j + dimi * c];
+      for (int c = 0; c < nu; ++c) w[LQ::W_PHIU + j + nf * c] = Phiu[j + dimi * c];
+    }
+    HIP_TRY(hipMemcpy(rec, w.data(), w.size() * sizeof(double), hipMemcpyHostToDevice));
+  }
+  return IDOCP_OK;
+}
+
+// The multiplier policy dxi = M dx + m the backward sweep wrote into the swc record of a chain position: M (dimi x NX, column-major, leading
+// dimension dimi) and m (dimi).  Returns dimi, or a negative error code.
+int idocp_ocp_get_switching_policy(idocp_ocp_t* h, int instance, int position, double* M, double* m) {
+  const char* who = "idocp_ocp_get_switching_policy";
+  const OcpNode* nd = nullptr;
+  int rc = chainPositionO(h, who, instance, 0, position, true, &nd); if (rc) return rc;
+  const int dimi = nd->sw_dimi, nx = DQ::NX, nf = DQ::NF;
+  std::vector<double> w(LQ::SWC);
+  HIP_TRY(hipMemcpyAsync(w.data(), h->B.swc + ((size_t)instance * h->NS + nd->slot) * LQ::SWC, w.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  HIP_TRY(hipStreamSynchronize(h->stream));
+  for (int j = 0; j < dimi; ++j) {
+    if (M) for (int c = 0; c < nx; ++c) M[j + dimi * c] = w[LQ::W_M + j + nf * c];
+    if (m) m[j] = w[LQ::W_m + j];
+  }
+  return dimi;
 }
 
 // ContactDynamicsData of a grid stage as the condensation kernel left it (contact_dynamics_data.hxx:8-29: MJtJinv, MJtJinv_dIDCdqv, MJtJinv_IDC), dense and

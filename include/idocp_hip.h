@@ -560,6 +560,25 @@ int idocp_ocp_get_constraint_data(idocp_ocp_t* h, int instance, double* slack, d
 int idocp_ocp_set_lqr_stage(idocp_ocp_t* h, int stage, int terminal, const double* Qxx, const double* Qxu, const double* Quu,
                             const double* Fqq6, const double* Fqv6, const double* Fvq, const double* Fvv, const double* Fvu,
                             const double* lx, const double* lu, const double* Fx);
+/* For tests: the same blocks by position in the chain of the current discretisation (grid, impulse, aux, lift and terminal nodes), of one
+ * instance or, with instance == -1, of all.  The node's kind decides what is read: a terminal node takes Qxx and lx only; an impulse node has no
+ * control -- its record gets what the condensation leaves there (Quu = I, Qxu = 0, Fvu = 0, lu = 0, Fqv6 = 0) and Qxu, Quu, Fqv6, Fvu, lu may be
+ * NULL.  idocp_ocp_set_lqr_stage is this entry on a grid stage for all instances.  IDOCP_E_ARG, with a text that begins with the entry's name,
+ * for a ParNMPC handle and an instance or position out of range. */
+int idocp_ocp_set_lqr_stage_chain(idocp_ocp_t* h, int instance, int position, const double* Qxx, const double* Qxu, const double* Quu,
+                                  const double* Fqq6, const double* Fqv6, const double* Fvq, const double* Fvv, const double* Fvu,
+                                  const double* lx, const double* lu, const double* Fx);
+/* For tests: the switching constraint Phix dx + Phiu du + P = 0 carried by one chain position, as the backward sweep reads it: P [dimi],
+ * Phix [dimi x 2nv], Phiu [dimi x nu], column-major with leading dimension dimi; of one instance or, with instance == -1, of all.  Rows
+ * dimi .. max_dimf - 1 of the record stay as they are: the kernels that fill it write rows 0 .. dimi - 1 only.  IDOCP_E_ARG, with a text that
+ * begins with the entry's name, for a ParNMPC handle, a position out of range, a position without a switching constraint, and a dimi that is
+ * not the node's (idocp_ocp_get_chain: sw_dimi). */
+int idocp_ocp_set_switching_constraint(idocp_ocp_t* h, int instance, int position, int dimi, const double* P, const double* Phix,
+                                       const double* Phiu);
+/* For tests: the multiplier policy dxi = M dx + m the backward sweep left at one chain position (SplitConstrainedRiccatiFactorization,
+ * split_riccati_factorizer.hxx:71-74): M [dimi x 2nv] column-major with leading dimension dimi, m [dimi]; either may be NULL.  Returns dimi, or
+ * IDOCP_E_ARG with a text as above. */
+int idocp_ocp_get_switching_policy(idocp_ocp_t* h, int instance, int position, double* M, double* m);
 /* ContactDynamicsData of a grid stage after the condensation (include/idocp/ocp/contact_dynamics_data.hxx:8-29): MJtJinv [n * n], MJtJinv_dIDCdqv
  * [n * 2 nv], MJtJinv_IDC [n], dense column-major with n = nv + dimf rows (the rows of the active contacts packed).  Returns dimf (>= 0) or an
  * error code (< 0).  For tests: M, J and the derivatives of [ID; C] follow from the three by one inverse. */

@@ -677,6 +677,66 @@ int oracle_ocp_backward_riccati_only(void* h) {
   try { static_cast<OCPSolver*>(h)->backwardRiccatiRecursion(); } catch (...) { return 1; }
   return 0;
 }
+// The same by CHAIN POSITION (tests/riccati_chain_cases.py: chains with impulse, aux and lift nodes): the node's kind decides what is read -- a
+// terminal node takes Qxx and lx, an impulse node has no control (the recursion never reads Qxu, Quu, Fqv6, Fvu, lu there; they may be null).
+int oracle_ocp_inject_lqr_stage_chain(void* h, int position, const double* Qxx, const double* Qxu, const double* Quu, const double* Fqq6,
+                                      const double* Fqv6, const double* Fvq, const double* Fvv, const double* Fvu, const double* lx,
+                                      const double* lu, const double* Fx) {
+  OCPSolver* s = static_cast<OCPSolver*>(h);
+  if (position < 0 || position >= s->M()) return -1;
+  const NodeC& nd = s->chain[position];
+  if (nd.kind == NodeC::Terminal) return oracle_ocp_inject_lqr_stage(h, nd.slot, 1, Qxx, Qxu, Quu, Fqq6, Fqv6, Fvq, Fvv, Fvu, lx, lu, Fx);
+  if (nd.kind != NodeC::Impulse) return oracle_ocp_inject_lqr_stage(h, nd.slot, 0, Qxx, Qxu, Quu, Fqq6, Fqv6, Fvq, Fvv, Fvu, lx, lu, Fx);
+  const int nv = s->robot.dimv(), nx = 2 * nv;
+  SplitKKTMatrixC& M = s->kkt_matrix[nd.slot];
+  SplitKKTResidualC& R = s->kkt_residual[nd.slot];
+  auto put = [](Mat& m, const double* src, int r, int c) { Mat t(r, c); xcpy(t.d.data(), src, sizeof(double) * r * c); m = t; };
+  put(M.Qxx, Qxx, nx, nx);
+  put(M.Fqq6, Fqq6, 6, 6); put(M.Fvq, Fvq, nv, nv); put(M.Fvv, Fvv, nv, nv);
+  for (int r = 0; r < nv; ++r) { R.lq[r] = lx[r]; R.lv[r] = lx[nv + r]; R.Fq[r] = Fx[r]; R.Fv[r] = Fx[nv + r]; }
+  return 0;
+}
+// The switching constraint Phix dx + Phiu du + P = 0 of the chain position that carries one, as the backward recursion reads it (column-major,
+// dimi rows).  -1: position out of range; -2: no switching constraint there; -3: dimi is not the node's.
+int oracle_ocp_inject_switching_constraint(void* h, int position, int dimi, const double* P, const double* Phix, const double* Phiu) {
+  OCPSolver* s = static_cast<OCPSolver*>(h);
+  if (position < 0 || position >= s->M()) return -1;
+  const NodeC& nd = s->chain[position];
+  if (nd.sw_event < 0) return -2;
+  SwitchingC& W = s->sw[nd.slot];
+  if (dimi != W.Phix.r) return -3;
+  const int nv = s->robot.dimv(), nu = s->robot.dimu();
+  auto put = [](Mat& m, const double* src, int r, int c) { Mat t(r, c); xcpy(t.d.data(), src, sizeof(double) * r * c); m = t; };
+  put(W.Phix, Phix, dimi, 2 * nv); put(W.Phiu, Phiu, dimi, nu);
+  Mat p(dimi);
+  for (int r = 0; r < dimi; ++r) p[r] = P[r];
+  s->kkt_residual[nd.slot].P = p;
+  return 0;
+}
+// rows of the switching constraint carried by a chain position (0: none)
+int oracle_ocp_switching_rows(void* h, int position) {
+  OCPSolver* s = static_cast<OCPSolver*>(h);
+  if (position < 0 || position >= s->M()) return -1;
+  const NodeC& nd = s->chain[position];
+  return nd.sw_event < 0 ? 0 : s->sw[nd.slot].Phix.r;
+}
+// The multiplier policy dxi = M dx + m of the last backward recursion at a chain position: M (dimi x 2nv, column-major), m (dimi).  Returns dimi.
+int oracle_ocp_get_switching_policy(void* h, int position, double* M, double* m) {
+  OCPSolver* s = static_cast<OCPSolver*>(h);
+  if (position < 0 || position >= s->M()) return -1;
+  const NodeC& nd = s->chain[position];
+  if (nd.sw_event < 0) return -2;
+  const SwitchingC& W = s->sw[nd.slot];
+  for (int c = 0; c < W.M.c; ++c) for (int r = 0; r < W.M.r; ++r) M[r + W.M.r * c] = W.M(r, c);
+  for (int r = 0; r < W.m.size(); ++r) m[r] = W.m[r];
+  return W.M.r;
+}
+// the forward recursion and the direction behind it (dxi = M dx + m lives there), on whatever the backward recursion left
+int oracle_ocp_forward_riccati_only(void* h, const double* q, const double* v) {
+  OCPSolver* s = static_cast<OCPSolver*>(h);
+  try { s->forwardRiccatiRecursion(toVec(q, s->robot.dimq()), toVec(v, s->robot.dimv())); s->computeDirection(); } catch (...) { return 1; }
+  return 0;
+}
 int oracle_ocp_compute_kkt_residual(void* h, double t, const double* q, const double* v) {
   OCPSolver* s = static_cast<OCPSolver*>(h);
   s->computeKKTResidual(t, toVec(q, s->robot.dimq()), toVec(v, s->robot.dimv()));

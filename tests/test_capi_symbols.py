@@ -131,3 +131,17 @@ def test_get_ext_terms_is_declared_and_refuses_a_null_handle():
     # the test-facing getter of the ext record (tests/test_ocp_ext_terms_gpu.py): declared, exported, IDOCP_E_ARG without a handle
     assert "idocp_ocp_get_ext_terms" in declared_functions()
     assert capi.lib().idocp_ocp_get_ext_terms(None, 0, 0, *[None] * 9) == -1
+
+
+def test_chain_injection_entries_are_declared_and_refuse_a_null_handle():
+    # the test-facing entries of tests/test_riccati_chain_gpu.py: declared, exported, IDOCP_E_ARG under their own name without a handle (the
+    # refusals that need a handle -- position out of range, no switching constraint there, a ParNMPC handle -- are held there)
+    lib = capi.lib()
+    calls = {"idocp_ocp_set_lqr_stage_chain": lambda f: f(None, 0, 0, *[None] * 11),
+             "idocp_ocp_set_switching_constraint": lambda f: f(None, 0, 0, 3, None, None, None),
+             "idocp_ocp_get_switching_policy": lambda f: f(None, 0, 0, None, None)}
+    for name, call in calls.items():
+        assert name in declared_functions()
+        assert call(getattr(lib, name)) == -1
+        assert lib.idocp_last_error() == (name + ": null handle").encode()
+    assert lib.idocp_ocp_set_lqr_stage(None, 0, 0, *[None] * 11) == -1
